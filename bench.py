@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): RK4 rollout steps/s (batch x horizon) on MI355X, fp64, plus the EDMDc Gram build
 samples/s and the sharded 2^20-rollout ensemble (config 4), each against its roofline, with the CPU baselines timed beside.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment starts its N ranks itself (a child
@@ -11,8 +11,12 @@ samples/s and the sharded 2^20-rollout ensemble (config 4), each against its roo
 One "step" = one pass of the hot path over one batch = ONE launch of the rollout kernel over 65 536 trajectories x
 5 000 RK4 steps (BASELINE config 2: thruster model, dt = 0.02, iid U(-1,1) commands from the counter-based stream, every
 state stored).  Inputs are resident in HBM before the timed region.  With N GPUs every rank runs its own 65 536-trajectory
-shard (weak scaling, no collective on the rollout path).  Legs after the timed headline loop (all reported in the same JSON
-line, rank 0):
+shard (weak scaling, no collective on the rollout path).
+
+A plain run sets up, warms up, times the K steps, writes what the last timed step computed if --dump-outputs is given
+(`dump_outputs`), and prints the one JSON line: the headline figure and the roofline of the timed launches.  With --full,
+the legs after the timed headline loop run as well (all reported in the same JSON line, rank 0; the full record of every
+leg goes to the --details file):
   verified     the trajectories the TIMED launches wrote, lanes 0..7, every 50th state, against the reference's own
                states (tests/golden/fossen_rollouts.npz: cfg2_rk4), plus random lanes against single-lane re-runs
   rollout_ar1  the same launch on the AR(1) command stream ("dist B", training/train_sim_brov2_koopmanEDMDc.py:161-164)
@@ -182,6 +186,10 @@ def parse():
     ap.add_argument("--cpu-seconds", type=float, default=3.0, help="budget of EACH host baseline leg")
     ap.add_argument("--details", default=None, help="where the full record of every leg goes (default: bench_details.json in the repo root); "
                                                     "stdout carries ONE compact JSON line")
+    ap.add_argument("--full", action="store_true", help="also run the legs after the headline loop: verification of the timed launches, "
+                                                        "rollout variants, EDMDc Gram / fit, config 4, CPU baselines, and the --details file")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last step computed as DIR/<name>.npy "
+                                                                         "(float64; rank 0's shard; see dump_outputs)")
     return ap.parse_args()
 
 
@@ -454,6 +462,38 @@ def rel_err(a, b):
     return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b)))) if a.size else 0.0
 
 
+# ---------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_XT_BYTES = 16_000_000           # end states: all of them up to this size (65 536 x 12 fp64 = 6.3 MB)
+DUMP_TRAJ_BYTES = 40_000_000         # stored states: a fixed sample of lanes x rows up to this size (64 x 5 001 x 12 fp64 = 30.7 MB)
+DUMP_TRAJ_LANES = 64
+
+
+def dump_plan(B, T):
+    """Which end states and which stored states `dump_outputs` writes for B trajectories x T steps: every lane of xT while they
+    fit DUMP_XT_BYTES (else a seeded sample), and DUMP_TRAJ_LANES seeded lanes x every row of the trajectory buffer while they fit
+    DUMP_TRAJ_BYTES (else evenly spaced rows, first and last included).  Depends on (B, T) only: two runs with the same arguments
+    dump the same elements."""
+    def lanes(n, k, seed):
+        return np.arange(n) if n <= k else np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+    end = lanes(B, DUMP_XT_BYTES // (12 * 8), 0x5EED)
+    traj_lanes = lanes(B, DUMP_TRAJ_LANES, 0xD0)
+    m = max(2, DUMP_TRAJ_BYTES // (12 * 8 * len(traj_lanes)))
+    rows = np.arange(T + 1) if T + 1 <= m else np.unique(np.linspace(0, T, m).round().astype(np.int64))
+    return end, traj_lanes, rows
+
+
+def dump_outputs(path, xT, traj, lay, T):
+    """What a caller of the timed path receives from its last step, as float64 .npy files under `path`:
+    xT.npy           [len(end), 12] end states of the lanes dump_plan picks (all of them at the default sizes)
+    traj_sample.npy  [lanes, rows, 12] stored states of dump_plan's lanes and rows (absent with --no-store)"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    end, lanes, rows = dump_plan(xT.shape[0], T)
+    np.save(os.path.join(path, "xT.npy"), xT.index_select(0, torch.as_tensor(end, device=xT.device)).cpu().numpy().astype(np.float64))
+    if traj is not None:
+        np.save(os.path.join(path, "traj_sample.npy"), lanes_from_traj(traj, lay, lanes, rows).astype(np.float64))
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -607,8 +647,11 @@ def main():
                      "traffic": traffic},
     }
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, xT, traj, lay, T)        # before any later leg overwrites traj / xT
+
     # ------------------------------------------------------------------ what did the timed launches write?
-    if traj is not None and rank == 0:
+    if a.full and traj is not None and rank == 0:
         ver = {}
         gpath = os.path.join(REPO, "tests", "golden", "fossen_rollouts.npz")
         defaults = (a.integrator in ("rk4", "euler") and a.controls == "iid" and B >= 8 and os.path.exists(gpath))
@@ -638,7 +681,7 @@ def main():
         del Ul, tl
 
     # ------------------------------------------------------------------ AR(1) commands (dist B), same launch
-    if not a.no_ar1 and a.controls == "iid":
+    if a.full and not a.no_ar1 and a.controls == "iid":
         engine.fill_controls_dev(U, lay, "ar1", seed=0x5EED, b0=rank * B, T_total=T, ctx=ctx)
         step()
         w2, k2 = timed_launches(max(1, min(2, a.steps)))
@@ -649,7 +692,7 @@ def main():
     # ------------------------------------------------------------------ config 2's other runs (SURVEY 8(d) cfg 2: "trajectories stored
     # in one run and endpoint-only in another"; the reference's comparison script integrates with Euler,
     # training/train_tank_brov2_full_comparison.py:453-466): same commands, same sizes, each verified
-    if not a.no_variants and a.controls == "iid" and a.integrator == "rk4" and traj is not None:
+    if a.full and not a.no_variants and a.controls == "iid" and a.integrator == "rk4" and traj is not None:
         engine.fill_controls_dev(U, lay, "iid", seed=0x5EED, b0=rank * B, T_total=T, ctx=ctx)     # back to dist A
         xT_stored = {}
         variants = {}
@@ -722,7 +765,7 @@ def main():
     n, r, k, gamma, ridge = 12, 8, 512, 1.0, 1e-3
     p, d = n + k + r, n + k
     Cc = None
-    if not a.no_edmdc:
+    if a.full and not a.no_edmdc:
         L = 500
         nb = max(1, a.edmdc_samples // L)
         Ue = torch.empty((nb, L, r), dtype=torch.float64, device=dev)
@@ -1020,7 +1063,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ config 4: the sharded ensemble (strong scaling)
-    if not a.no_cfg4:
+    if a.full and not a.no_cfg4:
         Bt, T4 = a.cfg4_rollouts, a.cfg4_horizon
         b0, b1 = bdist.shard_range(Bt, rank, world)
         Bl = b1 - b0
@@ -1114,7 +1157,7 @@ def main():
         del U4, X4, GG4, G4, Y4, Xa, Xb, chk
         torch.cuda.empty_cache()
 
-    if rank == 0 and not a.no_cpu:
+    if a.full and rank == 0 and not a.no_cpu:
         # (N > 1: rank 0 times the same bounded host samples after every timed region; the other ranks have nothing left to do
         # but wait at the final barrier)
         out["cpu_baseline"] = cpu_baseline_rollout(a.cpu_seconds, a.integrator)
@@ -1123,8 +1166,10 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
-        out["cpu_seconds_budget_per_leg"] = a.cpu_seconds
-        details = write_details(out, a.details)
+        details = None
+        if a.full:
+            out["cpu_seconds_budget_per_leg"] = a.cpu_seconds
+            details = write_details(out, a.details)
         line = json.dumps(compact_line(out, details), separators=(",", ":"))
         assert len(line) <= MAX_LINE_BYTES, len(line)
         sys.stdout.flush()

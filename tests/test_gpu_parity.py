@@ -2262,7 +2262,7 @@ def test_config4_shard_rollouts_and_gram(eng, fc):
 
 
 def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
-    """bench.py at toy sizes with the driver's flags (--steps 20 --warmup 5): ONE compact JSON line on stdout (<= 4096 bytes: round 5's
+    """bench.py --full at toy sizes with the driver's flags (--steps 20 --warmup 5): ONE compact JSON line on stdout (<= 4096 bytes: round 5's
     25 KB line came back from the driver unparsed) with every field of the driver's contract, the roofline object of the dominant
     kernel, the CPU baseline (kind "port" = the C oracle on the host cores) and a flat summary of the other legs; the full record
     of every leg goes to the --details file."""
@@ -2272,7 +2272,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     import sys
     from conftest import REPO
     det = str(tmp_path / "details.json")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "20", "--warmup", "5", "--batch", "1024", "--horizon", "40",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--batch", "1024", "--horizon", "40",
            "--edmdc-samples", "40000", "--edmdc-steps", "1", "--kmeans-iters", "2", "--cpu-seconds", "0.3",
            "--cfg4-rollouts", "4096", "--cfg4-horizon", "50", "--details", det]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=REPO)
@@ -2365,6 +2365,48 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
     assert len(c4["per_rank_ms"]) == 1 and c4["rollout_steps_per_s"] > 0 and c4["gram_samples_per_s"] > 0
     assert d["cpu_baseline_reference_shape"]["cores"] == 1 and d["cpu_baseline_reference_shape"]["value"] > 0
     assert 0 < d["roofline"]["frac"] <= 1.0 and 0 < d["roofline"]["frac_of_measured_ceiling"]
+
+
+def test_plain_bench_run_times_the_headline_only_and_dumps_its_outputs(tmp_path, fc):
+    """bench.py without --full: the headline launches and nothing else (no verification, CPU baseline, other legs or details file),
+    --steps timed steps, and with --dump-outputs the end states and a fixed sample of the stored states of the last timed launch --
+    the same bits in two runs, and the C oracle's trajectories of those lanes."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    from conftest import REPO
+    from oracle import controls
+    B, T, steps = 1024, 40, 7
+    dumps = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "2", "--batch", str(B), "--horizon", str(T),
+               "--dump-outputs", d]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=REPO)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1 and len(lines[0]) <= 4096, lines
+        c = json.loads(lines[0])
+        assert c["metric"] == "rk4_rollout_steps_per_s" and c["unit"] == "steps/s" and c["higher_is_better"] is True and c["dtype"] == "f64"
+        assert c["steps"] == steps and c["warmup"] == 2 and c["n_gpus"] == 1 and 0 < c["roofline"]["frac"] <= 1
+        assert abs(c["value"] - B * T * steps / (c["ms_per_step"] * steps * 1e-3)) / c["value"] < 1e-6
+        assert "cpu_baseline" not in c and "verified" not in c and c["summary"] == {} and c["details"] is None
+        assert sorted(os.listdir(d)) == ["traj_sample.npy", "xT.npy"]
+        dumps.append({f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)})
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= 64_000_000
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+    end, lanes, rows = bench.dump_plan(B, T)
+    assert a["xT"].shape == (B, 12) and a["traj_sample"].shape == (len(lanes), len(rows), 12)
+    U = controls.controls_iid(0x5EED, 0, B, T)
+    x0 = np.zeros((B, 12))
+    x0[:, 2] = 5.0
+    o = fc.rollout(fc.MODEL_THRUSTER_EULER, fc.INTEG_RK4, x0, U, 0.02, nthreads=4)
+    assert rel_err(a["xT"], o["xT"][end]) < 1e-9
+    assert rel_err(a["traj_sample"], o["traj"][lanes][:, rows]) < 1e-9
 
 
 def test_randomised_parity_sweep_short(eng):

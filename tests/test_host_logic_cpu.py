@@ -140,8 +140,24 @@ def test_driver_entry_points_exist_and_bench_parses_its_flags():
     assert callable(ge.build) and callable(ge.smoke)
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out.stdout
+
+
+def test_bench_dump_plan_is_fixed_and_bounded():
+    """what `bench.py --dump-outputs` writes: at the default sizes every end state and 64 whole stored trajectories, at any size at most
+    64 MB, the same elements from run to run (seeded), sorted distinct lanes and rows inside the buffers, first and last rows kept"""
+    import bench
+    for B, T in ((65536, 5000), (1024, 40), (7, 3), (1 << 22, 100_000), (1 << 20, 500)):
+        end, lanes, rows = bench.dump_plan(B, T)
+        again = bench.dump_plan(B, T)
+        assert all(np.array_equal(x, y) for x, y in zip((end, lanes, rows), again))
+        for idx, n in ((end, B), (lanes, B), (rows, T + 1)):
+            assert len(idx) and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < n
+        assert rows[0] == 0 and rows[-1] == T and len(lanes) == min(B, 64)
+        assert (len(end) + len(lanes) * len(rows)) * 12 * 8 <= 64_000_000 - 1024
+    end, lanes, rows = bench.dump_plan(65536, 5000)
+    assert len(end) == 65536 and len(rows) == 5001
 
 
 def test_thruster_geometry_entries_are_views_of_one_block():

@@ -5,6 +5,7 @@
 set -o pipefail
 mkdir -p gpurun_out
 out=gpurun_out/variants.txt
+dir=$(dirname $out)
 : > $out
 libs=bluerov2_dynamics_amd/libbrov2.so
 if [ -n "$VARIANTS" ]; then for v in $VARIANTS; do libs="$libs build_variants/$v/libbrov2.so"; done
@@ -13,9 +14,9 @@ for rep in $(seq 1 ${REPS:-1}); do
 for lib in $libs; do
   [ -f "$lib" ] || continue
   name=$(basename $(dirname $lib))
-  BROV2_LIBRARY=$PWD/$lib timeout -k 10 300 python3 bench.py --no-edmdc --no-cfg4 --no-cpu --no-ar1 --steps 4 --warmup 1 "$@" > gpurun_out/var_$name.json 2> gpurun_out/var_$name.err
+  BROV2_LIBRARY=$PWD/$lib timeout -k 10 300 python3 bench.py --full --no-edmdc --no-cfg4 --no-cpu --no-ar1 --steps 4 --warmup 1 "$@" > $dir/var_$name.json 2> $dir/var_$name.err
   rc=$?
-  python3 - "$name" "$rc" gpurun_out/var_$name.json >> $out <<'PY'
+  python3 - "$name" "$rc" $dir/var_$name.json >> $out <<'PY'
 import json, sys
 name, rc, path = sys.argv[1:4]
 try:

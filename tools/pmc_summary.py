@@ -43,7 +43,7 @@ for p, d in out.items():
         if d.get("GRBM_GUI_ACTIVE"):
             d["mfma_busy_fraction"] = d["SQ_VALU_MFMA_BUSY_CYCLES"] / (d["GRBM_GUI_ACTIVE"] / 8.0 * 1024.0)
 out = {NAMES.get(p, p): d for p, d in out.items()}
-out["_method"] = ("rocprofv3 --pmc <group> --kernel-trace, one pass per counter group (tools/profile_round.sh), python3 bench.py --steps 1 "
+out["_method"] = ("rocprofv3 --pmc <group> --kernel-trace, one pass per counter group (tools/profile_round.sh), python3 bench.py --full --steps 1 "
                   "--warmup 1 --edmdc-steps 1 --no-cpu; per-kernel means over the dispatches of each pass; FETCH_SIZE doubled per "
                   "MI355X_MICROARCH.md (gfx950 tallies 128-B requests at 64 B); sizes in KiB; SQ_*_CYCLES in units of 4 clocks")
 import os

@@ -9,15 +9,15 @@ tag=${1:-r04}
 out=gpurun_out/prof_$tag
 mkdir -p $out
 root=$(pwd)
-python3 bench.py --details $root/$out/bench_details.json > $out/bench.json 2> $out/bench.err
+python3 bench.py --full --details $root/$out/bench_details.json > $out/bench.json 2> $out/bench.err
 echo "bench done"
-( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/trace -o run -- python3 $root/bench.py --no-cpu --no-variants > $root/$out/trace.log 2>&1 )
+( cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $root/$out/trace -o run -- python3 $root/bench.py --full --no-cpu --no-variants > $root/$out/trace.log 2>&1 )
 cp $(find $out/trace -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 # per-kernel launch times WITHOUT the first launch of each kernel in the profiled process (code-object load, cold caches): median /
 # min / mean -- the figures comparable with bench.py's own ms_per_step (the --stats average includes that first launch)
 python3 tools/kernel_times.py $(find $out/trace -name "*kernel_trace.csv" | head -1) > $out/kernel_times.json
 echo "trace done"
-short="--steps 1 --warmup 1 --edmdc-steps 1 --no-cpu --no-cfg4 --no-ar1 --no-variants --no-fit --kmeans-iters 10"
+short="--full --steps 1 --warmup 1 --edmdc-steps 1 --no-cpu --no-cfg4 --no-ar1 --no-variants --no-fit --kmeans-iters 10"
 tools/pmc_pass.sh $out/pmc/fetch "FETCH_SIZE" -- python3 $root/bench.py $short
 tools/pmc_pass.sh $out/pmc/write "WRITE_SIZE" -- python3 $root/bench.py $short
 tools/pmc_pass.sh $out/pmc/sq1 "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_SMEM SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES" -- python3 $root/bench.py $short

@@ -14,11 +14,11 @@ python3 tools/time_multistep_linear.py 2>&1 | grep -v amdgpu.ids > $o/multistep_
 python3 tools/time_upload.py 2>&1 | grep -v amdgpu.ids > $o/upload.txt
 echo "timings done"
 timeout -k 10 900 python -m pytest tests -m gpu -q > $o/gpu_tests.log 2>&1; tail -2 $o/gpu_tests.log
-python bench.py --steps 20 --warmup 5 --details $o/bench_details.json > $o/bench.json 2> $o/bench.err; echo "bench rc=$? bytes=$(wc -c < $o/bench.json)"
+python bench.py --full --steps 20 --warmup 5 --details $o/bench_details.json > $o/bench.json 2> $o/bench.err; echo "bench rc=$? bytes=$(wc -c < $o/bench.json)"
 fi
 if [ "$part" = "b" ] || [ "$part" = "all" ]; then
 BROV2_LIBRARY=$PWD/build_variants/experiments/libbrov2.so timeout -k 10 900 python -m pytest tests -m gpu -q > $o/gpu_tests_experiments.log 2>&1; tail -2 $o/gpu_tests_experiments.log
 timeout -k 10 400 python3 tests/stress_parity.py 30 6 > $o/stress_parity.log 2>&1; tail -2 $o/stress_parity.log
 BROV2_LIBRARY=$PWD/build_variants/experiments/libbrov2.so timeout -k 10 400 python3 tests/stress_parity.py 30 7 > $o/stress_experiments.log 2>&1; tail -2 $o/stress_experiments.log
-BROV2_BENCH_SHARE_GPU=1 BROV2_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --gpus 2 --steps 20 --warmup 5 --details $o/rehearsal_2ranks_details.json > $o/rehearsal_2ranks.json 2> $o/rehearsal_2ranks.err; echo "rehearsal rc=$? bytes=$(wc -c < $o/rehearsal_2ranks.json) lines=$(wc -l < $o/rehearsal_2ranks.json)"
+BROV2_BENCH_SHARE_GPU=1 BROV2_BENCH_BACKEND=gloo timeout -k 10 900 python bench.py --full --gpus 2 --steps 20 --warmup 5 --details $o/rehearsal_2ranks_details.json > $o/rehearsal_2ranks.json 2> $o/rehearsal_2ranks.err; echo "rehearsal rc=$? bytes=$(wc -c < $o/rehearsal_2ranks.json) lines=$(wc -l < $o/rehearsal_2ranks.json)"
 fi
