@@ -446,13 +446,22 @@ struct LagZ {
             z[k][2] = fma(c2, a2, fma(c1, a1, fma(c0, a0, g2 * acmd[k])));
         }
     }
+    // The last FMA of each row is written over the old z[k][j] in place (inline asm, "+v"): the compiler accumulates a row in the
+    // register of its first product (v_fmac), which is live while the old state is, so it would carry the new bank in other
+    // registers and copy it back every step (18 v_mov_b64 per step in the thrust wave of rollout_pair_kernel).  The unused asm
+    // inputs order the three writes behind every read of the values they replace.  Same operations in the same order: same values.
     __device__ __forceinline__ void advance(const double __attribute__((address_space(4)))* A, const double __attribute__((address_space(4)))* b, const double acmd[6]) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) {
             const double a0 = z[k][0], a1 = z[k][1], a2 = z[k][2];
-            z[k][0] = fma(A[2], a2, fma(A[1], a1, fma(A[0], a0, b[0] * acmd[k])));
-            z[k][1] = fma(A[5], a2, fma(A[4], a1, fma(A[3], a0, b[1] * acmd[k])));
-            z[k][2] = fma(A[8], a2, fma(A[7], a1, fma(A[6], a0, b[2] * acmd[k])));
+            const double q0 = fma(A[1], a1, fma(A[0], a0, b[0] * acmd[k]));
+            const double q1 = fma(A[4], a1, fma(A[3], a0, b[1] * acmd[k]));
+            const double q2 = fma(A[7], a1, fma(A[6], a0, b[2] * acmd[k]));
+            double n0 = a0, n1 = a1, n2 = a2;
+            asm("v_fma_f64 %0, %1, %2, %3" : "+v"(n0) : "s"(A[2]), "v"(a2), "v"(q0), "v"(q1), "v"(q2));            // fma(A[2], a2, q0)
+            asm("v_fma_f64 %0, %1, %2, %3" : "+v"(n1) : "s"(A[5]), "v"(a2), "v"(q1), "v"(q0), "v"(q2));            // fma(A[5], a2, q1)
+            asm("v_fma_f64 %0, %1, %0, %2" : "+v"(n2) : "s"(A[8]), "v"(q2), "v"(n0), "v"(n1));                     // fma(A[8], a2, q2)
+            z[k][0] = n0; z[k][1] = n1; z[k][2] = n2;
         }
     }
 };

@@ -319,6 +319,21 @@ __global__ void __launch_bounds__(256) rollout_kernel(const FastParams* __restri
 #endif
 __device__ __forceinline__ void pair_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
+// LAYOUT_TPB streams (control rows in, states out) addressed in the saddr form: a wave-uniform 64-bit base in SGPRs that advances one
+// row per step with SALU, plus a fixed 32-bit offset per lane and pair (lane's pair 0 + i x pair stride).  The 64-bit VGPR address
+// arithmetic of the plain form costs one VALU slot per access and step.  The offsets must fit 32 bits: pair_saddr_fits(B), checked by
+// the launcher, which takes rollout_kernel for larger batches.
+__host__ __device__ constexpr bool pair_saddr_fits(int64_t B) { return B > 0 && B <= (int64_t)((0xFFFFFFFFull - 64 * 16) / (5 * 16)); }
+// The offset passes through an empty asm at each access, in place (a loop-carried register, no copy): a 32-bit value the compiler
+// cannot widen once outside the loop -- it would then add two 64-bit registers per access, the plain form's VALU slot.
+__device__ __forceinline__ uint64_t lane_offset(unsigned& o) { asm volatile("" : "+v"(o)); return o; }
+typedef __attribute__((address_space(1))) char* gptr_t;         // global address space: global_* (not flat_*) instructions
+__device__ __forceinline__ gptr_t wave_uniform(const void* ptr) {
+    const uint64_t a = reinterpret_cast<uint64_t>(ptr);
+    return (gptr_t)(((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) |
+                    (uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a & 0xFFFFFFFFull)));
+}
+
 template <int INTEG, int LAYOUT, int LAGMODE, bool TRACK, bool GENERIC>
 __global__ void __launch_bounds__(512) rollout_pair_kernel(const FastParams* __restrict__ pg, int64_t B, int64_t T, double dt,
                                                            const double* __restrict__ X0, const double* __restrict__ U,
@@ -363,28 +378,42 @@ __global__ void __launch_bounds__(512) rollout_pair_kernel(const FastParams* __r
         if constexpr (TRACK) { load_row<24>(lag_io + b * 24, &Xl[0][0]); lz.from_thrusters(p, Xl); }
         else lz.zero();
         if constexpr (!GENERIC) lz.to_observer(p);
-        const double* up;
+        const double* up = nullptr;
         int64_t ustep;
         if constexpr (LAYOUT == LAYOUT_BTU) { up = U + b * T * NU; ustep = NU; }
         else if constexpr (LAYOUT == LAYOUT_TUB) { up = U + b; ustep = (int64_t)NU * B; }
-        else { up = U + 2 * b; ustep = (int64_t)NUP * 2 * B; }
-        double un[NU];
+        else ustep = (int64_t)NUP * 2 * B;
+        // LAYOUT_TPB: wave-uniform row base + per-lane offsets (pair_saddr_fits)
+        const int64_t bw_c = (int64_t)blockIdx.x * 256 + pair * 64 < B ? (int64_t)blockIdx.x * 256 + pair * 64 : B - 1;
+        gptr_t ub = LAYOUT == LAYOUT_TPB ? wave_uniform(U + 2 * bw_c) : nullptr;
+        unsigned uoff[NUP];
+#pragma unroll
+        for (int i = 0; i < NUP; ++i) uoff[i] = (unsigned)((b - bw_c) * 16 + (int64_t)i * 16 * B);
+        double un[NU];                                        // the controls of the next step to produce
         int64_t tl = 0;                                       // step whose controls sit in `un`
         auto load_controls = [&]() {
             if constexpr (LAYOUT == LAYOUT_BTU) load_row<NU>(up, un);
             else if constexpr (LAYOUT == LAYOUT_TUB) load_soa<NU>(up, B, un);
-            else load_pairs<NU>(up, 2 * B, un);
+            else {
+                typedef double v2d __attribute__((ext_vector_type(2)));
+#pragma unroll
+                for (int i = 0; i < NUP; ++i) {
+                    const v2d w = __builtin_nontemporal_load(reinterpret_cast<const __attribute__((address_space(1))) v2d*>(ub + lane_offset(uoff[i])));
+                    un[2 * i] = w[0]; un[2 * i + 1] = w[1];
+                }
+            }
         };
         if (T > 0) load_controls();
         auto produce = [&](int slot) {
-            double u[NU], fcmd[8], acmd[6], a[6];
-#pragma unroll
-            for (int i = 0; i < NU; ++i) u[i] = un[i];
-            up += (tl + 1 < T) ? ustep : 0;                   // prefetch the next row (the last step re-reads its own, unused)
+            double fcmd[8], acmd[6], a[6];
+            const CFP pp = relaunder(p);
+            command_accel<MODEL, !GENERIC>(pp, un, fcmd, acmd);
+            // the row is consumed: prefetch the next one into the same registers (no copy of the row); it has the rest of this
+            // step and the next barrier to land.  The last step re-reads its own row, unused.
+            if constexpr (LAYOUT == LAYOUT_TPB) ub += (tl + 1 != T) ? ustep * 8 : 0;     // (tl < T: a scalar compare)
+            else up += (tl + 1 != T) ? ustep : 0;
             ++tl;
             load_controls();
-            const CFP pp = relaunder(p);
-            command_accel<MODEL, !GENERIC>(pp, u, fcmd, acmd);
 #pragma unroll
             for (int s = 1; s <= NS; ++s) {
                 lag_stage_accel<LAGMODE, GENERIC>(h, pp, lz, s, acmd, a);
@@ -415,11 +444,13 @@ __global__ void __launch_bounds__(512) rollout_pair_kernel(const FastParams* __r
             }
         }
 #else
+        // T barriers, the body wave's count: produce a(t) behind barrier t - 1
         if (T > 0) produce(0);
-        for (int64_t t = 0; t < T; ++t) {
+        for (int64_t t = 1; t < T; ++t) {
             pair_barrier();
-            if (t + 1 < T) produce((int)((t + 1) & 1));
+            produce((int)(t & 1));
         }
+        if (T > 0) pair_barrier();
 #endif
         if constexpr (TRACK) { if (live) store_row<24>(lag_io + b * 24, &Xl[0][0]); }
     } else {
@@ -430,8 +461,15 @@ __global__ void __launch_bounds__(512) rollout_pair_kernel(const FastParams* __r
         if (traj) {
             if constexpr (LAYOUT == LAYOUT_BTU) { tp = traj + b * (T / stride + 1) * NX; tstep = NX; }
             else if constexpr (LAYOUT == LAYOUT_TUB) { tp = traj + b; tstep = (int64_t)NX * B; }
-            else { tp = traj + 2 * b; tstep = (int64_t)NXP * 2 * B; }
+            else tstep = (int64_t)NXP * 2 * B;
         }
+        // LAYOUT_TPB: wave-uniform row base + per-lane offsets (pair_saddr_fits).  Dead lanes shadow trajectory B - 1 and store its
+        // values, bit for bit what lane B - 1 stores, so the stores need no lane mask.
+        const int64_t sw_c = (int64_t)blockIdx.x * 256 + pair * 64 < B ? (int64_t)blockIdx.x * 256 + pair * 64 : B - 1;
+        gptr_t sb = LAYOUT == LAYOUT_TPB ? wave_uniform(traj + 2 * sw_c) : nullptr;
+        unsigned soff[NXP];
+#pragma unroll
+        for (int i = 0; i < NXP; ++i) soff[i] = (unsigned)((b - sw_c) * 16 + (int64_t)i * 16 * B);
         // staged stores (LAYOUT_BTU, stride 1).  Write-out of a tile: STG_PER = 12 lanes per trajectory, five trajectories per instruction (lanes
         // 60-63 idle), 13 instructions for the wave's 64 trajectories -- lane l always handles piece l % 12 of trajectory 5 it + l / 12, so
         // its global offset and LDS index are one register each plus a wave-uniform term per instruction
@@ -489,10 +527,19 @@ __global__ void __launch_bounds__(512) rollout_pair_kernel(const FastParams* __r
                     return;
                 }
             }
+            if constexpr (LAYOUT == LAYOUT_TPB) {
+                typedef double v2d __attribute__((ext_vector_type(2)));
+#pragma unroll
+                for (int i = 0; i < NXP; ++i) {
+                    v2d w; w[0] = x[2 * i]; w[1] = x[2 * i + 1];
+                    __builtin_nontemporal_store(w, reinterpret_cast<__attribute__((address_space(1))) v2d*>(sb + lane_offset(soff[i])));
+                }
+                sb += tstep * 8;
+                return;
+            }
             if (live) {
                 if constexpr (LAYOUT == LAYOUT_BTU) store_row<NX>(tp, x);
                 else if constexpr (LAYOUT == LAYOUT_TUB) store_soa<NX>(tp, B, x);
-                else store_pairs<NX>(tp, 2 * B, x);
             }
             tp += tstep;
         };
@@ -846,7 +893,7 @@ static hipError_t launch_rollout_g(hipStream_t st, const FastParams* p, int64_t 
         // the caller layout BTU takes the two-wave kernel where the one-lane kernel would use lane-per-row accesses anyway
         // (RK4: instruction-bound); the memory-bound Euler case keeps its LDS-staged kernel
         const bool staged_btu = LAYOUT == LAYOUT_BTU && (!traj || stride == 1) && T > 0 && want_lds;
-        if (want_pair && !staged_btu) {
+        if (want_pair && !staged_btu && (LAYOUT != LAYOUT_TPB || pair_saddr_fits(B))) {
             hipLaunchKernelGGL((rollout_pair_kernel<INTEG, LAYOUT, LAGMODE, TRACK, GENERIC>), dim3(nblk(B, 256)), dim3(512), 0, st,
                                p, B, T, dt, x0, U, lag, traj, stride, xT);
             return hipGetLastError();
