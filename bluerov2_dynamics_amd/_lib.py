@@ -107,6 +107,14 @@ SIGNATURES = {
                                                c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "brov_window_endpoint_se_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.c_double,
                                                    c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
+    "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
+    "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),
+    "brov_pinc_rollout_dev": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),
+    "brov_pinc_window_endpoint_se": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p,
+                                                    c_void_p, c_void_p, c_void_p]),
+    "brov_pinc_window_endpoint_se_dev": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p,
+                                                        c_void_p, c_void_p, c_void_p]),
     "brov_fill_controls_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.c_int,
                                               ctypes.c_uint64, i64, i64, c_void_p, c_void_p]),
     "edmdc_lift": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]),

@@ -104,6 +104,11 @@ hipError_t launch_endpoint_se(hipStream_t st, const PropShape& s, int64_t xstrid
 hipError_t launch_extract_state(hipStream_t st, const PropShape& s, int64_t T1, int64_t t, const double* Zt, double* Xp);
 hipError_t launch_useq_t(hipStream_t st, const PropShape& s, int64_t T, const double* Us, double* Ust);
 int window_scan_chunk();
+// blocked scan of the windows' initial lag states (rollout.hip): x_{k+1} = Phi x_k + resp_k over nc lag banks of 3 states
+// (6: the Fossen evaluator's wrench space, 8: the PINc evaluator's thruster space).  d_phi9 [Phi | Phi^window_scan_chunk()],
+// d_resp [nwin][nc][3], d_start [nwin + nchunks][nc][3] (the chunk states behind the nwin start states), d_s0 [nc][3] or nullptr (zero)
+hipError_t launch_window_lag_scan(hipStream_t st, int nc, int64_t nwin, const double* d_phi9, const double* d_resp, double* d_start,
+                                  const double* d_s0);
 hipError_t launch_sum(hipStream_t st, int64_t n, const double* v, double* out);
 
 // ---- column statistics (colstats.hip) -------------------------------------------------------
@@ -221,5 +226,17 @@ hipError_t launch_kmeanspp_sharded(hipStream_t st, int64_t N, int n, int k, int 
                                    long long first, const double* u, double* Xt, double* xsq, double* closest, double* S,
                                    void* state, double* C, long long* indices, float* Xf, int world, int rank, long long row0,
                                    double* shard, int (*exch)(void*, void*, int64_t, int), void* user, int* comm_failed, void* rowbuf = nullptr);
+
+// ---- PINc residual network (pinc.hip) -------------------------------------------------------
+// w: the packed fp32 weight blob (PINC_NPARAMS floats, state-dict order), p: the thruster map at this call's dt
+constexpr int PINC_NPARAMS = 14541;
+hipError_t launch_pinc_forward(hipStream_t st, const float* w, int64_t B, const float* z, float* x_next);
+hipError_t launch_pinc_rollout(hipStream_t st, const float* w, const DevParams& p, int64_t B, int64_t T, double dt, const double* x0,
+                               const double* U, double* lag_io, double* traj, int64_t stride, double* xT);
+// d_resp / d_start: scratch of launch_window_lag_scan (nc = 8), used when carry_lag; d_lag_io [8][3] (nullptr = zero) is the lag before
+// the first window and, with carry_lag, receives the lag after the last one; d_lag_starts [nwin][8][3] optional
+hipError_t launch_pinc_window_endpoint(hipStream_t st, const float* w, const DevParams& p, int64_t N, int64_t H, double dt,
+                                       const double* X, const double* U, int carry_lag, const double* d_phi9, double* d_resp,
+                                       double* d_start, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total);
 
 }  // namespace brov

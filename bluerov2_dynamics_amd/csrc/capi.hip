@@ -43,6 +43,8 @@ struct brov_ctx {
     FastParams* d_fp = nullptr;   // device copy read by the time-loop kernels through the constant address space
     FastParams* d_fp_di = nullptr;    // same struct for the double-integrator models: Tm holds the gains [K_lin | K_ang]^T
     bool di_set = false;
+    float* d_pinc = nullptr;      // packed PINc weights (PINC_NPARAMS fp32, brov_pinc_set_weights)
+    bool pinc_set = false;
     // EDMDc
     int btu_staging = 0;
     int single_lane = 0;          // 1: never use the two-wave rollout kernel (A/B measurements: BROV2_ROLLOUT_SINGLE_LANE=1)
@@ -529,6 +531,7 @@ void brov_destroy(brov_ctx* c) {
     for (int m = 0; m < 3; ++m) if (c->d_tasks[m]) (void)hipFree(c->d_tasks[m]);
     if (c->d_fp) (void)hipFree(c->d_fp);
     if (c->d_fp_di) (void)hipFree(c->d_fp_di);
+    if (c->d_pinc) (void)hipFree(c->d_pinc);
     if (c->d_partial) (void)hipFree(c->d_partial);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1258,6 +1261,154 @@ int brov_window_endpoint_se(brov_ctx* c, int model, int integ, int64_t N, int64_
     if (rc) return rc;
     HIPCK(c, d2h_copy(c, se_total, dtot, 8));
     if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+// ---- PINc residual network -------------------------------------------------------------------------------
+int brov_pinc_set_weights(brov_ctx* c, const float* blob, int64_t n) {
+    if (!c || !blob || n != PINC_NPARAMS)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_set_weights: need the 14541 packed fp32 parameters of the 14-64x4-9 network");
+    DeviceGuard g(c);
+    if (!c->d_pinc) HIPCK(c, hipMalloc((void**)&c->d_pinc, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, h2d_copy(c, c->d_pinc, blob, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, hipStreamSynchronize(c->stream));     // the caller's blob may go away on return
+    c->pinc_set = true;
+    return BROV_OK;
+}
+
+static int pinc_ready(brov_ctx* c, const char* who) {
+    if (!c->pinc_set) return fail(c, BROV_ERR_ARG, std::string(who) + ": no PINc weights: call brov_pinc_set_weights first");
+    return BROV_OK;
+}
+
+int brov_pinc_forward_dev(brov_ctx* c, int64_t B, const float* d_z, float* d_x_next) {
+    if (!c || B < 0 || (B && (!d_z || !d_x_next))) return fail(c, BROV_ERR_ARG, "brov_pinc_forward_dev: bad argument");
+    int rc = pinc_ready(c, "brov_pinc_forward_dev");
+    if (rc || B == 0) return rc;
+    DeviceGuard g(c);
+    CallTimer t(c);
+    HIPCK(c, launch_pinc_forward(c->stream, c->d_pinc, B, d_z, d_x_next));
+    return BROV_OK;
+}
+
+int brov_pinc_rollout_dev(brov_ctx* c, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U, double* d_lag_io,
+                          double* d_traj, int64_t stride, double* d_xT) {
+    if (!c || B < 0 || T < 0 || (B && (!d_x0 || (T && !d_U))) || (d_traj && stride < 1))
+        return fail(c, BROV_ERR_ARG, "brov_pinc_rollout_dev: bad argument");
+    int rc = pinc_ready(c, "brov_pinc_rollout_dev");
+    if (rc || B == 0) return rc;
+    DeviceGuard g(c);
+    const DevParams* dp;
+    rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
+    CallTimer t(c);
+    HIPCK(c, launch_pinc_rollout(c->stream, c->d_pinc, *dp, B, T, dt, d_x0, d_U, d_lag_io, d_traj, d_traj ? stride : 1, d_xT));
+    return BROV_OK;
+}
+
+int brov_pinc_rollout(brov_ctx* c, int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag_io,
+                      double* traj, int64_t stride, double* xT) {
+    if (!c || B < 0 || T < 0 || (B && (!x0 || (T && !U))) || (traj && stride < 1))
+        return fail(c, BROV_ERR_ARG, "brov_pinc_rollout: bad argument");
+    int rc = pinc_ready(c, "brov_pinc_rollout");
+    if (rc || B == 0) return rc;
+    DeviceGuard g(c);
+    const int64_t rows = traj ? T / stride + 1 : 0;
+    Arena a(c);
+    rc = a.reserve(Arena::al(B * 12 * 8) * 2 + Arena::al((size_t)B * T * 8 * 8) + Arena::al(B * 24 * 8) + Arena::al((size_t)B * rows * 12 * 8));
+    if (rc) return rc;
+    double* dx0 = a.take<double>(B * 12);
+    double* dU = a.take<double>((size_t)B * T * 8);
+    double* dxT = a.take<double>(B * 12);
+    double* dl = lag_io ? a.take<double>(B * 24) : nullptr;
+    double* dtr = traj ? a.take<double>((size_t)B * rows * 12) : nullptr;
+    HIPCK(c, h2d_copy(c, dx0, x0, B * 12 * 8));
+    if (T) HIPCK(c, h2d_copy(c, dU, U, (size_t)B * T * 8 * 8));
+    if (lag_io) HIPCK(c, h2d_copy(c, dl, lag_io, B * 24 * 8));
+    rc = brov_pinc_rollout_dev(c, B, T, dt, dx0, dU, dl, dtr, stride, dxT);
+    if (rc) return rc;
+    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, B * 12 * 8));
+    if (lag_io) HIPCK(c, d2h_copy(c, lag_io, dl, B * 24 * 8));
+    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, (size_t)B * rows * 12 * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+static size_t pinc_window_scratch(int64_t nwin) {
+    const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
+    return Arena::al(nwin * 24 * 8) + Arena::al((nwin + nchunks) * 24 * 8) + Arena::al(32 * 8);
+}
+
+static int pinc_window_impl(brov_ctx* c, int64_t N, int64_t H, double dt, const double* dX, const double* dU, int carry,
+                            double* d_lag_io, double* d_lag_starts, double* d_total, double* d_se, Arena& a) {
+    const DevParams* dp;
+    int rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
+    const int64_t nwin = N - H;
+    double *d_resp = nullptr, *d_start = nullptr, *d_phi = nullptr;
+    if (carry) {
+        const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
+        d_resp = a.take<double>(nwin * 24);
+        d_start = a.take<double>((nwin + nchunks) * 24);     // start states + chunk states
+        d_phi = a.take<double>(32);
+        double Phi[18];                                       // Phi = Ad^H (one lag sample per step), Phi^chunk
+        lag_window_phi(*dp, H, Phi);
+        lag_window_phi(*dp, H * window_scan_chunk(), Phi + 9);
+        HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
+        HIPCK(c, hipStreamSynchronize(c->stream));            // Phi is a stack temporary
+    }
+    CallTimer t(c);
+    HIPCK(c, launch_pinc_window_endpoint(c->stream, c->d_pinc, *dp, N, H, dt, dX, dU, carry, d_phi, d_resp, d_start, d_lag_io,
+                                         d_lag_starts, d_se, d_total));
+    return BROV_OK;
+}
+
+int brov_pinc_window_endpoint_se_dev(brov_ctx* c, int64_t N, int64_t H, double dt, const double* d_X, const double* d_U, int carry_lag,
+                                     double* d_lag_io, double* d_se_total, double* d_per_window, double* d_lag_starts) {
+    if (!c || N < 0 || H < 0 || !d_se_total) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se_dev: bad argument");
+    int rc = pinc_ready(c, "brov_pinc_window_endpoint_se_dev");
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const int64_t nwin = N - H;
+    if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
+    if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se_dev: NULL array");
+    Arena a(c);
+    rc = a.reserve(pinc_window_scratch(nwin));
+    if (rc) return rc;
+    return pinc_window_impl(c, N, H, dt, d_X, d_U, carry_lag, d_lag_io, d_lag_starts, d_se_total, d_per_window, a);
+}
+
+int brov_pinc_window_endpoint_se(brov_ctx* c, int64_t N, int64_t H, double dt, const double* X, const double* U, int carry_lag,
+                                 double* lag_io, double* se_total, double* per_window, double* lag_starts) {
+    if (!c || N < 0 || H < 0 || !se_total) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se: bad argument");
+    int rc = pinc_ready(c, "brov_pinc_window_endpoint_se");
+    if (rc) return rc;
+    const int64_t nwin = N - H;
+    if (nwin <= 0) { *se_total = 0.0; return BROV_OK; }
+    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se: NULL array");
+    DeviceGuard g(c);
+    const bool starts = lag_starts && carry_lag;
+    Arena a(c);
+    rc = a.reserve(Arena::al(N * 12 * 8) + Arena::al(N * 8 * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) + Arena::al(24 * 8) +
+                   (starts ? Arena::al(nwin * 24 * 8) : 0) + pinc_window_scratch(nwin));
+    if (rc) return rc;
+    double* dX = a.take<double>(N * 12);
+    double* dU = a.take<double>(N * 8);
+    double* dse = a.take<double>(nwin);
+    double* dtot = a.take<double>(8);
+    double* dlag = a.take<double>(24);
+    double* dstarts = starts ? a.take<double>(nwin * 24) : nullptr;
+    HIPCK(c, h2d_copy(c, dX, X, N * 12 * 8));
+    HIPCK(c, h2d_copy(c, dU, U, N * 8 * 8));
+    if (lag_io) HIPCK(c, h2d_copy(c, dlag, lag_io, 24 * 8));
+    else HIPCK(c, hipMemsetAsync(dlag, 0, 24 * 8, c->stream));
+    rc = pinc_window_impl(c, N, H, dt, dX, dU, carry_lag, dlag, dstarts, dtot, dse, a);
+    if (rc) return rc;
+    HIPCK(c, d2h_copy(c, se_total, dtot, 8));
+    if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
+    if (lag_io && carry_lag) HIPCK(c, d2h_copy(c, lag_io, dlag, 24 * 8));
+    if (starts) HIPCK(c, d2h_copy(c, lag_starts, dstarts, nwin * 24 * 8));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BROV_OK;
 }

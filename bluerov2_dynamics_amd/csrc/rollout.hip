@@ -762,43 +762,51 @@ __device__ __forceinline__ void wscan_step(const double P[9], double& x0, double
 }
 
 // phase 1 (store_start = 0): chunk_io[c] <- end state of chunk c from zero;  phase 3 (store_start = 1): start[k] for the
-// chunk's windows, beginning from chunk_io[c]
+// chunk's windows, beginning from chunk_io[c].  NC lag banks of 3 states per window: 6 wrench components (the Fossen evaluator,
+// acceleration space) or 8 thrusters (the PINc evaluator, pinc.hip, thruster space).
+template <int NC>
 __global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, const double* __restrict__ Phi9, const double* __restrict__ resp,
                                                               double* __restrict__ chunk_io, double* __restrict__ start, int store_start) {
+    constexpr int W = NC * 3;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t c = g / 6;
-    const int i = (int)(g - c * 6);
+    const int64_t c = g / NC;
+    const int i = (int)(g - c * NC);
     const int64_t k0 = c * WSCAN_CHUNK;
     if (k0 >= nwin) return;
     double P[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) P[j] = Phi9[j];
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    if (store_start) { x0 = chunk_io[c * 18 + i * 3]; x1 = chunk_io[c * 18 + i * 3 + 1]; x2 = chunk_io[c * 18 + i * 3 + 2]; }
+    if (store_start) { x0 = chunk_io[c * W + i * 3]; x1 = chunk_io[c * W + i * 3 + 1]; x2 = chunk_io[c * W + i * 3 + 2]; }
     const int64_t k1 = k0 + WSCAN_CHUNK < nwin ? k0 + WSCAN_CHUNK : nwin;
     for (int64_t k = k0; k < k1; ++k) {
-        const double* r = resp + k * 18 + i * 3;
-        if (store_start) { double* s = start + k * 18 + i * 3; s[0] = x0; s[1] = x1; s[2] = x2; }
+        const double* r = resp + k * W + i * 3;
+        if (store_start) { double* s = start + k * W + i * 3; s[0] = x0; s[1] = x1; s[2] = x2; }
         wscan_step(P, x0, x1, x2, r[0], r[1], r[2]);
     }
-    if (!store_start) { chunk_io[c * 18 + i * 3] = x0; chunk_io[c * 18 + i * 3 + 1] = x1; chunk_io[c * 18 + i * 3 + 2] = x2; }
+    if (!store_start) { chunk_io[c * W + i * 3] = x0; chunk_io[c * W + i * 3 + 1] = x1; chunk_io[c * W + i * 3 + 2] = x2; }
 }
 
 // phase 2: in place, chunk_io[c] (end-from-zero) -> state at the beginning of chunk c.  PhiC9 = Phi^WSCAN_CHUNK.
-__global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, const double* __restrict__ PhiC9, double* __restrict__ chunk_io) {
-    const int i = threadIdx.x;  // wrench component
-    if (i >= 6) return;
+// s0 [NC][3]: state before the first window (nullptr = zero, a fresh vehicle).
+template <int NC>
+__global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, const double* __restrict__ PhiC9, double* __restrict__ chunk_io,
+                                                             const double* __restrict__ s0) {
+    constexpr int W = NC * 3;
+    const int i = threadIdx.x;  // lag bank
+    if (i >= NC) return;
     double P[9];
 #pragma unroll
     for (int j = 0; j < 9; ++j) P[j] = PhiC9[j];
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    if (s0) { x0 = s0[i * 3]; x1 = s0[i * 3 + 1]; x2 = s0[i * 3 + 2]; }
     double* e = chunk_io + i * 3;
     double b0 = 0, b1 = 0, b2 = 0;
     if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; }
     for (int64_t c = 0; c < nchunks; ++c) {
         const double c0 = b0, c1 = b1, c2 = b2;
-        if (c + 1 < nchunks) { b0 = e[(c + 1) * 18 + 0]; b1 = e[(c + 1) * 18 + 1]; b2 = e[(c + 1) * 18 + 2]; }
-        e[c * 18 + 0] = x0; e[c * 18 + 1] = x1; e[c * 18 + 2] = x2;
+        if (c + 1 < nchunks) { b0 = e[(c + 1) * W + 0]; b1 = e[(c + 1) * W + 1]; b2 = e[(c + 1) * W + 2]; }
+        e[c * W + 0] = x0; e[c * W + 1] = x1; e[c * W + 2] = x2;
         wscan_step(P, x0, x1, x2, c0, c1, c2);
     }
 }
@@ -968,6 +976,28 @@ static hipError_t launch_window_t(hipStream_t st, const FastParams* p, int64_t n
 // scratch: resp [nwin][18], start [nwin][18], phi [9] (device) -- only used for the thruster model with carry_lag
 int window_scan_chunk() { return WSCAN_CHUNK; }
 
+hipError_t launch_window_lag_scan(hipStream_t st, int nc, int64_t nwin, const double* d_phi9, const double* d_resp, double* d_start,
+                                  const double* d_s0) {
+    if (nwin <= 0) return hipSuccess;
+    // d_phi9: [Phi (9) | Phi^WSCAN_CHUNK (9)]; the chunk states live behind the nwin start states in d_start
+    const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
+    double* d_chunk = d_start + nwin * nc * 3;
+    if (nc == 6) {
+        hipLaunchKernelGGL(window_lag_chunk_kernel<6>, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 0);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_scan_kernel<6>, dim3(1), dim3(64), 0, st, nchunks, d_phi9 + 9, d_chunk, d_s0);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_chunk_kernel<6>, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 1);
+    } else {
+        hipLaunchKernelGGL(window_lag_chunk_kernel<8>, dim3(nblk(nchunks * 8, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 0);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_scan_kernel<8>, dim3(1), dim3(64), 0, st, nchunks, d_phi9 + 9, d_chunk, d_s0);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_chunk_kernel<8>, dim3(nblk(nchunks * 8, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 1);
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model, int integ, int64_t N, int64_t H, double dt,
                                   const double* X, const double* U, int carry_lag, const double* d_phi9,
                                   double* d_resp, double* d_start, double* d_se, double* d_total) {
@@ -980,15 +1010,8 @@ hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model
         else
             hipLaunchKernelGGL(window_lag_response_kernel<1>, dim3(nblk(nwin, 256)), dim3(256), 0, st, p, nwin, H, U, d_resp);
         BROV_LAUNCH_CHECK();
-        // d_phi9: [Phi (9) | Phi^WSCAN_CHUNK (9)]; the chunk states live behind the nwin start states in d_start
-        const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
-        double* d_chunk = d_start + nwin * 18;
-        hipLaunchKernelGGL(window_lag_chunk_kernel, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_scan_kernel, dim3(1), dim3(64), 0, st, nchunks, d_phi9 + 9, d_chunk);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_chunk_kernel, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 1);
-        BROV_LAUNCH_CHECK();
+        const hipError_t e = launch_window_lag_scan(st, 6, nwin, d_phi9, d_resp, d_start, nullptr);
+        if (e != hipSuccess) return e;
         lag_start = d_start;
     }
     hipError_t e;

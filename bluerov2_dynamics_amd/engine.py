@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -363,6 +363,52 @@ def window_endpoint_se_dev(model, integrator, X, U, H, dt, se_total, per_window,
     ctx.check(ctx.lib.brov_window_endpoint_se_dev(ctx.h, model, INTEGRATORS[integrator], N, int(H), float(dt), _dptr(X), _dptr(U),
                                                   int(bool(carry_lag)), _dptr(se_total), _dptr(per_window)),
               "brov_window_endpoint_se_dev")
+
+
+# ------------------------------------------------------------------------------------------ PINc network (pinc.py holds the host API)
+def _dptr32(t):
+    """device pointer of a float32 DevArray or of a contiguous fp32 CUDA tensor."""
+    if isinstance(t, DevArray):
+        assert t.dtype == np.float32, "need a float32 DevArray"
+        return t.ptr
+    import torch
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), "need a contiguous fp32 CUDA tensor"
+    return t.data_ptr()
+
+
+def pinc_forward_dev(z, x_next, ctx=None):
+    """PINcNet.forward on device-resident fp32 arrays: z [B,14] -> x_next [B,9].  The ctx must hold the weights
+    (pinc.set_weights / brov_pinc_set_weights)."""
+    ctx = _ctx_of(z, ctx)
+    _bind(z, ctx)
+    B = z.shape[0]
+    assert tuple(z.shape) == (B, 14) and tuple(x_next.shape) == (B, 9)
+    ctx.check(ctx.lib.brov_pinc_forward_dev(ctx.h, B, _dptr32(z), _dptr32(x_next)), "brov_pinc_forward_dev")
+
+
+def pinc_rollout_dev(x0, U, dt, lag=None, traj=None, xT=None, stride=1, ctx=None):
+    """simulate_pinc on device-resident fp64 arrays: x0 [B,12], U [B,T,8], lag [B,8,3] (in place; None = zero, not returned),
+    traj [B,T//stride+1,12] and xT [B,12] written when given."""
+    ctx = _ctx_of(x0, ctx)
+    _bind(x0, ctx)
+    B, T = U.shape[0], U.shape[1]
+    assert tuple(x0.shape) == (B, 12) and U.shape[2] == 8
+    if traj is not None:
+        assert tuple(traj.shape) == (B, T // stride + 1, 12), f"traj shape {tuple(traj.shape)}"
+    ctx.check(ctx.lib.brov_pinc_rollout_dev(ctx.h, B, T, float(dt), _dptr(x0), _dptr(U), _dptr(lag), _dptr(traj), int(stride),
+                                            _dptr(xT)), "brov_pinc_rollout_dev")
+
+
+def pinc_window_endpoint_se_dev(X, U, H, dt, se_total, per_window, lag=None, carry_lag=True, lag_starts=None, ctx=None):
+    """multistep_rmse_endpoint_pinc's sum on device-resident fp64 arrays: X [N,12], U [N,8], se_total [1], per_window [N-H];
+    lag [8,3]: the vehicle's lag before the first window (None = zero), replaced by the lag after the last one when carry_lag;
+    lag_starts [N-H,8,3] optional (carry_lag only)."""
+    ctx = _ctx_of(X, ctx)
+    _bind(X, ctx)
+    N = X.shape[0]
+    ctx.check(ctx.lib.brov_pinc_window_endpoint_se_dev(ctx.h, N, int(H), float(dt), _dptr(X), _dptr(U), int(bool(carry_lag)), _dptr(lag),
+                                                       _dptr(se_total), _dptr(per_window), _dptr(lag_starts)),
+              "brov_pinc_window_endpoint_se_dev")
 
 
 # ------------------------------------------------------------------------------------------ EDMDc

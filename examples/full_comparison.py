@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """The reference's 4-model comparison (training/train_tank_brov2_full_comparison.py: main :894-1048) on the MI355X
-engine, for the rows this engine covers: Koopman EDMDc, Fossen (BlueROV2) and the learned double integrator.
-The PINc row is a PyTorch network of the reference that runs unchanged on PyTorch-ROCm; it is not part of this repo: its
-three RMSEs (from the reference's own multistep_rmse_endpoint_pinc) can be handed in with --pinc-row to complete the table
-and the ranking (tests/golden/cfg5_pinc.npz holds them for the CSV fixture).
+engine: Koopman EDMDc, Fossen (BlueROV2), the learned double integrator and, given the PINc checkpoint (--pinc-ckpt: the
+reference's models/pinc_best.pt or a .npz of its arrays), the PINc residual network's row (bluerov2_dynamics_amd.pinc: one
+thruster-map vehicle for H = 1, 10, 100, as the script's rov_old).  Without a checkpoint the PINc row's three RMSEs can still be
+handed in with --pinc-row to complete the table and the ranking (tests/golden/cfg5_pinc.npz holds them for the CSV fixture).
 
     python examples/full_comparison.py path/to/koopman_dataset_50Hz.csv [--rbfs 500 --gamma 3 --ridge 0.1 --rk4]
+    python examples/full_comparison.py path/to/koopman_dataset_50Hz.csv --pinc-ckpt models/pinc_best.pt
     python examples/full_comparison.py path/to/koopman_dataset_50Hz_with_wrench.csv --variant wrench   # train_tank_brov2_wrench_comp.py
     python examples/full_comparison.py path/to/koopman_dataset_50Hz_with_wrench.csv --variant quat     # train_tank_brov2_wrench_quat.py
 
@@ -27,6 +28,7 @@ from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2             # noqa: E
 from bluerov2_dynamics_amd.fossen.BlueROV2_thrust import BlueROV2 as BlueROV2Wrench          # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2_wrench import BlueROV2 as BlueROV2Quat            # noqa: E402
 from bluerov2_dynamics_amd.Koopman.koopmanEDMDc import KoopmanEDMDc    # noqa: E402
+from bluerov2_dynamics_amd.pinc import PINcWeights, multistep_rmse_endpoint_pinc      # noqa: E402
 
 TRAIN_SPLIT = 0.80
 
@@ -34,12 +36,20 @@ TRAIN_SPLIT = 0.80
 ROWS = ("Koopman", "Fossen (BlueROV2)", "Double Integrator", "PINc (ResDNN)")
 
 
-def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None):
-    """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc_row (the
-    reference network's three RMSEs, computed elsewhere) the table has the reference's four rows and `ranking` [4,3] gives
-    each model's rank per horizon (0 = best), training/train_tank_brov2_full_comparison.py:996-1001.
+def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None,
+            pinc=None):
+    """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc (the PINc network's
+    weights: a PINcWeights, a .npz / .pt path, a state dict or the reference's PINcNet; thruster variant only) or pinc_row (its
+    three RMSEs, computed elsewhere) the table has the reference's four rows and `ranking` [4,3] gives each model's rank per
+    horizon (0 = best), training/train_tank_brov2_full_comparison.py:996-1001.
     variant: "thruster" (8 PWM inputs, Euler angles), "wrench" (6-D body wrench, Euler angles), "quat" (wrench, quaternion
     state; RK4 exists only for the thruster script in the reference)."""
+    if pinc is not None and pinc_row is not None:
+        raise ValueError("give the PINc network (pinc) or its precomputed row (pinc_row), not both")
+    if pinc is not None and variant != "thruster":
+        raise ValueError("the PINc network takes the thruster commands: variant must be 'thruster'")
+    if pinc is not None:
+        pinc = PINcWeights(pinc)               # before the first device context (a .pt checkpoint imports torch)
     X, U, dt = load_dataset(csv_path, verbose=verbose, variant=variant)
     nx, nu = X.shape[1], U.shape[1]
     make_rov = {"thruster": lambda: BlueROV2(dt=dt), "wrench": BlueROV2Wrench, "quat": BlueROV2Quat}[variant]
@@ -65,7 +75,15 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
             vals.append(fn(H))
             t[f"{name}_H{H}"] = perf_counter() - t0
         rows.append(vals)
-    if pinc_row is not None:
+    if pinc is not None:
+        rov_old = BlueROV2(dt=dt)              # the script's thruster-map vehicle: its lag carries across H = 1, 10, 100 (:947, :992-994)
+        vals = []
+        for H in (1, 10, 100):
+            t0 = perf_counter()
+            vals.append(multistep_rmse_endpoint_pinc(Xte, Ute, H, dt, pinc, rov_old))
+            t[f"PINc_H{H}"] = perf_counter() - t0
+        rows.append(vals)
+    elif pinc_row is not None:
         rows.append([float(v) for v in pinc_row])
     table = np.array(rows)
     if verbose:
@@ -88,5 +106,7 @@ if __name__ == "__main__":
     ap.add_argument("--variant", default="thruster", choices=["thruster", "wrench", "quat"])
     ap.add_argument("--pinc-row", type=float, nargs=3, default=None, metavar=("RMSE1", "RMSE10", "RMSE100"),
                     help="the reference PINc network's endpoint RMSEs on the same test split (completes the table)")
+    ap.add_argument("--pinc-ckpt", default=None, metavar="PATH",
+                    help="PINc checkpoint (.pt state dict or .npz of its arrays): computes the fourth row on the engine")
     a = ap.parse_args()
-    compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row)
+    compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt)

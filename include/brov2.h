@@ -190,6 +190,37 @@ BROV_API int brov_window_endpoint_se_dev(brov_ctx* ctx, int model, int integrato
                                 const double* d_X, const double* d_U, int carry_lag,
                                 double* d_se_total, double* d_per_window /* [N-H], required */);
 
+/* ---- PINc residual network (inference) ----------------------------------------------------
+ * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
+ * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.
+ * x9 = [x y z cos(psi) sin(psi) u v w r]; u4 = tau[0,1,2,5] of the thruster map (compute_thruster_forces, fp64, stateful lag
+ * [8][3] as in brov_thruster_forces, discretised at dt), rounded to fp32 with the rest of z.  12-D states follow
+ * dataset12_to_9 / state9_to_12 (:612-646): phi, theta, p, q of a predicted state are 0, psi = atan2(sin, cos). */
+/* The packed parameters: n = 14541 fp32 values in state-dict order (net.0.weight [64][14], net.0.bias, net.1.beta,
+ * net.2.weight, net.2.bias, net.3.weight ... net.12.weight [9][64], net.12.bias), i.e. the checkpoint the script loads at
+ * :948-952.  Copied to the device; every other brov_pinc_* call fails (BROV_ERR_ARG) until this one has succeeded. */
+BROV_API int brov_pinc_set_weights(brov_ctx* ctx, const float* blob, int64_t n);
+/* PINcNet.forward (:695-721): d_z [B][14] fp32 -> d_x_next [B][9] fp32. */
+BROV_API int brov_pinc_forward_dev(brov_ctx* ctx, int64_t B, const float* d_z, float* d_x_next);
+/* simulate_pinc (:838-863) for B trajectories: x0 [B][12], U [B][T][8]; lag_io [B][8][3] is each trajectory's map vehicle
+ * (advanced in place; NULL = zero lag, not returned); traj [B][T/traj_stride+1][12] (row 0 = x0 unchanged; NULL = not stored),
+ * xT [B][12] (optional). */
+BROV_API int brov_pinc_rollout(brov_ctx* ctx, int64_t B, int64_t T, double dt, const double* x0, const double* U,
+                      double* lag_io, double* traj, int64_t traj_stride, double* xT);
+BROV_API int brov_pinc_rollout_dev(brov_ctx* ctx, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U,
+                          double* d_lag_io, double* d_traj, int64_t traj_stride, double* d_xT);
+/* multistep_rmse_endpoint_pinc (:866-890): windows k = 0..N-H-1 as in brov_window_endpoint_se, X [N][12], U [N][8].
+ * lag_io [8][3] is the map vehicle's lag before the first window (NULL = zero).  carry_lag=1 is the reference: one vehicle serves
+ * every window, window k starts from the lag window k-1 left, and lag_io receives the lag after the last window (the vehicle
+ * carries it into the next call).  carry_lag=0: every window starts from lag_io, which is left unchanged.
+ * se_total = sum_k |x_end - X[k+H]|^2 (12-D, fp64); per_window [N-H] and lag_starts [N-H][8][3] (each window's initial lag,
+ * carry_lag=1 only) optional (NULL); the _dev form requires d_per_window. */
+BROV_API int brov_pinc_window_endpoint_se(brov_ctx* ctx, int64_t N, int64_t H, double dt, const double* X, const double* U,
+                                 int carry_lag, double* lag_io, double* se_total, double* per_window, double* lag_starts);
+BROV_API int brov_pinc_window_endpoint_se_dev(brov_ctx* ctx, int64_t N, int64_t H, double dt, const double* d_X, const double* d_U,
+                                     int carry_lag, double* d_lag_io, double* d_se_total, double* d_per_window,
+                                     double* d_lag_starts);
+
 /* Synthetic control sequences on device (benchmarks):
  * counter-based splitmix64 stream, value for (trajectory b0+b, step t, channel j) independent
  * of layout and of how trajectories are sharded.  scale[nu] multiplies each channel (NULL = 1). */

@@ -22,6 +22,7 @@ Fixtures (all float64):
   cfg5w_dataset.csv.gz + cfg5w.npz  the same recording with wrench inputs through the wrench_comp / wrench_quat scripts' functions
   cfg5_dataset.csv.gz + cfg5.npz   script-level run (loader, split, Koopman / Fossen / DI RMSE table)
   cfg5_pinc.npz         the fourth row of that table: the reference's PINc evaluator with the shipped checkpoint (fixture only)
+  pinc_weights.npz + pinc_kat.npz  the shipped PINc checkpoint's arrays; forward / simulate_pinc / evaluator-sequence vectors
 """
 import argparse
 import os
@@ -483,6 +484,68 @@ def gen_cfg5_pinc():
     print("PINc row", row, f"({time.time() - t0:.1f} s); table of the other rows:\n", g["table"])
 
 
+def gen_pinc():
+    """PINc inference fixtures (training/train_tank_brov2_full_comparison.py:601-721, 838-890) from the shipped checkpoint
+    (models/pinc_best.pt), reference code unmodified, CPU:
+      pinc_weights.npz  the checkpoint's 22 state-dict arrays (fp32; data the reference's own code reads)
+      pinc_kat.npz      z rows -> PINcNet.forward(z) (cfg5 rows and scaled rows that cross softplus's threshold 20);
+                        the 500-step simulate_pinc from X[1000] under U[1000:1500] with a fresh vehicle, and its lag afterwards;
+                        the evaluator sequence H = 1, 10, 100 on cfg5's test split with ONE map vehicle (per-window endpoints,
+                        the lag before each horizon and after the last)."""
+    import torch
+    import train_tank_brov2_full_comparison as ref
+    g = np.load(os.path.join(OUT, "cfg5.npz"))
+    X, U, dt, split = g["X"], g["U"], float(g["dt"]), int(g["split"])
+    device = torch.device("cpu")
+    sd = torch.load(os.path.join(REF, "models", "pinc_best.pt"), map_location=device)
+    np.savez(os.path.join(OUT, "pinc_weights.npz"), **{k: v.detach().cpu().numpy().astype(np.float32) for k, v in sd.items()})
+    net = ref.PINcNet(hidden_sizes=ref.PINc_HIDDEN).to(device)
+    net.load_state_dict(sd)
+    net.eval()
+
+    def lag_of(rov):
+        return np.array([l._x.copy() for l in rov.thruster_lags], dtype=float)
+
+    # forward KAT: z built as simulate_pinc builds it, from the recording (x9 of X[k], u4 from one map vehicle), then scaled rows
+    rov = RefThruster(dt=dt)
+    rows = []
+    for k in range(0, 2000, 3):
+        u4 = ref.thrusters_to_body_wrenches(U[k], dt, rov)
+        rows.append(np.hstack([ref.dataset12_to_9(X[k]), u4, [dt]]))
+    z = np.array(rows)
+    rng = np.random.default_rng(20251016)
+    zs = z[rng.integers(0, len(z), 333)] * rng.uniform(2.0, 60.0, (333, 1))
+    z = np.vstack([z, zs]).astype(np.float32)
+    with torch.no_grad():
+        zt = torch.from_numpy(z)
+        y = net(zt).numpy()
+        pre = net.net[0](zt) * net.net[1].beta
+    n_thr = int((pre > 20).any(dim=1).sum())
+
+    # one 500-step rollout with a fresh vehicle
+    rov = RefThruster(dt=dt)
+    traj = ref.simulate_pinc(X[1000], U[1000:1500], dt, net, rov, device)
+    lag500 = lag_of(rov)
+
+    # the script's evaluator sequence with one map vehicle
+    Xte, Ute = X[split:], U[split:]
+    rov = RefThruster(dt=dt)
+    out = {}
+    rmse = []
+    for H in (1, 10, 100):
+        out[f"lag_before_H{H}"] = lag_of(rov)
+        ends = np.array([ref.simulate_pinc(Xte[k], Ute[k:k + H], dt, net, rov, device)[-1] for k in range(len(Xte) - H)])
+        err = ends - Xte[H:]
+        rmse.append(float(np.sqrt(np.sum(err * err) / (err.shape[0] * 12))))
+        if H == 10:
+            out["endpoints_H10"] = ends
+    out["lag_after_seq"] = lag_of(rov)
+    np.savez_compressed(os.path.join(OUT, "pinc_kat.npz"), z=z, x_next=y.astype(np.float32), n_threshold_rows=np.int64(n_thr),
+                        traj500=traj, lag500=lag500, start500=np.int64(1000), rmse_seq=np.array(rmse), dt=np.float64(dt),
+                        torch_version=np.array([torch.__version__]), versions=versions(), **out)
+    print("PINc rmse sequence", rmse, "rows crossing the softplus threshold:", n_thr)
+
+
 def gen_torchrhs():
     """fossen/bluerov_torch.py: bluerov_compute and ssa on random batches (float64 and float32)."""
     import torch
@@ -600,7 +663,7 @@ def gen_kmeans_empty():
     np.savez_compressed(os.path.join(OUT, "kmeans_empty.npz"), versions=versions(), **out)
 
 
-GENS = dict(edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
+GENS = dict(pinc=gen_pinc, edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
