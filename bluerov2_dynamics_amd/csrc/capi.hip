@@ -1389,18 +1389,19 @@ int brov_pinc_window_endpoint_se(brov_ctx* c, int64_t N, int64_t H, double dt, c
     if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se: NULL array");
     DeviceGuard g(c);
     const bool starts = lag_starts && carry_lag;
+    const int64_t nu_rows = H > 0 ? N - 1 : 0;             // window k reads U[k .. k+H-1]: the caller's U may end at row N-2
     Arena a(c);
-    rc = a.reserve(Arena::al(N * 12 * 8) + Arena::al(N * 8 * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) + Arena::al(24 * 8) +
+    rc = a.reserve(Arena::al(N * 12 * 8) + Arena::al(nu_rows * 8 * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) + Arena::al(24 * 8) +
                    (starts ? Arena::al(nwin * 24 * 8) : 0) + pinc_window_scratch(nwin));
     if (rc) return rc;
     double* dX = a.take<double>(N * 12);
-    double* dU = a.take<double>(N * 8);
+    double* dU = a.take<double>(nu_rows * 8);
     double* dse = a.take<double>(nwin);
     double* dtot = a.take<double>(8);
     double* dlag = a.take<double>(24);
     double* dstarts = starts ? a.take<double>(nwin * 24) : nullptr;
     HIPCK(c, h2d_copy(c, dX, X, N * 12 * 8));
-    HIPCK(c, h2d_copy(c, dU, U, N * 8 * 8));
+    if (nu_rows) HIPCK(c, h2d_copy(c, dU, U, nu_rows * 8 * 8));
     if (lag_io) HIPCK(c, h2d_copy(c, dlag, lag_io, 24 * 8));
     else HIPCK(c, hipMemsetAsync(dlag, 0, 24 * 8, c->stream));
     rc = pinc_window_impl(c, N, H, dt, dX, dU, carry_lag, dlag, dstarts, dtot, dse, a);

@@ -150,14 +150,15 @@ class PINc:
         return dict(traj=traj, xT=xT, lag=lag_io)
 
     def window_endpoint_se(self, X, U, H, dt, lag=None, carry_lag=True, want_lag_starts=False):
-        """Sum of the squared 12-D endpoint errors over the windows k = 0..N-H-1.  lag [8,3]: the map vehicle's lag before the first
-        window (None = zero).  Returns dict(se, per_window [N-H], lag [8,3] after the last window (carry_lag) or the given one,
+        """Sum of the squared 12-D endpoint errors over the windows k = 0..N-H-1 (X [N,12], U [>= N-1, 8]).  lag [8,3]: the map
+        vehicle's lag before the first window (None = zero).  Returns dict(se, per_window [N-H], lag [8,3] after the last window (carry_lag) or the given one,
         lag_starts [N-H,8,3] (want_lag_starts and carry_lag, else None))."""
         ctx = self._ready()
         X = _lib.as_f64(X).reshape(-1, 12)
         U = _lib.as_f64(U).reshape(-1, 8)
         N, H = X.shape[0], int(H)
-        assert U.shape[0] >= N, "U must be aligned with X"
+        # window k reads U[k .. k+H-1], so rows up to N-2: the reference accepts len(U) == len(X) - 1
+        assert U.shape[0] >= (N - 1 if H > 0 else 0), "U must be aligned with X (at least len(X) - 1 rows)"
         nwin = max(N - H, 0)
         lag_io = np.zeros((8, 3)) if lag is None else _lib.as_f64(lag).reshape(8, 3).copy()
         per = np.zeros(nwin)

@@ -209,7 +209,8 @@ BROV_API int brov_pinc_rollout(brov_ctx* ctx, int64_t B, int64_t T, double dt, c
                       double* lag_io, double* traj, int64_t traj_stride, double* xT);
 BROV_API int brov_pinc_rollout_dev(brov_ctx* ctx, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U,
                           double* d_lag_io, double* d_traj, int64_t traj_stride, double* d_xT);
-/* multistep_rmse_endpoint_pinc (:866-890): windows k = 0..N-H-1 as in brov_window_endpoint_se, X [N][12], U [N][8].
+/* multistep_rmse_endpoint_pinc (:866-890): windows k = 0..N-H-1 as in brov_window_endpoint_se, X [N][12], U [N-1][8] (window k reads
+ * U[k .. k+H-1], so rows up to N-2 only; no row of U is read when H = 0).
  * lag_io [8][3] is the map vehicle's lag before the first window (NULL = zero).  carry_lag=1 is the reference: one vehicle serves
  * every window, window k starts from the lag window k-1 left, and lag_io receives the lag after the last window (the vehicle
  * carries it into the next call).  carry_lag=0: every window starts from lag_io, which is left unchanged.

@@ -82,6 +82,14 @@ def discretise_lag(dt):
     return Ad, Bd
 
 
+def thrust_poly(u):
+    """The command-to-thrust polynomial of thruster_forces (before the lag), elementwise."""
+    u = _c(u)
+    F = np.empty_like(u)
+    lib().orc_thrust_poly(ctypes.c_long(u.size), _p(u), _p(F))
+    return F
+
+
 def rhs(model, x, u, dt=0.02, lag=None, current=None):
     """Batched dynamics(); returns (xdot, lag_after)."""
     x = _c(x).reshape(-1, NX[model])

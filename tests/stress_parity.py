@@ -3,14 +3,14 @@
 strides, bag structures and chunk sizes through the C ABI against the oracle.  Prints the worst relative error per family
 and exits non-zero on the first violation.
 
-    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp]
+    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp,pinc]
 
 Lives under tests/ because it checks against oracle/ (test infrastructure); tests/test_gpu_parity.py runs a short sweep."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 from bluerov2_dynamics_amd import _lib, engine
-from oracle import fossen_c, edmdc_numpy as ek
+from oracle import fossen_c, edmdc_numpy as ek, pinc_numpy
 
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 40.0
 rng = np.random.default_rng(int(sys.argv[2]) if len(sys.argv) > 2 else 0)
@@ -358,8 +358,87 @@ def lloyds_list():
         LIST_FORM = False
 
 
+def pinc():
+    """PINc forward / rollouts / windowed evaluator (oracle/pinc_numpy.py) with the checkpoint and the random weight sets of
+    tests/golden/pinc_rand_kat.npz; sizes across the 2048-wave grid-stride cap.  Bound: 4x (forward) or 8x (multi-step) the oracle's
+    own fp32-vs-fp64 error + 5e-6 (mixed error), the lag 1e-12 (as tests/test_pinc_parity_gpu.py)."""
+    from bluerov2_dynamics_amd.pinc import KEYS, PINc
+    gd = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    g = np.load(os.path.join(gd, "pinc_weights.npz"))
+    r = np.load(os.path.join(gd, "pinc_rand_kat.npz"))
+    c5 = np.load(os.path.join(gd, "cfg5.npz"))
+    X5, U5 = c5["X"], c5["U"]
+    sets = [({k: g[k] for k in g.files}, np.load(os.path.join(gd, "pinc_kat.npz"))["z"])]
+    sets += [({k: r[f"w{s}_{k}"] for k in KEYS}, r[f"z{s}"]) for s in range(3)]
+    nets = [PINc(sd) for sd, _ in sets]
+
+    def mixed(a, b):
+        return float(np.max(np.abs(a - b) / np.maximum(1.0, np.abs(b)))) if np.size(b) else 0.0
+
+    worst = dict(forward=0.0, rollout=0.0, windows=0.0, lag=0.0)
+    n, t0 = 0, time.time()
+    while time.time() - t0 < budget:
+        i = int(rng.integers(0, len(sets)))
+        sd, pool = sets[i]
+        dt = float(rng.choice([0.02, 0.05]))
+        kind = str(rng.choice(["forward", "rollout", "windows"]))
+        if kind == "forward":
+            B = int(rng.choice([0, 1, 63, 64, 65, 2047, 2048, 2049, 4097, 6000]))
+            z = pool[rng.integers(0, len(pool), B)]
+            got = nets[i].forward(z)
+            o64, o32 = pinc_numpy.forward(sd, z), pinc_numpy.forward(sd, z, fp32=True)
+            e, tol = mixed(got, o64), 4 * mixed(o32, o64) + 5e-6
+            assert got.shape == (B, 9) and e <= tol, ("pinc forward", i, B, e, tol)
+        elif kind == "rollout":
+            B = int(rng.choice([1, 2, 63, 64, 65, 2047, 2048, 2049, 3000]))
+            T = int(rng.choice([0, 1, 2, 3, 7, 16]))
+            stride = int(rng.choice([1, 2, 3, max(T, 1), T + 1]))
+            x0 = X5[rng.integers(0, len(X5), B)]
+            U = rng.uniform(-1, 1, (B, T, 8))
+            lag = rng.normal(0, 0.5, (B, 8, 3)) if rng.random() < 0.5 else None
+            store = bool(rng.random() < 0.8)
+            ks = np.unique(np.concatenate([[0, B - 1], rng.integers(0, B, 16), [k for k in (2047, 2048) if k < B]]).astype(np.int64))
+            got = nets[i].rollout(x0, U, dt, lag=lag, stride=stride, store=store)
+            lk = None if lag is None else lag[ks]
+            o64 = pinc_numpy.rollout(sd, x0[ks], U[ks], dt, lag=lk, stride=stride, store=store)
+            o32 = pinc_numpy.rollout(sd, x0[ks], U[ks], dt, lag=lk, stride=stride, store=store, fp32=True)
+            a, b, c = (got["traj"][ks], o64["traj"], o32["traj"]) if store else (got["xT"][ks], o64["xT"], o32["xT"])
+            e, tol = mixed(a, b), 8 * mixed(c, b) + 5e-6
+            el = mixed(got["lag"][ks], o64["lag"])
+            assert e <= tol and el < 1e-12, ("pinc rollout", i, B, T, stride, store, e, tol, el)
+            worst["lag"] = max(worst["lag"], el)
+        else:
+            nwin = int(rng.choice([1, 2, 63, 64, 65, 129, 2047, 2048, 2049, 3100]))
+            H = int(rng.choice([0, 1, 2, 5, 12]))
+            carry = bool(rng.random() < 0.7)
+            N = nwin + H
+            off = int(rng.integers(0, len(X5)))
+            idx = (off + np.arange(N)) % len(X5)
+            X, U = X5[idx] + (np.arange(N) // len(X5))[:, None] * 0.3, U5[idx]
+            Ug = U[:N - 1] if (H and rng.random() < 0.3) else U           # the reference's len(U) == len(X) - 1
+            s0 = rng.normal(0, 0.5, (8, 3)) if rng.random() < 0.7 else None
+            got = nets[i].window_endpoint_se(X, Ug, H, dt, lag=s0, carry_lag=carry, want_lag_starts=True)
+            ks = np.unique(np.concatenate([[0, nwin - 1], rng.integers(0, nwin, 12), [k for k in (2047, 2048) if k < nwin]]).astype(np.int64))
+            o = pinc_numpy.window_endpoint_se(sd, X, U, H, dt, lag=s0, carry_lag=carry, windows=ks)
+            l0 = o["lag_starts"][ks] if carry else (None if s0 is None else np.broadcast_to(s0, (len(ks), 8, 3)))
+            x32 = pinc_numpy.rollout(sd, X[ks], U[ks[:, None] + np.arange(H)[None, :]], dt, lag=l0, store=False, fp32=True)["xT"]
+            tol = np.sqrt(12) * (8 * mixed(x32, o["x_end"]) + 5e-6)
+            d = np.abs(np.sqrt(got["per_window"][ks]) - np.sqrt(o["per_window"])) / np.maximum(1.0, np.linalg.norm(o["x_end"], axis=1))
+            e = float(d.max())
+            el = mixed(got["lag"], o["lag"])
+            if carry:
+                el = max(el, mixed(got["lag_starts"], o["lag_starts"]))
+            tot = float(got["per_window"].sum())
+            assert e <= tol and el < 1e-12 and abs(got["se"] - tot) <= 1e-12 * max(tot, 1e-300), \
+                ("pinc windows", i, nwin, H, carry, e, tol, el)
+            worst["lag"] = max(worst["lag"], el)
+        worst[kind] = max(worst[kind], e)
+        n += 1
+    print(f"pinc       : {n} cases, worst mixed err " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()), flush=True)
+
+
 if __name__ == "__main__":
-    fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp)
+    fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp, pinc=pinc)
     for name in (sys.argv[3].split(",") if len(sys.argv) > 3 else list(fams)):
         fams[name]()
     print("stress parity: ok")

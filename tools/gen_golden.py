@@ -23,6 +23,8 @@ Fixtures (all float64):
   cfg5_dataset.csv.gz + cfg5.npz   script-level run (loader, split, Koopman / Fossen / DI RMSE table)
   cfg5_pinc.npz         the fourth row of that table: the reference's PINc evaluator with the shipped checkpoint (fixture only)
   pinc_weights.npz + pinc_kat.npz  the shipped PINc checkpoint's arrays; forward / simulate_pinc / evaluator-sequence vectors
+  pinc_rand_kat.npz     PINcNet.forward in fp32 and fp64 with three seeded random weight sets (beta 8 / 0.05 / -0.5, LayerNorm
+                        variance ~ eps, cos/sin at the renormalisation clamp)
 """
 import argparse
 import os
@@ -546,6 +548,71 @@ def gen_pinc():
     print("PINc rmse sequence", rmse, "rows crossing the softplus threshold:", n_thr)
 
 
+def gen_pinc_random():
+    """PINcNet.forward (training/train_tank_brov2_full_comparison.py:648-721, reference code unmodified, CPU) with three seeded
+    random weight sets that reach what the shipped checkpoint does not, in torch fp32 and in torch fp64 (net.double()):
+      set 0  beta = 8 (layer 0: pre-activations past softplus's threshold in beta*a but not in a) and beta = 0.05 (layer 1: a past
+             20 while beta*a stays below it)
+      set 1  beta = -0.5 (layer 0) and layer 2 scaled so that LayerNorm's input variance is ~ eps = 1e-5
+      set 2  output rows 3 / 4 zero and their bias placed a few fp32 ulps from -(cos, sin) of a third of the rows: |(cos, sin)|
+             below the 1e-6 clamp
+    pinc_rand_kat.npz: w{s}_<key> (fp32 state dict), z{s} [B,14] fp32, y32_{s}, y64_{s}."""
+    import torch
+    import train_tank_brov2_full_comparison as ref
+    from bluerov2_dynamics_amd.pinc import KEYS
+    g = np.load(os.path.join(OUT, "cfg5.npz"))
+    X, U, dt = g["X"], g["U"], float(g["dt"])
+    rov = RefThruster(dt=dt)
+    zc = np.array([np.hstack([ref.dataset12_to_9(X[k]), ref.thrusters_to_body_wrenches(U[k], dt, rov), [dt]]) for k in range(0, 1500, 5)])
+    out = {}
+    for s in range(3):
+        torch.manual_seed(100 + s)
+        rng = np.random.default_rng(200 + s)
+        net = ref.PINcNet(hidden_sizes=ref.PINc_HIDDEN)
+        z = zc[rng.permutation(len(zc))[:200]].copy()
+        z[100:] *= rng.uniform(0.5, 4.0, (100, 1))                   # rows further from the recording
+        z = z.astype(np.float32)
+        with torch.no_grad():
+            for p in net.parameters():                               # LayerNorm affine away from (1, 0)
+                if p.dim() == 1 and p.shape[0] == 64:
+                    p.add_(torch.randn_like(p) * 0.3)
+            if s == 0:
+                net.net[0].weight.mul_(12.0)
+                net.net[1].beta.fill_(8.0)
+                net.net[3].weight.mul_(6.0)
+                net.net[3].bias.mul_(30.0)
+                net.net[4].beta.fill_(0.05)
+            elif s == 1:
+                net.net[0].weight.mul_(20.0)
+                net.net[1].beta.fill_(-0.5)
+                zt = torch.from_numpy(z)
+                for _ in range(3):                                   # the LayerNorm input of layer 2 is net.net[:8](z)
+                    var = net.net[:8](zt).var(dim=1, unbiased=False).median()
+                    f = float(torch.sqrt(1e-5 / var))
+                    net.net[6].weight.mul_(f)
+                    net.net[6].bias.mul_(f)
+                net.net[7].beta.fill_(1.7)
+            else:
+                c0, s0 = z[:70, 3].copy(), z[:70, 4].copy()
+                z[:70, 3], z[:70, 4] = c0[0], s0[0]                  # one heading for the clamped rows
+                net.net[12].weight[3:5].zero_()
+                ulp = np.spacing(np.abs(np.float32(c0[0]))), np.spacing(np.abs(np.float32(s0[0])))
+                net.net[12].bias[3] = float(-np.float32(c0[0]) + np.float32(3) * ulp[0])
+                net.net[12].bias[4] = float(-np.float32(s0[0]) - np.float32(2) * ulp[1])
+            y32 = net(torch.from_numpy(z)).numpy()
+            y64 = net.double()(torch.from_numpy(z).double()).numpy()
+        sd = {k: v.detach().float().numpy() for k, v in net.state_dict().items()}
+        assert list(sd) == list(KEYS)
+        out.update({f"w{s}_{k}": v for k, v in sd.items()})
+        out.update({f"z{s}": z, f"y32_{s}": y32.astype(np.float32), f"y64_{s}": y64})
+        if s == 1:
+            v = net.net[:8](torch.from_numpy(z).double()).var(dim=1, unbiased=False)
+            print("set 1: LayerNorm-2 input variance median", float(v.median()), "min", float(v.min()))
+        if s == 2:
+            print("set 2: clamped rows", int((np.hypot(z[:, 3] + sd["net.12.bias"][3], z[:, 4] + sd["net.12.bias"][4]) < 1e-6).sum()))
+    np.savez_compressed(os.path.join(OUT, "pinc_rand_kat.npz"), torch_version=np.array([torch.__version__]), versions=versions(), **out)
+
+
 def gen_torchrhs():
     """fossen/bluerov_torch.py: bluerov_compute and ssa on random batches (float64 and float32)."""
     import torch
@@ -663,7 +730,7 @@ def gen_kmeans_empty():
     np.savez_compressed(os.path.join(OUT, "kmeans_empty.npz"), versions=versions(), **out)
 
 
-GENS = dict(pinc=gen_pinc, edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
+GENS = dict(pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
