@@ -39,6 +39,13 @@ class BrovParams(ctypes.Structure):
     ]
 
 
+class PincHyper(ctypes.Structure):
+    """struct brov_pinc_hyper (include/brov2.h)."""
+    _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("max_norm", ctypes.c_double),
+                ("batch", ctypes.c_int32), ("rollout_steps", ctypes.c_int32), ("use_physics", ctypes.c_int32), ("use_rollout", ctypes.c_int32)]
+
+
 class BrovError(RuntimeError):
     pass
 
@@ -115,6 +122,16 @@ SIGNATURES = {
                                                     c_void_p, c_void_p, c_void_p]),
     "brov_pinc_window_endpoint_se_dev": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p,
                                                         c_void_p, c_void_p, c_void_p]),
+    "brov_pinc_loss_grad_dev": (ctypes.c_int, [c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                               c_void_p, c_void_p]),
+    "brov_pinc_adamw_step_dev": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, i64] + [ctypes.c_double] * 6 + [c_void_p]),
+    "brov_pinc_train_begin": (ctypes.c_int, [c_void_p, c_void_p, i64, ctypes.POINTER(PincHyper)]),
+    "brov_pinc_train_set_state": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, i64]),
+    "brov_pinc_train_epoch_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "brov_pinc_train_get": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(i64)]),
+    "brov_pinc_train_end": (ctypes.c_int, [c_void_p]),
+    "brov_thruster_stream": (ctypes.c_int, [c_void_p, i64, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
+    "brov_thruster_stream_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, ctypes.c_double, c_void_p, c_void_p]),
     "brov_fill_controls_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.c_int,
                                               ctypes.c_uint64, i64, i64, c_void_p, c_void_p]),
     "edmdc_lift": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]),

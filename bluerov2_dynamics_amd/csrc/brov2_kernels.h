@@ -239,4 +239,22 @@ hipError_t launch_pinc_window_endpoint(hipStream_t st, const float* w, const Dev
                                        const double* X, const double* U, int carry_lag, const double* d_phi9, double* d_resp,
                                        double* d_start, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total);
 
+// ---- PINc training (pinc_train.hip) ------------------------------------------------------------
+constexpr int PINC_PART_STRIDE = PINC_NPARAMS + 3;    // one workgroup's partial: the gradient in blob order, then three loss sums
+constexpr int PINC_TRAIN_MAX_K = 16;                  // rollout steps whose activations fit the LDS tape
+struct PincAdam { double lr, beta1, beta2, eps, weight_decay, max_norm; };
+int pinc_grad_parts(int B);                           // partials launch_pinc_grad writes for a minibatch of B rows
+// one minibatch: Z [*][14], Y [*][9], U4 [*][4] fp32, row r of the batch = row perm[r] (perm nullptr: row r); K rollout steps from
+// batch row 0 (0 = none, <= PINC_TRAIN_MAX_K and < B) -> part [pinc_grad_parts(B)][PINC_PART_STRIDE]
+hipError_t launch_pinc_grad(hipStream_t st, const float* w, int B, const float* Z, const float* Y, const float* U4, const int* perm,
+                            int K, int use_physics, float* part);
+// fixed-order sum of the partials -> grad_out [PINC_NPARAMS], loss_out [3] = (mse, physics mean square, rollout), norm_out [1] (each
+// optional); ad != nullptr: clip to ad->max_norm and take AdamW step number `step` (1-based) on w, m, v in place
+hipError_t launch_pinc_reduce(hipStream_t st, int nparts, int stride, const float* part, int B, float* grad_out, float* loss_out,
+                              float* norm_out, const PincAdam* ad, int64_t step, float* w, float* m, float* v);
+// one map vehicle over N consecutive samples U [N][8] -> tau [N][6]; d_lag_io [8][3] in / out; d_phi9 = [Ad | Ad^window_scan_chunk()],
+// d_resp [N][24], d_start [(N + chunks)][24]: scratch of launch_window_lag_scan (nc = 8)
+hipError_t launch_thruster_stream(hipStream_t st, const DevParams& p, int64_t N, const double* U, const double* d_phi9, double* d_resp,
+                                  double* d_start, double* d_lag_io, double* tau);
+
 }  // namespace brov

@@ -45,6 +45,13 @@ struct brov_ctx {
     bool di_set = false;
     float* d_pinc = nullptr;      // packed PINc weights (PINC_NPARAMS fp32, brov_pinc_set_weights)
     bool pinc_set = false;
+    // PINc training: the partials of the gradient kernel (grow-only) and the session of brov_pinc_train_begin
+    float* d_pinc_part = nullptr;
+    int pinc_part_cap = 0;        // partials behind d_pinc_part
+    float* d_train = nullptr;     // [w | m | v], PINC_NPARAMS each
+    bool train_on = false;
+    int64_t train_step = 0;
+    brov_pinc_hyper train_hyper = {};
     // EDMDc
     int btu_staging = 0;
     int single_lane = 0;          // 1: never use the two-wave rollout kernel (A/B measurements: BROV2_ROLLOUT_SINGLE_LANE=1)
@@ -532,6 +539,8 @@ void brov_destroy(brov_ctx* c) {
     if (c->d_fp) (void)hipFree(c->d_fp);
     if (c->d_fp_di) (void)hipFree(c->d_fp_di);
     if (c->d_pinc) (void)hipFree(c->d_pinc);
+    if (c->d_pinc_part) (void)hipFree(c->d_pinc_part);
+    if (c->d_train) (void)hipFree(c->d_train);
     if (c->d_partial) (void)hipFree(c->d_partial);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1410,6 +1419,179 @@ int brov_pinc_window_endpoint_se(brov_ctx* c, int64_t N, int64_t H, double dt, c
     if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
     if (lag_io && carry_lag) HIPCK(c, d2h_copy(c, lag_io, dlag, 24 * 8));
     if (starts) HIPCK(c, d2h_copy(c, lag_starts, dstarts, nwin * 24 * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+// ---- PINc training -----------------------------------------------------------------------------------------
+static int pinc_parts_reserve(brov_ctx* c, int nparts) {
+    if (nparts <= c->pinc_part_cap) return BROV_OK;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (c->d_pinc_part) (void)hipFree(c->d_pinc_part);
+    c->d_pinc_part = nullptr;
+    c->pinc_part_cap = 0;
+    HIPCK(c, hipMalloc((void**)&c->d_pinc_part, (size_t)nparts * PINC_PART_STRIDE * sizeof(float)));
+    c->pinc_part_cap = nparts;
+    return BROV_OK;
+}
+
+static bool adam_args_ok(double lr, double b1, double b2, double eps, double wd, double max_norm) {
+    return lr >= 0.0 && b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0 && eps >= 0.0 && wd >= 0.0 && max_norm > 0.0;
+}
+
+int brov_pinc_loss_grad_dev(brov_ctx* c, const float* d_w, int64_t B, const float* d_z, const float* d_y, const float* d_u4, int K,
+                            int use_physics, float* d_grad, float* d_loss) {
+    if (!c || !d_w || B < 1 || B > ((int64_t)1 << 24) || !d_z || !d_y || (use_physics && !d_u4) || !d_grad || !d_loss)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_loss_grad_dev: bad argument (B must be >= 1)");
+    if (K < 0 || K > PINC_TRAIN_MAX_K || K >= B)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_loss_grad_dev: K must be in 0..16 and below B");
+    DeviceGuard g(c);
+    const int np = pinc_grad_parts((int)B);
+    int rc = pinc_parts_reserve(c, np);
+    if (rc) return rc;
+    CallTimer t(c);
+    HIPCK(c, launch_pinc_grad(c->stream, d_w, (int)B, d_z, d_y, d_u4, nullptr, K, use_physics, c->d_pinc_part));
+    HIPCK(c, launch_pinc_reduce(c->stream, np, PINC_PART_STRIDE, c->d_pinc_part, (int)B, d_grad, d_loss, nullptr, nullptr, 0, nullptr,
+                                nullptr, nullptr));
+    return BROV_OK;
+}
+
+int brov_pinc_adamw_step_dev(brov_ctx* c, float* d_w, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr, double beta1,
+                             double beta2, double eps, double weight_decay, double max_norm, float* d_norm_out) {
+    if (!c || !d_w || !d_m || !d_v || !d_grad || step < 1 || !adam_args_ok(lr, beta1, beta2, eps, weight_decay, max_norm))
+        return fail(c, BROV_ERR_ARG, "brov_pinc_adamw_step_dev: bad argument (step is 1-based, betas in [0, 1), max_norm > 0)");
+    DeviceGuard g(c);
+    const PincAdam ad = {lr, beta1, beta2, eps, weight_decay, max_norm};
+    CallTimer t(c);
+    HIPCK(c, launch_pinc_reduce(c->stream, 1, PINC_NPARAMS, d_grad, 1, nullptr, nullptr, d_norm_out, &ad, step, d_w, d_m, d_v));
+    return BROV_OK;
+}
+
+int brov_pinc_train_begin(brov_ctx* c, const float* blob, int64_t n, const brov_pinc_hyper* h) {
+    if (!c || !blob || n != PINC_NPARAMS || !h)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_train_begin: need the 14541 packed fp32 parameters and the hyper-parameters");
+    if (!adam_args_ok(h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->max_norm) || h->batch < 1 || h->rollout_steps < 0 ||
+        h->rollout_steps > PINC_TRAIN_MAX_K)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_train_begin: bad hyper-parameter (batch >= 1, rollout_steps in 0..16, betas in [0, 1))");
+    DeviceGuard g(c);
+    c->train_on = false;
+    if (!c->d_train) HIPCK(c, hipMalloc((void**)&c->d_train, 3 * (size_t)PINC_NPARAMS * sizeof(float)));
+    int rc = pinc_parts_reserve(c, pinc_grad_parts(h->batch));
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, c->d_train, blob, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, hipMemsetAsync(c->d_train + PINC_NPARAMS, 0, 2 * (size_t)PINC_NPARAMS * sizeof(float), c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    c->train_hyper = *h;
+    c->train_step = 0;
+    c->train_on = true;
+    return BROV_OK;
+}
+
+int brov_pinc_train_set_state(brov_ctx* c, const float* m, const float* v, int64_t step) {
+    if (!c || !c->train_on) return fail(c, BROV_ERR_ARG, "brov_pinc_train_set_state: no training session: call brov_pinc_train_begin first");
+    if (!m || !v || step < 0) return fail(c, BROV_ERR_ARG, "brov_pinc_train_set_state: bad argument");
+    DeviceGuard g(c);
+    HIPCK(c, h2d_copy(c, c->d_train + PINC_NPARAMS, m, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, h2d_copy(c, c->d_train + 2 * PINC_NPARAMS, v, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    c->train_step = step;
+    return BROV_OK;
+}
+
+int brov_pinc_train_epoch_dev(brov_ctx* c, int64_t N, const float* d_Z, const float* d_Y, const float* d_U4, const int32_t* d_perm,
+                              float* d_loss_log) {
+    if (!c || !c->train_on) return fail(c, BROV_ERR_ARG, "brov_pinc_train_epoch_dev: no training session: call brov_pinc_train_begin first");
+    const brov_pinc_hyper& h = c->train_hyper;
+    if (N < 1 || N > ((int64_t)1 << 30) || !d_Z || !d_Y || (h.use_physics && !d_U4) || !d_perm || !d_loss_log)
+        return fail(c, BROV_ERR_ARG, "brov_pinc_train_epoch_dev: bad argument (N must be >= 1)");
+    DeviceGuard g(c);
+    const PincAdam ad = {h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, h.max_norm};
+    float *w = c->d_train, *m = w + PINC_NPARAMS, *v = m + PINC_NPARAMS;
+    CallTimer t(c);
+    int64_t it = 0;
+    for (int64_t r0 = 0; r0 < N; r0 += h.batch, ++it) {
+        const int B = (int)std::min<int64_t>(h.batch, N - r0);
+        const int K = h.use_rollout ? std::min(h.rollout_steps, B - 1) : 0;
+        HIPCK(c, launch_pinc_grad(c->stream, w, B, d_Z, d_Y, d_U4, d_perm + r0, K, h.use_physics, c->d_pinc_part));
+        HIPCK(c, launch_pinc_reduce(c->stream, pinc_grad_parts(B), PINC_PART_STRIDE, c->d_pinc_part, B, nullptr, d_loss_log + 3 * it,
+                                    nullptr, &ad, c->train_step + 1, w, m, v));
+        ++c->train_step;            // counts the updates queued: a failed launch leaves it at the state on the device
+    }
+    return BROV_OK;
+}
+
+int brov_pinc_train_get(brov_ctx* c, float* blob_out, float* m_out, float* v_out, int64_t* step_out) {
+    if (!c || !c->train_on) return fail(c, BROV_ERR_ARG, "brov_pinc_train_get: no training session: call brov_pinc_train_begin first");
+    DeviceGuard g(c);
+    float* outs[3] = {blob_out, m_out, v_out};
+    for (int i = 0; i < 3; ++i)
+        if (outs[i]) HIPCK(c, d2h_copy(c, outs[i], c->d_train + (size_t)i * PINC_NPARAMS, PINC_NPARAMS * sizeof(float)));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (step_out) *step_out = c->train_step;
+    return BROV_OK;
+}
+
+int brov_pinc_train_end(brov_ctx* c) {
+    if (!c) return BROV_ERR_ARG;
+    if (!c->train_on) return BROV_OK;
+    DeviceGuard g(c);
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    (void)hipFree(c->d_train);
+    c->d_train = nullptr;
+    c->train_on = false;
+    c->train_step = 0;
+    return BROV_OK;
+}
+
+static size_t stream_scratch(int64_t N) {
+    const int64_t nchunks = (N + window_scan_chunk() - 1) / window_scan_chunk();
+    return Arena::al(N * 24 * 8) + Arena::al((N + nchunks) * 24 * 8) + Arena::al(32 * 8);
+}
+
+static int thruster_stream_impl(brov_ctx* c, int64_t N, const double* dU, double dt, double* d_lag_io, double* d_tau, Arena& a) {
+    const DevParams* dp;
+    int rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
+    const int64_t nchunks = (N + window_scan_chunk() - 1) / window_scan_chunk();
+    double* d_resp = a.take<double>(N * 24);
+    double* d_start = a.take<double>((N + nchunks) * 24);
+    double* d_phi = a.take<double>(32);
+    double Phi[18];                                           // Ad (one lag sample per row), Ad^chunk
+    lag_window_phi(*dp, 1, Phi);
+    lag_window_phi(*dp, window_scan_chunk(), Phi + 9);
+    HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
+    HIPCK(c, hipStreamSynchronize(c->stream));                // Phi is a stack temporary
+    CallTimer t(c);
+    HIPCK(c, launch_thruster_stream(c->stream, *dp, N, dU, d_phi, d_resp, d_start, d_lag_io, d_tau));
+    return BROV_OK;
+}
+
+int brov_thruster_stream_dev(brov_ctx* c, int64_t N, const double* d_U, double dt, double* d_lag_io, double* d_tau) {
+    if (!c || N < 0 || (N && (!d_U || !d_lag_io || !d_tau))) return fail(c, BROV_ERR_ARG, "brov_thruster_stream_dev: bad argument");
+    if (N == 0) return BROV_OK;
+    DeviceGuard g(c);
+    Arena a(c);
+    int rc = a.reserve(stream_scratch(N));
+    if (rc) return rc;
+    return thruster_stream_impl(c, N, d_U, dt, d_lag_io, d_tau, a);
+}
+
+int brov_thruster_stream(brov_ctx* c, int64_t N, const double* U, double dt, double* lag_io, double* tau) {
+    if (!c || N < 0 || (N && (!U || !lag_io || !tau))) return fail(c, BROV_ERR_ARG, "brov_thruster_stream: bad argument");
+    if (N == 0) return BROV_OK;
+    DeviceGuard g(c);
+    Arena a(c);
+    int rc = a.reserve(Arena::al(N * 8 * 8) + Arena::al(N * 6 * 8) + Arena::al(24 * 8) + stream_scratch(N));
+    if (rc) return rc;
+    double* dU = a.take<double>(N * 8);
+    double* dtau = a.take<double>(N * 6);
+    double* dlag = a.take<double>(24);
+    HIPCK(c, h2d_copy(c, dU, U, N * 8 * 8));
+    HIPCK(c, h2d_copy(c, dlag, lag_io, 24 * 8));
+    rc = thruster_stream_impl(c, N, dU, dt, dlag, dtau, a);
+    if (rc) return rc;
+    HIPCK(c, d2h_copy(c, tau, dtau, N * 6 * 8));
+    HIPCK(c, d2h_copy(c, lag_io, dlag, 24 * 8));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BROV_OK;
 }

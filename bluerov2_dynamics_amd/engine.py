@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -409,6 +409,40 @@ def pinc_window_endpoint_se_dev(X, U, H, dt, se_total, per_window, lag=None, car
     ctx.check(ctx.lib.brov_pinc_window_endpoint_se_dev(ctx.h, N, int(H), float(dt), _dptr(X), _dptr(U), int(bool(carry_lag)), _dptr(lag),
                                                        _dptr(se_total), _dptr(per_window), _dptr(lag_starts)),
               "brov_pinc_window_endpoint_se_dev")
+
+
+def thruster_stream(U, dt=0.02, lag=None, ctx=None):
+    """compute_thruster_forces of ONE stateful vehicle fed the rows of U [N,8] in order (make_pinc_dataset's loop).
+    Returns (tau [N,6], lag_after [8,3])."""
+    ctx = ctx or default_context()
+    ctx.use_null_stream()
+    U = as_f64(U).reshape(-1, 8)
+    N = U.shape[0]
+    lag_io = np.zeros((8, 3)) if lag is None else as_f64(lag).reshape(8, 3).copy()
+    tau = np.empty((N, 6))
+    ctx.check(ctx.lib.brov_thruster_stream(ctx.h, N, _hptr(U), float(dt), _hptr(lag_io), _hptr(tau)), "brov_thruster_stream")
+    return tau, lag_io
+
+
+def pinc_loss_grad_dev(w, z, y, u4, K, use_physics, grad, loss, ctx=None):
+    """Loss terms and gradient of one minibatch on device-resident fp32 arrays: w [14541], z [B,14], y [B,9], u4 [B,4] ->
+    grad [14541], loss [3] (brov_pinc_loss_grad_dev)."""
+    ctx = _ctx_of(z, ctx)
+    _bind(z, ctx)
+    B = z.shape[0]
+    assert tuple(z.shape) == (B, 14) and tuple(y.shape) == (B, 9) and tuple(u4.shape) == (B, 4)
+    ctx.check(ctx.lib.brov_pinc_loss_grad_dev(ctx.h, _dptr32(w), B, _dptr32(z), _dptr32(y), _dptr32(u4), int(K), int(bool(use_physics)),
+                                              _dptr32(grad), _dptr32(loss)), "brov_pinc_loss_grad_dev")
+
+
+def pinc_adamw_step_dev(w, m, v, grad, step, lr=3e-3, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.01, max_norm=5.0, norm_out=None,
+                        ctx=None):
+    """clip_grad_norm_(max_norm) + one torch.optim.AdamW step (number `step`, 1-based) on device-resident fp32 arrays, in place."""
+    ctx = _ctx_of(w, ctx)
+    _bind(w, ctx)
+    ctx.check(ctx.lib.brov_pinc_adamw_step_dev(ctx.h, _dptr32(w), _dptr32(m), _dptr32(v), _dptr32(grad), int(step), float(lr),
+                                               float(beta1), float(beta2), float(eps), float(weight_decay), float(max_norm),
+                                               None if norm_out is None else _dptr32(norm_out)), "brov_pinc_adamw_step_dev")
 
 
 # ------------------------------------------------------------------------------------------ EDMDc

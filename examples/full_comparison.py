@@ -3,7 +3,7 @@
 engine: Koopman EDMDc, Fossen (BlueROV2), the learned double integrator and, given the PINc checkpoint (--pinc-ckpt: the
 reference's models/pinc_best.pt or a .npz of its arrays), the PINc residual network's row (bluerov2_dynamics_amd.pinc: one
 thruster-map vehicle for H = 1, 10, 100, as the script's rov_old).  Without a checkpoint the PINc row's three RMSEs can still be
-handed in with --pinc-row to complete the table and the ranking (tests/golden/cfg5_pinc.npz holds them for the CSV fixture).
+trained here with --pinc-train EPOCHS (train_pinc on the train split), or handed in with --pinc-row to complete the table and the ranking (tests/golden/cfg5_pinc.npz holds them for the CSV fixture).
 
     python examples/full_comparison.py path/to/koopman_dataset_50Hz.csv [--rbfs 500 --gamma 3 --ridge 0.1 --rk4]
     python examples/full_comparison.py path/to/koopman_dataset_50Hz.csv --pinc-ckpt models/pinc_best.pt
@@ -28,7 +28,7 @@ from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2             # noqa: E
 from bluerov2_dynamics_amd.fossen.BlueROV2_thrust import BlueROV2 as BlueROV2Wrench          # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2_wrench import BlueROV2 as BlueROV2Quat            # noqa: E402
 from bluerov2_dynamics_amd.Koopman.koopmanEDMDc import KoopmanEDMDc    # noqa: E402
-from bluerov2_dynamics_amd.pinc import PINcWeights, multistep_rmse_endpoint_pinc      # noqa: E402
+from bluerov2_dynamics_amd.pinc import PINcWeights, make_pinc_dataset, multistep_rmse_endpoint_pinc, train_pinc      # noqa: E402
 
 TRAIN_SPLIT = 0.80
 
@@ -37,16 +37,18 @@ ROWS = ("Koopman", "Fossen (BlueROV2)", "Double Integrator", "PINc (ResDNN)")
 
 
 def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None,
-            pinc=None):
+            pinc=None, pinc_train=None, pinc_seed=0):
     """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc (the PINc network's
     weights: a PINcWeights, a .npz / .pt path, a state dict or the reference's PINcNet; thruster variant only) or pinc_row (its
-    three RMSEs, computed elsewhere) the table has the reference's four rows and `ranking` [4,3] gives each model's rank per
+    three RMSEs, computed elsewhere) or pinc_train (epochs: the network is trained on the train split with train_pinc, seed
+    pinc_seed, and returned as `pinc_weights`) the table has the reference's four rows and `ranking` [4,3] gives each model's rank per
     horizon (0 = best), training/train_tank_brov2_full_comparison.py:996-1001.
     variant: "thruster" (8 PWM inputs, Euler angles), "wrench" (6-D body wrench, Euler angles), "quat" (wrench, quaternion
     state; RK4 exists only for the thruster script in the reference)."""
-    if pinc is not None and pinc_row is not None:
-        raise ValueError("give the PINc network (pinc) or its precomputed row (pinc_row), not both")
-    if pinc is not None and variant != "thruster":
+    if sum(v is not None for v in (pinc, pinc_row, pinc_train)) > 1:
+        raise ValueError("give the PINc network (pinc), its precomputed row (pinc_row) or the epochs to train it for (pinc_train), "
+                         "not more than one")
+    if (pinc is not None or pinc_train is not None) and variant != "thruster":
         raise ValueError("the PINc network takes the thruster commands: variant must be 'thruster'")
     if pinc is not None:
         pinc = PINcWeights(pinc)               # before the first device context (a .pt checkpoint imports torch)
@@ -65,6 +67,12 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
     t0 = perf_counter()
     di = DoubleIntegrator.fit(Xtr, Utr, dt, ridge=1e-3, quaternion=(variant == "quat"))
     t["fit_di"] = perf_counter() - t0
+    if pinc_train is not None:
+        t0 = perf_counter()
+        rov_old = BlueROV2(dt=dt)              # the script's one map vehicle: the dataset advances its lag by the train split (:947-960)
+        z_tr, y_tr, u4_tr = make_pinc_dataset(Xtr, Utr, dt, rov_old)
+        pinc = train_pinc(z_tr, y_tr, u4_tr, dt, epochs=int(pinc_train), seed=pinc_seed, verbose=verbose)
+        t["train_pinc"] = perf_counter() - t0
     rows = []
     for name, fn in (("Koopman", lambda H: koop.multistep_rmse(Xte, Ute, H=H)),
                      ("Fossen (BlueROV2)", lambda H: make_rov().multistep_rmse_endpoint(Xte, Ute, H, dt, integrator)),
@@ -76,7 +84,8 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
             t[f"{name}_H{H}"] = perf_counter() - t0
         rows.append(vals)
     if pinc is not None:
-        rov_old = BlueROV2(dt=dt)              # the script's thruster-map vehicle: its lag carries across H = 1, 10, 100 (:947, :992-994)
+        if pinc_train is None:
+            rov_old = BlueROV2(dt=dt)          # the script's thruster-map vehicle: its lag carries across H = 1, 10, 100 (:947, :992-994)
         vals = []
         for H in (1, 10, 100):
             t0 = perf_counter()
@@ -93,7 +102,8 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
         for name, r in zip(ROWS, table):
             print(f"  {name:<21s} | {r[0]:11.6f} | {r[1]:12.6f} | {r[2]:13.6f}")
         print("\n[timing] seconds:", {k: round(v, 4) for k, v in t.items()})
-    return dict(table=table, timings=t, dt=dt, split=split, model=koop, ranking=np.argsort(np.argsort(table, axis=0), axis=0), rows=ROWS[:len(table)])
+    return dict(table=table, timings=t, dt=dt, split=split, model=koop, ranking=np.argsort(np.argsort(table, axis=0), axis=0), rows=ROWS[:len(table)],
+                pinc_weights=pinc)
 
 
 if __name__ == "__main__":
@@ -108,5 +118,10 @@ if __name__ == "__main__":
                     help="the reference PINc network's endpoint RMSEs on the same test split (completes the table)")
     ap.add_argument("--pinc-ckpt", default=None, metavar="PATH",
                     help="PINc checkpoint (.pt state dict or .npz of its arrays): computes the fourth row on the engine")
+    ap.add_argument("--pinc-train", type=int, default=None, metavar="EPOCHS",
+                    help="train the PINc network on the train split for EPOCHS epochs on the engine, then compute the fourth row with it")
     a = ap.parse_args()
-    compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt)
+    if sum(v is not None for v in (a.pinc_row, a.pinc_ckpt, a.pinc_train)) > 1:
+        ap.error("--pinc-row, --pinc-ckpt and --pinc-train are mutually exclusive")
+    compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt,
+            pinc_train=a.pinc_train)

@@ -222,6 +222,45 @@ BROV_API int brov_pinc_window_endpoint_se_dev(brov_ctx* ctx, int64_t N, int64_t 
                                      int carry_lag, double* d_lag_io, double* d_se_total, double* d_per_window,
                                      double* d_lag_starts);
 
+/* ---- PINc residual network (training) -----------------------------------------------------
+ * train_pinc's loop body (training/train_tank_brov2_full_comparison.py:790-835) in fp32.  A minibatch of B rows z [B][14],
+ * y [B][9], u4 [B][4] (all fp32, what the reference's .float() makes of make_pinc_dataset's arrays) gives three loss terms
+ *   loss[0] = mse(model(z), y)                                  mean over B*9
+ *   loss[1] = physics_loss(model(z), u4)                         mean square of the 4-DOF right-hand side; a value only (no_grad)
+ *   loss[2] = rollout_loss(model, z, K)                          K steps from batch row 0, step i scored against row i+1
+ * with total = loss[0] + 0.5 loss[1] + loss[2], and the gradient of loss[0] + loss[2] over the 14541 parameters in blob order.
+ * K must be < B and <= 16 (0 = no rollout term).  Sums run in a fixed order: the same inputs give the same bits. */
+typedef struct brov_pinc_hyper {
+    double lr, beta1, beta2, eps, weight_decay;   /* torch.optim.AdamW: 3e-3, 0.9, 0.999, 1e-8, 0.01 */
+    double max_norm;                              /* clip_grad_norm_: 5.0 */
+    int32_t batch, rollout_steps;                 /* 256, 10; each iteration uses K = min(rollout_steps, rows - 1) */
+    int32_t use_physics, use_rollout;
+} brov_pinc_hyper;
+/* One minibatch, no update: d_weights [14541] fp32 (device) -> d_grad [14541] (unclipped), d_loss [3].  Asynchronous. */
+BROV_API int brov_pinc_loss_grad_dev(brov_ctx* ctx, const float* d_weights, int64_t B, const float* d_z, const float* d_y,
+                                     const float* d_u4, int K, int use_physics, float* d_grad, float* d_loss);
+/* clip_grad_norm_(max_norm) on d_grad (which is left as given) then AdamW step number `step` (1-based) on d_w, d_m, d_v [14541]
+ * in place; d_norm_out [1] (optional) receives the 2-norm before clipping.  Asynchronous. */
+BROV_API int brov_pinc_adamw_step_dev(brov_ctx* ctx, float* d_w, float* d_m, float* d_v, const float* d_grad, int64_t step, double lr,
+                                      double beta1, double beta2, double eps, double weight_decay, double max_norm, float* d_norm_out);
+/* A training session owned by the ctx: begin copies blob [n = 14541] (host) to a device copy of its own with m = v = 0, step = 0;
+ * the weights brov_pinc_set_weights gave the ctx are neither read nor written.  A second begin replaces the session. */
+BROV_API int brov_pinc_train_begin(brov_ctx* ctx, const float* blob, int64_t n, const brov_pinc_hyper* hyper);
+/* Optimiser state of a resumed run: m, v [14541] (host), step >= 0. */
+BROV_API int brov_pinc_train_set_state(brov_ctx* ctx, const float* m, const float* v, int64_t step);
+/* One epoch over d_Z [N][14], d_Y [N][9], d_U4 [N][4] (device, fp32) in the order d_perm [N] (device, int32, a permutation of
+ * 0..N-1): queues all ceil(N / batch) iterations on the ctx stream and returns; iteration i writes its three loss terms to
+ * d_loss_log[3 i ..].  The arrays must stay valid until the stream has been synchronised. */
+BROV_API int brov_pinc_train_epoch_dev(brov_ctx* ctx, int64_t N, const float* d_Z, const float* d_Y, const float* d_U4,
+                                       const int32_t* d_perm, float* d_loss_log);
+/* Weights and optimiser state to the host (each optional): blob_out, m_out, v_out [14541], step_out [1].  Synchronises. */
+BROV_API int brov_pinc_train_get(brov_ctx* ctx, float* blob_out, float* m_out, float* v_out, int64_t* step_out);
+BROV_API int brov_pinc_train_end(brov_ctx* ctx);
+/* make_pinc_dataset's loop over compute_thruster_forces (:732-735): ONE stateful vehicle fed U [N][8] in order -> tau [N][6];
+ * lag_io [8][3] is its lag before the first sample and receives the lag after the last. */
+BROV_API int brov_thruster_stream(brov_ctx* ctx, int64_t N, const double* U, double dt, double* lag_io, double* tau);
+BROV_API int brov_thruster_stream_dev(brov_ctx* ctx, int64_t N, const double* d_U, double dt, double* d_lag_io, double* d_tau);
+
 /* Synthetic control sequences on device (benchmarks):
  * counter-based splitmix64 stream, value for (trajectory b0+b, step t, channel j) independent
  * of layout and of how trajectories are sharded.  scale[nu] multiplies each channel (NULL = 1). */

@@ -730,7 +730,104 @@ def gen_kmeans_empty():
     np.savez_compressed(os.path.join(OUT, "kmeans_empty.npz"), versions=versions(), **out)
 
 
-GENS = dict(pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
+def gen_pinc_train():
+    """PINc training fixtures (training/train_tank_brov2_full_comparison.py:724-835, reference code unmodified, CPU), data only.
+    The 1 MiB limit on a committed file splits them over four files:
+      pinc_train.npz        a seeded fresh PINcNet() (the other weight set is pinc_weights.npz), cfg5's train split (1 600 rows)
+                            through make_pinc_dataset (z, y, U4, the vehicle's lag afterwards), the index lists of three minibatches
+                            (256, 254 and 2 rows) and of 20 training iterations, and the loss terms of everything below
+      pinc_train_grad.npz   the flat fp64 gradient (model.double()) of mse + rollout_loss for both weight sets x three minibatches
+      pinc_train_opt.npz    weights, exp_avg, exp_avg_sq (fp64) after 1 and 5 iterations of train_pinc's loop body from the fresh set
+      pinc_train_opt20.npz  the same after 20 iterations, and the fp32 run's final weights
+    The fp32 runs leave their loss terms, gradient norms and final weights (the full fp32 gradients would not fit): the CPU tests
+    check with them that torch's own fp32 run lands as far from fp64 as the restatement's fp32 mode does.
+    Inputs are rounded to fp32 first (train_pinc's .float()); the fp64 runs widen those values."""
+    import torch
+    import torch.nn.functional as F
+    import train_tank_brov2_full_comparison as ref
+    g = np.load(os.path.join(OUT, "cfg5.npz"))
+    X, U, dt, split = g["X"], g["U"], float(g["dt"]), int(g["split"])
+    rov = RefThruster(dt=dt)
+    z, y, U4 = ref.make_pinc_dataset(X[:split], U[:split], dt, rov)      # the whole train split (1 600 of the recording's 2 000 rows)
+    lag_after = np.array([l._x.copy() for l in rov.thruster_lags], dtype=float)
+    torch.manual_seed(20251017)
+    fresh = ref.PINcNet(hidden_sizes=ref.PINc_HIDDEN)
+    sets = dict(ckpt=torch.load(os.path.join(REF, "models", "pinc_best.pt"), map_location="cpu"),
+                fresh={k: v.detach().clone() for k, v in fresh.state_dict().items()})
+    keys = list(sets["fresh"])
+    rng = np.random.default_rng(20251017)
+    N = len(z)
+    batches = dict(b256=rng.permutation(N)[:256], b254=rng.permutation(N)[:254], b2=rng.permutation(N)[:2])
+    iters = np.stack([rng.permutation(N)[:256] for _ in range(20)])
+
+    def tensors(dtype):
+        return [torch.from_numpy(a.astype(np.float32)).to(dtype) for a in (z, y, U4[:-1])]
+
+    def model_of(sd, dtype):
+        net = ref.PINcNet(hidden_sizes=ref.PINc_HIDDEN)
+        net.load_state_dict(sd)
+        return net.to(dtype).train()
+
+    def terms(net, z_b, y_b, u_b):
+        x_pred = net(z_b)
+        mse = F.mse_loss(x_pred, y_b)
+        phys = ref.physics_loss(ref.bluerov_compute, x_pred, u_b)
+        K = min(10, z_b.shape[0] - 1)
+        roll = ref.rollout_loss(net, z_b, K) if K > 0 else torch.zeros((), dtype=z_b.dtype)
+        return mse, phys, roll
+
+    out, grads = {}, {}
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        Zt, Yt, Ut = tensors(dtype)
+        for sname, sd in sets.items():
+            for bname, idx in batches.items():
+                net = model_of(sd, dtype)
+                i = torch.from_numpy(idx)
+                mse, phys, roll = terms(net, Zt[i], Yt[i], Ut[i])
+                (mse + 0.5 * phys + roll).backward()
+                flat = np.concatenate([dict(net.named_parameters())[k].grad.numpy().ravel() for k in keys])
+                out[f"loss_{tag}_{sname}_{bname}"] = np.array([mse.item(), phys.item(), roll.item()])
+                if tag == "f64":
+                    grads[f"grad_{sname}_{bname}"] = flat
+                else:
+                    out[f"gradnorm_f32_{sname}_{bname}"] = np.float64(np.linalg.norm(flat.astype(np.float64)))
+    opt, opt20 = {}, {}
+    for dtype, tag in ((torch.float64, "f64"), (torch.float32, "f32")):
+        Zt, Yt, Ut = tensors(dtype)
+        net = model_of(sets["fresh"], dtype)
+        adam = torch.optim.AdamW(net.parameters(), lr=3e-3)
+        params = dict(net.named_parameters())
+        losses = []
+        for it, idx in enumerate(iters, 1):
+            i = torch.from_numpy(idx)
+            mse, phys, roll = terms(net, Zt[i], Yt[i], Ut[i])
+            loss = mse + 0.5 * phys + roll
+            adam.zero_grad()
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(net.parameters(), 5.0)
+            adam.step()
+            losses.append([mse.item(), phys.item(), roll.item()])
+            if it in (1, 5, 20):
+                w = np.concatenate([params[k].detach().numpy().ravel() for k in keys])
+                if tag == "f64":
+                    dst = opt20 if it == 20 else opt
+                    dst[f"w_{it}"] = w
+                    dst[f"m_{it}"] = np.concatenate([adam.state[params[k]]["exp_avg"].numpy().ravel() for k in keys])
+                    dst[f"v_{it}"] = np.concatenate([adam.state[params[k]]["exp_avg_sq"].numpy().ravel() for k in keys])
+                elif it == 20:
+                    opt20["w_20_f32"] = w
+        out[f"train_losses_{tag}"] = np.array(losses)
+    meta = dict(torch_version=np.array([torch.__version__]), versions=versions())
+    np.savez(os.path.join(OUT, "pinc_train.npz"), z=z, y=y, U4=U4, lag_after=lag_after, dt=np.float64(dt),
+             keys=np.array(keys), iters=iters.astype(np.int32), **{f"idx_{k}": v.astype(np.int32) for k, v in batches.items()},
+             **{f"fresh.{k}": v.numpy().astype(np.float32) for k, v in sets["fresh"].items()}, **out, **meta)
+    np.savez(os.path.join(OUT, "pinc_train_grad.npz"), **grads, **meta)
+    np.savez(os.path.join(OUT, "pinc_train_opt.npz"), **opt, **meta)
+    np.savez(os.path.join(OUT, "pinc_train_opt20.npz"), **opt20, **meta)
+    print("loss terms (fp64):", {k: v for k, v in out.items() if k.startswith("loss_f64")})
+
+
+GENS = dict(pinc_train=gen_pinc_train, pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
