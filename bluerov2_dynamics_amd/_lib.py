@@ -114,6 +114,12 @@ SIGNATURES = {
                                                c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "brov_window_endpoint_se_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.c_double,
                                                    c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_window_endpoint_pop": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, i64,
+                                                ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_window_endpoint_pop_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, i64,
+                                                    ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_fd_normal_eq_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

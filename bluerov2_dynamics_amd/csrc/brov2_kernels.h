@@ -20,6 +20,17 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* d_fp, int model, int
 hipError_t launch_window_endpoint(hipStream_t st, const FastParams* d_fp, int model, int integ, int64_t N, int64_t H, double dt,
                                   const double* X, const double* U, int carry_lag, const double* d_phi9,
                                   double* d_resp, double* d_start, double* d_se, double* d_total);
+// The same evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y).  Candidate-major scratch: d_phi [P][18]
+// ([Phi | Phi^window_scan_chunk()] of each candidate), d_lag [P][N-H][18] and d_chunk [P][chunks][18] (thruster model with
+// carry_lag only), d_se [P][N-H]; d_total [P]; d_endpoints [P][N-H][nx] or nullptr.  The launch count does not depend on P.
+hipError_t launch_window_endpoint_pop(hipStream_t st, const FastParams* d_fp, int model, int integ, int P, int64_t N, int64_t H, double dt,
+                                      const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                      double* d_chunk, double* d_se, double* d_total, double* d_endpoints);
+// Finite-difference normal equations (rollout.hip): d_E [(m+1)][R], R = W nx; d_part fd_normal_blocks(R) x (m+1)(m+2)/2 doubles;
+// d_out = [JtJ (m x m) | Jtr (m)].
+int fd_normal_blocks(int64_t R);
+hipError_t launch_fd_normal_eq(hipStream_t st, int nx, int m, int64_t R, const double* d_E, const double* d_target, const double* d_delta,
+                               const double* d_weight, double* d_part, double* d_out);
 hipError_t launch_fill_controls(hipStream_t st, int layout, int dist, int64_t B, int64_t T, int nu, uint64_t seed,
                                 int64_t b0, int64_t T_total, const double* scale8, double* U);
 

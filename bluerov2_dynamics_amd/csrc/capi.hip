@@ -1274,6 +1274,133 @@ int brov_window_endpoint_se(brov_ctx* c, int model, int integ, int64_t N, int64_
     return BROV_OK;
 }
 
+// ---- the window evaluator over a population of parameter sets; finite-difference normal equations -----------------
+// (parameter identification: fossen/identify.py).  The ctx's own parameters and their derived cache are not touched.
+static bool pop_args_ok(const brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, const double* se) {
+    return c && (model == BROV_THRUSTER_EULER || model == BROV_WRENCH_EULER || model == BROV_WRENCH_QUAT) &&
+           (integ == BROV_EULER || integ == BROV_RK4) && P >= 1 && P <= 65535 && params && N >= 0 && H >= 0 && se;
+}
+static size_t window_pop_scratch(int model, int carry, int64_t P, int64_t nwin) {
+    size_t b = Arena::al(P * sizeof(FastParams)) + Arena::al(P * nwin * 8);
+    if (model == BROV_THRUSTER_EULER && carry) {
+        const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
+        b += Arena::al(P * nwin * 18 * 8) + Arena::al(P * nchunks * 18 * 8) + Arena::al(P * 18 * 8);
+    }
+    return b;
+}
+static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, int64_t N, int64_t H, double dt,
+                           const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints, Arena& a) {
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, BROV_ERR_ARG, "dt must be finite and > 0");
+    const int64_t nwin = N - H;
+    const bool scan = model == BROV_THRUSTER_EULER && carry;
+    const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
+    const int64_t spw = H * (integ == BROV_RK4 ? 4 : 1);
+    // derive_fast once per candidate; one upload carries the whole FastParams[P] array (and one more the scan matrices)
+    std::vector<FastParams> fp((size_t)P);
+    std::vector<double> phi(scan ? (size_t)P * 18 : 0);          // per candidate: Phi, Phi^chunk (blocked scan of rollout.hip)
+    for (int j = 0; j < P; ++j) {
+        const brov_params& p = params[j];
+        const double md[6] = {p.m - p.added_mass[0], p.m - p.added_mass[1], p.m - p.added_mass[2],
+                              p.Ix - p.added_mass[3], p.Iy - p.added_mass[4], p.Iz - p.added_mass[5]};
+        for (int i = 0; i < 6; ++i)
+            if (!(md[i] != 0.0) || !std::isfinite(md[i])) return fail(c, BROV_ERR_ARG, "candidate " + std::to_string(j) + ": singular mass matrix");
+        DevParams dp;
+        if (!derive(p, dt, dp)) return fail(c, BROV_ERR_ARG, "thruster-lag discretisation failed (singular Pade system)");
+        derive_fast(p, dp, fp[j]);
+        if (scan) {
+            lag_window_phi(dp, spw, &phi[(size_t)j * 18]);
+            lag_window_phi(dp, spw * window_scan_chunk(), &phi[(size_t)j * 18 + 9]);
+        }
+    }
+    FastParams* d_fp = a.take<FastParams>(P);
+    double* d_se = a.take<double>(P * nwin);
+    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    if (scan) {
+        d_lag = a.take<double>(P * nwin * 18);
+        d_chunk = a.take<double>(P * nchunks * 18);
+        d_phi = a.take<double>(P * 18);
+        HIPCK(c, h2d_copy(c, d_phi, phi.data(), phi.size() * 8));
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp / phi are locals
+    CallTimer t(c);
+    HIPCK(c, launch_window_endpoint_pop(c->stream, d_fp, model, integ, P, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_se, d_total,
+                                        d_endpoints));
+    return BROV_OK;
+}
+
+int brov_window_endpoint_pop_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
+                                 const double* d_X, const double* d_U, int carry_lag, double* d_se, double* d_endpoints) {
+    if (!pop_args_ok(c, model, integ, P, params, N, H, d_se)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_dev: bad argument");
+    DeviceGuard g(c);
+    const int64_t nwin = N - H;
+    if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se, 0, (size_t)P * 8, c->stream)); return BROV_OK; }
+    if (!d_X || !d_U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_dev: NULL array");
+    Arena a(c);
+    int rc = a.reserve(window_pop_scratch(model, carry_lag, P, nwin) + 4096);
+    if (rc) return rc;
+    return window_pop_impl(c, model, integ, (int)P, params, N, H, dt, d_X, d_U, carry_lag, d_se, d_endpoints, a);
+}
+
+int brov_window_endpoint_pop(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
+                             const double* X, const double* U, int carry_lag, double* se, double* endpoints) {
+    if (!pop_args_ok(c, model, integ, P, params, N, H, se)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop: bad argument");
+    const int64_t nwin = N - H;
+    if (nwin <= 0) { for (int64_t j = 0; j < P; ++j) se[j] = 0.0; return BROV_OK; }
+    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop: NULL array");
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    Arena a(c);
+    int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(P * 8) + (endpoints ? Arena::al(P * nwin * nx * 8) : 0) +
+                       window_pop_scratch(model, carry_lag, P, nwin) + 4096);
+    if (rc) return rc;
+    double* dX = a.take<double>(N * nx);
+    double* dU = a.take<double>(N * nu);
+    double* dtot = a.take<double>(P);
+    double* dE = endpoints ? a.take<double>(P * nwin * nx) : nullptr;
+    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
+    HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
+    rc = window_pop_impl(c, model, integ, (int)P, params, N, H, dt, dX, dU, carry_lag, dtot, dE, a);
+    if (rc) return rc;
+    HIPCK(c, d2h_copy(c, se, dtot, (size_t)P * 8));
+    if (endpoints) HIPCK(c, d2h_copy(c, endpoints, dE, (size_t)P * nwin * nx * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+int brov_fd_normal_eq_dev(brov_ctx* c, int nx, int m, int64_t W, const double* d_endpoints, const double* d_target, const double* delta,
+                          const double* weight, double* JtJ, double* Jtr) {
+    if (!c || nx < 1 || nx > 64 || m < 1 || m > 48 || W < 0 || !delta || !JtJ || !Jtr)
+        return fail(c, BROV_ERR_ARG, "brov_fd_normal_eq_dev: bad argument (1 <= m <= 48)");
+    for (int j = 0; j < m; ++j)
+        if (delta[j] == 0.0 || !std::isfinite(delta[j])) return fail(c, BROV_ERR_ARG, "brov_fd_normal_eq_dev: delta must be finite and non-zero");
+    if (W == 0) { std::fill(JtJ, JtJ + m * m, 0.0); std::fill(Jtr, Jtr + m, 0.0); return BROV_OK; }
+    if (!d_endpoints || !d_target) return fail(c, BROV_ERR_ARG, "brov_fd_normal_eq_dev: NULL array");
+    DeviceGuard g(c);
+    const int64_t R = W * nx;
+    const int nb = fd_normal_blocks(R), npair = (m + 1) * (m + 2) / 2, nout = m * m + m;
+    Arena a(c);
+    int rc = a.reserve(Arena::al((m + nx) * 8) + Arena::al((size_t)nb * npair * 8) + Arena::al(nout * 8) + 4096);
+    if (rc) return rc;
+    double* d_dw = a.take<double>(m + nx);       // [delta | weight]
+    double* d_part = a.take<double>((size_t)nb * npair);
+    double* d_out = a.take<double>(nout);
+    std::vector<double> dw((size_t)(m + nx), 1.0), out((size_t)nout);
+    std::copy(delta, delta + m, dw.begin());
+    if (weight) std::copy(weight, weight + nx, dw.begin() + m);
+    HIPCK(c, h2d_copy(c, d_dw, dw.data(), dw.size() * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // dw is a local
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_fd_normal_eq(c->stream, nx, m, R, d_endpoints, d_target, d_dw, d_dw + m, d_part, d_out));
+    }
+    HIPCK(c, d2h_copy(c, out.data(), d_out, out.size() * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    std::copy(out.begin(), out.begin() + m * m, JtJ);
+    std::copy(out.begin() + m * m, out.end(), Jtr);
+    return BROV_OK;
+}
+
 // ---- PINc residual network -------------------------------------------------------------------------------
 int brov_pinc_set_weights(brov_ctx* c, const float* blob, int64_t n) {
     if (!c || !blob || n != PINC_NPARAMS)

@@ -1038,4 +1038,262 @@ hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------
+// K3p: the window evaluator over a POPULATION of parameter sets (parameter identification, fossen/identify.py).
+// pg is a FastParams[P] array; the candidate is blockIdx.y, uniform per block, so as_constant(pg + blockIdx.y) keeps every
+// constant read a scalar load exactly as in K3.  Candidate j runs the arithmetic of K3 on its own constants: same step
+// function, same order, same fixed-shape sum -- what brov_set_params(params[j]) + brov_window_endpoint_se computes.
+// The carried-lag pre-scan is batched the same way; its matrices (Phi, Phi^WSCAN_CHUNK) are per candidate because the
+// acceleration-space lag folds in Minv T.  Per-candidate arrays are candidate-major: resp/start [P][nwin][18],
+// chunk [P][nchunks][18], phi [P][18], se [P][nwin], endpoints [P][nwin][NX].
+// ---------------------------------------------------------------------------------------
+template <int NSUB>
+__global__ void __launch_bounds__(256) window_lag_response_pop_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H,
+                                                                      const double* __restrict__ U, double* __restrict__ resp) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nwin) return;
+    LagZ lz;
+    lz.zero();
+    for (int64_t t = 0; t < H; ++t) {
+        const CFP pp = relaunder(as_constant(pg + blockIdx.y));
+        double u[8], fcmd[8], acmd[6];
+        load_row<8>(U + (k + t) * 8, u);
+        command_accel<MODEL_THRUSTER_EULER, false>(pp, u, fcmd, acmd);
+        lz.advance(NSUB == 4 ? pp->A4 : pp->A1, NSUB == 4 ? pp->b4 : pp->b1, acmd);
+    }
+    store_row<18>(resp + ((int64_t)blockIdx.y * nwin + k) * 18, &lz.z[0][0]);
+}
+
+// phases 1 and 3 of the blocked scan (window_lag_chunk_kernel) for candidate blockIdx.y.  Phase 3 writes the start states over the
+// responses it has just consumed (rs holds resp on entry, start on exit): the population form keeps one [P][nwin][18] array.
+__global__ void __launch_bounds__(256) window_lag_chunk_pop_kernel(int64_t nwin, int64_t nchunks, const double* __restrict__ phi,
+                                                                  double* rs, double* __restrict__ chunk_io, int store_start) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t c = g / 6;
+    const int i = (int)(g - c * 6);
+    const int64_t k0 = c * WSCAN_CHUNK;
+    if (k0 >= nwin) return;
+    const int64_t j = blockIdx.y;
+    double P[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + q];
+    double* ce = chunk_io + (j * nchunks + c) * 18 + i * 3;
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    if (store_start) { x0 = ce[0]; x1 = ce[1]; x2 = ce[2]; }
+    const int64_t k1 = k0 + WSCAN_CHUNK < nwin ? k0 + WSCAN_CHUNK : nwin;
+    for (int64_t k = k0; k < k1; ++k) {
+        double* r = rs + (j * nwin + k) * 18 + i * 3;
+        const double r0 = r[0], r1 = r[1], r2 = r[2];
+        if (store_start) { r[0] = x0; r[1] = x1; r[2] = x2; }
+        wscan_step(P, x0, x1, x2, r0, r1, r2);
+    }
+    if (!store_start) { ce[0] = x0; ce[1] = x1; ce[2] = x2; }
+}
+
+// phase 2 (window_lag_scan_kernel from a zero state): one block per candidate
+__global__ void __launch_bounds__(64) window_lag_scan_pop_kernel(int64_t nchunks, const double* __restrict__ phi, double* __restrict__ chunk_io) {
+    const int i = threadIdx.x;  // lag bank
+    if (i >= 6) return;
+    const int64_t j = blockIdx.x;
+    double P[9];
+#pragma unroll
+    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + 9 + q];
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
+    double* e = chunk_io + j * nchunks * 18 + i * 3;
+    double b0 = 0, b1 = 0, b2 = 0;
+    if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; }
+    for (int64_t c = 0; c < nchunks; ++c) {
+        const double c0 = b0, c1 = b1, c2 = b2;
+        if (c + 1 < nchunks) { b0 = e[(c + 1) * 18 + 0]; b1 = e[(c + 1) * 18 + 1]; b2 = e[(c + 1) * 18 + 2]; }
+        e[c * 18 + 0] = x0; e[c * 18 + 1] = x1; e[c * 18 + 2] = x2;
+        wscan_step(P, x0, x1, x2, c0, c1, c2);
+    }
+}
+
+template <int MODEL, int INTEG>
+__global__ void __launch_bounds__(256) window_endpoint_pop_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H, double dt,
+                                                                  const double* __restrict__ X, const double* __restrict__ U,
+                                                                  const double* __restrict__ lag_start, double* __restrict__ se,
+                                                                  double* __restrict__ endpoints) {
+    constexpr int NX = Dims<MODEL>::NX, NU = Dims<MODEL>::NU;
+    __shared__ double2 qt[4];
+    init_quadrant_table(qt);
+    __syncthreads();
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= nwin) return;
+    const int64_t row = (int64_t)blockIdx.y * nwin + k;       // window k of candidate blockIdx.y
+    const CFP p = as_constant(pg + blockIdx.y);
+    HotConsts h;
+    load_hot(p, h);
+    double x[NX];
+    load_row<NX>(X + k * NX, x);
+    LagZ lz;
+    double Xl[8][3];
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (lag_start) load_row<18>(lag_start + row * 18, &lz.z[0][0]);
+        else lz.zero();
+    }
+    for (int64_t t = 0; t < H; ++t) {
+        double u[NU];
+        load_row<NU>(U + (k + t) * NU, u);
+        // the GENERIC step whatever the candidates' flags say, as in K3: one kernel serves mixed populations
+        step_fast<MODEL, INTEG, 0, false, true>(h, p, dt, x, u, lz, Xl, qt);
+    }
+    double ref[NX], e = 0.0;
+    load_row<NX>(X + (k + H) * NX, ref);
+#pragma unroll
+    for (int i = 0; i < NX; ++i) { const double d = x[i] - ref[i]; e = fma(d, d, e); }
+    se[row] = e;
+    if (endpoints) store_row<NX>(endpoints + row * NX, x);   // lane k writes row k of its candidate
+}
+
+// sum_kernel per candidate: out[j] = sum of v[j][0..n), the same fixed-shape tree
+__global__ void __launch_bounds__(1024) sum_pop_kernel(int64_t n, const double* __restrict__ v, double* __restrict__ out) {
+    __shared__ double sh[1024];
+    const double* vj = v + (int64_t)blockIdx.x * n;
+    double a = 0.0;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) a += vj[i];
+    sh[threadIdx.x] = a;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+}
+
+template <int MODEL>
+static hipError_t launch_window_pop_m(hipStream_t st, const FastParams* p, int integ, int P, int64_t nwin, int64_t H, double dt,
+                                      const double* X, const double* U, const double* lag_start, double* se, double* endpoints) {
+    const dim3 grid(nblk(nwin, 256), (unsigned)P);
+    if (integ == INTEG_RK4)
+        hipLaunchKernelGGL((window_endpoint_pop_kernel<MODEL, INTEG_RK4>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+    else
+        hipLaunchKernelGGL((window_endpoint_pop_kernel<MODEL, INTEG_EULER>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+    return hipGetLastError();
+}
+
+// Six launches with carry_lag on the thruster model, two otherwise, whatever P is.
+hipError_t launch_window_endpoint_pop(hipStream_t st, const FastParams* p, int model, int integ, int P, int64_t N, int64_t H, double dt,
+                                      const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                      double* d_chunk, double* d_se, double* d_total, double* d_endpoints) {
+    const int64_t nwin = N - H;
+    if (nwin <= 0 || P <= 0) return hipSuccess;
+    const double* lag_start = nullptr;
+    if (model == MODEL_THRUSTER_EULER && carry_lag) {
+        const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
+        const dim3 gw(nblk(nwin, 256), (unsigned)P), gc(nblk(nchunks * 6, 256), (unsigned)P);
+        if (integ == INTEG_RK4)
+            hipLaunchKernelGGL(window_lag_response_pop_kernel<4>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
+        else
+            hipLaunchKernelGGL(window_lag_response_pop_kernel<1>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_chunk_pop_kernel, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_lag, d_chunk, 0);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_scan_pop_kernel, dim3((unsigned)P), dim3(64), 0, st, nchunks, d_phi, d_chunk);
+        BROV_LAUNCH_CHECK();
+        hipLaunchKernelGGL(window_lag_chunk_pop_kernel, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_lag, d_chunk, 1);
+        BROV_LAUNCH_CHECK();
+        lag_start = d_lag;
+    }
+    hipError_t e;
+    if (model == MODEL_THRUSTER_EULER) e = launch_window_pop_m<MODEL_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
+    else if (model == MODEL_WRENCH_EULER) e = launch_window_pop_m<MODEL_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
+    else e = launch_window_pop_m<MODEL_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sum_pop_kernel, dim3((unsigned)P), dim3(1024), 0, st, nwin, d_se, d_total);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
+// Finite-difference normal equations of the identification loop.  E [(m+1)][R] holds the window endpoints of the base
+// parameters (row block 0) and of base + delta_j e_j (row block j + 1), R = W nx values each.  With
+//     J[r][j] = w_i (E_{j+1}[r] - E_0[r]) / delta_j,   res[r] = w_i (E_0[r] - target[r]),   i = r mod nx,
+// every block forms A = [J | res] for tiles of FDN_TILE rows in LDS and adds the tile's share of the upper triangle of A^T A
+// (thread q owns entries q, q + 256, ...) to its own partial, tile after tile in index order; fd_normal_reduce_kernel adds the
+// blocks' partials in index order.  No atomics: the same bits from run to run.
+// ---------------------------------------------------------------------------------------
+constexpr int FDN_TILE = 64, FDN_MAX_M = 48, FDN_THREADS = 256;
+constexpr int FDN_MAX_Q = ((FDN_MAX_M + 1) * (FDN_MAX_M + 2) / 2 + FDN_THREADS - 1) / FDN_THREADS;   // entries per thread: 5
+
+// entry q of the packed upper triangle of an n x n matrix -> (a, b), a <= b, row-major
+__host__ __device__ inline void fdn_unpack(int q, int n, int& a, int& b) {
+    a = 0;
+    while (q >= n - a) { q -= n - a; ++a; }
+    b = a + q;
+}
+
+__global__ void __launch_bounds__(FDN_THREADS) fd_normal_partial_kernel(int nx, int m, int64_t R, const double* __restrict__ E,
+                                                                        const double* __restrict__ target,
+                                                                        const double* __restrict__ delta,
+                                                                        const double* __restrict__ weight, double* __restrict__ part) {
+    __shared__ double tile[FDN_MAX_M + 1][FDN_TILE + 1];     // [column of A][row of the tile]; + 1: columns on different banks
+    const int n = m + 1, npair = n * (n + 1) / 2;
+    int ia[FDN_MAX_Q], ib[FDN_MAX_Q];
+    double acc[FDN_MAX_Q];
+#pragma unroll
+    for (int s = 0; s < FDN_MAX_Q; ++s) {
+        const int q = (int)threadIdx.x + s * FDN_THREADS;
+        ia[s] = 0; ib[s] = 0; acc[s] = 0.0;
+        if (q < npair) fdn_unpack(q, n, ia[s], ib[s]);
+    }
+    const int64_t ntiles = (R + FDN_TILE - 1) / FDN_TILE;
+    for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const int64_t r0 = t * FDN_TILE;
+        for (int idx = threadIdx.x; idx < n * FDN_TILE; idx += FDN_THREADS) {
+            const int col = idx / FDN_TILE, lr = idx - col * FDN_TILE;
+            const int64_t r = r0 + lr;
+            double v = 0.0;
+            if (r < R) {
+                const double w = weight[r % nx], e0 = E[r];
+                v = col < m ? w * (E[(int64_t)(col + 1) * R + r] - e0) / delta[col] : w * (e0 - target[r]);
+            }
+            tile[col][lr] = v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < FDN_MAX_Q; ++s) {
+            if ((int)threadIdx.x + s * FDN_THREADS < npair) {
+                double ts = 0.0;
+                for (int lr = 0; lr < FDN_TILE; ++lr) ts = fma(tile[ia[s]][lr], tile[ib[s]][lr], ts);
+                acc[s] += ts;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int s = 0; s < FDN_MAX_Q; ++s) {
+        const int q = (int)threadIdx.x + s * FDN_THREADS;
+        if (q < npair) part[(int64_t)blockIdx.x * npair + q] = acc[s];
+    }
+}
+
+// out = [JtJ (m x m, both triangles) | Jtr (m)]
+__global__ void __launch_bounds__(FDN_THREADS) fd_normal_reduce_kernel(int m, int nblocks, const double* __restrict__ part, double* __restrict__ out) {
+    const int n = m + 1, npair = n * (n + 1) / 2;
+    const int q = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (q >= npair) return;
+    double s = 0.0;
+    for (int g = 0; g < nblocks; ++g) s += part[(int64_t)g * npair + q];
+    int a, b;
+    fdn_unpack(q, n, a, b);
+    if (b < m) { out[a * m + b] = s; out[b * m + a] = s; }
+    else if (a < m) out[m * m + a] = s;
+}
+
+int fd_normal_blocks(int64_t R) {
+    const int64_t ntiles = (R + FDN_TILE - 1) / FDN_TILE;
+    return (int)(ntiles < 1 ? 1 : (ntiles > 512 ? 512 : ntiles));
+}
+
+// d_part: fd_normal_blocks(R) x (m + 1)(m + 2) / 2 doubles; d_out: m m + m doubles
+hipError_t launch_fd_normal_eq(hipStream_t st, int nx, int m, int64_t R, const double* d_E, const double* d_target, const double* d_delta,
+                               const double* d_weight, double* d_part, double* d_out) {
+    const int nb = fd_normal_blocks(R), npair = (m + 1) * (m + 2) / 2;
+    hipLaunchKernelGGL(fd_normal_partial_kernel, dim3(nb), dim3(FDN_THREADS), 0, st, nx, m, R, d_E, d_target, d_delta, d_weight, d_part);
+    BROV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(fd_normal_reduce_kernel, dim3(nblk(npair, FDN_THREADS)), dim3(FDN_THREADS), 0, st, m, nb, d_part, d_out);
+    return hipGetLastError();
+}
+
 }  // namespace brov

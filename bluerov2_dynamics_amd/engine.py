@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "fd_normal_eq"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -363,6 +363,55 @@ def window_endpoint_se_dev(model, integrator, X, U, H, dt, se_total, per_window,
     ctx.check(ctx.lib.brov_window_endpoint_se_dev(ctx.h, model, INTEGRATORS[integrator], N, int(H), float(dt), _dptr(X), _dptr(U),
                                                   int(bool(carry_lag)), _dptr(se_total), _dptr(per_window)),
               "brov_window_endpoint_se_dev")
+
+
+def window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=True, endpoints=False, ctx=None):
+    """The window evaluator for a population of parameter sets in one call (include/brov2.h: brov_window_endpoint_pop_dev).
+
+    params_list: sequence of _lib.BrovParams; X [N,nx], U [N,nu]: host arrays (uploaded) or device-resident arrays (DevArray /
+    torch CUDA tensors, used in place).  Returns rmse [P] (NaN when N <= H, like window_rmse), and with endpoints=True also the
+    window end states as a device array [P, N-H, nx].  Candidate j scores what ctx.set_params(params_list[j]) + window_rmse
+    scores; the ctx's own parameters are left alone."""
+    P = len(params_list)
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    nx, nu = NX.get(model, 12), NU.get(model, 8)
+    if isinstance(X, np.ndarray) or isinstance(X, (list, tuple)):
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        arr.bind()
+        X = arr.upload(as_f64(X).reshape(-1, nx))
+        U = arr.upload(as_f64(U).reshape(-1, nu))
+    else:
+        ctx = _ctx_of(X, ctx)
+        arr = arrays_of(X, ctx)
+        arr.bind()
+    N = int(X.shape[0])
+    assert int(U.shape[0]) >= N, "U must be aligned with X"
+    nwin = max(N - int(H), 0)
+    d_se = arr.empty((max(P, 1),))
+    E = arr.empty((P, nwin, nx)) if endpoints and nwin > 0 and P > 0 else None
+    ctx.check(ctx.lib.brov_window_endpoint_pop_dev(ctx.h, model, INTEGRATORS[integrator], P, pa, N, int(H), float(dt), _dptr(X), _dptr(U),
+                                                   int(bool(carry_lag)), _dptr(d_se), _dptr(E)), "brov_window_endpoint_pop_dev")
+    se = np.asarray(arr.download(d_se), dtype=np.float64)[:P]
+    rmse = np.sqrt(se / (nwin * nx)) if nwin > 0 else np.full(P, np.nan)
+    return (rmse, E) if endpoints else rmse
+
+
+def fd_normal_eq(endpoints, target, delta, weights=None, ctx=None):
+    """Finite-difference normal equations (include/brov2.h: brov_fd_normal_eq_dev).  endpoints [m+1, W, nx] (row block 0 = base,
+    block j+1 = base + delta[j] e_j) and target [W, nx] are device arrays; returns (JtJ [m,m], Jtr [m]) on the host."""
+    ctx = _ctx_of(endpoints, ctx)
+    _bind(endpoints, ctx)
+    m1, W, nx = (int(v) for v in endpoints.shape)
+    m = m1 - 1
+    assert tuple(int(v) for v in target.shape) == (W, nx), "target must be [W, nx]"
+    delta = as_f64(delta).reshape(-1)
+    assert delta.shape[0] == m, "one step per perturbed parameter"
+    w = None if weights is None else as_f64(weights).reshape(nx)
+    JtJ, Jtr = np.zeros((max(m, 0), max(m, 0))), np.zeros(max(m, 0))
+    ctx.check(ctx.lib.brov_fd_normal_eq_dev(ctx.h, nx, m, W, _dptr(endpoints), _dptr(target), delta.ctypes.data, _hptr(w),
+                                            JtJ.ctypes.data, Jtr.ctypes.data), "brov_fd_normal_eq_dev")
+    return JtJ, Jtr
 
 
 # ------------------------------------------------------------------------------------------ PINc network (pinc.py holds the host API)

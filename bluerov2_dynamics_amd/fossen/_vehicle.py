@@ -182,3 +182,22 @@ class VehicleBase:
         """multistep_rmse_endpoint_physics (training/train_tank_brov2_full_comparison.py:469-487)."""
         self._sync_params()
         return engine.window_rmse(self.MODEL, integrator, X, U, H, dt, carry_lag=carry_lag, ctx=self._ctx)
+
+    def fit_parameters(self, X, U, dt, H=10, integrator="euler", assign=True, **kwargs):
+        """Fit this vehicle's parameters to a recording (fossen/identify.py: fit_parameters; `free`, `iters`, `weights`, `bounds`,
+        ... pass through).  assign=True stores the fitted values in the attributes, so the next call uses them."""
+        from . import identify
+        res = identify.fit_parameters(self, X, U, dt, H=H, integrator=integrator, **kwargs)
+        if assign:
+            cur = None
+            for name, value in res.params.items():
+                if name in identify._CURRENT:
+                    if cur is None:
+                        cs = self.current_speed
+                        cur = np.zeros(3) if cs is None else np.array(cs, dtype=float).reshape(3)
+                    cur[identify._CURRENT.index(name)] = value
+                else:
+                    setattr(self, name, value)
+            if cur is not None:
+                self.current_speed = cur
+        return res

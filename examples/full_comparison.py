@@ -37,14 +37,17 @@ ROWS = ("Koopman", "Fossen (BlueROV2)", "Double Integrator", "PINc (ResDNN)")
 
 
 def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None,
-            pinc=None, pinc_train=None, pinc_seed=0):
+            pinc=None, pinc_train=None, pinc_seed=0, fit_fossen=False, fit_iters=20):
     """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc (the PINc network's
     weights: a PINcWeights, a .npz / .pt path, a state dict or the reference's PINcNet; thruster variant only) or pinc_row (its
     three RMSEs, computed elsewhere) or pinc_train (epochs: the network is trained on the train split with train_pinc, seed
     pinc_seed, and returned as `pinc_weights`) the table has the reference's four rows and `ranking` [4,3] gives each model's rank per
     horizon (0 = best), training/train_tank_brov2_full_comparison.py:996-1001.
     variant: "thruster" (8 PWM inputs, Euler angles), "wrench" (6-D body wrench, Euler angles), "quat" (wrench, quaternion
-    state; RK4 exists only for the thruster script in the reference)."""
+    state; RK4 exists only for the thruster script in the reference).
+    fit_fossen: also fit the Fossen model's damping to the train split (fossen/identify.py, H = 10, at most fit_iters iterations) and
+    score the fitted vehicle on the test split: `fossen_fitted` [3] and `fossen_fit` (the FitResult); printed as one more line under
+    the table, which -- like `table` and `ranking` -- is otherwise unchanged."""
     if sum(v is not None for v in (pinc, pinc_row, pinc_train)) > 1:
         raise ValueError("give the PINc network (pinc), its precomputed row (pinc_row) or the epochs to train it for (pinc_train), "
                          "not more than one")
@@ -95,15 +98,26 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
     elif pinc_row is not None:
         rows.append([float(v) for v in pinc_row])
     table = np.array(rows)
+    fitted_row = fit = None
+    if fit_fossen:
+        t0 = perf_counter()
+        rov_fit = make_rov()
+        fit = rov_fit.fit_parameters(Xtr, Utr, dt, H=10, integrator=integrator, iters=fit_iters)
+        t["fit_fossen"] = perf_counter() - t0
+        fitted_row = [rov_fit.multistep_rmse_endpoint(Xte, Ute, H, dt, integrator) for H in (1, 10, 100)]
     if verbose:
         print(f"\n[metrics] Endpoint RMSE (full {nx}D state) with identical evaluator:")
         print("  Model                 | 1-step RMSE | 10-step RMSE | 100-step RMSE")
         print("  ----------------------|------------:|-------------:|--------------:")
         for name, r in zip(ROWS, table):
             print(f"  {name:<21s} | {r[0]:11.6f} | {r[1]:12.6f} | {r[2]:13.6f}")
+        if fitted_row is not None:
+            print(f"  {'Fossen (fitted)':<21s} | {fitted_row[0]:11.6f} | {fitted_row[1]:12.6f} | {fitted_row[2]:13.6f}")
+            print(f"  [fit] train-split 10-step RMSE {fit.rmse_history[0]:.6f} -> {fit.rmse_history[-1]:.6f} in {sum(fit.accepted)} steps, "
+                  f"{fit.n_evals} window evaluations: " + ", ".join(f"{k} = {v:.4g}" for k, v in fit.params.items()))
         print("\n[timing] seconds:", {k: round(v, 4) for k, v in t.items()})
     return dict(table=table, timings=t, dt=dt, split=split, model=koop, ranking=np.argsort(np.argsort(table, axis=0), axis=0), rows=ROWS[:len(table)],
-                pinc_weights=pinc)
+                pinc_weights=pinc, fossen_fitted=None if fitted_row is None else np.array(fitted_row), fossen_fit=fit)
 
 
 if __name__ == "__main__":
@@ -120,8 +134,10 @@ if __name__ == "__main__":
                     help="PINc checkpoint (.pt state dict or .npz of its arrays): computes the fourth row on the engine")
     ap.add_argument("--pinc-train", type=int, default=None, metavar="EPOCHS",
                     help="train the PINc network on the train split for EPOCHS epochs on the engine, then compute the fourth row with it")
+    ap.add_argument("--fit-fossen", action="store_true",
+                    help="fit the Fossen model's damping to the train split at H = 10 and print a 'Fossen (fitted)' row under the table")
     a = ap.parse_args()
     if sum(v is not None for v in (a.pinc_row, a.pinc_ckpt, a.pinc_train)) > 1:
         ap.error("--pinc-row, --pinc-ckpt and --pinc-train are mutually exclusive")
     compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt,
-            pinc_train=a.pinc_train)
+            pinc_train=a.pinc_train, fit_fossen=a.fit_fossen)

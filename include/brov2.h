@@ -190,6 +190,30 @@ BROV_API int brov_window_endpoint_se_dev(brov_ctx* ctx, int model, int integrato
                                 const double* d_X, const double* d_U, int carry_lag,
                                 double* d_se_total, double* d_per_window /* [N-H], required */);
 
+/* ---- parameter identification: the window evaluator over a population, finite-difference normal equations ----------
+ * brov_window_endpoint_pop scores P parameter sets against one recording in one call: se[j] (and endpoints[j], the window end
+ * states x_end, [P][N-H][nx], NULL = not wanted) are what brov_set_params(&params[j]) followed by brov_window_endpoint_se gives,
+ * carried lag (carry_lag) and the four lag advances per RK4 step included.  The number of kernel launches does not depend on P
+ * (the candidate is a grid dimension).  params is a HOST array in both forms; the ctx's own parameters (brov_set_params) are
+ * neither read nor written.  Models: BROV_THRUSTER_EULER, BROV_WRENCH_EULER, BROV_WRENCH_QUAT (the double-integrator gains are
+ * not brov_params: BROV_ERR_ARG); 1 <= P <= 65535.  N <= H: se[j] = 0, nothing else written.
+ * rmse_j = sqrt(se[j] / ((N-H) * nx)).  se[j] is summed in a fixed order: the same bits from run to run. */
+BROV_API int brov_window_endpoint_pop(brov_ctx* ctx, int model, int integrator, int64_t P, const brov_params* params /* [P], host */,
+                             int64_t N, int64_t H, double dt, const double* X, const double* U, int carry_lag,
+                             double* se /* [P] */, double* endpoints /* [P][N-H][nx], NULL ok */);
+BROV_API int brov_window_endpoint_pop_dev(brov_ctx* ctx, int model, int integrator, int64_t P, const brov_params* params /* [P], host */,
+                                 int64_t N, int64_t H, double dt, const double* d_X, const double* d_U, int carry_lag,
+                                 double* d_se /* [P] */, double* d_endpoints /* [P][N-H][nx], NULL ok */);
+/* Normal equations of a Gauss-Newton / Levenberg-Marquardt step from endpoints scored at base (row block 0) and at
+ * base + delta_j e_j (row block j + 1), j = 0..m-1, 1 <= m <= 48, over W windows of nx coordinates:
+ *     J[(k,i)][j] = w_i (E_{j+1}[k][i] - E_0[k][i]) / delta_j,    r[(k,i)] = w_i (E_0[k][i] - target[k][i]),
+ *     JtJ = J^T J [m][m],  Jtr = J^T r [m].
+ * d_endpoints [m+1][W][nx] and d_target [W][nx] (= X[H:]) are device arrays; delta [m] (finite, non-zero), weight [nx] (NULL = 1),
+ * JtJ and Jtr are host arrays, valid on return.  Partial sums per block, added in index order, no atomics: the same bits from
+ * run to run. */
+BROV_API int brov_fd_normal_eq_dev(brov_ctx* ctx, int nx, int m, int64_t W, const double* d_endpoints, const double* d_target,
+                          const double* delta_host, const double* weight_host, double* JtJ_host, double* Jtr_host);
+
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
  * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.

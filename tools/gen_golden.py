@@ -12,6 +12,7 @@ Fixtures (all float64):
   fossen_rollouts.npz   config-2 stream, first 8 trajectories, 5000 RK4 / Euler steps
                         (every 50th state) + wrench / quaternion rollouts
   windows.npz           multistep_rmse_endpoint_physics (lag carried across windows)
+  fossen_pop.npz        the same loop with four parameter sets (nominal, damping changes, zb, a current) on 160 rows of windows.npz
   edmdc.npz             KoopmanEDMDc fit / fit_multi / evaluate / multistep_rmse / simulate
   edmdc_fit.npz         KoopmanEDMDc.fit at the class defaults (k=200, ridge=1e-8) and the tank script's settings (k=500, gamma=3,
                         ridge=0.1) on 10 000 samples: the cases where fit()'s own product order matters
@@ -282,6 +283,54 @@ def gen_windows():
     out["wq_onestep_rmse"] = np.float64(ref_wq.one_step_rmse_physics(Xq, TAU, dt))
     out["versions"] = versions()
     np.savez(os.path.join(OUT, "windows.npz"), **out)
+
+
+def gen_fossen_pop():
+    """fossen_pop.npz: multistep_rmse_endpoint_physics (full_comparison.py:469-487) with NON-nominal vehicles, for the population
+    evaluator.  That function builds its own BlueROV2, so its loop is restated here around the reference's simulate_physics and a
+    reference vehicle whose attributes were changed after construction -- only quantities the reference reads at call time
+    (damping, zb, current_speed; its Minv is frozen in __init__).  160 rows of the windows.npz data, Euler, H = 1 and 10."""
+    import train_tank_brov2_full_comparison as ref_eul
+    w = np.load(os.path.join(OUT, "windows.npz"))
+    dt = float(w["dt"])
+    X, U = w["X"][:160].copy(), w["U"][:160].copy()
+    lin, quad = ("Xu", "Yv", "Zw", "Kp", "Mq", "Nr"), tuple(n + "_abs" for n in ("Xu", "Yv", "Zw", "Kp", "Mq", "Nr"))
+
+    def nominal(rov):
+        pass
+
+    def quad13(rov):
+        for n in quad:
+            setattr(rov, n, getattr(rov, n) * 1.3)
+
+    def lin07_zb2(rov):
+        for n in lin:
+            setattr(rov, n, getattr(rov, n) * 0.7)
+        rov.zb = rov.zb * 2.0
+
+    def current(rov):
+        rov.current_speed = np.array([0.12, -0.07, 0.03])
+
+    Hs = (1, 10)
+    sets = (nominal, quad13, lin07_zb2, current)
+    rmse = np.zeros((len(Hs), len(sets)))
+    values = {}
+    for j, change in enumerate(sets):
+        for i, H in enumerate(Hs):
+            rov = RefThruster(dt=dt)          # one vehicle object for all windows of a run: the lag state is carried
+            change(rov)
+            se = 0.0
+            for k in range(len(X) - H):
+                x_end = ref_eul.simulate_physics(X[k], U[k:k + H], dt, rov)[-1]
+                err = x_end - X[k + H]
+                se += float(np.dot(err, err))
+            rmse[i, j] = np.sqrt(se / ((len(X) - H) * X.shape[1]))
+        values[f"lin_damp_{j}"] = np.array([getattr(rov, n) for n in lin], dtype=float)
+        values[f"quad_damp_{j}"] = np.array([getattr(rov, n) for n in quad], dtype=float)
+        values[f"zb_{j}"] = np.float64(rov.zb)
+        values[f"current_{j}"] = np.asarray(rov.current_speed, dtype=float).reshape(3)
+    np.savez(os.path.join(OUT, "fossen_pop.npz"), X=X, U=U, dt=np.float64(dt), H=np.array(Hs), rmse=rmse,
+             set_names=np.array([f.__name__ for f in sets]), versions=versions(), **values)
 
 
 # --------------------------------------------------------------------------- EDMDc
@@ -827,7 +876,7 @@ def gen_pinc_train():
     print("loss terms (fp64):", {k: v for k, v in out.items() if k.startswith("loss_f64")})
 
 
-GENS = dict(pinc_train=gen_pinc_train, pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
+GENS = dict(fossen_pop=gen_fossen_pop, pinc_train=gen_pinc_train, pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
