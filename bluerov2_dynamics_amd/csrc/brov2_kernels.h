@@ -17,15 +17,13 @@ hipError_t launch_thruster_forces(hipStream_t st, const DevParams& p, int64_t B,
 hipError_t launch_rollout(hipStream_t st, const FastParams* d_fp, int model, int integ, int lag_mode, int layout, int64_t B,
                           int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj,
                           int64_t stride, double* xT, int btu_staging);
-hipError_t launch_window_endpoint(hipStream_t st, const FastParams* d_fp, int model, int integ, int64_t N, int64_t H, double dt,
-                                  const double* X, const double* U, int carry_lag, const double* d_phi9,
-                                  double* d_resp, double* d_start, double* d_se, double* d_total);
-// The same evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y).  Candidate-major scratch: d_phi [P][18]
-// ([Phi | Phi^window_scan_chunk()] of each candidate), d_lag [P][N-H][18] and d_chunk [P][chunks][18] (thruster model with
-// carry_lag only), d_se [P][N-H]; d_total [P]; d_endpoints [P][N-H][nx] or nullptr.  The launch count does not depend on P.
-hipError_t launch_window_endpoint_pop(hipStream_t st, const FastParams* d_fp, int model, int integ, int P, int64_t N, int64_t H, double dt,
-                                      const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
-                                      double* d_chunk, double* d_se, double* d_total, double* d_endpoints);
+// The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major
+// scratch: d_phi [P][18] ([Phi | Phi^window_scan_chunk()] of each candidate), d_lag [P][N-H][18] and d_chunk [P][chunks][18]
+// (thruster model with carry_lag only), d_se [P][N-H]; d_total [P]; d_endpoints [P][N-H][nx] or nullptr.  The launch count does
+// not depend on P.
+hipError_t launch_window_endpoint(hipStream_t st, const FastParams* d_fp, int model, int integ, int P, int64_t N, int64_t H, double dt,
+                                  const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                  double* d_chunk, double* d_se, double* d_total, double* d_endpoints);
 // Finite-difference normal equations (rollout.hip): d_E [(m+1)][R], R = W nx; d_part fd_normal_blocks(R) x (m+1)(m+2)/2 doubles;
 // d_out = [JtJ (m x m) | Jtr (m)].
 int fd_normal_blocks(int64_t R);
@@ -116,10 +114,12 @@ hipError_t launch_extract_state(hipStream_t st, const PropShape& s, int64_t T1, 
 hipError_t launch_useq_t(hipStream_t st, const PropShape& s, int64_t T, const double* Us, double* Ust);
 int window_scan_chunk();
 // blocked scan of the windows' initial lag states (rollout.hip): x_{k+1} = Phi x_k + resp_k over nc lag banks of 3 states
-// (6: the Fossen evaluator's wrench space, 8: the PINc evaluator's thruster space).  d_phi9 [Phi | Phi^window_scan_chunk()],
-// d_resp [nwin][nc][3], d_start [nwin + nchunks][nc][3] (the chunk states behind the nwin start states), d_s0 [nc][3] or nullptr (zero)
-hipError_t launch_window_lag_scan(hipStream_t st, int nc, int64_t nwin, const double* d_phi9, const double* d_resp, double* d_start,
+// (6: the Fossen evaluator's wrench space, 8: the PINc evaluator's thruster space), for P candidates, in place.
+// d_phi [P][18] = [Phi | Phi^window_scan_chunk()], d_rs [P][nwin][nc][3]: the responses on entry, the start states on exit;
+// d_chunk [P][nchunks][nc][3]: scratch; d_s0 [nc][3] or nullptr (zero): the state before the first window, every candidate's
+hipError_t launch_window_lag_scan(hipStream_t st, int nc, int P, int64_t nwin, const double* d_phi, double* d_rs, double* d_chunk,
                                   const double* d_s0);
+// out[0] = the sum of v[0..n), a fixed-shape tree
 hipError_t launch_sum(hipStream_t st, int64_t n, const double* v, double* out);
 
 // ---- column statistics (colstats.hip) -------------------------------------------------------
@@ -244,11 +244,12 @@ constexpr int PINC_NPARAMS = 14541;
 hipError_t launch_pinc_forward(hipStream_t st, const float* w, int64_t B, const float* z, float* x_next);
 hipError_t launch_pinc_rollout(hipStream_t st, const float* w, const DevParams& p, int64_t B, int64_t T, double dt, const double* x0,
                                const double* U, double* lag_io, double* traj, int64_t stride, double* xT);
-// d_resp / d_start: scratch of launch_window_lag_scan (nc = 8), used when carry_lag; d_lag_io [8][3] (nullptr = zero) is the lag before
-// the first window and, with carry_lag, receives the lag after the last one; d_lag_starts [nwin][8][3] optional
+// d_lag [nwin][24] / d_chunk [chunks][24]: the arrays of launch_window_lag_scan (nc = 8, P = 1), used when carry_lag; d_lag_io [8][3]
+// (nullptr = zero) is the lag before the first window and, with carry_lag, receives the lag after the last one; d_lag_starts
+// [nwin][8][3] optional
 hipError_t launch_pinc_window_endpoint(hipStream_t st, const float* w, const DevParams& p, int64_t N, int64_t H, double dt,
-                                       const double* X, const double* U, int carry_lag, const double* d_phi9, double* d_resp,
-                                       double* d_start, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total);
+                                       const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                       double* d_chunk, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total);
 
 // ---- PINc training (pinc_train.hip) ------------------------------------------------------------
 constexpr int PINC_PART_STRIDE = PINC_NPARAMS + 3;    // one workgroup's partial: the gradient in blob order, then three loss sums
@@ -263,9 +264,9 @@ hipError_t launch_pinc_grad(hipStream_t st, const float* w, int B, const float* 
 // optional); ad != nullptr: clip to ad->max_norm and take AdamW step number `step` (1-based) on w, m, v in place
 hipError_t launch_pinc_reduce(hipStream_t st, int nparts, int stride, const float* part, int B, float* grad_out, float* loss_out,
                               float* norm_out, const PincAdam* ad, int64_t step, float* w, float* m, float* v);
-// one map vehicle over N consecutive samples U [N][8] -> tau [N][6]; d_lag_io [8][3] in / out; d_phi9 = [Ad | Ad^window_scan_chunk()],
-// d_resp [N][24], d_start [(N + chunks)][24]: scratch of launch_window_lag_scan (nc = 8)
-hipError_t launch_thruster_stream(hipStream_t st, const DevParams& p, int64_t N, const double* U, const double* d_phi9, double* d_resp,
-                                  double* d_start, double* d_lag_io, double* tau);
+// one map vehicle over N consecutive samples U [N][8] -> tau [N][6]; d_lag_io [8][3] in / out; d_phi = [Ad | Ad^window_scan_chunk()],
+// d_lag [N][24], d_chunk [chunks][24]: the arrays of launch_window_lag_scan (nc = 8, P = 1)
+hipError_t launch_thruster_stream(hipStream_t st, const DevParams& p, int64_t N, const double* U, const double* d_phi, double* d_lag,
+                                  double* d_chunk, double* d_lag_io, double* tau);
 
 }  // namespace brov

@@ -1208,29 +1208,50 @@ static void lag_window_phi(const DevParams& dp, int64_t samples, double Phi[9]) 
     std::memcpy(Phi, R, sizeof R);
 }
 
+static int64_t window_chunks(int64_t nwin) { return (nwin + window_scan_chunk() - 1) / window_scan_chunk(); }
+// [Phi | Phi^chunk], Phi = Ad^samples: the two matrices of the blocked scan (rollout.hip)
+static void lag_window_phi_pair(const DevParams& dp, int64_t samples, double out18[18]) {
+    lag_window_phi(dp, samples, out18);
+    lag_window_phi(dp, samples * window_scan_chunk(), out18 + 9);
+}
+
+// what window_impl takes from the arena: the pre-scan's arrays (thruster model with carried lag only)
+static size_t window_scratch(int model, int carry, int64_t P, int64_t nwin) {
+    if (model != BROV_THRUSTER_EULER || !carry) return 0;
+    return Arena::al(P * nwin * 18 * 8) + Arena::al(P * window_chunks(nwin) * 18 * 8) + Arena::al(P * 18 * 8);
+}
+// The evaluator for the P parameter sets d_fp [P] (device).  phi [P][18] (host): each candidate's lag_window_phi_pair, read with the
+// thruster model and carried lag only.  host_temps: the caller has uploads from temporaries of its own on the stream.
+static int window_impl(brov_ctx* c, const FastParams* d_fp, const double* phi, bool host_temps, int model, int integ, int P, int64_t N,
+                       int64_t H, double dt, const double* dX, const double* dU, int carry, double* d_se, double* d_total,
+                       double* d_endpoints, Arena& a) {
+    const int64_t nwin = N - H;
+    const bool scan = model == BROV_THRUSTER_EULER && carry;
+    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    if (scan) {
+        d_lag = a.take<double>(P * nwin * 18);
+        d_chunk = a.take<double>(P * window_chunks(nwin) * 18);
+        d_phi = a.take<double>(P * 18);
+        HIPCK(c, h2d_copy(c, d_phi, phi, (size_t)P * 18 * 8));
+    }
+    if (scan || host_temps) HIPCK(c, hipStreamSynchronize(c->stream));   // phi and the caller's arrays are temporaries
+    CallTimer t(c);
+    HIPCK(c, launch_window_endpoint(c->stream, d_fp, model, integ, P, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_se, d_total,
+                                    d_endpoints));
+    return BROV_OK;
+}
+
+// one parameter set: the ctx's own
 static int window_dev_impl(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* dX, const double* dU,
                            int carry, double* d_total, double* d_se, Arena& a) {
     const DevParams* dp;
     int rc = get_dp(c, dt, &dp);
     if (rc) return rc;
-    const int64_t nwin = N - H;
-    double *d_resp = nullptr, *d_start = nullptr, *d_phi = nullptr;
-    if (model == BROV_THRUSTER_EULER && carry) {
-        d_resp = a.take<double>(nwin * 18);
-        d_start = a.take<double>((nwin + (nwin + window_scan_chunk() - 1) / window_scan_chunk()) * 18);   // start states + chunk states
-        d_phi = a.take<double>(32);
-        double Phi[18];                             // Phi, Phi^chunk (blocked scan of rollout.hip)
-        const int64_t spw = H * (integ == BROV_RK4 ? 4 : 1);
-        lag_window_phi(*dp, spw, Phi);
-        lag_window_phi(*dp, spw * window_scan_chunk(), Phi + 9);
-        HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
-        HIPCK(c, hipStreamSynchronize(c->stream));   // Phi is a stack temporary
-    }
     if (model_is_di_h(model) && !c->di_set) return fail(c, BROV_ERR_ARG, "double-integrator model: call brov_set_di_gains first");
-    CallTimer t(c);
-    HIPCK(c, launch_window_endpoint(c->stream, model_is_di_h(model) ? c->d_fp_di : c->d_fp, model, integ, N, H, dt, dX, dU, carry, d_phi,
-                                    d_resp, d_start, d_se, d_total));
-    return BROV_OK;
+    double Phi[18];
+    lag_window_phi_pair(*dp, H * (integ == BROV_RK4 ? 4 : 1), Phi);
+    return window_impl(c, model_is_di_h(model) ? c->d_fp_di : c->d_fp, Phi, false, model, integ, 1, N, H, dt, dX, dU, carry, d_se, d_total,
+                       nullptr, a);
 }
 
 int brov_window_endpoint_se_dev(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* d_X,
@@ -1242,7 +1263,7 @@ int brov_window_endpoint_se_dev(brov_ctx* c, int model, int integ, int64_t N, in
     if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
     if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_dev: NULL array");
     Arena a(c);
-    int rc = a.reserve(Arena::al(nwin * 24 * 8) * 2 + Arena::al((nwin / window_scan_chunk() + 2) * 18 * 8) + 4096);
+    int rc = a.reserve(window_scratch(model, carry_lag, 1, nwin));
     if (rc) return rc;
     return window_dev_impl(c, model, integ, N, H, dt, d_X, d_U, carry_lag, d_se_total, d_per_window, a);
 }
@@ -1257,8 +1278,8 @@ int brov_window_endpoint_se(brov_ctx* c, int model, int integ, int64_t N, int64_
     DeviceGuard g(c);
     const int nx = NX(model), nu = NU(model);
     Arena a(c);
-    int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(nwin * 8) + Arena::al(nwin * 24 * 8) * 2 +
-                       Arena::al((nwin / window_scan_chunk() + 2) * 18 * 8) + 4096);
+    int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) +
+                       window_scratch(model, carry_lag, 1, nwin));
     if (rc) return rc;
     double* dX = a.take<double>(N * nx);
     double* dU = a.take<double>(N * nu);
@@ -1281,23 +1302,16 @@ static bool pop_args_ok(const brov_ctx* c, int model, int integ, int64_t P, cons
            (integ == BROV_EULER || integ == BROV_RK4) && P >= 1 && P <= 65535 && params && N >= 0 && H >= 0 && se;
 }
 static size_t window_pop_scratch(int model, int carry, int64_t P, int64_t nwin) {
-    size_t b = Arena::al(P * sizeof(FastParams)) + Arena::al(P * nwin * 8);
-    if (model == BROV_THRUSTER_EULER && carry) {
-        const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
-        b += Arena::al(P * nwin * 18 * 8) + Arena::al(P * nchunks * 18 * 8) + Arena::al(P * 18 * 8);
-    }
-    return b;
+    return Arena::al(P * sizeof(FastParams)) + Arena::al(P * nwin * 8) + window_scratch(model, carry, P, nwin);
 }
 static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, int64_t N, int64_t H, double dt,
                            const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints, Arena& a) {
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, BROV_ERR_ARG, "dt must be finite and > 0");
     const int64_t nwin = N - H;
     const bool scan = model == BROV_THRUSTER_EULER && carry;
-    const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
-    const int64_t spw = H * (integ == BROV_RK4 ? 4 : 1);
     // derive_fast once per candidate; one upload carries the whole FastParams[P] array (and one more the scan matrices)
     std::vector<FastParams> fp((size_t)P);
-    std::vector<double> phi(scan ? (size_t)P * 18 : 0);          // per candidate: Phi, Phi^chunk (blocked scan of rollout.hip)
+    std::vector<double> phi(scan ? (size_t)P * 18 : 0);
     for (int j = 0; j < P; ++j) {
         const brov_params& p = params[j];
         const double md[6] = {p.m - p.added_mass[0], p.m - p.added_mass[1], p.m - p.added_mass[2],
@@ -1307,26 +1321,12 @@ static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_
         DevParams dp;
         if (!derive(p, dt, dp)) return fail(c, BROV_ERR_ARG, "thruster-lag discretisation failed (singular Pade system)");
         derive_fast(p, dp, fp[j]);
-        if (scan) {
-            lag_window_phi(dp, spw, &phi[(size_t)j * 18]);
-            lag_window_phi(dp, spw * window_scan_chunk(), &phi[(size_t)j * 18 + 9]);
-        }
+        if (scan) lag_window_phi_pair(dp, H * (integ == BROV_RK4 ? 4 : 1), &phi[(size_t)j * 18]);
     }
     FastParams* d_fp = a.take<FastParams>(P);
     double* d_se = a.take<double>(P * nwin);
-    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
-    if (scan) {
-        d_lag = a.take<double>(P * nwin * 18);
-        d_chunk = a.take<double>(P * nchunks * 18);
-        d_phi = a.take<double>(P * 18);
-        HIPCK(c, h2d_copy(c, d_phi, phi.data(), phi.size() * 8));
-    }
-    HIPCK(c, hipStreamSynchronize(c->stream));   // fp / phi are locals
-    CallTimer t(c);
-    HIPCK(c, launch_window_endpoint_pop(c->stream, d_fp, model, integ, P, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_se, d_total,
-                                        d_endpoints));
-    return BROV_OK;
+    return window_impl(c, d_fp, phi.data(), true, model, integ, P, N, H, dt, dX, dU, carry, d_se, d_total, d_endpoints, a);
 }
 
 int brov_window_endpoint_pop_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
@@ -1337,7 +1337,7 @@ int brov_window_endpoint_pop_dev(brov_ctx* c, int model, int integ, int64_t P, c
     if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se, 0, (size_t)P * 8, c->stream)); return BROV_OK; }
     if (!d_X || !d_U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_dev: NULL array");
     Arena a(c);
-    int rc = a.reserve(window_pop_scratch(model, carry_lag, P, nwin) + 4096);
+    int rc = a.reserve(window_pop_scratch(model, carry_lag, P, nwin));
     if (rc) return rc;
     return window_pop_impl(c, model, integ, (int)P, params, N, H, dt, d_X, d_U, carry_lag, d_se, d_endpoints, a);
 }
@@ -1352,7 +1352,7 @@ int brov_window_endpoint_pop(brov_ctx* c, int model, int integ, int64_t P, const
     const int nx = NX(model), nu = NU(model);
     Arena a(c);
     int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(P * 8) + (endpoints ? Arena::al(P * nwin * nx * 8) : 0) +
-                       window_pop_scratch(model, carry_lag, P, nwin) + 4096);
+                       window_pop_scratch(model, carry_lag, P, nwin));
     if (rc) return rc;
     double* dX = a.take<double>(N * nx);
     double* dU = a.take<double>(N * nu);
@@ -1472,8 +1472,7 @@ int brov_pinc_rollout(brov_ctx* c, int64_t B, int64_t T, double dt, const double
 }
 
 static size_t pinc_window_scratch(int64_t nwin) {
-    const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
-    return Arena::al(nwin * 24 * 8) + Arena::al((nwin + nchunks) * 24 * 8) + Arena::al(32 * 8);
+    return Arena::al(nwin * 24 * 8) + Arena::al(window_chunks(nwin) * 24 * 8) + Arena::al(18 * 8);
 }
 
 static int pinc_window_impl(brov_ctx* c, int64_t N, int64_t H, double dt, const double* dX, const double* dU, int carry,
@@ -1482,20 +1481,18 @@ static int pinc_window_impl(brov_ctx* c, int64_t N, int64_t H, double dt, const 
     int rc = get_dp(c, dt, &dp);
     if (rc) return rc;
     const int64_t nwin = N - H;
-    double *d_resp = nullptr, *d_start = nullptr, *d_phi = nullptr;
+    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
     if (carry) {
-        const int64_t nchunks = (nwin + window_scan_chunk() - 1) / window_scan_chunk();
-        d_resp = a.take<double>(nwin * 24);
-        d_start = a.take<double>((nwin + nchunks) * 24);     // start states + chunk states
-        d_phi = a.take<double>(32);
+        d_lag = a.take<double>(nwin * 24);                    // responses, then start states
+        d_chunk = a.take<double>(window_chunks(nwin) * 24);
+        d_phi = a.take<double>(18);
         double Phi[18];                                       // Phi = Ad^H (one lag sample per step), Phi^chunk
-        lag_window_phi(*dp, H, Phi);
-        lag_window_phi(*dp, H * window_scan_chunk(), Phi + 9);
+        lag_window_phi_pair(*dp, H, Phi);
         HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
         HIPCK(c, hipStreamSynchronize(c->stream));            // Phi is a stack temporary
     }
     CallTimer t(c);
-    HIPCK(c, launch_pinc_window_endpoint(c->stream, c->d_pinc, *dp, N, H, dt, dX, dU, carry, d_phi, d_resp, d_start, d_lag_io,
+    HIPCK(c, launch_pinc_window_endpoint(c->stream, c->d_pinc, *dp, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_lag_io,
                                          d_lag_starts, d_se, d_total));
     return BROV_OK;
 }
@@ -1671,25 +1668,22 @@ int brov_pinc_train_end(brov_ctx* c) {
 }
 
 static size_t stream_scratch(int64_t N) {
-    const int64_t nchunks = (N + window_scan_chunk() - 1) / window_scan_chunk();
-    return Arena::al(N * 24 * 8) + Arena::al((N + nchunks) * 24 * 8) + Arena::al(32 * 8);
+    return Arena::al(N * 24 * 8) + Arena::al(window_chunks(N) * 24 * 8) + Arena::al(18 * 8);
 }
 
 static int thruster_stream_impl(brov_ctx* c, int64_t N, const double* dU, double dt, double* d_lag_io, double* d_tau, Arena& a) {
     const DevParams* dp;
     int rc = get_dp(c, dt, &dp);
     if (rc) return rc;
-    const int64_t nchunks = (N + window_scan_chunk() - 1) / window_scan_chunk();
-    double* d_resp = a.take<double>(N * 24);
-    double* d_start = a.take<double>((N + nchunks) * 24);
-    double* d_phi = a.take<double>(32);
+    double* d_lag = a.take<double>(N * 24);                   // responses, then start states
+    double* d_chunk = a.take<double>(window_chunks(N) * 24);
+    double* d_phi = a.take<double>(18);
     double Phi[18];                                           // Ad (one lag sample per row), Ad^chunk
-    lag_window_phi(*dp, 1, Phi);
-    lag_window_phi(*dp, window_scan_chunk(), Phi + 9);
+    lag_window_phi_pair(*dp, 1, Phi);
     HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
     HIPCK(c, hipStreamSynchronize(c->stream));                // Phi is a stack temporary
     CallTimer t(c);
-    HIPCK(c, launch_thruster_stream(c->stream, *dp, N, dU, d_phi, d_resp, d_start, d_lag_io, d_tau));
+    HIPCK(c, launch_thruster_stream(c->stream, *dp, N, dU, d_phi, d_lag, d_chunk, d_lag_io, d_tau));
     return BROV_OK;
 }
 

@@ -282,20 +282,20 @@ hipError_t launch_pinc_rollout(hipStream_t st, const float* w, const DevParams& 
 }
 
 hipError_t launch_pinc_window_endpoint(hipStream_t st, const float* w, const DevParams& p, int64_t N, int64_t H, double dt,
-                                       const double* X, const double* U, int carry_lag, const double* d_phi9, double* d_resp,
-                                       double* d_start, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total) {
+                                       const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                       double* d_chunk, double* d_lag_io, double* d_lag_starts, double* d_se, double* d_total) {
     const int64_t nwin = N - H;
     if (nwin <= 0) return hipSuccess;
     const double* lag_start = nullptr;
     if (carry_lag) {
-        hipLaunchKernelGGL(pinc_lag_response_kernel, dim3((unsigned)((nwin * 8 + 255) / 256)), dim3(256), 0, st, p, nwin, H, U, d_resp);
+        hipLaunchKernelGGL(pinc_lag_response_kernel, dim3((unsigned)((nwin * 8 + 255) / 256)), dim3(256), 0, st, p, nwin, H, U, d_lag);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-        e = launch_window_lag_scan(st, 8, nwin, d_phi9, d_resp, d_start, d_lag_io);
+        e = launch_window_lag_scan(st, 8, 1, nwin, d_phi, d_lag, d_chunk, d_lag_io);      // responses -> start states, in place
         if (e != hipSuccess) return e;
-        lag_start = d_start;
+        lag_start = d_lag;
         if (d_lag_starts) {
-            e = hipMemcpyAsync(d_lag_starts, d_start, (size_t)nwin * 24 * sizeof(double), hipMemcpyDeviceToDevice, st);
+            e = hipMemcpyAsync(d_lag_starts, d_lag, (size_t)nwin * 24 * sizeof(double), hipMemcpyDeviceToDevice, st);
             if (e != hipSuccess) return e;
         }
     }

@@ -491,15 +491,15 @@ hipError_t launch_pinc_reduce(hipStream_t st, int nparts, int stride, const floa
     return hipGetLastError();
 }
 
-hipError_t launch_thruster_stream(hipStream_t st, const DevParams& p, int64_t N, const double* U, const double* d_phi9, double* d_resp,
-                                  double* d_start, double* d_lag_io, double* tau) {
+hipError_t launch_thruster_stream(hipStream_t st, const DevParams& p, int64_t N, const double* U, const double* d_phi, double* d_lag,
+                                  double* d_chunk, double* d_lag_io, double* tau) {
     if (N <= 0) return hipSuccess;
-    hipLaunchKernelGGL(stream_resp_kernel, dim3((unsigned)((N * 8 + 255) / 256)), dim3(256), 0, st, p, N, U, d_resp);
+    hipLaunchKernelGGL(stream_resp_kernel, dim3((unsigned)((N * 8 + 255) / 256)), dim3(256), 0, st, p, N, U, d_lag);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    e = launch_window_lag_scan(st, 8, N, d_phi9, d_resp, d_start, d_lag_io);
+    e = launch_window_lag_scan(st, 8, 1, N, d_phi, d_lag, d_chunk, d_lag_io);      // responses -> start states, in place
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(stream_tau_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p, N, U, d_start, tau, d_lag_io);
+    hipLaunchKernelGGL(stream_tau_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, p, N, U, d_lag, tau, d_lag_io);
     return hipGetLastError();
 }
 

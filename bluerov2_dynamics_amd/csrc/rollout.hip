@@ -720,12 +720,17 @@ __global__ void __launch_bounds__(256) rollout_btu_lds_kernel(const FastParams* 
 
 // ---------------------------------------------------------------------------------------
 // K3: sliding-window endpoint error (multistep_rmse_endpoint_physics,
-// training/train_tank_brov2_full_comparison.py:469-487).  Quirk Q2: the reference uses ONE
-// vehicle object for all windows, so window k starts from the lag state window k-1 left.
+// training/train_tank_brov2_full_comparison.py:469-487) for P parameter sets at once; one set (the ctx's own) is P = 1.
+// Quirk Q2: the reference uses ONE vehicle object for all windows, so window k starts from the lag state window k-1 left.
 // The lag bank is LTI and driven by the commands only, so:
 //   (A) zero-state response b_k of each window (parallel over windows),
-//   (B) x_{k+1} = Phi x_k + b_k, Phi = Ad^(samples per window)  (sequential, 8 lanes, 9 FMA/iter),
+//   (B) x_{k+1} = Phi x_k + b_k, Phi = Ad^(samples per window)  (blocked scan, below),
 //   (C) every window is an independent lane starting from its own x_k.
+// pg is a FastParams[P] array; the candidate is blockIdx.y (blockIdx.x where one block serves a candidate), uniform per block,
+// so as_constant(pg + blockIdx.y) keeps every constant read a scalar load.  Candidate j computes what
+// brov_set_params(params[j]) + brov_window_endpoint_se computes.  The matrices of (B) are per candidate because the
+// acceleration-space lag folds in Minv T.  Per-candidate arrays are candidate-major: lag [P][nwin][18], chunk [P][nchunks][18],
+// phi [P][18], se [P][nwin], endpoints [P][nwin][NX].
 // ---------------------------------------------------------------------------------------
 template <int NSUB>
 __global__ void __launch_bounds__(256) window_lag_response_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H,
@@ -735,23 +740,25 @@ __global__ void __launch_bounds__(256) window_lag_response_kernel(const FastPara
     LagZ lz;
     lz.zero();
     for (int64_t t = 0; t < H; ++t) {
-        const CFP pp = relaunder(as_constant(pg));
+        const CFP pp = relaunder(as_constant(pg + blockIdx.y));
         double u[8], fcmd[8], acmd[6];
         load_row<8>(U + (k + t) * 8, u);
         command_accel<MODEL_THRUSTER_EULER, false>(pp, u, fcmd, acmd);
         lz.advance(NSUB == 4 ? pp->A4 : pp->A1, NSUB == 4 ? pp->b4 : pp->b1, acmd);
     }
-    store_row<18>(resp + k * 18, &lz.z[0][0]);
+    store_row<18>(resp + ((int64_t)blockIdx.y * nwin + k) * 18, &lz.z[0][0]);
 }
 
-// start[k] = acceleration-space lag state at the beginning of window k; start[0] = 0 (fresh vehicle object):
+// start[k] = lag state at the beginning of window k:
 //     x_{k+1} = Phi x_k + b_k,  Phi = Ad^(samples per window), the same matrix for every window.
-// Blocked scan over chunks of WSCAN_CHUNK windows, one lane per (chunk, wrench component):
+// Blocked scan over chunks of WSCAN_CHUNK windows, one lane per (chunk, lag bank):
 //   (1) chunk_end[c]   = the recurrence over chunk c from a zero state               (parallel over chunks)
 //   (2) chunk_start[c] : S_{c+1} = Phi^CHUNK S_c + chunk_end[c]                      (sequential over nwin/CHUNK chunks)
 //   (3) start[k]       = the recurrence over chunk c from chunk_start[c]             (parallel over chunks)
 // A single sequential pass over all windows (the first version) paid one exposed global-memory latency per window:
 // 11 ms for the reference's 45 723 windows, more than everything else in the evaluator together.
+// NC lag banks of 3 states per window: 6 wrench components (the Fossen evaluator, acceleration space) or 8 thrusters (the PINc
+// evaluator and the thruster stream, pinc.hip / pinc_train.hip, thruster space).  phi [P][18] = [Phi | Phi^WSCAN_CHUNK].
 constexpr int WSCAN_CHUNK = 64;
 
 __device__ __forceinline__ void wscan_step(const double P[9], double& x0, double& x1, double& x2, double b0, double b1, double b2) {
@@ -761,46 +768,50 @@ __device__ __forceinline__ void wscan_step(const double P[9], double& x0, double
     x0 = n0; x1 = n1; x2 = n2;
 }
 
-// phase 1 (store_start = 0): chunk_io[c] <- end state of chunk c from zero;  phase 3 (store_start = 1): start[k] for the
-// chunk's windows, beginning from chunk_io[c].  NC lag banks of 3 states per window: 6 wrench components (the Fossen evaluator,
-// acceleration space) or 8 thrusters (the PINc evaluator, pinc.hip, thruster space).
+// phases 1 (store_start = 0: chunk_io[c] <- end state of chunk c from zero) and 3 (store_start = 1: the chunk's start states,
+// beginning from chunk_io[c]) for candidate blockIdx.y.  In place: phase 3 writes each start state over the response it has just
+// consumed, so rs [P][nwin][NC][3] holds the responses on entry and the start states on exit.
 template <int NC>
-__global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, const double* __restrict__ Phi9, const double* __restrict__ resp,
-                                                              double* __restrict__ chunk_io, double* __restrict__ start, int store_start) {
+__global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, int64_t nchunks, const double* __restrict__ phi,
+                                                              double* rs, double* __restrict__ chunk_io, int store_start) {
     constexpr int W = NC * 3;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t c = g / NC;
     const int i = (int)(g - c * NC);
     const int64_t k0 = c * WSCAN_CHUNK;
     if (k0 >= nwin) return;
+    const int64_t j = blockIdx.y;
     double P[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) P[j] = Phi9[j];
+    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + q];
+    double* ce = chunk_io + (j * nchunks + c) * W + i * 3;
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    if (store_start) { x0 = chunk_io[c * W + i * 3]; x1 = chunk_io[c * W + i * 3 + 1]; x2 = chunk_io[c * W + i * 3 + 2]; }
+    if (store_start) { x0 = ce[0]; x1 = ce[1]; x2 = ce[2]; }
     const int64_t k1 = k0 + WSCAN_CHUNK < nwin ? k0 + WSCAN_CHUNK : nwin;
     for (int64_t k = k0; k < k1; ++k) {
-        const double* r = resp + k * W + i * 3;
-        if (store_start) { double* s = start + k * W + i * 3; s[0] = x0; s[1] = x1; s[2] = x2; }
-        wscan_step(P, x0, x1, x2, r[0], r[1], r[2]);
+        double* r = rs + (j * nwin + k) * W + i * 3;
+        const double r0 = r[0], r1 = r[1], r2 = r[2];
+        if (store_start) { r[0] = x0; r[1] = x1; r[2] = x2; }
+        wscan_step(P, x0, x1, x2, r0, r1, r2);
     }
-    if (!store_start) { chunk_io[c * W + i * 3] = x0; chunk_io[c * W + i * 3 + 1] = x1; chunk_io[c * W + i * 3 + 2] = x2; }
+    if (!store_start) { ce[0] = x0; ce[1] = x1; ce[2] = x2; }
 }
 
-// phase 2: in place, chunk_io[c] (end-from-zero) -> state at the beginning of chunk c.  PhiC9 = Phi^WSCAN_CHUNK.
-// s0 [NC][3]: state before the first window (nullptr = zero, a fresh vehicle).
+// phase 2, one block per candidate: in place, chunk_io[c] (end-from-zero) -> state at the beginning of chunk c.
+// s0 [NC][3]: state before the first window, the same for every candidate (nullptr = zero, a fresh vehicle).
 template <int NC>
-__global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, const double* __restrict__ PhiC9, double* __restrict__ chunk_io,
+__global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, const double* __restrict__ phi, double* __restrict__ chunk_io,
                                                              const double* __restrict__ s0) {
     constexpr int W = NC * 3;
     const int i = threadIdx.x;  // lag bank
     if (i >= NC) return;
+    const int64_t j = blockIdx.x;
     double P[9];
 #pragma unroll
-    for (int j = 0; j < 9; ++j) P[j] = PhiC9[j];
+    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + 9 + q];
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
     if (s0) { x0 = s0[i * 3]; x1 = s0[i * 3 + 1]; x2 = s0[i * 3 + 2]; }
-    double* e = chunk_io + i * 3;
+    double* e = chunk_io + j * nchunks * W + i * 3;
     double b0 = 0, b1 = 0, b2 = 0;
     if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; }
     for (int64_t c = 0; c < nchunks; ++c) {
@@ -811,17 +822,19 @@ __global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, co
     }
 }
 
-template <int MODEL, int INTEG, bool GENERIC>
+template <int MODEL, int INTEG>
 __global__ void __launch_bounds__(256) window_endpoint_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H, double dt,
                                                               const double* __restrict__ X, const double* __restrict__ U,
-                                                              const double* __restrict__ lag_start, double* __restrict__ se) {
+                                                              const double* __restrict__ lag_start, double* __restrict__ se,
+                                                              double* __restrict__ endpoints) {
     constexpr int NX = Dims<MODEL>::NX, NU = Dims<MODEL>::NU;
     __shared__ double2 qt[4];
     init_quadrant_table(qt);
     __syncthreads();
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nwin) return;
-    const CFP p = as_constant(pg);
+    const int64_t row = (int64_t)blockIdx.y * nwin + k;       // window k of candidate blockIdx.y
+    const CFP p = as_constant(pg + blockIdx.y);
     HotConsts h;
     load_hot(p, h);
     double x[NX];
@@ -829,36 +842,38 @@ __global__ void __launch_bounds__(256) window_endpoint_kernel(const FastParams* 
     LagZ lz;
     double Xl[8][3];
     if constexpr (MODEL == MODEL_THRUSTER_EULER) {
-        if (lag_start) load_row<18>(lag_start + k * 18, &lz.z[0][0]);
+        if (lag_start) load_row<18>(lag_start + row * 18, &lz.z[0][0]);
         else lz.zero();
-        if constexpr (!GENERIC) lz.to_observer(p);
     }
     for (int64_t t = 0; t < H; ++t) {
         double u[NU];
         load_row<NU>(U + (k + t) * NU, u);   // lane k reads row k+t: coalesced across the wave
         // full sin/cos at every step (no carry): the evaluator's windows are short, and recorded wrench sequences drive the
-        // open-loop models far off the data (RMSE ~ 20), where every ulp is amplified
-        step_fast<MODEL, INTEG, 0, false, GENERIC>(h, p, dt, x, u, lz, Xl, qt);
+        // open-loop models far off the data (RMSE ~ 20), where every ulp is amplified.  The GENERIC step (current / xb, yb
+        // branches) whatever the candidates' flags say: one kernel serves mixed populations, and this is not the benchmark path
+        step_fast<MODEL, INTEG, 0, false, true>(h, p, dt, x, u, lz, Xl, qt);
     }
     double ref[NX], e = 0.0;
     load_row<NX>(X + (k + H) * NX, ref);
 #pragma unroll
     for (int i = 0; i < NX; ++i) { const double d = x[i] - ref[i]; e = fma(d, d, e); }
-    se[k] = e;
+    se[row] = e;
+    if (endpoints) store_row<NX>(endpoints + row * NX, x);   // lane k writes row k of its candidate
 }
 
-// Deterministic sum of n doubles: fixed-shape tree, one block.  out[0] = sum.
+// Deterministic sum of n doubles per candidate blockIdx.x: fixed-shape tree, one block each.  out[j] = sum of v[j][0..n).
 __global__ void __launch_bounds__(1024) sum_kernel(int64_t n, const double* __restrict__ v, double* __restrict__ out) {
     __shared__ double sh[1024];
+    const double* vj = v + (int64_t)blockIdx.x * n;
     double a = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) a += v[i];
+    for (int64_t i = threadIdx.x; i < n; i += 1024) a += vj[i];
     sh[threadIdx.x] = a;
     __syncthreads();
     for (int s = 512; s > 0; s >>= 1) {
         if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
         __syncthreads();
     }
-    if (threadIdx.x == 0) out[0] = sh[0];
+    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
 // ---------------------------------------------------------------------------------------
@@ -966,242 +981,67 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* p, int model, int in
     }
 }
 
-template <int MODEL, int INTEG>
-static hipError_t launch_window_t(hipStream_t st, const FastParams* p, int64_t nwin, int64_t H, double dt, const double* X,
-                                  const double* U, const double* lag_start, double* se) {
-    // the evaluator always uses the generic form (current / xb, yb branches): it is short-lived and not the benchmark path
-    hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG, true>), dim3(nblk(nwin, 256)), dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se);
-    return hipGetLastError();
-}
-// scratch: resp [nwin][18], start [nwin][18], phi [9] (device) -- only used for the thruster model with carry_lag
 int window_scan_chunk() { return WSCAN_CHUNK; }
 
-hipError_t launch_window_lag_scan(hipStream_t st, int nc, int64_t nwin, const double* d_phi9, const double* d_resp, double* d_start,
-                                  const double* d_s0) {
-    if (nwin <= 0) return hipSuccess;
-    // d_phi9: [Phi (9) | Phi^WSCAN_CHUNK (9)]; the chunk states live behind the nwin start states in d_start
+template <int NC>
+static hipError_t launch_window_lag_scan_n(hipStream_t st, int P, int64_t nwin, const double* d_phi, double* d_rs, double* d_chunk,
+                                           const double* d_s0) {
     const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
-    double* d_chunk = d_start + nwin * nc * 3;
-    if (nc == 6) {
-        hipLaunchKernelGGL(window_lag_chunk_kernel<6>, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_scan_kernel<6>, dim3(1), dim3(64), 0, st, nchunks, d_phi9 + 9, d_chunk, d_s0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_chunk_kernel<6>, dim3(nblk(nchunks * 6, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 1);
-    } else {
-        hipLaunchKernelGGL(window_lag_chunk_kernel<8>, dim3(nblk(nchunks * 8, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_scan_kernel<8>, dim3(1), dim3(64), 0, st, nchunks, d_phi9 + 9, d_chunk, d_s0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_chunk_kernel<8>, dim3(nblk(nchunks * 8, 256)), dim3(256), 0, st, nwin, d_phi9, d_resp, d_chunk, d_start, 1);
-    }
+    const dim3 gc(nblk(nchunks * NC, 256), (unsigned)P);
+    hipLaunchKernelGGL(window_lag_chunk_kernel<NC>, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 0);
+    BROV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(window_lag_scan_kernel<NC>, dim3((unsigned)P), dim3(64), 0, st, nchunks, d_phi, d_chunk, d_s0);
+    BROV_LAUNCH_CHECK();
+    hipLaunchKernelGGL(window_lag_chunk_kernel<NC>, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 1);
     return hipGetLastError();
 }
-
-hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model, int integ, int64_t N, int64_t H, double dt,
-                                  const double* X, const double* U, int carry_lag, const double* d_phi9,
-                                  double* d_resp, double* d_start, double* d_se, double* d_total) {
-    const int64_t nwin = N - H;
-    if (nwin <= 0) return hipSuccess;
-    const double* lag_start = nullptr;
-    if (model == MODEL_THRUSTER_EULER && carry_lag) {
-        if (integ == INTEG_RK4)
-            hipLaunchKernelGGL(window_lag_response_kernel<4>, dim3(nblk(nwin, 256)), dim3(256), 0, st, p, nwin, H, U, d_resp);
-        else
-            hipLaunchKernelGGL(window_lag_response_kernel<1>, dim3(nblk(nwin, 256)), dim3(256), 0, st, p, nwin, H, U, d_resp);
-        BROV_LAUNCH_CHECK();
-        const hipError_t e = launch_window_lag_scan(st, 6, nwin, d_phi9, d_resp, d_start, nullptr);
-        if (e != hipSuccess) return e;
-        lag_start = d_start;
-    }
-    hipError_t e;
-    if (model == MODEL_THRUSTER_EULER)
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_THRUSTER_EULER, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_THRUSTER_EULER, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    else if (model == MODEL_WRENCH_EULER)
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_WRENCH_EULER, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_WRENCH_EULER, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    else if (model == MODEL_WRENCH_QUAT)
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_WRENCH_QUAT, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_WRENCH_QUAT, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    else if (model == MODEL_DI_THRUSTER_EULER)
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_DI_THRUSTER_EULER, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_DI_THRUSTER_EULER, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    else if (model == MODEL_DI_WRENCH_EULER)
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_DI_WRENCH_EULER, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_DI_WRENCH_EULER, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    else
-        e = integ == INTEG_RK4 ? launch_window_t<MODEL_DI_WRENCH_QUAT, INTEG_RK4>(st, p, nwin, H, dt, X, U, lag_start, d_se)
-                               : launch_window_t<MODEL_DI_WRENCH_QUAT, INTEG_EULER>(st, p, nwin, H, dt, X, U, lag_start, d_se);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(1024), 0, st, nwin, d_se, d_total);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// K3p: the window evaluator over a POPULATION of parameter sets (parameter identification, fossen/identify.py).
-// pg is a FastParams[P] array; the candidate is blockIdx.y, uniform per block, so as_constant(pg + blockIdx.y) keeps every
-// constant read a scalar load exactly as in K3.  Candidate j runs the arithmetic of K3 on its own constants: same step
-// function, same order, same fixed-shape sum -- what brov_set_params(params[j]) + brov_window_endpoint_se computes.
-// The carried-lag pre-scan is batched the same way; its matrices (Phi, Phi^WSCAN_CHUNK) are per candidate because the
-// acceleration-space lag folds in Minv T.  Per-candidate arrays are candidate-major: resp/start [P][nwin][18],
-// chunk [P][nchunks][18], phi [P][18], se [P][nwin], endpoints [P][nwin][NX].
-// ---------------------------------------------------------------------------------------
-template <int NSUB>
-__global__ void __launch_bounds__(256) window_lag_response_pop_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H,
-                                                                      const double* __restrict__ U, double* __restrict__ resp) {
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nwin) return;
-    LagZ lz;
-    lz.zero();
-    for (int64_t t = 0; t < H; ++t) {
-        const CFP pp = relaunder(as_constant(pg + blockIdx.y));
-        double u[8], fcmd[8], acmd[6];
-        load_row<8>(U + (k + t) * 8, u);
-        command_accel<MODEL_THRUSTER_EULER, false>(pp, u, fcmd, acmd);
-        lz.advance(NSUB == 4 ? pp->A4 : pp->A1, NSUB == 4 ? pp->b4 : pp->b1, acmd);
-    }
-    store_row<18>(resp + ((int64_t)blockIdx.y * nwin + k) * 18, &lz.z[0][0]);
-}
-
-// phases 1 and 3 of the blocked scan (window_lag_chunk_kernel) for candidate blockIdx.y.  Phase 3 writes the start states over the
-// responses it has just consumed (rs holds resp on entry, start on exit): the population form keeps one [P][nwin][18] array.
-__global__ void __launch_bounds__(256) window_lag_chunk_pop_kernel(int64_t nwin, int64_t nchunks, const double* __restrict__ phi,
-                                                                  double* rs, double* __restrict__ chunk_io, int store_start) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t c = g / 6;
-    const int i = (int)(g - c * 6);
-    const int64_t k0 = c * WSCAN_CHUNK;
-    if (k0 >= nwin) return;
-    const int64_t j = blockIdx.y;
-    double P[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + q];
-    double* ce = chunk_io + (j * nchunks + c) * 18 + i * 3;
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    if (store_start) { x0 = ce[0]; x1 = ce[1]; x2 = ce[2]; }
-    const int64_t k1 = k0 + WSCAN_CHUNK < nwin ? k0 + WSCAN_CHUNK : nwin;
-    for (int64_t k = k0; k < k1; ++k) {
-        double* r = rs + (j * nwin + k) * 18 + i * 3;
-        const double r0 = r[0], r1 = r[1], r2 = r[2];
-        if (store_start) { r[0] = x0; r[1] = x1; r[2] = x2; }
-        wscan_step(P, x0, x1, x2, r0, r1, r2);
-    }
-    if (!store_start) { ce[0] = x0; ce[1] = x1; ce[2] = x2; }
-}
-
-// phase 2 (window_lag_scan_kernel from a zero state): one block per candidate
-__global__ void __launch_bounds__(64) window_lag_scan_pop_kernel(int64_t nchunks, const double* __restrict__ phi, double* __restrict__ chunk_io) {
-    const int i = threadIdx.x;  // lag bank
-    if (i >= 6) return;
-    const int64_t j = blockIdx.x;
-    double P[9];
-#pragma unroll
-    for (int q = 0; q < 9; ++q) P[q] = phi[j * 18 + 9 + q];
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0;
-    double* e = chunk_io + j * nchunks * 18 + i * 3;
-    double b0 = 0, b1 = 0, b2 = 0;
-    if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; }
-    for (int64_t c = 0; c < nchunks; ++c) {
-        const double c0 = b0, c1 = b1, c2 = b2;
-        if (c + 1 < nchunks) { b0 = e[(c + 1) * 18 + 0]; b1 = e[(c + 1) * 18 + 1]; b2 = e[(c + 1) * 18 + 2]; }
-        e[c * 18 + 0] = x0; e[c * 18 + 1] = x1; e[c * 18 + 2] = x2;
-        wscan_step(P, x0, x1, x2, c0, c1, c2);
-    }
-}
-
-template <int MODEL, int INTEG>
-__global__ void __launch_bounds__(256) window_endpoint_pop_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H, double dt,
-                                                                  const double* __restrict__ X, const double* __restrict__ U,
-                                                                  const double* __restrict__ lag_start, double* __restrict__ se,
-                                                                  double* __restrict__ endpoints) {
-    constexpr int NX = Dims<MODEL>::NX, NU = Dims<MODEL>::NU;
-    __shared__ double2 qt[4];
-    init_quadrant_table(qt);
-    __syncthreads();
-    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= nwin) return;
-    const int64_t row = (int64_t)blockIdx.y * nwin + k;       // window k of candidate blockIdx.y
-    const CFP p = as_constant(pg + blockIdx.y);
-    HotConsts h;
-    load_hot(p, h);
-    double x[NX];
-    load_row<NX>(X + k * NX, x);
-    LagZ lz;
-    double Xl[8][3];
-    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
-        if (lag_start) load_row<18>(lag_start + row * 18, &lz.z[0][0]);
-        else lz.zero();
-    }
-    for (int64_t t = 0; t < H; ++t) {
-        double u[NU];
-        load_row<NU>(U + (k + t) * NU, u);
-        // the GENERIC step whatever the candidates' flags say, as in K3: one kernel serves mixed populations
-        step_fast<MODEL, INTEG, 0, false, true>(h, p, dt, x, u, lz, Xl, qt);
-    }
-    double ref[NX], e = 0.0;
-    load_row<NX>(X + (k + H) * NX, ref);
-#pragma unroll
-    for (int i = 0; i < NX; ++i) { const double d = x[i] - ref[i]; e = fma(d, d, e); }
-    se[row] = e;
-    if (endpoints) store_row<NX>(endpoints + row * NX, x);   // lane k writes row k of its candidate
-}
-
-// sum_kernel per candidate: out[j] = sum of v[j][0..n), the same fixed-shape tree
-__global__ void __launch_bounds__(1024) sum_pop_kernel(int64_t n, const double* __restrict__ v, double* __restrict__ out) {
-    __shared__ double sh[1024];
-    const double* vj = v + (int64_t)blockIdx.x * n;
-    double a = 0.0;
-    for (int64_t i = threadIdx.x; i < n; i += 1024) a += vj[i];
-    sh[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = 512; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
+hipError_t launch_window_lag_scan(hipStream_t st, int nc, int P, int64_t nwin, const double* d_phi, double* d_rs, double* d_chunk,
+                                  const double* d_s0) {
+    if (nwin <= 0 || P <= 0) return hipSuccess;
+    return nc == 6 ? launch_window_lag_scan_n<6>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0)
+                   : launch_window_lag_scan_n<8>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0);
 }
 
 template <int MODEL>
-static hipError_t launch_window_pop_m(hipStream_t st, const FastParams* p, int integ, int P, int64_t nwin, int64_t H, double dt,
-                                      const double* X, const double* U, const double* lag_start, double* se, double* endpoints) {
+static hipError_t launch_window_m(hipStream_t st, const FastParams* p, int integ, int P, int64_t nwin, int64_t H, double dt,
+                                  const double* X, const double* U, const double* lag_start, double* se, double* endpoints) {
     const dim3 grid(nblk(nwin, 256), (unsigned)P);
     if (integ == INTEG_RK4)
-        hipLaunchKernelGGL((window_endpoint_pop_kernel<MODEL, INTEG_RK4>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_RK4>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
     else
-        hipLaunchKernelGGL((window_endpoint_pop_kernel<MODEL, INTEG_EULER>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_EULER>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
     return hipGetLastError();
 }
 
 // Six launches with carry_lag on the thruster model, two otherwise, whatever P is.
-hipError_t launch_window_endpoint_pop(hipStream_t st, const FastParams* p, int model, int integ, int P, int64_t N, int64_t H, double dt,
-                                      const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
-                                      double* d_chunk, double* d_se, double* d_total, double* d_endpoints) {
+hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model, int integ, int P, int64_t N, int64_t H, double dt,
+                                  const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                  double* d_chunk, double* d_se, double* d_total, double* d_endpoints) {
     const int64_t nwin = N - H;
     if (nwin <= 0 || P <= 0) return hipSuccess;
     const double* lag_start = nullptr;
     if (model == MODEL_THRUSTER_EULER && carry_lag) {
-        const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
-        const dim3 gw(nblk(nwin, 256), (unsigned)P), gc(nblk(nchunks * 6, 256), (unsigned)P);
+        const dim3 gw(nblk(nwin, 256), (unsigned)P);
         if (integ == INTEG_RK4)
-            hipLaunchKernelGGL(window_lag_response_pop_kernel<4>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
+            hipLaunchKernelGGL(window_lag_response_kernel<4>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
         else
-            hipLaunchKernelGGL(window_lag_response_pop_kernel<1>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
+            hipLaunchKernelGGL(window_lag_response_kernel<1>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
         BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_chunk_pop_kernel, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_lag, d_chunk, 0);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_scan_pop_kernel, dim3((unsigned)P), dim3(64), 0, st, nchunks, d_phi, d_chunk);
-        BROV_LAUNCH_CHECK();
-        hipLaunchKernelGGL(window_lag_chunk_pop_kernel, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_lag, d_chunk, 1);
-        BROV_LAUNCH_CHECK();
+        const hipError_t e = launch_window_lag_scan(st, 6, P, nwin, d_phi, d_lag, d_chunk, nullptr);
+        if (e != hipSuccess) return e;
         lag_start = d_lag;
     }
     hipError_t e;
-    if (model == MODEL_THRUSTER_EULER) e = launch_window_pop_m<MODEL_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
-    else if (model == MODEL_WRENCH_EULER) e = launch_window_pop_m<MODEL_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
-    else e = launch_window_pop_m<MODEL_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints);
+    switch (model) {
+        case MODEL_THRUSTER_EULER: e = launch_window_m<MODEL_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+        case MODEL_WRENCH_EULER: e = launch_window_m<MODEL_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+        case MODEL_WRENCH_QUAT: e = launch_window_m<MODEL_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+        case MODEL_DI_THRUSTER_EULER: e = launch_window_m<MODEL_DI_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+        case MODEL_DI_WRENCH_EULER: e = launch_window_m<MODEL_DI_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+        default: e = launch_window_m<MODEL_DI_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
+    }
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sum_pop_kernel, dim3((unsigned)P), dim3(1024), 0, st, nwin, d_se, d_total);
+    hipLaunchKernelGGL(sum_kernel, dim3((unsigned)P), dim3(1024), 0, st, nwin, d_se, d_total);
     return hipGetLastError();
 }
 

@@ -502,6 +502,26 @@ def test_window_se_vs_oracle_larger(eng, fc):
                 assert abs(se_g - se_o) / se_o < 1e-8      # sum of ~3000 terms each matched to 1e-9
 
 
+def test_window_se_vs_oracle_chunk_edges(eng, fc):
+    """The carried-lag pre-scan at the sizes where it takes another path: one window, a full 64-window chunk, a chunk plus one,
+    and more than one 256-lane block; H = 1 makes the window's response a single lag sample.  Same data recipe and bounds as
+    test_window_se_vs_oracle_larger."""
+    rng = np.random.default_rng(3)
+    N = 257 + 3
+    U = 0.5 * np.sin(np.cumsum(rng.normal(0, 0.05, (N, 8)), 0))     # smooth, bounded commands
+    X = fc.rollout(0, fc.INTEG_EULER, np.zeros((1, 12)), U[None], 0.02)["traj"][0][1:] + rng.normal(0, 1e-3, (N, 12))
+    for integ, oi in (("euler", fc.INTEG_EULER), ("rk4", fc.INTEG_RK4)):
+        for H in (1, 3):
+            for nwin in (1, 64, 65, 257):
+                n = nwin + H
+                for carry in (True, False):
+                    se_o, per_o = fc.window_endpoint_se(0, oi, X[:n], U[:n], H, 0.02, carry_lag=carry)
+                    se_g, per_g = eng.window_endpoint_se(0, integ, X[:n], U[:n], H, 0.02, carry_lag=carry)
+                    assert per_g.shape == (nwin,)
+                    assert rel_err(per_g, per_o) < 1e-9, (integ, H, nwin, carry)
+                    assert abs(se_g - se_o) / se_o < 1e-8, (integ, H, nwin, carry)
+
+
 def test_double_integrator_baseline_matches_reference_fixture(fc):
     from bluerov2_dynamics_amd.baselines import DoubleIntegrator, estimate_di_gains
     g, w = load_golden("di.npz"), load_golden("windows.npz")
