@@ -127,7 +127,13 @@ def test_population_equals_one_at_a_time(eng, ctx, seq_ctx, model, P, nwin, H):
     """Candidate j of one population call == brov_set_params(params[j]) + brov_window_endpoint_se_dev: end states (through the
     per-window squared errors) and totals to 1e-12, the bound between two paths of the same arithmetic.  The shapes cross the
     256-lane block, the 64-window scan chunk and the chunk-of-chunks scan, and include a single window.  The first candidate
-    has another added mass: a pre-scan shared across candidates would hand it the wrong initial lag states."""
+    has another added mass: a pre-scan shared across candidates would hand it the wrong initial lag states.
+
+    Since the window evaluator was unified, the single-set entry point is the P = 1 case of the population kernels: both sides of
+    this comparison are one kernel family, so it checks that a candidate's result does not depend on its neighbours or on P, and
+    that runs repeat bit for bit -- not that the numbers are right.  The independent check of these candidates' kind (added mass,
+    tilted thruster, thrust curve and lag, current) is tests/test_fossen_params_gpu.py: test_window_population_against_oracle and
+    test_window_evaluator_single_set, against oracle/fossen_params.py."""
     from bluerov2_dynamics_amd import _lib
     N, dt, nx = nwin + H, 0.02, _lib.NX[model]
     X, U = _recording(model, N, seed=100 * model + P)

@@ -356,3 +356,179 @@ def test_far_row_selection_is_numpys_own_introselect():
     assert used_mom >= 2                                          # the killer cases reach the median of medians of 5
     assert any(not np.array_equal(g[nm + "_far"], g[nm + "_far_simd"]) for nm in names) or len(g["simd_host_features"]) == 0
     assert lib.edmdc_far_select_numpy(None, 5, 1, None) == -1
+
+
+# ------------------------------------------------------------------------------------------ oracle/fossen_params.py
+# The parameterised NumPy oracle, pinned three ways: the reference's fixtures at the nominal vehicle (the bounds of the C oracle's
+# tests above), the C oracle on random nominal batches, and tests/golden/fossen_vehicles.npz at edited vehicles.
+def _fp():
+    from oracle import fossen_params
+    return fossen_params
+
+
+def test_params_oracle_nominal_constants_and_rhs_fixtures():
+    fp = _fp()
+    g = load_golden("fossen_constants.npz")
+    v = fp.Vehicle()
+    Minv, T = fp.derived(v)
+    assert rel_err(Minv, np.diag(g["Minv"])) < 1e-15 and rel_err(T, g["alloc"]) < 1e-15
+    assert rel_err(v.thr_r, g["thr_r"]) < 1e-15 and rel_err(v.thr_dir, g["thr_dir"]) < 1e-15
+    for dt in g["dts"]:
+        Ad, Bd = fp.discretise_lag(v, float(dt))
+        assert rel_err(Ad, g[f"Ad_{dt}"]) < 1e-14 and rel_err(Bd, g[f"Bd_{dt}"]) < 1e-14
+    g = load_golden("fossen_rhs_kat.npz")
+    for tag in ("thr", "thr_cur"):
+        X, U, dt = g[f"{tag}_X"], g[f"{tag}_U"], float(g[f"{tag}_dt"])
+        vc = fp.Vehicle(current=g[f"{tag}_cur"])
+        lag = None
+        for c in range(3):
+            xd, lag = fp.rhs(0, vc, X, U, dt, lag=lag)
+            ref = g[f"{tag}_XDOT"][c]
+            assert np.array_equal(np.isfinite(xd), np.isfinite(ref))
+            assert rel_err(xd[2:], ref[2:]) < TOL
+            assert np.max(np.abs(xd[:2] - ref[:2]) / np.maximum(1.0, np.abs(ref[:2]))) < 1e-9       # theta = +-pi/2 rows, as above
+            assert rel_err(lag, g[f"{tag}_LAG"][c]) < TOL
+        tau, _ = fp.thruster_forces(v, U, dt)
+        assert rel_err(tau, g[f"{tag}_TAU1"]) < TOL
+    for tag, model in (("we", 1), ("we_cur", 1), ("wq", 2), ("wq_cur", 2)):
+        xd, _ = fp.rhs(model, fp.Vehicle(current=g[f"{tag}_cur"]), g[f"{tag}_X"], g[f"{tag}_U"], 0.02)
+        ref = g[f"{tag}_XDOT"]
+        lo = 2 if model == 1 else 0
+        assert rel_err(xd[lo:], ref[lo:]) < TOL, tag
+        assert np.max(np.abs(xd[:lo] - ref[:lo]) / np.maximum(1.0, np.abs(ref[:lo])), initial=0.0) < 1e-9
+
+
+def test_params_oracle_nominal_rollouts_windows_and_population_fixtures():
+    """Slices of fossen_rollouts.npz (the first 500 of 5000 config-2 steps of two trajectories, the first 200 steps of the AR(1)
+    and wrench runs), windows.npz in full, and fossen_pop.npz, whose vehicles change damping, zb and the current."""
+    fp = _fp()
+    g = load_golden("fossen_rollouts.npz")
+    T, dt, sub = 500, float(g["cfg2_dt"]), int(g["cfg2_sub"])
+    U = controls.controls_iid(int(g["cfg2_seed"]), 0, 2, int(g["cfg2_T"]))[:, :T]
+    x0 = np.tile(g["cfg2_x0"], (2, 1))
+    for integ, key in ((fp.RK4, "cfg2_rk4"), (fp.EULER, "cfg2_euler")):
+        r = fp.rollout(0, integ, 0, None, x0, U, dt, sub=sub)
+        assert rel_err(r["traj"], g[key][:2, :T // sub + 1]) < 1e-10, key
+    T, dt, sub = 200, float(g["ar1_dt"]), int(g["ar1_sub"])
+    for integ, key in ((fp.RK4, "ar1_rk4"), (fp.EULER, "ar1_euler")):
+        r = fp.rollout(0, integ, 0, None, g["ar1_X0"], g["ar1_U"][:, :T], dt, sub=sub)
+        assert rel_err(r["traj"], g[key][:, :T // sub + 1]) < 1e-10, key
+    dt, sub = float(g["w_dt"]), int(g["w_sub"])
+    for model, integ, x0k, key in ((1, fp.EULER, "we_X0", "we_euler"), (1, fp.RK4, "we_X0", "we_rk4"),
+                                   (2, fp.EULER, "wq_X0", "wq_euler"), (2, fp.RK4, "wq_X0", "wq_rk4_ext")):
+        r = fp.rollout(model, integ, 0, None, g[x0k], g["w_TAU"][:, :T], dt, sub=sub)
+        assert rel_err(r["traj"], g[key][:, :T // sub + 1]) < 1e-10, key
+    g = load_golden("windows.npz")
+    X, U, TAU, Xq, dt = g["X"], g["U"], g["TAU"], g["Xq"], float(g["dt"])
+
+    def rmse(model, integ, v, Xm, Um, H):
+        se, per, _ = fp.window_endpoints(model, integ, v, Xm, Um, H, dt)
+        return float(np.sqrt(se / (len(per) * fp.NX[model])))
+    for i, H in enumerate(g["H"]):
+        H = int(H)
+        assert abs(rmse(0, fp.EULER, None, X, U, H) - g["thr_euler_rmse"][i]) < 1e-12
+        assert abs(rmse(0, fp.RK4, None, X, U, H) - g["thr_rk4_rmse"][i]) < 1e-12
+        assert abs(rmse(1, fp.EULER, None, X, TAU, H) - g["we_euler_rmse"][i]) < 1e-12
+        assert abs(rmse(2, fp.EULER, None, Xq, TAU, H) - g["wq_euler_rmse"][i]) < 1e-12
+    g = load_golden("fossen_pop.npz")
+    for j in range(4):
+        v = fp.Vehicle(lin_damp=g[f"lin_damp_{j}"], quad_damp=g[f"quad_damp_{j}"], zb=float(g[f"zb_{j}"]), current=g[f"current_{j}"])
+        for i, H in enumerate(g["H"]):
+            se, per, _ = fp.window_endpoints(0, fp.EULER, v, g["X"], g["U"], int(H), float(g["dt"]))
+            assert abs(np.sqrt(se / (len(per) * 12)) - g["rmse"][i, j]) < 1e-10, (j, H)      # the bound of the GPU test of this fixture
+
+
+def test_params_oracle_equals_c_oracle_on_random_nominal_batches():
+    """All three models: RHS, rollouts (Euler, RK4, both lag modes, random initial lag) and windows (carried and fresh lag), and
+    the long-double mode against the fp64 mode (same code, so only rounding separates them)."""
+    fp = _fp()
+    rng = np.random.default_rng(12)
+    B, T, dt = 100, 16, 0.02
+    for model in (0, 1, 2):
+        nx, nu = fp.NX[model], fp.NU[model]
+        X = rng.uniform(-1.2, 1.2, (B, nx))
+        U = rng.uniform(-1, 1, (B, nu)) * (1.0 if model == 0 else 20.0)
+        lag0 = rng.uniform(-2, 2, (B, 8, 3)) if model == 0 else None
+        cur = np.array([0.2, -0.1, 0.05]) if model == 1 else None
+        a, la = fp.rhs(model, fp.Vehicle(current=cur if cur is not None else np.zeros(3)), X, U, 0.05, lag=lag0)
+        b, lb = fc.rhs(model, X, U, 0.05, lag=lag0, current=cur)
+        al, _ = fp.rhs(model, fp.Vehicle(current=cur if cur is not None else np.zeros(3)), X, U, 0.05, lag=lag0, dtype=np.longdouble)
+        assert al.dtype == np.longdouble
+        assert rel_err(a, b) < TOL and rel_err(al.astype(float), b) < TOL
+        if model == 0:
+            assert rel_err(la, lb) < TOL
+        X0 = rng.uniform(-0.5, 0.5, (B, nx))
+        UU = rng.uniform(-1, 1, (B, T, nu)) * (1.0 if model == 0 else 15.0)
+        for integ in (fp.EULER, fp.RK4):
+            for lag_mode in ((0, 1) if (model == 0 and integ == fp.RK4) else (0,)):
+                o = fp.rollout(model, integ, lag_mode, None, X0, UU, dt, lag=lag0, sub=4)
+                r = fc.rollout(model, integ, X0, UU, dt, lag=lag0, lag_mode=lag_mode, sub=4)
+                assert max(rel_err(o[k], r[k]) for k in ("traj", "xT", "lag")) < 1e-12, (model, integ, lag_mode)
+    N = 140
+    U = 0.5 * np.sin(np.cumsum(rng.normal(0, 0.05, (N, 8)), 0))
+    X = fc.rollout(0, fc.INTEG_EULER, np.zeros((1, 12)), U[None], dt)["traj"][0][1:] + rng.normal(0, 1e-3, (N, 12))
+    for integ in (fp.EULER, fp.RK4):
+        for H in (1, 7):
+            for carry in (True, False):
+                se, per, E = fp.window_endpoints(0, integ, None, X, U, H, dt, carry_lag=carry)
+                se_c, per_c = fc.window_endpoint_se(0, integ, X, U, H, dt, carry_lag=carry)
+                assert rel_err(per, per_c) < 1e-13 and abs(se - se_c) / se_c < 1e-13, (integ, H, carry)
+                assert np.allclose(np.sum((E - X[H:]) ** 2, axis=1), per, rtol=1e-14, atol=0)
+
+
+def test_params_oracle_matches_reference_at_edited_vehicles():
+    """tests/golden/fossen_vehicles.npz: the unmodified reference classes with their attributes edited to V1, V2, V3 (without the
+    polynomial change, which the reference hard-codes), V4, V5, V6.  RHS rows and lag states to 1e-12, trajectories and window
+    RMSE to 1e-10.  The fixture's vehicles are the ones tests/fossen_vehicles.py builds."""
+    import fossen_vehicles as fv
+    fp = _fp()
+    g = load_golden("fossen_vehicles.npz")
+    X, Xq, U, TAU, dt = g["X"], g["Xq"], g["U"], g["TAU"], float(g["dt"])
+    assert tuple(g["names"]) == fv.FIXTURE_NAMES
+    for name in fv.FIXTURE_NAMES:
+        v = fp.Vehicle.from_arrays(g, name + "_")
+        mine = fv.vehicle(name)
+        assert all(np.array_equal(getattr(v, f), getattr(mine, f)) for f in fp.FIELDS), name
+        lag = None
+        for c in range(3):
+            xd, lag = fp.rhs(0, v, X, U, dt, lag=lag)
+            assert rel_err(xd, g[f"{name}_XDOT"][c]) < 1e-12, (name, c)
+            assert rel_err(lag, g[f"{name}_LAG"][c]) < 1e-12, (name, c)
+        for integ, tag in ((fp.EULER, "euler"), (fp.RK4, "rk4")):
+            r = fp.rollout(0, integ, 0, v, g["x0"][None], g["U40"][None], dt)
+            assert rel_err(r["traj"][0], g[f"{name}_{tag}"]) < 1e-10, (name, tag)
+            assert rel_err(r["lag"][0], g[f"{name}_lag_{tag}"]) < 1e-10, (name, tag)
+            for i, H in enumerate(g["H"]):
+                se, per, _ = fp.window_endpoints(0, integ, v, g["Xw"], g["Uw"], int(H), dt)
+                assert abs(np.sqrt(se / (len(per) * 12)) - g[f"{name}_rmse_{tag}"][i]) < 1e-10, (name, tag, H)
+        if name in tuple(g["wrench_names"]):
+            assert rel_err(fp.rhs(1, v, X, TAU)[0], g[f"{name}_we_XDOT"]) < 1e-12, name
+            assert rel_err(fp.rhs(2, v, Xq, TAU)[0], g[f"{name}_wq_XDOT"]) < 1e-12, name
+    # the vehicles are not interchangeable: every fixture vehicle's RHS differs from the nominal one's
+    nom = fp.rhs(0, None, X, U, dt)[0]
+    assert all(rel_err(g[f"{n}_XDOT"][0], nom) > 1e-3 for n in fv.FIXTURE_NAMES)
+
+
+def test_host_entry_points_against_params_oracle_every_vehicle():
+    """brov_get_derived and brov_discretise_lag (host only: the library loads without a device) against derived() /
+    discretise_lag() for V0..V8 at dt = 0.05, 0.02, 0.001, 0.0005.  Bound: 1e-13 of the matrix's largest entry."""
+    import fossen_vehicles as fv
+    from bluerov2_dynamics_amd import _lib
+    fp = _fp()
+    for name in fv.NAMES:
+        p, v = fv.params(name), fv.vehicle(name)
+        Minv, T = _lib.derived(p)
+        Mo, To = fp.derived(v)
+        ML, TL = fp.derived(v, dtype=np.longdouble)
+        assert np.max(np.abs(Minv - Mo)) <= 1e-13 * np.max(np.abs(Mo)), name
+        assert np.max(np.abs(T - To)) <= 1e-13 * np.max(np.abs(To)), name
+        assert float(np.max(np.abs(ML - Mo))) <= 1e-14 * np.max(np.abs(Mo)) and float(np.max(np.abs(TL - To))) <= 1e-14
+        for dt in (0.05, 0.02, 0.001, 0.0005):
+            Ad, Bd = _lib.discretise_lag(dt, p)
+            Ao, Bo = fp.discretise_lag(v, dt)
+            assert np.max(np.abs(Ad - Ao)) <= 1e-13 * np.max(np.abs(Ao)), (name, dt)
+            assert np.max(np.abs(Bd - Bo)) <= 1e-13 * np.max(np.abs(Bo)), (name, dt)
+    # the figures the conditioning-edge GPU test rests on: the nominal lag's observer matrix at the four steps
+    c = [fp.observer_cond(None, dt) for dt in (0.05, 0.02, 0.001, 0.0005)]
+    assert c[0] < 30 and c[1] < 30 and 5e3 < c[2] < 1e4 < c[3] < 3e4, c
+    assert fp.observer_cond(fv.vehicle("V8"), 0.02) > 1e12

@@ -13,6 +13,8 @@ Fixtures (all float64):
                         (every 50th state) + wrench / quaternion rollouts
   windows.npz           multistep_rmse_endpoint_physics (lag carried across windows)
   fossen_pop.npz        the same loop with four parameter sets (nominal, damping changes, zb, a current) on 160 rows of windows.npz
+  fossen_vehicles.npz   the three model classes with attributes edited to six non-nominal vehicles (tests/fossen_vehicles.py): RHS rows,
+                        40-step Euler / RK4 trajectories, window RMSE
   edmdc.npz             KoopmanEDMDc fit / fit_multi / evaluate / multistep_rmse / simulate
   edmdc_fit.npz         KoopmanEDMDc.fit at the class defaults (k=200, ridge=1e-8) and the tank script's settings (k=500, gamma=3,
                         ridge=0.1) on 10 000 samples: the cases where fit()'s own product order matters
@@ -331,6 +333,93 @@ def gen_fossen_pop():
         values[f"current_{j}"] = np.asarray(rov.current_speed, dtype=float).reshape(3)
     np.savez(os.path.join(OUT, "fossen_pop.npz"), X=X, U=U, dt=np.float64(dt), H=np.array(Hs), rmse=rmse,
              set_names=np.array([f.__name__ for f in sets]), versions=versions(), **values)
+
+
+def _apply_vehicle(rov, v, thrusters):
+    """Set a reference vehicle object's attributes from an oracle.fossen_params.Vehicle (a container of the brov_params fields) and
+    recompute what its __init__ derives from them (W, B, MRB, MA, M, Minv).  dynamics() reads all of these at call time."""
+    rov.rho, rov.g, rov.m, rov.volume = v.rho, v.g, v.m, v.volume
+    rov.W = rov.m * rov.g
+    rov.B = rov.rho * rov.g * rov.volume
+    rov.xb, rov.yb, rov.zb = v.xb, v.yb, v.zb
+    rov.Ix, rov.Iy, rov.Iz = v.Ix, v.Iy, v.Iz
+    for i, n in enumerate(("Xu", "Yv", "Zw", "Kp", "Mq", "Nr")):
+        setattr(rov, n + "_dot", float(v.added_mass[i]))
+        setattr(rov, n, float(v.lin_damp[i]))
+        setattr(rov, n + "_abs", float(v.quad_damp[i]))
+    rov.MRB = np.diag([rov.m, rov.m, rov.m, rov.Ix, rov.Iy, rov.Iz]).astype(float)
+    rov.MA = np.diag([-float(a) for a in v.added_mass])
+    rov.M = rov.MRB + rov.MA
+    rov.Minv = np.linalg.inv(rov.M)
+    rov.current_speed = v.current.copy()
+    if thrusters:
+        rov.thrusters_r = [{"r": v.thr_r[i].copy(), "dir": v.thr_dir[i].copy()} for i in range(8)]
+        for lag in rov.thruster_lags:
+            lag._Ac, lag._Bc, lag._Cc = v.lag_Ac.copy(), v.lag_Bc.reshape(3, 1).copy(), v.lag_Cc.reshape(1, 3).copy()
+    return rov
+
+
+def gen_fossen_vehicles():
+    """fossen_vehicles.npz: the reference's three model classes at NON-nominal vehicles, for oracle/fossen_params.py.  The classes
+    are imported unmodified; their attributes are edited after construction (_apply_vehicle) to the vehicles of
+    tests/fossen_vehicles.py.  fossen/BlueROV2.py reads at call time: m, Ix..Iz, X*_dot, the damping terms, W, B, xb/yb/zb, Minv,
+    thrusters_r, current_speed and each ThrusterLag's matrices; it does NOT read the thrust polynomial from anywhere (hard-coded in
+    _thruster_force_from_input), hence V3n = V3 without the polynomial change.  The two wrench classes (BlueROV2_thrust.py,
+    BlueROV2_wrench.py) read the same rigid-body, damping, hydrostatic and current attributes at call time and have no thrusters, lag
+    or polynomial: they are run at V1, V2, V4, V5 (V3n and V6 are their nominal vehicle).  Per vehicle:
+      <V>_<field>                       the vehicle (brov_params fields)
+      <V>_XDOT [3,64,12], <V>_LAG [3,64,8,3]   thruster model, rows X / U, three stateful calls per row with a fresh object, dt 0.02
+      <V>_euler, <V>_rk4 [41,12]        simulate_physics (full_comparison.py / rk4.py) from x0 under U40, fresh object
+      <V>_lag_euler, <V>_lag_rk4        its lag states afterwards
+      <V>_rmse_euler, <V>_rmse_rk4 [2]  the window loop of gen_fossen_pop (lag carried) on 160 rows of windows.npz, H = 1 and 10
+      <V>_we_XDOT [64,12], <V>_wq_XDOT [64,13]   the wrench classes on rows X / Xq with TAU"""
+    import train_tank_brov2_rk4 as ref_rk4
+    import train_tank_brov2_full_comparison as ref_eul
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import fossen_vehicles as fv
+    w = np.load(os.path.join(OUT, "windows.npz"))
+    dt = float(w["dt"])
+    Xw, Uw = w["X"][:160].copy(), w["U"][:160].copy()
+    rng = np.random.default_rng(20251018)
+    n = 64
+    X, Xq = _rand_states(rng, n), _rand_states(rng, n, quat=True)
+    U = rng.uniform(-1, 1, (n, 8))
+    TAU = rng.uniform(-1, 1, (n, 6)) * np.array([40, 40, 40, 4, 4, 4.0])
+    x0 = _rand_states(rng, 1)[0] * 0.4
+    U40 = rng.uniform(-1, 1, (40, 8))
+    Hs = (1, 10)
+    out = dict(X=X, Xq=Xq, U=U, TAU=TAU, dt=np.float64(dt), x0=x0, U40=U40, Xw=Xw, Uw=Uw, H=np.array(Hs),
+               names=np.array(fv.FIXTURE_NAMES), wrench_names=np.array(["V1", "V2", "V4", "V5"]))
+    for name in fv.FIXTURE_NAMES:
+        v = fv.vehicle(name)
+        out.update(v.arrays(name + "_"))
+        D, LAG = np.zeros((3, n, 12)), np.zeros((3, n, 8, 3))
+        for i in range(n):
+            rov = _apply_vehicle(RefThruster(), v, True)
+            for c in range(3):
+                D[c, i] = rov.dynamics(X[i], U[i], dt)
+                LAG[c, i] = np.stack([l._x for l in rov.thruster_lags])
+        out[f"{name}_XDOT"], out[f"{name}_LAG"] = D, LAG
+        for tag, mod in (("euler", ref_eul), ("rk4", ref_rk4)):
+            rov = _apply_vehicle(RefThruster(dt=dt), v, True)
+            out[f"{name}_{tag}"] = np.asarray(mod.simulate_physics(x0, U40, dt, rov))
+            out[f"{name}_lag_{tag}"] = np.stack([l._x for l in rov.thruster_lags])
+            rmse = []
+            for H in Hs:
+                rov = _apply_vehicle(RefThruster(dt=dt), v, True)      # one object for all windows of a run: the lag state is carried
+                se = 0.0
+                for k in range(len(Xw) - H):
+                    err = mod.simulate_physics(Xw[k], Uw[k:k + H], dt, rov)[-1] - Xw[k + H]
+                    se += float(np.dot(err, err))
+                rmse.append(np.sqrt(se / ((len(Xw) - H) * 12)))
+            out[f"{name}_rmse_{tag}"] = np.array(rmse)
+        if name in ("V1", "V2", "V4", "V5"):
+            we, wq = _apply_vehicle(RefWrenchEuler(), v, False), _apply_vehicle(RefWrenchQuat(), v, False)
+            out[f"{name}_we_XDOT"] = np.stack([we.dynamics(X[i], TAU[i]) for i in range(n)])
+            out[f"{name}_wq_XDOT"] = np.stack([wq.dynamics(Xq[i], TAU[i]) for i in range(n)])
+        print(f"  {name}: rmse euler {out[name + '_rmse_euler']} rk4 {out[name + '_rmse_rk4']}", flush=True)
+    out["versions"] = versions()
+    np.savez(os.path.join(OUT, "fossen_vehicles.npz"), **out)
 
 
 # --------------------------------------------------------------------------- EDMDc
@@ -876,7 +965,7 @@ def gen_pinc_train():
     print("loss terms (fp64):", {k: v for k, v in out.items() if k.startswith("loss_f64")})
 
 
-GENS = dict(fossen_pop=gen_fossen_pop, pinc_train=gen_pinc_train, pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
+GENS = dict(fossen_vehicles=gen_fossen_vehicles, fossen_pop=gen_fossen_pop,pinc_train=gen_pinc_train, pinc=gen_pinc, pinc_random=gen_pinc_random,edmdc_illcond=gen_edmdc_illcond, kmeans_empty=gen_kmeans_empty, cfg5_pinc=gen_cfg5_pinc, torchrhs=gen_torchrhs, cfg5w=gen_cfg5w, simscript=gen_simscript, cfg5=gen_cfg5, di=gen_di, constants=gen_constants, rhs=gen_rhs_kat, rollouts=gen_rollouts, windows=gen_windows, edmdc=gen_edmdc, edmdc_fit=gen_edmdc_fit)
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
