@@ -118,6 +118,15 @@ SIGNATURES = {
                                                 ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "brov_window_endpoint_pop_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, i64,
                                                     ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_window_endpoint_pop_ragged": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, c_void_p,
+                                                       i64, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "brov_window_endpoint_pop_ragged_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                                           c_void_p, i64, ctypes.c_double, c_void_p, c_void_p, ctypes.c_int, c_void_p,
+                                                           c_void_p, c_void_p, c_void_p]),
+    "brov_window_endpoint_se_ragged": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, c_void_p, i64, ctypes.c_double,
+                                                      c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
+    "brov_window_endpoint_se_ragged_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, c_void_p, i64, ctypes.c_double,
+                                                          c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "brov_fd_normal_eq_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),

@@ -24,6 +24,15 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* d_fp, int model, int
 hipError_t launch_window_endpoint(hipStream_t st, const FastParams* d_fp, int model, int integ, int P, int64_t N, int64_t H, double dt,
                                   const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
                                   double* d_chunk, double* d_se, double* d_total, double* d_endpoints);
+// The same over several recordings (bags) in row-aligned X and U.  d_tab = [wpre [nbags + 1] | off [nbags + 1]] (int64): the windows
+// before each bag and its first row; nwin = wpre[nbags].  d_wrow [nwin] and d_wopen [chunks] are scratch for the window-to-row map,
+// built by the first launch; d_target [nwin][nx] or nullptr: the rows the windows are scored against.  With carry_lag every bag
+// starts from zero lag.  P = 0 writes d_target alone.  One launch more than launch_window_endpoint, whatever nbags and P are.
+hipError_t launch_window_endpoint_ragged(hipStream_t st, const FastParams* d_fp, int model, int integ, int P, int64_t nbags,
+                                         const int64_t* d_tab, int64_t nwin, int64_t H, double dt, const double* X, const double* U,
+                                         int carry_lag, const double* d_phi, double* d_lag, double* d_chunk, int64_t* d_wrow,
+                                         unsigned long long* d_wopen, double* d_se, double* d_total, double* d_endpoints,
+                                         double* d_target);
 // Finite-difference normal equations (rollout.hip): d_E [(m+1)][R], R = W nx; d_part fd_normal_blocks(R) x (m+1)(m+2)/2 doubles;
 // d_out = [JtJ (m x m) | Jtr (m)].
 int fd_normal_blocks(int64_t R);

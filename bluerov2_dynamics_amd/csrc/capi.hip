@@ -1304,14 +1304,12 @@ static bool pop_args_ok(const brov_ctx* c, int model, int integ, int64_t P, cons
 static size_t window_pop_scratch(int model, int carry, int64_t P, int64_t nwin) {
     return Arena::al(P * sizeof(FastParams)) + Arena::al(P * nwin * 8) + window_scratch(model, carry, P, nwin);
 }
-static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, int64_t N, int64_t H, double dt,
-                           const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints, Arena& a) {
+// derive_fast once per candidate: fp [P], and with `scan` each candidate's lag_window_phi_pair in phi [P][18]
+static int derive_candidates(brov_ctx* c, int integ, int P, const brov_params* params, int64_t H, double dt, bool scan,
+                             std::vector<FastParams>& fp, std::vector<double>& phi) {
     if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, BROV_ERR_ARG, "dt must be finite and > 0");
-    const int64_t nwin = N - H;
-    const bool scan = model == BROV_THRUSTER_EULER && carry;
-    // derive_fast once per candidate; one upload carries the whole FastParams[P] array (and one more the scan matrices)
-    std::vector<FastParams> fp((size_t)P);
-    std::vector<double> phi(scan ? (size_t)P * 18 : 0);
+    fp.resize((size_t)P);
+    phi.resize(scan ? (size_t)P * 18 : 0);
     for (int j = 0; j < P; ++j) {
         const brov_params& p = params[j];
         const double md[6] = {p.m - p.added_mass[0], p.m - p.added_mass[1], p.m - p.added_mass[2],
@@ -1323,6 +1321,16 @@ static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_
         derive_fast(p, dp, fp[j]);
         if (scan) lag_window_phi_pair(dp, H * (integ == BROV_RK4 ? 4 : 1), &phi[(size_t)j * 18]);
     }
+    return BROV_OK;
+}
+static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, int64_t N, int64_t H, double dt,
+                           const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints, Arena& a) {
+    const int64_t nwin = N - H;
+    // one upload carries the whole FastParams[P] array (and one more the scan matrices)
+    std::vector<FastParams> fp;
+    std::vector<double> phi;
+    int rc = derive_candidates(c, integ, P, params, H, dt, model == BROV_THRUSTER_EULER && carry, fp, phi);
+    if (rc) return rc;
     FastParams* d_fp = a.take<FastParams>(P);
     double* d_se = a.take<double>(P * nwin);
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
@@ -1364,6 +1372,189 @@ int brov_window_endpoint_pop(brov_ctx* c, int model, int integ, int64_t P, const
     if (rc) return rc;
     HIPCK(c, d2h_copy(c, se, dtot, (size_t)P * 8));
     if (endpoints) HIPCK(c, d2h_copy(c, endpoints, dE, (size_t)P * nwin * nx * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+// ---- the window evaluator over several recordings (bags): brov_window_endpoint_{pop,se}_ragged(_dev) ---------------
+// the bag list as the kernels want it: tab = [wpre [nbags + 1] | off [nbags + 1]], wpre[b] = windows before bag b
+struct WindowBags {
+    int64_t nbags = 0, rows = 0, nwin = 0;
+    std::vector<int64_t> tab;
+};
+static int window_bags(brov_ctx* c, int64_t nbags, const int64_t* off, int64_t H, WindowBags* wb, const char* who) {
+    if (nbags < 0 || !off) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad bag list (nbags >= 0, bag_offsets [nbags + 1])");
+    if (off[0] != 0) return fail(c, BROV_ERR_ARG, std::string(who) + ": bag_offsets[0] must be 0");
+    wb->tab.assign((size_t)(2 * (nbags + 1)), 0);
+    int64_t* wpre = wb->tab.data();
+    for (int64_t b = 0; b < nbags; ++b) {
+        const int64_t L = off[b + 1] - off[b];
+        if (L < 0) return fail(c, BROV_ERR_ARG, std::string(who) + ": bag_offsets must not decrease");
+        wpre[b + 1] = wpre[b] + (L > H ? L - H : 0);
+    }
+    std::copy(off, off + nbags + 1, wpre + nbags + 1);
+    wb->nbags = nbags;
+    wb->rows = off[nbags];
+    wb->nwin = wpre[nbags];
+    return BROV_OK;
+}
+// the map (table, rows, open bits) and the pre-scan's arrays
+static size_t window_ragged_scratch(int model, int carry, int64_t P, const WindowBags& wb) {
+    return Arena::al(wb.tab.size() * 8) + Arena::al(wb.nwin * 8) + Arena::al(window_chunks(wb.nwin) * 8) +
+           window_scratch(model, carry, P, wb.nwin);
+}
+// window_impl over bags, wb.nwin > 0.  P = 0: d_target alone.
+static int window_ragged_impl(brov_ctx* c, const FastParams* d_fp, const double* phi, int model, int integ, int P, const WindowBags& wb,
+                              int64_t H, double dt, const double* dX, const double* dU, int carry, double* d_se, double* d_total,
+                              double* d_endpoints, double* d_target, Arena& a) {
+    const int64_t nwin = wb.nwin;
+    const bool scan = model == BROV_THRUSTER_EULER && carry && P > 0;
+    int64_t* d_tab = a.take<int64_t>(wb.tab.size());
+    int64_t* d_wrow = a.take<int64_t>(nwin);
+    unsigned long long* d_wopen = a.take<unsigned long long>(window_chunks(nwin));
+    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    HIPCK(c, h2d_copy(c, d_tab, wb.tab.data(), wb.tab.size() * 8));
+    if (scan) {
+        d_lag = a.take<double>(P * nwin * 18);
+        d_chunk = a.take<double>(P * window_chunks(nwin) * 18);
+        d_phi = a.take<double>(P * 18);
+        HIPCK(c, h2d_copy(c, d_phi, phi, (size_t)P * 18 * 8));
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));   // the table, phi and the caller's arrays are temporaries
+    CallTimer t(c);
+    HIPCK(c, launch_window_endpoint_ragged(c->stream, d_fp, model, integ, P, wb.nbags, d_tab, nwin, H, dt, dX, dU, carry, d_phi, d_lag,
+                                           d_chunk, d_wrow, d_wopen, d_se, d_total, d_endpoints, d_target));
+    return BROV_OK;
+}
+
+static bool pop_ragged_args_ok(const brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t H, const double* se,
+                               const double* target) {
+    return c && (model == BROV_THRUSTER_EULER || model == BROV_WRENCH_EULER || model == BROV_WRENCH_QUAT) &&
+           (integ == BROV_EULER || integ == BROV_RK4) && H >= 0 &&
+           ((P >= 1 && P <= 65535 && params && se) || (P == 0 && target));
+}
+static size_t window_pop_ragged_scratch(int model, int carry, int64_t P, const WindowBags& wb, bool own_se) {
+    return Arena::al(P * sizeof(FastParams)) + (own_se ? Arena::al(P * wb.nwin * 8) : 0) + window_ragged_scratch(model, carry, P, wb);
+}
+static int window_pop_ragged_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, const WindowBags& wb, int64_t H,
+                                  double dt, const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints,
+                                  double* d_target, double* d_per_window, Arena& a) {
+    std::vector<FastParams> fp;
+    std::vector<double> phi;
+    int rc = P ? derive_candidates(c, integ, P, params, H, dt, model == BROV_THRUSTER_EULER && carry, fp, phi) : BROV_OK;
+    if (rc) return rc;
+    FastParams* d_fp = a.take<FastParams>(P);
+    double* d_se = d_per_window ? d_per_window : a.take<double>(P * wb.nwin);
+    if (P) HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    return window_ragged_impl(c, d_fp, phi.data(), model, integ, P, wb, H, dt, dX, dU, carry, d_se, d_total, d_endpoints, d_target, a);
+}
+
+int brov_window_endpoint_pop_ragged_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t nbags,
+                                        const int64_t* bag_offsets, int64_t H, double dt, const double* d_X, const double* d_U,
+                                        int carry_lag, double* d_se, double* d_endpoints, double* d_target, double* d_per_window) {
+    if (!pop_ragged_args_ok(c, model, integ, P, params, H, d_se, d_target))
+        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged_dev: bad argument");
+    WindowBags wb;
+    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_pop_ragged_dev");
+    if (rc) return rc;
+    DeviceGuard g(c);
+    if (wb.nwin == 0) { if (P) HIPCK(c, hipMemsetAsync(d_se, 0, (size_t)P * 8, c->stream)); return BROV_OK; }
+    if (!d_X || (P && !d_U)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged_dev: NULL array");
+    Arena a(c);
+    rc = a.reserve(window_pop_ragged_scratch(model, carry_lag, P, wb, !d_per_window));
+    if (rc) return rc;
+    return window_pop_ragged_impl(c, model, integ, (int)P, params, wb, H, dt, d_X, d_U, carry_lag, d_se, d_endpoints, d_target,
+                                  d_per_window, a);
+}
+
+int brov_window_endpoint_pop_ragged(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t nbags,
+                                    const int64_t* bag_offsets, int64_t H, double dt, const double* X, const double* U, int carry_lag,
+                                    double* se, double* endpoints, double* target) {
+    if (!pop_ragged_args_ok(c, model, integ, P, params, H, se, target))
+        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged: bad argument");
+    WindowBags wb;
+    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_pop_ragged");
+    if (rc) return rc;
+    if (wb.nwin == 0) { for (int64_t j = 0; j < P; ++j) se[j] = 0.0; return BROV_OK; }
+    if (!X || (P && !U)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged: NULL array");
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const int64_t N = wb.rows, nwin = wb.nwin;
+    Arena a(c);
+    rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(P * 8) + (endpoints ? Arena::al(P * nwin * nx * 8) : 0) +
+                   (target ? Arena::al(nwin * nx * 8) : 0) + window_pop_ragged_scratch(model, carry_lag, P, wb, true));
+    if (rc) return rc;
+    double* dX = a.take<double>(N * nx);
+    double* dU = a.take<double>(N * nu);
+    double* dtot = a.take<double>(P);
+    double* dE = endpoints ? a.take<double>(P * nwin * nx) : nullptr;
+    double* dT = target ? a.take<double>(nwin * nx) : nullptr;
+    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
+    if (P) HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
+    rc = window_pop_ragged_impl(c, model, integ, (int)P, params, wb, H, dt, dX, dU, carry_lag, dtot, dE, dT, nullptr, a);
+    if (rc) return rc;
+    if (P) HIPCK(c, d2h_copy(c, se, dtot, (size_t)P * 8));
+    if (endpoints) HIPCK(c, d2h_copy(c, endpoints, dE, (size_t)P * nwin * nx * 8));
+    if (target) HIPCK(c, d2h_copy(c, target, dT, (size_t)nwin * nx * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+// one parameter set over bags: the ctx's own
+static int window_ragged_dev_impl(brov_ctx* c, int model, int integ, const WindowBags& wb, int64_t H, double dt, const double* dX,
+                                  const double* dU, int carry, double* d_total, double* d_se, Arena& a) {
+    const DevParams* dp;
+    int rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
+    if (model_is_di_h(model) && !c->di_set) return fail(c, BROV_ERR_ARG, "double-integrator model: call brov_set_di_gains first");
+    double Phi[18];
+    lag_window_phi_pair(*dp, H * (integ == BROV_RK4 ? 4 : 1), Phi);
+    return window_ragged_impl(c, model_is_di_h(model) ? c->d_fp_di : c->d_fp, Phi, model, integ, 1, wb, H, dt, dX, dU, carry, d_se, d_total,
+                              nullptr, nullptr, a);
+}
+
+int brov_window_endpoint_se_ragged_dev(brov_ctx* c, int model, int integ, int64_t nbags, const int64_t* bag_offsets, int64_t H, double dt,
+                                       const double* d_X, const double* d_U, int carry_lag, double* d_se_total, double* d_per_window) {
+    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || H < 0 || !d_se_total)
+        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged_dev: bad argument");
+    WindowBags wb;
+    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_se_ragged_dev");
+    if (rc) return rc;
+    DeviceGuard g(c);
+    if (wb.nwin == 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
+    if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged_dev: NULL array");
+    Arena a(c);
+    rc = a.reserve(window_ragged_scratch(model, carry_lag, 1, wb));
+    if (rc) return rc;
+    return window_ragged_dev_impl(c, model, integ, wb, H, dt, d_X, d_U, carry_lag, d_se_total, d_per_window, a);
+}
+
+int brov_window_endpoint_se_ragged(brov_ctx* c, int model, int integ, int64_t nbags, const int64_t* bag_offsets, int64_t H, double dt,
+                                   const double* X, const double* U, int carry_lag, double* se_total, double* per_window) {
+    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || H < 0 || !se_total)
+        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged: bad argument");
+    WindowBags wb;
+    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_se_ragged");
+    if (rc) return rc;
+    if (wb.nwin == 0) { *se_total = 0.0; return BROV_OK; }
+    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged: NULL array");
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const int64_t N = wb.rows, nwin = wb.nwin;
+    Arena a(c);
+    rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) +
+                   window_ragged_scratch(model, carry_lag, 1, wb));
+    if (rc) return rc;
+    double* dX = a.take<double>(N * nx);
+    double* dU = a.take<double>(N * nu);
+    double* dse = a.take<double>(nwin);
+    double* dtot = a.take<double>(8);
+    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
+    HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
+    rc = window_ragged_dev_impl(c, model, integ, wb, H, dt, dX, dU, carry_lag, dtot, dse, a);
+    if (rc) return rc;
+    HIPCK(c, d2h_copy(c, se_total, dtot, 8));
+    if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BROV_OK;
 }

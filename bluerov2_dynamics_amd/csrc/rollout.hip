@@ -731,18 +731,60 @@ __global__ void __launch_bounds__(256) rollout_btu_lds_kernel(const FastParams* 
 // brov_set_params(params[j]) + brov_window_endpoint_se computes.  The matrices of (B) are per candidate because the
 // acceleration-space lag folds in Minv T.  Per-candidate arrays are candidate-major: lag [P][nwin][18], chunk [P][nchunks][18],
 // phi [P][18], se [P][nwin], endpoints [P][nwin][NX].
+//
+// Several recordings ("bags", RAGGED = true): X and U hold the bags' rows one after the other, the windows are numbered bag after
+// bag, and no window reads a row of another bag.  One map, built once per call by window_map_kernel, serves (A), (B) and (C):
+// wrow [nwin] = the row window w starts at, and wopen [chunks] = bit i of word c set when window 64 c + i is the first of its
+// bag (one word per scan chunk).  A lane pays one map load; the lanes of a wave still read consecutive rows except at a join.
+// With carry_lag every bag is a fresh vehicle: (B) becomes a segmented scan that restarts from zero at every bag opening.
+// RAGGED = false is the one-recording code, unchanged: window k starts at row k.
 // ---------------------------------------------------------------------------------------
-template <int NSUB>
+constexpr int WSCAN_CHUNK = 64;     // windows per chunk of the blocked scan (B), below
+static_assert(WSCAN_CHUNK == 64, "wopen packs one scan chunk per 64-bit word, filled by one wave's ballot");
+
+// tab = [wpre [nbags + 1] | off [nbags + 1]]: windows before bag b, and its first row.  Bags without a window are skipped:
+// window w belongs to the last bag b with wpre[b] <= w.
+__global__ void __launch_bounds__(256) window_map_kernel(int64_t nbags, const int64_t* __restrict__ tab, int64_t nwin,
+                                                         int64_t* __restrict__ wrow, unsigned long long* __restrict__ wopen) {
+    const int64_t w = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t* wpre = tab;
+    const int64_t* off = tab + nbags + 1;
+    bool open = false;
+    if (w < nwin) {
+        int64_t lo = 0, hi = nbags;                 // wpre[lo] <= w < wpre[hi]: wpre[0] = 0, wpre[nbags] = nwin
+        while (hi - lo > 1) {
+            const int64_t mid = (lo + hi) >> 1;
+            if (wpre[mid] <= w) lo = mid; else hi = mid;
+        }
+        open = w == wpre[lo];
+        wrow[w] = off[lo] + (w - wpre[lo]);
+    }
+    const unsigned long long m = __ballot(open);    // a wave = 64 consecutive windows = one scan chunk
+    if ((threadIdx.x & 63) == 0 && w < nwin) wopen[w >> 6] = m;
+}
+
+// target [nwin][nx] = X[wrow[w] + H]: the rows the windows are scored against, for a caller that wants them without a candidate
+__global__ void __launch_bounds__(256) window_target_kernel(int64_t nwin, int64_t H, int nx, const double* __restrict__ X,
+                                                            const int64_t* __restrict__ wrow, double* __restrict__ target) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= nwin * nx) return;
+    const int64_t w = g / nx;
+    target[g] = X[(wrow[w] + H) * nx + (g - w * nx)];
+}
+
+template <int NSUB, bool RAGGED>
 __global__ void __launch_bounds__(256) window_lag_response_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H,
-                                                                  const double* __restrict__ U, double* __restrict__ resp) {
+                                                                  const double* __restrict__ U, double* __restrict__ resp,
+                                                                  const int64_t* __restrict__ wrow) {
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nwin) return;
+    const int64_t r0 = RAGGED ? wrow[k] : k;        // first row of window k
     LagZ lz;
     lz.zero();
     for (int64_t t = 0; t < H; ++t) {
         const CFP pp = relaunder(as_constant(pg + blockIdx.y));
         double u[8], fcmd[8], acmd[6];
-        load_row<8>(U + (k + t) * 8, u);
+        load_row<8>(U + (r0 + t) * 8, u);
         command_accel<MODEL_THRUSTER_EULER, false>(pp, u, fcmd, acmd);
         lz.advance(NSUB == 4 ? pp->A4 : pp->A1, NSUB == 4 ? pp->b4 : pp->b1, acmd);
     }
@@ -759,8 +801,6 @@ __global__ void __launch_bounds__(256) window_lag_response_kernel(const FastPara
 // 11 ms for the reference's 45 723 windows, more than everything else in the evaluator together.
 // NC lag banks of 3 states per window: 6 wrench components (the Fossen evaluator, acceleration space) or 8 thrusters (the PINc
 // evaluator and the thruster stream, pinc.hip / pinc_train.hip, thruster space).  phi [P][18] = [Phi | Phi^WSCAN_CHUNK].
-constexpr int WSCAN_CHUNK = 64;
-
 __device__ __forceinline__ void wscan_step(const double P[9], double& x0, double& x1, double& x2, double b0, double b1, double b2) {
     const double n0 = fma(P[2], x2, fma(P[1], x1, fma(P[0], x0, b0)));
     const double n1 = fma(P[5], x2, fma(P[4], x1, fma(P[3], x0, b1)));
@@ -771,9 +811,12 @@ __device__ __forceinline__ void wscan_step(const double P[9], double& x0, double
 // phases 1 (store_start = 0: chunk_io[c] <- end state of chunk c from zero) and 3 (store_start = 1: the chunk's start states,
 // beginning from chunk_io[c]) for candidate blockIdx.y.  In place: phase 3 writes each start state over the response it has just
 // consumed, so rs [P][nwin][NC][3] holds the responses on entry and the start states on exit.
-template <int NC>
+// SEG (several bags): the state returns to zero at every bag-opening window (wopen, see above), so phase 1 measures a chunk from
+// its last opening and phase 3 gives a bag's first window a zero start, the chunk's first window included.
+template <int NC, bool SEG>
 __global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, int64_t nchunks, const double* __restrict__ phi,
-                                                              double* rs, double* __restrict__ chunk_io, int store_start) {
+                                                              double* rs, double* __restrict__ chunk_io, int store_start,
+                                                              const unsigned long long* __restrict__ wopen) {
     constexpr int W = NC * 3;
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t c = g / NC;
@@ -788,9 +831,14 @@ __global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, int
     double x0 = 0.0, x1 = 0.0, x2 = 0.0;
     if (store_start) { x0 = ce[0]; x1 = ce[1]; x2 = ce[2]; }
     const int64_t k1 = k0 + WSCAN_CHUNK < nwin ? k0 + WSCAN_CHUNK : nwin;
+    unsigned long long om = 0;
+    if constexpr (SEG) om = wopen[c];
     for (int64_t k = k0; k < k1; ++k) {
         double* r = rs + (j * nwin + k) * W + i * 3;
         const double r0 = r[0], r1 = r[1], r2 = r[2];
+        if constexpr (SEG) {
+            if ((om >> (k - k0)) & 1) { x0 = 0.0; x1 = 0.0; x2 = 0.0; }
+        }
         if (store_start) { r[0] = x0; r[1] = x1; r[2] = x2; }
         wscan_step(P, x0, x1, x2, r0, r1, r2);
     }
@@ -799,9 +847,11 @@ __global__ void __launch_bounds__(256) window_lag_chunk_kernel(int64_t nwin, int
 
 // phase 2, one block per candidate: in place, chunk_io[c] (end-from-zero) -> state at the beginning of chunk c.
 // s0 [NC][3]: state before the first window, the same for every candidate (nullptr = zero, a fresh vehicle).
-template <int NC>
+// SEG: a chunk that holds a bag opening hands on what phase 1 measured from that opening, S_{c+1} = chunk_end[c]; the state that
+// entered the chunk ended with the previous bag.
+template <int NC, bool SEG>
 __global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, const double* __restrict__ phi, double* __restrict__ chunk_io,
-                                                             const double* __restrict__ s0) {
+                                                             const double* __restrict__ s0, const unsigned long long* __restrict__ wopen) {
     constexpr int W = NC * 3;
     const int i = threadIdx.x;  // lag bank
     if (i >= NC) return;
@@ -813,20 +863,29 @@ __global__ void __launch_bounds__(64) window_lag_scan_kernel(int64_t nchunks, co
     if (s0) { x0 = s0[i * 3]; x1 = s0[i * 3 + 1]; x2 = s0[i * 3 + 2]; }
     double* e = chunk_io + j * nchunks * W + i * 3;
     double b0 = 0, b1 = 0, b2 = 0;
-    if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; }
+    unsigned long long bo = 0;
+    if (nchunks > 0) { b0 = e[0]; b1 = e[1]; b2 = e[2]; if constexpr (SEG) bo = wopen[0]; }
     for (int64_t c = 0; c < nchunks; ++c) {
         const double c0 = b0, c1 = b1, c2 = b2;
-        if (c + 1 < nchunks) { b0 = e[(c + 1) * W + 0]; b1 = e[(c + 1) * W + 1]; b2 = e[(c + 1) * W + 2]; }
+        const unsigned long long co = bo;
+        if (c + 1 < nchunks) {
+            b0 = e[(c + 1) * W + 0]; b1 = e[(c + 1) * W + 1]; b2 = e[(c + 1) * W + 2];
+            if constexpr (SEG) bo = wopen[c + 1];
+        }
         e[c * W + 0] = x0; e[c * W + 1] = x1; e[c * W + 2] = x2;
-        wscan_step(P, x0, x1, x2, c0, c1, c2);
+        if (SEG && co) { x0 = c0; x1 = c1; x2 = c2; }
+        else wscan_step(P, x0, x1, x2, c0, c1, c2);
     }
 }
 
-template <int MODEL, int INTEG>
+// RAGGED: window k starts at row wrow[k]; target [nwin][NX] (optional) receives the rows the windows are scored against, written
+// by the lanes of candidate 0.
+template <int MODEL, int INTEG, bool RAGGED>
 __global__ void __launch_bounds__(256) window_endpoint_kernel(const FastParams* __restrict__ pg, int64_t nwin, int64_t H, double dt,
                                                               const double* __restrict__ X, const double* __restrict__ U,
                                                               const double* __restrict__ lag_start, double* __restrict__ se,
-                                                              double* __restrict__ endpoints) {
+                                                              double* __restrict__ endpoints, const int64_t* __restrict__ wrow,
+                                                              double* __restrict__ target) {
     constexpr int NX = Dims<MODEL>::NX, NU = Dims<MODEL>::NU;
     __shared__ double2 qt[4];
     init_quadrant_table(qt);
@@ -834,11 +893,12 @@ __global__ void __launch_bounds__(256) window_endpoint_kernel(const FastParams* 
     const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= nwin) return;
     const int64_t row = (int64_t)blockIdx.y * nwin + k;       // window k of candidate blockIdx.y
+    const int64_t r0 = RAGGED ? wrow[k] : k;                  // its first row in X and U
     const CFP p = as_constant(pg + blockIdx.y);
     HotConsts h;
     load_hot(p, h);
     double x[NX];
-    load_row<NX>(X + k * NX, x);
+    load_row<NX>(X + r0 * NX, x);
     LagZ lz;
     double Xl[8][3];
     if constexpr (MODEL == MODEL_THRUSTER_EULER) {
@@ -847,18 +907,21 @@ __global__ void __launch_bounds__(256) window_endpoint_kernel(const FastParams* 
     }
     for (int64_t t = 0; t < H; ++t) {
         double u[NU];
-        load_row<NU>(U + (k + t) * NU, u);   // lane k reads row k+t: coalesced across the wave
+        load_row<NU>(U + (r0 + t) * NU, u);  // lane k reads row k+t: coalesced across the wave (ragged: except at a join)
         // full sin/cos at every step (no carry): the evaluator's windows are short, and recorded wrench sequences drive the
         // open-loop models far off the data (RMSE ~ 20), where every ulp is amplified.  The GENERIC step (current / xb, yb
         // branches) whatever the candidates' flags say: one kernel serves mixed populations, and this is not the benchmark path
         step_fast<MODEL, INTEG, 0, false, true>(h, p, dt, x, u, lz, Xl, qt);
     }
     double ref[NX], e = 0.0;
-    load_row<NX>(X + (k + H) * NX, ref);
+    load_row<NX>(X + (r0 + H) * NX, ref);
 #pragma unroll
     for (int i = 0; i < NX; ++i) { const double d = x[i] - ref[i]; e = fma(d, d, e); }
     se[row] = e;
     if (endpoints) store_row<NX>(endpoints + row * NX, x);   // lane k writes row k of its candidate
+    if constexpr (RAGGED) {
+        if (target && blockIdx.y == 0) store_row<NX>(target + k * NX, ref);
+    }
 }
 
 // Deterministic sum of n doubles per candidate blockIdx.x: fixed-shape tree, one block each.  out[j] = sum of v[j][0..n).
@@ -983,33 +1046,70 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* p, int model, int in
 
 int window_scan_chunk() { return WSCAN_CHUNK; }
 
-template <int NC>
+// d_wopen != nullptr: the segmented scan over several bags (SEG), from a zero state
+template <int NC, bool SEG>
 static hipError_t launch_window_lag_scan_n(hipStream_t st, int P, int64_t nwin, const double* d_phi, double* d_rs, double* d_chunk,
-                                           const double* d_s0) {
+                                           const double* d_s0, const unsigned long long* d_wopen) {
     const int64_t nchunks = (nwin + WSCAN_CHUNK - 1) / WSCAN_CHUNK;
     const dim3 gc(nblk(nchunks * NC, 256), (unsigned)P);
-    hipLaunchKernelGGL(window_lag_chunk_kernel<NC>, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 0);
+    hipLaunchKernelGGL((window_lag_chunk_kernel<NC, SEG>), gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 0, d_wopen);
     BROV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(window_lag_scan_kernel<NC>, dim3((unsigned)P), dim3(64), 0, st, nchunks, d_phi, d_chunk, d_s0);
+    hipLaunchKernelGGL((window_lag_scan_kernel<NC, SEG>), dim3((unsigned)P), dim3(64), 0, st, nchunks, d_phi, d_chunk, d_s0, d_wopen);
     BROV_LAUNCH_CHECK();
-    hipLaunchKernelGGL(window_lag_chunk_kernel<NC>, gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 1);
+    hipLaunchKernelGGL((window_lag_chunk_kernel<NC, SEG>), gc, dim3(256), 0, st, nwin, nchunks, d_phi, d_rs, d_chunk, 1, d_wopen);
     return hipGetLastError();
 }
 hipError_t launch_window_lag_scan(hipStream_t st, int nc, int P, int64_t nwin, const double* d_phi, double* d_rs, double* d_chunk,
                                   const double* d_s0) {
     if (nwin <= 0 || P <= 0) return hipSuccess;
-    return nc == 6 ? launch_window_lag_scan_n<6>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0)
-                   : launch_window_lag_scan_n<8>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0);
+    return nc == 6 ? launch_window_lag_scan_n<6, false>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0, nullptr)
+                   : launch_window_lag_scan_n<8, false>(st, P, nwin, d_phi, d_rs, d_chunk, d_s0, nullptr);
 }
 
-template <int MODEL>
+template <int MODEL, bool RAGGED>
 static hipError_t launch_window_m(hipStream_t st, const FastParams* p, int integ, int P, int64_t nwin, int64_t H, double dt,
-                                  const double* X, const double* U, const double* lag_start, double* se, double* endpoints) {
+                                  const double* X, const double* U, const double* lag_start, double* se, double* endpoints,
+                                  const int64_t* wrow, double* target) {
     const dim3 grid(nblk(nwin, 256), (unsigned)P);
     if (integ == INTEG_RK4)
-        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_RK4>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_RK4, RAGGED>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se,
+                           endpoints, wrow, target);
     else
-        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_EULER>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se, endpoints);
+        hipLaunchKernelGGL((window_endpoint_kernel<MODEL, INTEG_EULER, RAGGED>), grid, dim3(256), 0, st, p, nwin, H, dt, X, U, lag_start, se,
+                           endpoints, wrow, target);
+    return hipGetLastError();
+}
+
+// (A) and (B) for the thruster model with carried lag (d_lag: responses, then start states), (C), and the per-candidate totals.
+// d_wrow / d_wopen: the map of the ragged form (RAGGED), built by the caller's launch of window_map_kernel.
+template <bool RAGGED>
+static hipError_t launch_window_stages(hipStream_t st, const FastParams* p, int model, int integ, int P, int64_t nwin, int64_t H, double dt,
+                                       const double* X, const double* U, int carry_lag, const double* d_phi, double* d_lag,
+                                       double* d_chunk, double* d_se, double* d_total, double* d_endpoints, const int64_t* d_wrow,
+                                       const unsigned long long* d_wopen, double* d_target) {
+    const double* lag_start = nullptr;
+    if (model == MODEL_THRUSTER_EULER && carry_lag) {
+        const dim3 gw(nblk(nwin, 256), (unsigned)P);
+        if (integ == INTEG_RK4)
+            hipLaunchKernelGGL((window_lag_response_kernel<4, RAGGED>), gw, dim3(256), 0, st, p, nwin, H, U, d_lag, d_wrow);
+        else
+            hipLaunchKernelGGL((window_lag_response_kernel<1, RAGGED>), gw, dim3(256), 0, st, p, nwin, H, U, d_lag, d_wrow);
+        BROV_LAUNCH_CHECK();
+        const hipError_t e = launch_window_lag_scan_n<6, RAGGED>(st, P, nwin, d_phi, d_lag, d_chunk, nullptr, d_wopen);
+        if (e != hipSuccess) return e;
+        lag_start = d_lag;
+    }
+    hipError_t e;
+    switch (model) {
+        case MODEL_THRUSTER_EULER: e = launch_window_m<MODEL_THRUSTER_EULER, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+        case MODEL_WRENCH_EULER: e = launch_window_m<MODEL_WRENCH_EULER, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+        case MODEL_WRENCH_QUAT: e = launch_window_m<MODEL_WRENCH_QUAT, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+        case MODEL_DI_THRUSTER_EULER: e = launch_window_m<MODEL_DI_THRUSTER_EULER, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+        case MODEL_DI_WRENCH_EULER: e = launch_window_m<MODEL_DI_WRENCH_EULER, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+        default: e = launch_window_m<MODEL_DI_WRENCH_QUAT, RAGGED>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints, d_wrow, d_target); break;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(sum_kernel, dim3((unsigned)P), dim3(1024), 0, st, nwin, d_se, d_total);
     return hipGetLastError();
 }
 
@@ -1019,30 +1119,27 @@ hipError_t launch_window_endpoint(hipStream_t st, const FastParams* p, int model
                                   double* d_chunk, double* d_se, double* d_total, double* d_endpoints) {
     const int64_t nwin = N - H;
     if (nwin <= 0 || P <= 0) return hipSuccess;
-    const double* lag_start = nullptr;
-    if (model == MODEL_THRUSTER_EULER && carry_lag) {
-        const dim3 gw(nblk(nwin, 256), (unsigned)P);
-        if (integ == INTEG_RK4)
-            hipLaunchKernelGGL(window_lag_response_kernel<4>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
-        else
-            hipLaunchKernelGGL(window_lag_response_kernel<1>, gw, dim3(256), 0, st, p, nwin, H, U, d_lag);
-        BROV_LAUNCH_CHECK();
-        const hipError_t e = launch_window_lag_scan(st, 6, P, nwin, d_phi, d_lag, d_chunk, nullptr);
-        if (e != hipSuccess) return e;
-        lag_start = d_lag;
+    return launch_window_stages<false>(st, p, model, integ, P, nwin, H, dt, X, U, carry_lag, d_phi, d_lag, d_chunk, d_se, d_total,
+                                       d_endpoints, nullptr, nullptr, nullptr);
+}
+
+// The same over several bags: one launch more (the map), whatever P and the number of bags are.  P = 0: the map and d_target only.
+hipError_t launch_window_endpoint_ragged(hipStream_t st, const FastParams* p, int model, int integ, int P, int64_t nbags,
+                                         const int64_t* d_tab, int64_t nwin, int64_t H, double dt, const double* X, const double* U,
+                                         int carry_lag, const double* d_phi, double* d_lag, double* d_chunk, int64_t* d_wrow,
+                                         unsigned long long* d_wopen, double* d_se, double* d_total, double* d_endpoints,
+                                         double* d_target) {
+    if (nwin <= 0 || P < 0) return hipSuccess;
+    hipLaunchKernelGGL(window_map_kernel, dim3(nblk(nwin, 256)), dim3(256), 0, st, nbags, d_tab, nwin, d_wrow, d_wopen);
+    BROV_LAUNCH_CHECK();
+    if (P == 0) {
+        if (!d_target) return hipSuccess;
+        const int nx = model_is_quat(model) ? 13 : 12;
+        hipLaunchKernelGGL(window_target_kernel, dim3(nblk(nwin * nx, 256)), dim3(256), 0, st, nwin, H, nx, X, d_wrow, d_target);
+        return hipGetLastError();
     }
-    hipError_t e;
-    switch (model) {
-        case MODEL_THRUSTER_EULER: e = launch_window_m<MODEL_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-        case MODEL_WRENCH_EULER: e = launch_window_m<MODEL_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-        case MODEL_WRENCH_QUAT: e = launch_window_m<MODEL_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-        case MODEL_DI_THRUSTER_EULER: e = launch_window_m<MODEL_DI_THRUSTER_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-        case MODEL_DI_WRENCH_EULER: e = launch_window_m<MODEL_DI_WRENCH_EULER>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-        default: e = launch_window_m<MODEL_DI_WRENCH_QUAT>(st, p, integ, P, nwin, H, dt, X, U, lag_start, d_se, d_endpoints); break;
-    }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(sum_kernel, dim3((unsigned)P), dim3(1024), 0, st, nwin, d_se, d_total);
-    return hipGetLastError();
+    return launch_window_stages<true>(st, p, model, integ, P, nwin, H, dt, X, U, carry_lag, d_phi, d_lag, d_chunk, d_se, d_total,
+                                      d_endpoints, d_wrow, d_wopen, d_target);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "fd_normal_eq"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -315,9 +315,24 @@ def window_endpoint_se(model, integrator, X, U, H, dt, carry_lag=True, ctx=None)
     return se.value, per
 
 
-def window_rmse(model, integrator, X, U, H, dt, carry_lag=True, ctx=None):
-    """multistep_rmse_endpoint_physics (training/train_tank_brov2_full_comparison.py:469-487)."""
+def window_rmse(model, integrator, X, U, H, dt, carry_lag=True, ctx=None, bag_offsets=None):
+    """multistep_rmse_endpoint_physics (training/train_tank_brov2_full_comparison.py:469-487).  bag_offsets (host int64 [nbags + 1]):
+    X / U hold several recordings one after the other (bag b = rows bag_offsets[b] .. bag_offsets[b+1]-1); no window crosses a join and
+    every bag is a fresh vehicle (include/brov2.h: brov_window_endpoint_se_ragged)."""
     X = np.asarray(X)
+    if bag_offsets is not None:
+        ctx = ctx or default_context()
+        ctx.use_null_stream()
+        off = _offsets(bag_offsets)
+        X = as_f64(X).reshape(-1, NX[model])
+        U = as_f64(U).reshape(-1, NU[model])
+        assert X.shape[0] == off[-1] and U.shape[0] >= off[-1], "X rows must equal bag_offsets[-1], U must be aligned with X"
+        W = window_count(off, H)
+        se = ctypes.c_double(0.0)
+        ctx.check(ctx.lib.brov_window_endpoint_se_ragged(ctx.h, model, INTEGRATORS[integrator], off.size - 1, off.ctypes.data, int(H),
+                                                         float(dt), _hptr(X), _hptr(U), int(bool(carry_lag)), ctypes.addressof(se), None),
+                  "brov_window_endpoint_se_ragged")
+        return float(np.sqrt(se.value / (W * NX[model]))) if W > 0 else float("nan")
     n_start = len(X) - H
     if n_start <= 0:
         return float("nan")
@@ -365,13 +380,22 @@ def window_endpoint_se_dev(model, integrator, X, U, H, dt, se_total, per_window,
               "brov_window_endpoint_se_dev")
 
 
-def window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=True, endpoints=False, ctx=None):
+def window_count(bag_offsets, H):
+    """W = sum over the bags of max(L_b - H, 0): the windows of a bag list (include/brov2.h: brov_window_endpoint_pop_ragged)."""
+    return int(np.maximum(np.diff(_offsets(bag_offsets)) - int(H), 0).sum())
+
+
+def window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=True, endpoints=False, ctx=None, bag_offsets=None):
     """The window evaluator for a population of parameter sets in one call (include/brov2.h: brov_window_endpoint_pop_dev).
 
     params_list: sequence of _lib.BrovParams; X [N,nx], U [N,nu]: host arrays (uploaded) or device-resident arrays (DevArray /
     torch CUDA tensors, used in place).  Returns rmse [P] (NaN when N <= H, like window_rmse), and with endpoints=True also the
     window end states as a device array [P, N-H, nx].  Candidate j scores what ctx.set_params(params_list[j]) + window_rmse
-    scores; the ctx's own parameters are left alone."""
+    scores; the ctx's own parameters are left alone.
+
+    bag_offsets (host int64 [nbags + 1]): X / U hold several recordings one after the other, bag b = rows bag_offsets[b] ..
+    bag_offsets[b+1]-1.  No window crosses a join, every bag is a fresh vehicle, and the W = sum_b max(L_b - H, 0) windows are numbered
+    bag after bag (brov_window_endpoint_pop_ragged_dev): rmse over W windows (NaN when W = 0), end states [P, W, nx]."""
     P = len(params_list)
     pa = (_lib.BrovParams * max(P, 1))(*params_list)
     nx, nu = NX.get(model, 12), NU.get(model, 8)
@@ -387,14 +411,40 @@ def window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=True, endp
         arr.bind()
     N = int(X.shape[0])
     assert int(U.shape[0]) >= N, "U must be aligned with X"
-    nwin = max(N - int(H), 0)
+    if bag_offsets is None:
+        nwin = max(N - int(H), 0)
+    else:
+        off = _offsets(bag_offsets)
+        assert N == off[-1], "X rows must equal bag_offsets[-1]"
+        nwin = window_count(off, H)
     d_se = arr.empty((max(P, 1),))
     E = arr.empty((P, nwin, nx)) if endpoints and nwin > 0 and P > 0 else None
-    ctx.check(ctx.lib.brov_window_endpoint_pop_dev(ctx.h, model, INTEGRATORS[integrator], P, pa, N, int(H), float(dt), _dptr(X), _dptr(U),
-                                                   int(bool(carry_lag)), _dptr(d_se), _dptr(E)), "brov_window_endpoint_pop_dev")
+    if bag_offsets is None:
+        ctx.check(ctx.lib.brov_window_endpoint_pop_dev(ctx.h, model, INTEGRATORS[integrator], P, pa, N, int(H), float(dt), _dptr(X), _dptr(U),
+                                                       int(bool(carry_lag)), _dptr(d_se), _dptr(E)), "brov_window_endpoint_pop_dev")
+    else:
+        ctx.check(ctx.lib.brov_window_endpoint_pop_ragged_dev(ctx.h, model, INTEGRATORS[integrator], P, pa, off.size - 1, off.ctypes.data,
+                                                              int(H), float(dt), _dptr(X), _dptr(U), int(bool(carry_lag)), _dptr(d_se),
+                                                              _dptr(E), None, None), "brov_window_endpoint_pop_ragged_dev")
     se = np.asarray(arr.download(d_se), dtype=np.float64)[:P]
     rmse = np.sqrt(se / (nwin * nx)) if nwin > 0 else np.full(P, np.nan)
     return (rmse, E) if endpoints else rmse
+
+
+def window_target(X, H, bag_offsets, ctx=None):
+    """The rows the windows of a bag list are scored against, X[row + H] in window order, as a device array [W, nx]: the `target` of
+    fd_normal_eq next to window_pop(..., bag_offsets=...)'s end states.  X [rows, nx] device-resident (nx = 12 or 13)."""
+    ctx = _ctx_of(X, ctx)
+    arr = arrays_of(X, ctx)
+    arr.bind()
+    off = _offsets(bag_offsets)
+    nx = int(X.shape[1])
+    assert int(X.shape[0]) == off[-1] and nx in (12, 13), "X must be [bag_offsets[-1], 12 or 13]"
+    T = arr.empty((window_count(off, H), nx))
+    ctx.check(ctx.lib.brov_window_endpoint_pop_ragged_dev(ctx.h, _lib.WRENCH_QUAT if nx == 13 else _lib.WRENCH_EULER, 0, 0, None,
+                                                          off.size - 1, off.ctypes.data, int(H), 0.0, _dptr(X), None, 0, None, None,
+                                                          _dptr(T), None), "brov_window_endpoint_pop_ragged_dev")
+    return T
 
 
 def fd_normal_eq(endpoints, target, delta, weights=None, ctx=None):

@@ -183,21 +183,43 @@ class VehicleBase:
         self._sync_params()
         return engine.window_rmse(self.MODEL, integrator, X, U, H, dt, carry_lag=carry_lag, ctx=self._ctx)
 
+    def multistep_rmse_endpoint_multi(self, X_list, U_list, H, dt, integrator="euler", carry_lag=True):
+        """multistep_rmse_endpoint over several recordings scored together: no window crosses from one recording into the next,
+        every recording is a fresh vehicle, and the RMSE is over the windows of all of them (NaN when none has more than H rows).
+        U_list[b] is row-aligned with X_list[b] (at least as many rows)."""
+        from . import identify
+        X, U, off = identify.stack_recordings(X_list, U_list, self.MODEL)
+        self._sync_params()
+        return engine.window_rmse(self.MODEL, integrator, X, U, H, dt, carry_lag=carry_lag, ctx=self._ctx, bag_offsets=off)
+
     def fit_parameters(self, X, U, dt, H=10, integrator="euler", assign=True, **kwargs):
         """Fit this vehicle's parameters to a recording (fossen/identify.py: fit_parameters; `free`, `iters`, `weights`, `bounds`,
         ... pass through).  assign=True stores the fitted values in the attributes, so the next call uses them."""
         from . import identify
         res = identify.fit_parameters(self, X, U, dt, H=H, integrator=integrator, **kwargs)
         if assign:
-            cur = None
-            for name, value in res.params.items():
-                if name in identify._CURRENT:
-                    if cur is None:
-                        cs = self.current_speed
-                        cur = np.zeros(3) if cs is None else np.array(cs, dtype=float).reshape(3)
-                    cur[identify._CURRENT.index(name)] = value
-                else:
-                    setattr(self, name, value)
-            if cur is not None:
-                self.current_speed = cur
+            self._assign_fitted(res)
         return res
+
+    def fit_parameters_multi(self, X_list, U_list, dt, H=10, integrator="euler", assign=True, **kwargs):
+        """fit_parameters on several recordings at once (fossen/identify.py: fit_parameters_multi): windows never cross from one
+        recording into the next, and every recording starts from zero thruster lag."""
+        from . import identify
+        res = identify.fit_parameters_multi(self, X_list, U_list, dt, H=H, integrator=integrator, **kwargs)
+        if assign:
+            self._assign_fitted(res)
+        return res
+
+    def _assign_fitted(self, res):
+        from . import identify
+        cur = None
+        for name, value in res.params.items():
+            if name in identify._CURRENT:
+                if cur is None:
+                    cs = self.current_speed
+                    cur = np.zeros(3) if cs is None else np.array(cs, dtype=float).reshape(3)
+                cur[identify._CURRENT.index(name)] = value
+            else:
+                setattr(self, name, value)
+        if cur is not None:
+            self.current_speed = cur

@@ -12,7 +12,12 @@ state of every H-step window minus the recorded state.  One iteration is
 
 `evaluator` is the seam: any callable with window_pop's contract can stand in for the engine -- tests drive the same loop with
 NumPy models, and a derivative-free optimiser can call the engine's evaluator directly.  When the evaluator hands back its end
-states as a NumPy array the normal equations are formed on the host (normal_eq_numpy, the same formulas)."""
+states as a NumPy array the normal equations are formed on the host (normal_eq_numpy, the same formulas).
+
+Several recordings ("bags": free decay on each axis, a driven run, ...) are fitted together with fit_parameters_multi, or with
+fit_parameters(..., bag_offsets=...) on rows that are already stacked.  No window then starts in one recording and is scored against
+a row of the next, and every recording is a fresh vehicle (zero thruster lag at its first window): what concatenating the
+recordings cannot give.  The evaluator is then called with bag_offsets=...; without bags it never sees that keyword."""
 import ctypes
 from dataclasses import dataclass, field
 
@@ -101,23 +106,40 @@ class FitResult:
     rmse_history: list                 # window RMSE before the first iteration and after each one: non-increasing
     accepted: list                     # per iteration: was a step taken
     n_evals: int                       # candidates scored (window evaluations of one parameter set)
+    n_windows: int = 0                 # windows scored per candidate (over all bags)
     brov_params: object = field(default=None, repr=False)   # the fitted struct brov_params
 
 
 def _engine_evaluator(ctx):
     from .. import engine
 
-    def evaluate(model, integrator, params_list, X, U, H, dt, carry_lag=True, endpoints=False):
-        return engine.window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=carry_lag, endpoints=endpoints, ctx=ctx)
+    def evaluate(model, integrator, params_list, X, U, H, dt, carry_lag=True, endpoints=False, bag_offsets=None):
+        return engine.window_pop(model, integrator, params_list, X, U, H, dt, carry_lag=carry_lag, endpoints=endpoints, ctx=ctx,
+                                 bag_offsets=bag_offsets)
     return evaluate
+
+
+def window_rows(bag_offsets, H):
+    """First row of every window of a bag list, int64 [W]: bag b (rows bag_offsets[b] .. bag_offsets[b+1]-1, L_b of them) has
+    max(L_b - H, 0) windows, numbered bag after bag; window k of bag b starts at row bag_offsets[b] + k and is scored against row
+    bag_offsets[b] + k + H.  The numbering of include/brov2.h: brov_window_endpoint_pop_ragged."""
+    off = np.asarray(bag_offsets, dtype=np.int64).reshape(-1)
+    if off.size < 1 or off[0] != 0 or np.any(np.diff(off) < 0):
+        raise ValueError("bag_offsets must start at 0 and must not decrease")
+    w = np.maximum(np.diff(off) - int(H), 0)
+    return np.repeat(off[:-1] - (np.cumsum(w) - w), w) + np.arange(int(w.sum()), dtype=np.int64)
 
 
 _LAMBDA_TRIALS = (0.0, 1e-2, 1e-1, 1.0, 1e1, 1e2)     # times the running lambda; 0 = the Gauss-Newton step
 
 
 def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, iters=20, weights=None, bounds=None, carry_lag=True,
-                   rel_step=1e-4, evaluator=None, model=None):
+                   rel_step=1e-4, evaluator=None, model=None, bag_offsets=None):
     """Fit the parameters named in `free` to the recording X [N,nx], U [N,nu] (see the module docstring).
+
+    bag_offsets: int64 [nbags + 1], first 0, non-decreasing: X and U hold several recordings one after the other, recording b = rows
+              bag_offsets[b] .. bag_offsets[b+1]-1 (fit_parameters_multi builds this from a list).  The evaluator is then called
+              with bag_offsets=... and scores the windows of window_rows(bag_offsets, H).
 
     free    : names from FREE_NAMES; an unknown name raises ValueError.
     weights : [nx] weights of the state coordinates in the least-squares objective (None = 1).  Steps are still accepted on the
@@ -125,7 +147,8 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
     bounds  : {name: (lo, hi)}; start point, difference neighbours and trial points stay inside.
     rel_step: forward-difference step delta_j = rel_step * max(|theta_j|, 1) (backwards at an upper bound).
     evaluator: callable(model, integrator, params_list, X, U, H, dt, carry_lag=..., endpoints=...) -> rmse [P] or (rmse, E [P, N-H, nx]);
-              default: the engine on the vehicle's device context.
+              default: the engine on the vehicle's device context.  With bags it also takes bag_offsets=... and its end states are
+              [P, W, nx] in window_rows' order.
     Returns a FitResult."""
     names = tuple(free)
     unknown = [n for n in names if n not in FREE_NAMES]
@@ -156,9 +179,25 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
             X = arr.upload(_lib.as_f64(X).reshape(-1, _lib.NX[model]))
             U = arr.upload(_lib.as_f64(U).reshape(-1, _lib.NU[model]))
     N = int(X.shape[0])
-    if N - H <= 0:
-        raise ValueError(f"the recording has {N} rows: no window of H = {H} steps fits")
-    target = X.rows(H, N) if hasattr(X, "rows") else X[H:]
+    bag_kw = {}
+    if bag_offsets is None:
+        if N - H <= 0:
+            raise ValueError(f"the recording has {N} rows: no window of H = {H} steps fits")
+        target = X.rows(H, N) if hasattr(X, "rows") else X[H:]
+        n_windows = N - H
+    else:
+        rows = window_rows(bag_offsets, H)
+        off = np.ascontiguousarray(bag_offsets, dtype=np.int64).reshape(-1)
+        if int(off[-1]) != N:
+            raise ValueError(f"bag_offsets ends at row {int(off[-1])}, the recordings have {N} rows")
+        n_windows = int(rows.size)
+        if n_windows == 0:
+            raise ValueError(f"none of the {off.size - 1} recordings has more than H = {H} rows: no window fits")
+        bag_kw = dict(bag_offsets=off)
+        if device:
+            target = engine.window_target(X, H, off, ctx=ctx)
+        else:
+            target = np.asarray(X)[rows + H]         # the evaluator's NumPy end states are scored against the same rows
 
     def candidate(th):
         p = copy_params(base)
@@ -177,7 +216,7 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
         delta = rel_step * np.maximum(np.abs(theta), 1.0)
         delta = np.where(theta + delta > hi, -delta, delta)
         pop = [candidate(theta)] + [candidate(theta + delta[j] * np.eye(m)[j]) for j in range(m)]
-        rmse, E = evaluator(model, integrator, pop, X, U, H, dt, carry_lag=carry_lag, endpoints=True)
+        rmse, E = evaluator(model, integrator, pop, X, U, H, dt, carry_lag=carry_lag, endpoints=True, **bag_kw)
         n_evals += m + 1
         cur = float(rmse[0])
         if not history:
@@ -197,7 +236,7 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
         took = False
         if trials:
             score = np.asarray(evaluator(model, integrator, [candidate(t) for t in trials], X, U, H, dt, carry_lag=carry_lag,
-                                         endpoints=False), dtype=float)
+                                         endpoints=False, **bag_kw), dtype=float)
             n_evals += len(trials)
             score = np.where(np.isfinite(score), score, np.inf)
             b = int(np.argmin(score))
@@ -211,4 +250,45 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
             break
     fitted = candidate(theta)
     return FitResult(params={n: float(v) for n, v in zip(names, theta)}, rmse_history=history, accepted=accepted, n_evals=n_evals,
-                     brov_params=fitted)
+                     brov_params=fitted, n_windows=n_windows)
+
+
+def _check_recordings(X_list, U_list, model):
+    """the lists as fp64 [L_b, nx] / [L_b, nu] arrays, U cut to X's rows; ValueError where they do not pair up"""
+    X_list, U_list = list(X_list), list(U_list)
+    if len(X_list) != len(U_list):
+        raise ValueError(f"{len(X_list)} state recordings but {len(U_list)} input recordings")
+    if not X_list:
+        raise ValueError("need at least one recording")
+    nx, nu = _lib.NX[model], _lib.NU[model]
+    X_list = [_lib.as_f64(X).reshape(-1, nx) for X in X_list]
+    U_list = [_lib.as_f64(U).reshape(-1, nu) for U in U_list]
+    for b, (X, U) in enumerate(zip(X_list, U_list)):
+        if U.shape[0] < X.shape[0]:
+            raise ValueError(f"recording {b}: U has {U.shape[0]} rows, X has {X.shape[0]}: U must be row-aligned with X")
+    return X_list, [U[:X.shape[0]] for X, U in zip(X_list, U_list)]
+
+
+def stack_recordings(X_list, U_list, model):
+    """(X [rows, nx], U [rows, nu], bag_offsets int64 [nbags + 1]) of a list of recordings, stacked on the host"""
+    X_list, U_list = _check_recordings(X_list, U_list, model)
+    off = np.zeros(len(X_list) + 1, dtype=np.int64)
+    np.cumsum([X.shape[0] for X in X_list], out=off[1:])
+    return np.concatenate(X_list), np.concatenate(U_list), off
+
+
+def fit_parameters_multi(rov, X_list, U_list, dt, H=10, evaluator=None, model=None, **kwargs):
+    """fit_parameters over several recordings (KoopmanEDMDc.fit_multi's X_list / U_list): recording b is X_list[b] [L_b, nx] with
+    U_list[b] [>= L_b, nu] row-aligned.  No window crosses from one recording into the next and every recording starts from zero
+    thruster lag.  Recordings of H rows or fewer (empty ones included) contribute no window.  On the device path the list is
+    uploaded once, bag by bag (engine.upload_bags); with an `evaluator` the rows are stacked on the host.  The other arguments
+    are fit_parameters'."""
+    model = getattr(rov, "MODEL", _lib.THRUSTER_EULER) if model is None else model
+    X_list, U_list = _check_recordings(X_list, U_list, model)
+    if evaluator is None:
+        from .. import engine
+        ctx = getattr(rov, "_ctx", None) or _lib.default_context()
+        X, U, off = engine.upload_bags(X_list, U_list, _lib.NX[model], _lib.NU[model], ctx=ctx)
+    else:
+        X, U, off = stack_recordings(X_list, U_list, model)
+    return fit_parameters(rov, X, U, dt, H=H, evaluator=evaluator, model=model, bag_offsets=off, **kwargs)

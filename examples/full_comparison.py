@@ -37,7 +37,7 @@ ROWS = ("Koopman", "Fossen (BlueROV2)", "Double Integrator", "PINc (ResDNN)")
 
 
 def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None,
-            pinc=None, pinc_train=None, pinc_seed=0, fit_fossen=False, fit_iters=20):
+            pinc=None, pinc_train=None, pinc_seed=0, fit_fossen=False, fit_iters=20, fit_fossen_bags=None):
     """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc (the PINc network's
     weights: a PINcWeights, a .npz / .pt path, a state dict or the reference's PINcNet; thruster variant only) or pinc_row (its
     three RMSEs, computed elsewhere) or pinc_train (epochs: the network is trained on the train split with train_pinc, seed
@@ -47,7 +47,10 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
     state; RK4 exists only for the thruster script in the reference).
     fit_fossen: also fit the Fossen model's damping to the train split (fossen/identify.py, H = 10, at most fit_iters iterations) and
     score the fitted vehicle on the test split: `fossen_fitted` [3] and `fossen_fit` (the FitResult); printed as one more line under
-    the table, which -- like `table` and `ranking` -- is otherwise unchanged."""
+    the table, which -- like `table` and `ranking` -- is otherwise unchanged.
+    fit_fossen_bags: CSV paths of several recordings (free decay on each axis, a driven run, ...) to fit the damping on INSTEAD of
+    the train split, each file one bag (fossen/identify.py: fit_parameters_multi): no window crosses from one file into the next and
+    every file starts from zero thruster lag.  Scored and reported like fit_fossen."""
     if sum(v is not None for v in (pinc, pinc_row, pinc_train)) > 1:
         raise ValueError("give the PINc network (pinc), its precomputed row (pinc_row) or the epochs to train it for (pinc_train), "
                          "not more than one")
@@ -99,11 +102,23 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
         rows.append([float(v) for v in pinc_row])
     table = np.array(rows)
     fitted_row = fit = None
-    if fit_fossen:
+    fit_on = "train-split"
+    if fit_fossen_bags:
+        bags = [load_dataset(path, verbose=verbose, variant=variant) for path in fit_fossen_bags]
+        off_dt = [path for path, b in zip(fit_fossen_bags, bags) if abs(b[2] - dt) > 1e-6 * dt]
+        if off_dt:
+            raise ValueError(f"recordings sampled at another dt than {csv_path} ({dt}): {off_dt}")
+        t0 = perf_counter()
+        rov_fit = make_rov()
+        fit = rov_fit.fit_parameters_multi([b[0] for b in bags], [b[1] for b in bags], dt, H=10, integrator=integrator, iters=fit_iters)
+        t["fit_fossen"] = perf_counter() - t0
+        fit_on = f"{len(bags)}-recording ({fit.n_windows} windows)"
+    elif fit_fossen:
         t0 = perf_counter()
         rov_fit = make_rov()
         fit = rov_fit.fit_parameters(Xtr, Utr, dt, H=10, integrator=integrator, iters=fit_iters)
         t["fit_fossen"] = perf_counter() - t0
+    if fit is not None:
         fitted_row = [rov_fit.multistep_rmse_endpoint(Xte, Ute, H, dt, integrator) for H in (1, 10, 100)]
     if verbose:
         print(f"\n[metrics] Endpoint RMSE (full {nx}D state) with identical evaluator:")
@@ -113,7 +128,7 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
             print(f"  {name:<21s} | {r[0]:11.6f} | {r[1]:12.6f} | {r[2]:13.6f}")
         if fitted_row is not None:
             print(f"  {'Fossen (fitted)':<21s} | {fitted_row[0]:11.6f} | {fitted_row[1]:12.6f} | {fitted_row[2]:13.6f}")
-            print(f"  [fit] train-split 10-step RMSE {fit.rmse_history[0]:.6f} -> {fit.rmse_history[-1]:.6f} in {sum(fit.accepted)} steps, "
+            print(f"  [fit] {fit_on} 10-step RMSE {fit.rmse_history[0]:.6f} -> {fit.rmse_history[-1]:.6f} in {sum(fit.accepted)} steps, "
                   f"{fit.n_evals} window evaluations: " + ", ".join(f"{k} = {v:.4g}" for k, v in fit.params.items()))
         print("\n[timing] seconds:", {k: round(v, 4) for k, v in t.items()})
     return dict(table=table, timings=t, dt=dt, split=split, model=koop, ranking=np.argsort(np.argsort(table, axis=0), axis=0), rows=ROWS[:len(table)],
@@ -136,8 +151,11 @@ if __name__ == "__main__":
                     help="train the PINc network on the train split for EPOCHS epochs on the engine, then compute the fourth row with it")
     ap.add_argument("--fit-fossen", action="store_true",
                     help="fit the Fossen model's damping to the train split at H = 10 and print a 'Fossen (fitted)' row under the table")
+    ap.add_argument("--fit-fossen-bags", nargs="+", default=None, metavar="CSV",
+                    help="fit the Fossen model's damping on these recordings instead, each file one bag (no window crosses from one "
+                         "file into the next), and print the 'Fossen (fitted)' row")
     a = ap.parse_args()
     if sum(v is not None for v in (a.pinc_row, a.pinc_ckpt, a.pinc_train)) > 1:
         ap.error("--pinc-row, --pinc-ckpt and --pinc-train are mutually exclusive")
     compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt,
-            pinc_train=a.pinc_train, fit_fossen=a.fit_fossen)
+            pinc_train=a.pinc_train, fit_fossen=a.fit_fossen, fit_fossen_bags=a.fit_fossen_bags)

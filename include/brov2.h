@@ -204,6 +204,37 @@ BROV_API int brov_window_endpoint_pop(brov_ctx* ctx, int model, int integrator, 
 BROV_API int brov_window_endpoint_pop_dev(brov_ctx* ctx, int model, int integrator, int64_t P, const brov_params* params /* [P], host */,
                                  int64_t N, int64_t H, double dt, const double* d_X, const double* d_U, int carry_lag,
                                  double* d_se /* [P] */, double* d_endpoints /* [P][N-H][nx], NULL ok */);
+/* The same over several recordings ("bags") that must not be joined: X [rows][nx] and U [rows][nu] hold the bags' rows one after the
+ * other, row-aligned, and bag b is rows bag_offsets[b] .. bag_offsets[b+1]-1 (a HOST int64 array [nbags+1], bag_offsets[0] = 0,
+ * non-decreasing, nbags >= 0: the contract of edmdc_gram_ragged).  Bag b of L_b rows has w_b = max(L_b - H, 0) windows; the windows
+ * are numbered bag after bag, W = sum_b w_b.  Window k of bag b starts at row bag_offsets[b]+k, applies U rows ..+k .. ..+k+H-1 and is
+ * scored against row bag_offsets[b]+k+H: no window reads a row of another bag (the last row of a bag's U is never read).  Empty
+ * bags and bags of L_b <= H rows are allowed.  carry_lag=1 is a fresh vehicle per recording: the first window of every bag starts
+ * from zero lag, and inside a bag window k starts from what window k-1 left.  The results are those of one
+ * brov_window_endpoint_pop call per bag: se[j] = sum_b se_b[j], endpoints [P][W][nx] and per_window [P][W] the bags' arrays one
+ * after the other; rmse_j = sqrt(se[j] / (W * nx)).  target [W][nx] (NULL = not wanted) receives the rows the windows are scored
+ * against, X[row+H] in window order: the d_target of brov_fd_normal_eq_dev.  P = 0 with a target scores nothing and writes the
+ * target alone (U is not read).  W = 0: se[j] = 0, nothing else written.  The number of kernel launches depends neither on nbags
+ * nor on P; se[j] is summed in a fixed order.  Models and the range of P as in brov_window_endpoint_pop.  A bag list that breaks
+ * the contract is refused on the host (BROV_ERR_ARG, brov_last_error names the rule) before anything is launched. */
+BROV_API int brov_window_endpoint_pop_ragged(brov_ctx* ctx, int model, int integrator, int64_t P, const brov_params* params /* [P], host */,
+                                    int64_t nbags, const int64_t* bag_offsets /* [nbags+1], host */, int64_t H, double dt,
+                                    const double* X, const double* U, int carry_lag, double* se /* [P] */,
+                                    double* endpoints /* [P][W][nx], NULL ok */, double* target /* [W][nx], NULL ok */);
+BROV_API int brov_window_endpoint_pop_ragged_dev(brov_ctx* ctx, int model, int integrator, int64_t P, const brov_params* params /* [P], host */,
+                                        int64_t nbags, const int64_t* bag_offsets /* [nbags+1], host */, int64_t H, double dt,
+                                        const double* d_X, const double* d_U, int carry_lag, double* d_se /* [P] */,
+                                        double* d_endpoints /* [P][W][nx], NULL ok */, double* d_target /* [W][nx], NULL ok */,
+                                        double* d_per_window /* [P][W], NULL ok */);
+/* brov_window_endpoint_se over the same bag list, on the ctx's own parameters: the P = 1 case of the kernels above, for all six
+ * models (the double-integrator ones included, after brov_set_di_gains).  se_total = sum over the W windows of all bags;
+ * per_window [W] optional in the host form, required in the _dev form.  W = 0: se_total = 0, nothing else written. */
+BROV_API int brov_window_endpoint_se_ragged(brov_ctx* ctx, int model, int integrator, int64_t nbags,
+                                   const int64_t* bag_offsets /* [nbags+1], host */, int64_t H, double dt, const double* X,
+                                   const double* U, int carry_lag, double* se_total, double* per_window);
+BROV_API int brov_window_endpoint_se_ragged_dev(brov_ctx* ctx, int model, int integrator, int64_t nbags,
+                                       const int64_t* bag_offsets /* [nbags+1], host */, int64_t H, double dt, const double* d_X,
+                                       const double* d_U, int carry_lag, double* d_se_total, double* d_per_window /* [W], required */);
 /* Normal equations of a Gauss-Newton / Levenberg-Marquardt step from endpoints scored at base (row block 0) and at
  * base + delta_j e_j (row block j + 1), j = 0..m-1, 1 <= m <= 48, over W windows of nx coordinates:
  *     J[(k,i)][j] = w_i (E_{j+1}[k][i] - E_0[k][i]) / delta_j,    r[(k,i)] = w_i (E_0[k][i] - target[k][i]),
