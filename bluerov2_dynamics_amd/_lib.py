@@ -129,6 +129,12 @@ SIGNATURES = {
                                                           c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p]),
     "brov_fd_normal_eq_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, i64, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p]),
+    "brov_rollout_pop": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), ctypes.c_int,
+                                        i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),
+    "brov_rollout_pop_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams),
+                                            ctypes.c_int, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64,
+                                            c_void_p]),
+    "brov_ensemble_stats_dev": (ctypes.c_int, [c_void_p, i64, i64, c_void_p, c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

@@ -17,6 +17,14 @@ hipError_t launch_thruster_forces(hipStream_t st, const DevParams& p, int64_t B,
 hipError_t launch_rollout(hipStream_t st, const FastParams* d_fp, int model, int integ, int lag_mode, int layout, int64_t B,
                           int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj,
                           int64_t stride, double* xT, int btu_staging);
+// The BTU rollout for P parameter sets in one launch (d_fp [P], candidate = blockIdx.y; thruster and wrench models, always the
+// GENERIC step).  x0 [B][nx] and U [B][T][nu] shared by the candidates, or with per_candidate [P][B][nx] and [P][B][T][nu];
+// traj [P][B][T/stride+1][nx], xT [P][B][nx], lag [P][B][24] (in / out) per candidate, each or nullptr.  1 <= P <= 65535.
+hipError_t launch_rollout_pop(hipStream_t st, const FastParams* d_fp, int model, int integ, int lag_mode, int P, int per_candidate,
+                              int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj,
+                              int64_t stride, double* xT);
+// vals [P][M] -> out [4][M]: mean, sample standard deviation, minimum, maximum over the P candidates; NaN where any is non-finite
+hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out);
 // The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major
 // scratch: d_phi [P][18] ([Phi | Phi^window_scan_chunk()] of each candidate), d_lag [P][N-H][18] and d_chunk [P][chunks][18]
 // (thruster model with carry_lag only), d_se [P][N-H]; d_total [P]; d_endpoints [P][N-H][nx] or nullptr.  The launch count does

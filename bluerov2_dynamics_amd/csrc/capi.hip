@@ -1592,6 +1592,97 @@ int brov_fd_normal_eq_dev(brov_ctx* c, int nx, int m, int64_t W, const double* d
     return BROV_OK;
 }
 
+// ---- rollouts over a population of parameter sets; ensemble statistics ------------------------------------------------
+// (many vehicles in one launch: fitted against nominal, draws around a fit, a vehicle per trajectory).  As for the window evaluator
+// above, the ctx's own parameters and their derived cache are not touched.
+static int rollout_pop_args_ok(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t B, int64_t T,
+                               int64_t stride, const void* x0, const void* U, const void* traj) {
+    if (!c) return BROV_ERR_ARG;
+    if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) ||
+        P < 0 || B < 0 || T < 0)
+        return fail(c, BROV_ERR_ARG, "brov_rollout_pop: bad enum or negative size");
+    if (model_is_di_h(model))
+        return fail(c, BROV_ERR_ARG, "brov_rollout_pop: the double-integrator gains are not brov_params; thruster and wrench models only");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: P must be <= 65535");
+    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: B must be <= 2^31");
+    if (B == 0 || P == 0) return BROV_OK;
+    if (!params || !x0 || (T && !U)) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: NULL input");
+    if (traj && stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: traj_stride must be >= 1");
+    return BROV_OK;
+}
+// derive_fast per candidate, one upload of FastParams[P], one launch
+static int rollout_pop_impl(brov_ctx* c, int model, int integ, int lag_mode, int P, const brov_params* params, int per_candidate, int64_t B,
+                            int64_t T, double dt, const double* dx0, const double* dU, double* d_lag, double* d_traj, int64_t stride,
+                            double* d_xT, Arena& a) {
+    std::vector<FastParams> fp;
+    std::vector<double> phi;
+    int rc = derive_candidates(c, integ, P, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    FastParams* d_fp = a.take<FastParams>(P);
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp is a local
+    CallTimer t(c);
+    HIPCK(c, launch_rollout_pop(c->stream, d_fp, model, integ, lag_mode, P, per_candidate, B, T, dt, dx0, dU,
+                                model == BROV_THRUSTER_EULER ? d_lag : nullptr, d_traj, d_traj ? stride : 1, d_xT));
+    return BROV_OK;
+}
+
+int brov_rollout_pop_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int inputs_per_candidate,
+                         int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U, double* d_lag_io, double* d_traj,
+                         int64_t stride, double* d_xT) {
+    int rc = rollout_pop_args_ok(c, model, integ, lag_mode, P, params, B, T, stride, d_x0, d_U, d_traj);
+    if (rc) return rc;
+    if (B == 0 || P == 0) return BROV_OK;
+    DeviceGuard g(c);
+    Arena a(c);
+    rc = a.reserve(Arena::al(P * sizeof(FastParams)));
+    if (rc) return rc;
+    return rollout_pop_impl(c, model, integ, lag_mode, (int)P, params, inputs_per_candidate != 0, B, T, dt, d_x0, d_U, d_lag_io, d_traj, stride,
+                            d_xT, a);
+}
+
+int brov_rollout_pop(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int inputs_per_candidate,
+                     int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag_io, double* traj, int64_t stride,
+                     double* xT) {
+    int rc = rollout_pop_args_ok(c, model, integ, lag_mode, P, params, B, T, stride, x0, U, traj);
+    if (rc) return rc;
+    if (B == 0 || P == 0) return BROV_OK;
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
+    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
+    const size_t nin = inputs_per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
+    Arena a(c);
+    rc = a.reserve(Arena::al(nin * nx * 8) + Arena::al(nin * T * nu * 8) + Arena::al(nout * nx * 8) + (lag ? Arena::al(nout * 24 * 8) : 0) +
+                   Arena::al(nout * rows * nx * 8) + Arena::al(P * sizeof(FastParams)));
+    if (rc) return rc;
+    double* dx0 = a.take<double>(nin * nx);
+    double* dU = a.take<double>(nin * T * nu);
+    double* dxT = a.take<double>(nout * nx);
+    double* dl = lag ? a.take<double>(nout * 24) : nullptr;
+    double* dtr = traj ? a.take<double>(nout * rows * nx) : nullptr;
+    HIPCK(c, h2d_copy(c, dx0, x0, nin * nx * 8));
+    if (T) HIPCK(c, h2d_copy(c, dU, U, nin * T * nu * 8));
+    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, nout * 24 * 8));
+    rc = rollout_pop_impl(c, model, integ, lag_mode, (int)P, params, inputs_per_candidate != 0, B, T, dt, dx0, dU, dl, dtr, stride, dxT, a);
+    if (rc) return rc;
+    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, nout * nx * 8));
+    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, nout * 24 * 8));
+    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, nout * rows * nx * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+int brov_ensemble_stats_dev(brov_ctx* c, int64_t P, int64_t M, const double* d_vals, double* d_out) {
+    if (!c || P < 1 || M < 0 || M > ((int64_t)1 << 38)) return fail(c, BROV_ERR_ARG, "brov_ensemble_stats_dev: need P >= 1 and 0 <= M <= 2^38");
+    if (M == 0) return BROV_OK;
+    if (!d_vals || !d_out) return fail(c, BROV_ERR_ARG, "brov_ensemble_stats_dev: NULL array");
+    DeviceGuard g(c);
+    CallTimer t(c);
+    HIPCK(c, launch_ensemble_stats(c->stream, P, M, d_vals, d_out));
+    return BROV_OK;
+}
+
 // ---- PINc residual network -------------------------------------------------------------------------------
 int brov_pinc_set_weights(brov_ctx* c, const float* blob, int64_t n) {
     if (!c || !blob || n != PINC_NPARAMS)

@@ -284,6 +284,69 @@ __global__ void __launch_bounds__(256) rollout_kernel(const FastParams* __restri
 }
 
 // ---------------------------------------------------------------------------------------
+// K1 over a population of vehicles: grid (ceil(B / blockDim.x), P), candidate j = blockIdx.y runs B trajectories under pg[j].
+// A sibling of rollout_kernel<.., LAYOUT_BTU, .., GENERIC = true> rather than a flag on it (the listings of the existing
+// instantiations stay as they are); the step itself is the shared step_fast.  The candidate is uniform per block, so
+// as_constant(pg + blockIdx.y) keeps every constant a scalar load, as in window_endpoint_kernel, and the GENERIC step serves
+// mixed populations (a current, xb / yb, a dense allocation, obs_bad) with one kernel.  (x, per-thruster lag) is the whole
+// checkpoint: sin/cos of the attitude are evaluated in full at every step (no carry, as in window_endpoint_kernel) and with TRACK
+// the acceleration-space bank is formed from the per-thruster state at every step, so T1 + T2 steps in two launches give the bits
+// of T1 + T2 steps in one.  Candidate j therefore equals rollout_kernel<.., GENERIC = true> under pg[j] to rounding, not bit for bit.
+// Inputs shared (per_candidate = 0: X0 [B][nx], U [B][T][nu], every vehicle sees the same scenarios) or per candidate
+// (X0 [P][B][nx], U [P][B][T][nu]); outputs always per candidate: traj [P][B][T/stride+1][nx], XT [P][B][nx], lag_io [P][B][24]
+// (TRACK).  Launched with 64- or 256-thread blocks.
+// ---------------------------------------------------------------------------------------
+template <int MODEL, int INTEG, int LAGMODE, bool TRACK>
+__global__ void __launch_bounds__(256) rollout_pop_kernel(const FastParams* __restrict__ pg, int64_t B, int64_t T, double dt,
+                                                          const double* __restrict__ X0, const double* __restrict__ U, int per_candidate,
+                                                          double* __restrict__ lag_io, double* __restrict__ traj, int64_t stride,
+                                                          double* __restrict__ XT) {
+    constexpr int NX = Dims<MODEL>::NX, NU = Dims<MODEL>::NU;
+    __shared__ double2 qt[4];
+    init_quadrant_table(qt);
+    __syncthreads();
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t row = (int64_t)blockIdx.y * B + b;          // trajectory b of candidate blockIdx.y in the per-candidate arrays
+    const int64_t in = per_candidate ? row : b;               // its row in X0 and U
+    const CFP p = as_constant(pg + blockIdx.y);
+    HotConsts h;
+    load_hot(p, h);
+    double x[NX];
+    load_row<NX>(X0 + in * NX, x);
+    LagZ lz;
+    double Xl[8][3];
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if constexpr (TRACK) load_row<24>(lag_io + row * 24, &Xl[0][0]);
+        else lz.zero();
+    }
+    double* tp = traj ? traj + row * (T / stride + 1) * NX : nullptr;      // next trajectory row of this lane
+    const double* up = U + in * T * NU;
+    double un[NU];
+    if (T > 0) load_row<NU>(up, un);
+    if (traj) { store_row<NX>(tp, x); tp += NX; }
+    int64_t countdown = stride;
+    for (int64_t t = 0; t < T; ++t) {
+        double u[NU];
+#pragma unroll
+        for (int i = 0; i < NU; ++i) u[i] = un[i];
+        // the next control row, as in rollout_kernel: the last step re-reads its own row
+        up += (t + 1 < T) ? NU : 0;
+        load_row<NU>(up, un);
+        // the per-thruster state is the lag state: the acceleration-space bank is formed from it at every step, not carried
+        if constexpr (MODEL == MODEL_THRUSTER_EULER && TRACK) lz.from_thrusters(relaunder(p), Xl);
+        step_fast<MODEL, INTEG, LAGMODE, TRACK, true>(h, p, dt, x, u, lz, Xl, qt);
+        if (traj && --countdown == 0) {
+            countdown = stride;
+            store_row<NX>(tp, x);
+            tp += NX;
+        }
+    }
+    if (XT) store_row<NX>(XT + row * NX, x);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER && TRACK) store_row<24>(lag_io + row * 24, &Xl[0][0]);
+}
+
+// ---------------------------------------------------------------------------------------
 // K1p: thruster-model rollouts with every step split over TWO waves of one SIMD (time-major layouts).
 //
 // A lone wave issues one instruction of any kind every ~4.3 clocks (tools/gen_ubench_valu.py: fp64 FMA, mul, add, s_mov,
@@ -939,6 +1002,38 @@ __global__ void __launch_bounds__(1024) sum_kernel(int64_t n, const double* __re
     if (threadIdx.x == 0) out[blockIdx.x] = sh[0];
 }
 
+// Ensemble statistics over a population: vals [P][M] -> out [4][M] = mean, sample standard deviation (divisor P - 1; 0 when
+// P = 1), minimum, maximum over the P candidates.  One thread per element m, two passes over j = 0..P-1 in index order (lanes
+// read consecutive m: coalesced), no atomics: the same bits from run to run.  A non-finite value of any candidate at m makes all
+// four outputs at m NaN.
+__global__ void __launch_bounds__(256) ensemble_stats_kernel(int64_t P, int64_t M, const double* __restrict__ vals,
+                                                             double* __restrict__ out) {
+    const int64_t m = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (m >= M) return;
+    const double* v = vals + m;
+    double s = 0.0, lo = v[0], hi = lo;
+    bool finite = true;
+    for (int64_t j = 0; j < P; ++j) {
+        const double a = v[j * M];
+        finite = finite && isfinite(a);
+        s += a;
+        lo = a < lo ? a : lo;
+        hi = a > hi ? a : hi;
+    }
+    double mean = s / (double)P;
+    double q = 0.0;
+    for (int64_t j = 0; j < P; ++j) {
+        const double d = v[j * M] - mean;
+        q = fma(d, d, q);
+    }
+    double sd = P > 1 ? sqrt(q / (double)(P - 1)) : 0.0;
+    if (!finite) mean = sd = lo = hi = __builtin_nan("");
+    out[m] = mean;
+    out[M + m] = sd;
+    out[2 * M + m] = lo;
+    out[3 * M + m] = hi;
+}
+
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
@@ -1042,6 +1137,52 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* p, int model, int in
         case MODEL_DI_WRENCH_EULER: return launch_rollout_m<MODEL_DI_WRENCH_EULER>(st, p, integ, lag_mode, layout, B, T, dt, x0, U, nullptr, traj, stride, xT, btu_staging);
         default: return launch_rollout_m<MODEL_DI_WRENCH_QUAT>(st, p, integ, lag_mode, layout, B, T, dt, x0, U, nullptr, traj, stride, xT, btu_staging);
     }
+}
+
+// The population rollout: one launch, grid (blocks of B, P).  64-lane blocks when B <= 64, so that many vehicles with one or a
+// few trajectories each do not launch 256-lane blocks with one live lane.  lag (thruster model) selects TRACK.
+template <int MODEL, int INTEG, int LAGMODE>
+static hipError_t launch_rollout_pop_t(hipStream_t st, const FastParams* p, int P, int per_candidate, int64_t B, int64_t T, double dt,
+                                       const double* x0, const double* U, double* lag, double* traj, int64_t stride, double* xT) {
+    const int bs = B <= 64 ? 64 : 256;
+    const dim3 grid(nblk(B, bs), (unsigned)P);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (lag) {
+            hipLaunchKernelGGL((rollout_pop_kernel<MODEL, INTEG, LAGMODE, true>), grid, dim3(bs), 0, st, p, B, T, dt, x0, U, per_candidate,
+                               lag, traj, stride, xT);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((rollout_pop_kernel<MODEL, INTEG, LAGMODE, false>), grid, dim3(bs), 0, st, p, B, T, dt, x0, U, per_candidate,
+                       nullptr, traj, stride, xT);
+    return hipGetLastError();
+}
+template <int MODEL>
+static hipError_t launch_rollout_pop_m(hipStream_t st, const FastParams* p, int integ, int lag_mode, int P, int per_candidate, int64_t B,
+                                       int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj, int64_t stride,
+                                       double* xT) {
+    if (integ == INTEG_EULER) return launch_rollout_pop_t<MODEL, INTEG_EULER, 0>(st, p, P, per_candidate, B, T, dt, x0, U, lag, traj, stride, xT);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (lag_mode == 1) return launch_rollout_pop_t<MODEL, INTEG_RK4, 1>(st, p, P, per_candidate, B, T, dt, x0, U, lag, traj, stride, xT);
+    }
+    return launch_rollout_pop_t<MODEL, INTEG_RK4, 0>(st, p, P, per_candidate, B, T, dt, x0, U, lag, traj, stride, xT);
+}
+hipError_t launch_rollout_pop(hipStream_t st, const FastParams* p, int model, int integ, int lag_mode, int P, int per_candidate, int64_t B,
+                              int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj, int64_t stride,
+                              double* xT) {
+    if (B <= 0 || P <= 0) return hipSuccess;
+    switch (model) {
+        case MODEL_THRUSTER_EULER: return launch_rollout_pop_m<MODEL_THRUSTER_EULER>(st, p, integ, lag_mode, P, per_candidate, B, T, dt, x0, U, lag, traj, stride, xT);
+        case MODEL_WRENCH_EULER: return launch_rollout_pop_m<MODEL_WRENCH_EULER>(st, p, integ, lag_mode, P, per_candidate, B, T, dt, x0, U, nullptr, traj, stride, xT);
+        case MODEL_WRENCH_QUAT: return launch_rollout_pop_m<MODEL_WRENCH_QUAT>(st, p, integ, lag_mode, P, per_candidate, B, T, dt, x0, U, nullptr, traj, stride, xT);
+        default: return hipErrorInvalidValue;     // the double-integrator gains are not per-candidate parameters
+    }
+}
+
+hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out) {
+    if (P <= 0 || M <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ensemble_stats_kernel, dim3(nblk(M, 256)), dim3(256), 0, st, P, M, vals, out);
+    return hipGetLastError();
 }
 
 int window_scan_chunk() { return WSCAN_CHUNK; }

@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -462,6 +462,84 @@ def fd_normal_eq(endpoints, target, delta, weights=None, ctx=None):
     ctx.check(ctx.lib.brov_fd_normal_eq_dev(ctx.h, nx, m, W, _dptr(endpoints), _dptr(target), delta.ctypes.data, _hptr(w),
                                             JtJ.ctypes.data, Jtr.ctypes.data), "brov_fd_normal_eq_dev")
     return JtJ, Jtr
+
+
+def rollout_pop(model, integrator, params_list, x0, U, dt, lag=None, lag_mode=LAG_PER_CALL, stride=1, store=True, per_candidate=False,
+                ctx=None):
+    """simulate_physics for a population of vehicles in one launch (include/brov2.h: brov_rollout_pop_dev).
+
+    params_list: sequence of P _lib.BrovParams.  Shared inputs (per_candidate=False): x0 [B,nx], U [B,T,nu], every vehicle sees the
+    same scenarios; per_candidate=True: x0 [P,B,nx], U [P,B,T,nu].  lag [P,B,8,3] (thruster model) is the start lag; None starts
+    from zero and skips the per-thruster bookkeeping.  Host arrays are uploaded and the results come back as NumPy arrays; device
+    arrays (DevArray / torch CUDA tensors) are used in place and the results come back as device arrays of the same kind.
+    Returns dict(traj [P,B,T//stride+1,nx] | None, xT [P,B,nx], lag [P,B,8,3] | None); lag is a new array, the argument is not
+    written.  Candidate j computes, to rounding, what ctx.set_params(params_list[j]) + rollout computes; the ctx's own parameters
+    are left alone."""
+    P = len(params_list)
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    nx, nu = NX.get(model, 12), NU.get(model, 8)
+    host = isinstance(x0, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x0, U, lag = as_f64(x0), as_f64(U), (None if lag is None else as_f64(lag))
+    else:
+        ctx = _ctx_of(x0, ctx)
+        arr = arrays_of(x0, ctx)
+    arr.bind()
+    lead = (P,) if per_candidate else ()
+    assert len(U.shape) == len(lead) + 3 and tuple(U.shape[:len(lead)]) == lead and int(U.shape[-1]) == nu, \
+        f"U must be {'[P,B,T,nu]' if per_candidate else '[B,T,nu]'} with nu = {nu}"
+    B, T = int(U.shape[-3]), int(U.shape[-2])
+    assert tuple(int(v) for v in x0.shape) == lead + (B, nx), f"x0 shape {tuple(x0.shape)} != {lead + (B, nx)}"
+    track = model == THRUSTER_EULER and lag is not None
+    if track:
+        assert int(np.prod(lag.shape)) == P * B * 24, "lag must be [P,B,8,3]"
+    if host:
+        x0, U = arr.upload(x0), arr.upload(U)
+        lag_io = arr.upload(as_f64(lag).reshape(P, B, 8, 3)) if track else None
+    else:
+        lag_io = None
+        if track:          # in / out in the ABI: work on a copy
+            lag_io = lag.clone() if _is_torch(lag) else arr.upload(lag.numpy())
+            lag_io = lag_io.reshape(P, B, 8, 3)
+    stride = int(stride)
+    traj = arr.empty((P, B, T // stride + 1 if stride >= 1 else 1, nx)) if store else None     # stride < 1: refused by the library
+    xT = arr.empty((P, B, nx))
+    ctx.check(ctx.lib.brov_rollout_pop_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, int(bool(per_candidate)), B, T,
+                                           float(dt), _dptr(x0), _dptr(U), _dptr(lag_io), _dptr(traj), stride, _dptr(xT)),
+              "brov_rollout_pop_dev")
+    out = dict(traj=traj, xT=xT, lag=lag_io)
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def ensemble_stats(vals, ctx=None):
+    """Bands of a population of results (include/brov2.h: brov_ensemble_stats_dev): vals [P, ...] -> dict(mean, std, min, max), each
+    shaped like one candidate's block vals[0].  std is the sample standard deviation (divisor P - 1; 0 when P = 1); where any
+    candidate's value is not finite all four are NaN.  Host array in, NumPy arrays out; device array in, device arrays out."""
+    host = isinstance(vals, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        arr.bind()
+        vals = arr.upload(as_f64(vals))
+    else:
+        ctx = _ctx_of(vals, ctx)
+        arr = arrays_of(vals, ctx)
+        arr.bind()
+    shape = tuple(int(v) for v in vals.shape)
+    P, block = shape[0], shape[1:]
+    M = int(np.prod(block, dtype=np.int64))
+    out = arr.empty((4,) + block)
+    ctx.check(ctx.lib.brov_ensemble_stats_dev(ctx.h, P, M, _dptr(vals), _dptr(out)), "brov_ensemble_stats_dev")
+    if host:
+        o = arr.download(out)
+        return dict(mean=o[0], std=o[1], min=o[2], max=o[3])
+    if isinstance(out, DevArray):
+        return dict(zip(("mean", "std", "min", "max"), (out.rows(i, i + 1).view(block) for i in range(4))))
+    return dict(mean=out[0], std=out[1], min=out[2], max=out[3])
 
 
 # ------------------------------------------------------------------------------------------ PINc network (pinc.py holds the host API)

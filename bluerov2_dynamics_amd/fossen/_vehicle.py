@@ -173,6 +173,14 @@ class VehicleBase:
             self._lag[...] = r["lag"][0]
         return r["traj"][0]
 
+    def simulate_population(self, x0, U_seq, dt, params_list, integrator="euler"):
+        """simulate() for P vehicles in one launch (engine.rollout_pop): returns (P, len(U_seq)+1, nx), row j what simulate
+        returns on a fresh vehicle with the parameters params_list[j] (_lib.BrovParams, e.g. identify.sample_parameters' draws).
+        Every vehicle starts from zero thruster lag; this object's own lag state and parameters are neither read nor changed."""
+        r = engine.rollout_pop(self.MODEL, integrator, list(params_list), np.asarray(x0, float)[None], np.asarray(U_seq, float)[None],
+                               dt, ctx=self._ctx)
+        return r["traj"][:, 0]
+
     def one_step_rmse(self, X, U, dt):
         """one_step_rmse_physics (training/train_tank_brov2_koopmanEDMDc.py:237-247): Euler one-step predictions over a
         recording with ONE vehicle object (the lag runs through the whole sequence) == the H = 1 window evaluator."""

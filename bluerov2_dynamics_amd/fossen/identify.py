@@ -108,6 +108,7 @@ class FitResult:
     n_evals: int                       # candidates scored (window evaluations of one parameter set)
     n_windows: int = 0                 # windows scored per candidate (over all bags)
     brov_params: object = field(default=None, repr=False)   # the fitted struct brov_params
+    covariance: object = field(default=None, repr=False)    # [m, m] in the order of `free` (fit_parameters(covariance=True)), or None
 
 
 def _engine_evaluator(ctx):
@@ -134,7 +135,7 @@ _LAMBDA_TRIALS = (0.0, 1e-2, 1e-1, 1.0, 1e1, 1e2)     # times the running lambda
 
 
 def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, iters=20, weights=None, bounds=None, carry_lag=True,
-                   rel_step=1e-4, evaluator=None, model=None, bag_offsets=None):
+                   rel_step=1e-4, evaluator=None, model=None, bag_offsets=None, covariance=False):
     """Fit the parameters named in `free` to the recording X [N,nx], U [N,nu] (see the module docstring).
 
     bag_offsets: int64 [nbags + 1], first 0, non-decreasing: X and U hold several recordings one after the other, recording b = rows
@@ -149,6 +150,10 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
     evaluator: callable(model, integrator, params_list, X, U, H, dt, carry_lag=..., endpoints=...) -> rmse [P] or (rmse, E [P, N-H, nx]);
               default: the engine on the vehicle's device context.  With bags it also takes bag_offsets=... and its end states are
               [P, W, nx] in window_rows' order.
+    covariance: True = after the loop, one more population call at the fitted point (the base and one forward-difference neighbour
+              per free parameter, the loop's delta and bounds rule; counted in n_evals) gives the Gauss-Newton covariance
+              FitResult.covariance = s^2 pinv(J^T J), s^2 = r^T r / (W nx - m) with r the weighted residual at the fitted point:
+              what sample_parameters draws from.  NaN-filled when W nx <= m.
     Returns a FitResult."""
     names = tuple(free)
     unknown = [n for n in names if n not in FREE_NAMES]
@@ -211,12 +216,17 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
         from .. import engine
         return engine.fd_normal_eq(E, target, delta, weights)
 
+    def difference_population(th):
+        """the base and its m forward-difference neighbours (backwards at an upper bound), scored with their end states"""
+        delta = rel_step * np.maximum(np.abs(th), 1.0)
+        delta = np.where(th + delta > hi, -delta, delta)
+        pop = [candidate(th)] + [candidate(th + delta[j] * np.eye(m)[j]) for j in range(m)]
+        rmse, E = evaluator(model, integrator, pop, X, U, H, dt, carry_lag=carry_lag, endpoints=True, **bag_kw)
+        return delta, rmse, E
+
     history, accepted, n_evals, lam, stalled = [], [], 0, 1e-3, 0
     for _ in range(int(iters)):
-        delta = rel_step * np.maximum(np.abs(theta), 1.0)
-        delta = np.where(theta + delta > hi, -delta, delta)
-        pop = [candidate(theta)] + [candidate(theta + delta[j] * np.eye(m)[j]) for j in range(m)]
-        rmse, E = evaluator(model, integrator, pop, X, U, H, dt, carry_lag=carry_lag, endpoints=True, **bag_kw)
+        delta, rmse, E = difference_population(theta)
         n_evals += m + 1
         cur = float(rmse[0])
         if not history:
@@ -248,9 +258,60 @@ def fit_parameters(rov, X, U, dt, H=10, integrator="euler", free=DEFAULT_FREE, i
         stalled = 0 if took else stalled + 1
         if cur == 0.0 or stalled >= 3:
             break
+    cov = None
+    if covariance:
+        delta, _, E = difference_population(theta)
+        n_evals += m + 1
+        JtJ, _ = normal_eq(E, delta)
+        # r^T r of the weighted residual at the fitted point: block 0 of the end states against the target (one download each)
+        E0 = E[0] if isinstance(E, np.ndarray) else _to_host(E.rows(0, 1) if hasattr(E, "rows") else E[0])
+        nx = int(E.shape[2])
+        w = np.ones(nx) if weights is None else np.asarray(weights, dtype=float).reshape(nx)
+        r = (np.asarray(E0, dtype=float).reshape(-1, nx) - np.asarray(_to_host(target), dtype=float).reshape(-1, nx)) * w
+        dof = n_windows * nx - m
+        s2 = float(np.sum(r * r)) / dof if dof > 0 else np.nan
+        cov = s2 * np.linalg.pinv(np.asarray(JtJ, dtype=float), hermitian=True)
     fitted = candidate(theta)
     return FitResult(params={n: float(v) for n, v in zip(names, theta)}, rmse_history=history, accepted=accepted, n_evals=n_evals,
-                     brov_params=fitted, n_windows=n_windows)
+                     brov_params=fitted, n_windows=n_windows, covariance=cov)
+
+
+def _to_host(a):
+    """NumPy copy of a host array, a DevArray or a torch tensor"""
+    if isinstance(a, np.ndarray):
+        return a
+    return a.numpy() if hasattr(a, "ptr") else a.cpu().numpy()
+
+
+def sample_parameters(result, n, seed=0, bounds=None):
+    """n vehicles drawn around a fit: a list of BrovParams whose free parameters are theta_hat + L z, z standard normal from
+    np.random.default_rng(seed), L L^T = result.covariance (symmetric eigendecomposition, negative eigenvalues clipped to 0), each
+    clipped to bounds {name: (lo, hi)}; every other field is copied from result.brov_params.  Feed the list to engine.rollout_pop
+    or rov.simulate_population.  ValueError when the fit was made without covariance=True."""
+    if result.covariance is None:
+        raise ValueError("the fit carries no covariance: call fit_parameters(..., covariance=True)")
+    names = tuple(result.params)
+    bounds = dict(bounds or {})
+    stray = [k for k in bounds if k not in names]
+    if stray:
+        raise ValueError(f"bounds given for parameters that are not free: {stray}")
+    C = np.asarray(result.covariance, dtype=float)
+    if C.shape != (len(names), len(names)) or not np.all(np.isfinite(C)):
+        raise ValueError("the covariance must be a finite [m, m] array in the order of the fitted parameters")
+    lam, V = np.linalg.eigh(0.5 * (C + C.T))
+    L = V * np.sqrt(np.clip(lam, 0.0, None))
+    theta = np.array([result.params[k] for k in names], dtype=float)
+    lo = np.array([bounds.get(k, (-np.inf, np.inf))[0] for k in names], dtype=float)
+    hi = np.array([bounds.get(k, (-np.inf, np.inf))[1] for k in names], dtype=float)
+    z = np.random.default_rng(seed).standard_normal((int(n), len(names)))
+    draws = np.clip(theta + z @ L.T, lo, hi)
+    out = []
+    for row in draws:
+        p = copy_params(result.brov_params)
+        for k, v in zip(names, row):
+            set_param(p, k, v)
+        out.append(p)
+    return out
 
 
 def _check_recordings(X_list, U_list, model):

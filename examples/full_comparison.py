@@ -22,8 +22,10 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+from bluerov2_dynamics_amd import engine                             # noqa: E402
 from bluerov2_dynamics_amd.baselines import DoubleIntegrator          # noqa: E402
 from bluerov2_dynamics_amd.data import load_dataset                   # noqa: E402
+from bluerov2_dynamics_amd.fossen import identify                    # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2             # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2_thrust import BlueROV2 as BlueROV2Wrench          # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2_wrench import BlueROV2 as BlueROV2Quat            # noqa: E402
@@ -37,7 +39,7 @@ ROWS = ("Koopman", "Fossen (BlueROV2)", "Double Integrator", "PINc (ResDNN)")
 
 
 def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", centers=None, verbose=True, variant="thruster", pinc_row=None,
-            pinc=None, pinc_train=None, pinc_seed=0, fit_fossen=False, fit_iters=20, fit_fossen_bags=None):
+            pinc=None, pinc_train=None, pinc_seed=0, fit_fossen=False, fit_iters=20, fit_fossen_bags=None, ensemble=0):
     """Returns dict(table [3,3] rows Koopman / Fossen / DI x H = 1, 10, 100, timings, dt, split); with pinc (the PINc network's
     weights: a PINcWeights, a .npz / .pt path, a state dict or the reference's PINcNet; thruster variant only) or pinc_row (its
     three RMSEs, computed elsewhere) or pinc_train (epochs: the network is trained on the train split with train_pinc, seed
@@ -50,7 +52,12 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
     the table, which -- like `table` and `ranking` -- is otherwise unchanged.
     fit_fossen_bags: CSV paths of several recordings (free decay on each axis, a driven run, ...) to fit the damping on INSTEAD of
     the train split, each file one bag (fossen/identify.py: fit_parameters_multi): no window crosses from one file into the next and
-    every file starts from zero thruster lag.  Scored and reported like fit_fossen."""
+    every file starts from zero thruster lag.  Scored and reported like fit_fossen.
+    ensemble: N > 0 together with a fit: the fit also estimates its covariance, N vehicles are drawn from it
+    (identify.sample_parameters) and rolled open loop over the first 500 steps of the test split together with the fitted and the
+    nominal vehicle, all in one engine.rollout_pop call; engine.ensemble_stats reduces the draws to a band.  `ensemble` in the
+    result: dict(band_width [nx] = mean of max - min over the steps, inside [nx] = share of the recorded samples inside the band,
+    traj_fitted, traj_nominal, stats); printed per state under the fit line.  Without a fit, or with N = 0, nothing changes."""
     if sum(v is not None for v in (pinc, pinc_row, pinc_train)) > 1:
         raise ValueError("give the PINc network (pinc), its precomputed row (pinc_row) or the epochs to train it for (pinc_train), "
                          "not more than one")
@@ -103,6 +110,7 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
     table = np.array(rows)
     fitted_row = fit = None
     fit_on = "train-split"
+    cov_kw = dict(covariance=True) if ensemble else {}     # one more population call at the fitted point, only when asked for
     if fit_fossen_bags:
         bags = [load_dataset(path, verbose=verbose, variant=variant) for path in fit_fossen_bags]
         off_dt = [path for path, b in zip(fit_fossen_bags, bags) if abs(b[2] - dt) > 1e-6 * dt]
@@ -110,16 +118,29 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
             raise ValueError(f"recordings sampled at another dt than {csv_path} ({dt}): {off_dt}")
         t0 = perf_counter()
         rov_fit = make_rov()
-        fit = rov_fit.fit_parameters_multi([b[0] for b in bags], [b[1] for b in bags], dt, H=10, integrator=integrator, iters=fit_iters)
+        fit = rov_fit.fit_parameters_multi([b[0] for b in bags], [b[1] for b in bags], dt, H=10, integrator=integrator, iters=fit_iters,
+                                           **cov_kw)
         t["fit_fossen"] = perf_counter() - t0
         fit_on = f"{len(bags)}-recording ({fit.n_windows} windows)"
     elif fit_fossen:
         t0 = perf_counter()
         rov_fit = make_rov()
-        fit = rov_fit.fit_parameters(Xtr, Utr, dt, H=10, integrator=integrator, iters=fit_iters)
+        fit = rov_fit.fit_parameters(Xtr, Utr, dt, H=10, integrator=integrator, iters=fit_iters, **cov_kw)
         t["fit_fossen"] = perf_counter() - t0
     if fit is not None:
         fitted_row = [rov_fit.multistep_rmse_endpoint(Xte, Ute, H, dt, integrator) for H in (1, 10, 100)]
+    ens = None
+    if fit is not None and ensemble:
+        t0 = perf_counter()
+        steps = min(500, len(Xte) - 1)
+        vehicles = identify.sample_parameters(fit, int(ensemble)) + [identify.params_of(rov_fit), identify.params_of(make_rov())]
+        r = engine.rollout_pop(rov_fit.MODEL, integrator, vehicles, Xte[:1], Ute[None, :steps], dt, ctx=rov_fit._ctx)
+        traj = r["traj"][:, 0]                             # [N + 2, steps + 1, nx]
+        stats = engine.ensemble_stats(traj[:int(ensemble)], ctx=rov_fit._ctx)
+        rec = Xte[:steps + 1]
+        ens = dict(band_width=(stats["max"] - stats["min"]).mean(0), inside=((rec >= stats["min"]) & (rec <= stats["max"])).mean(0),
+                   traj_fitted=traj[-2], traj_nominal=traj[-1], stats=stats, steps=steps)
+        t["ensemble"] = perf_counter() - t0
     if verbose:
         print(f"\n[metrics] Endpoint RMSE (full {nx}D state) with identical evaluator:")
         print("  Model                 | 1-step RMSE | 10-step RMSE | 100-step RMSE")
@@ -130,9 +151,13 @@ def compare(csv_path, n_rbfs=500, gamma=3.0, ridge=1e-1, integrator="euler", cen
             print(f"  {'Fossen (fitted)':<21s} | {fitted_row[0]:11.6f} | {fitted_row[1]:12.6f} | {fitted_row[2]:13.6f}")
             print(f"  [fit] {fit_on} 10-step RMSE {fit.rmse_history[0]:.6f} -> {fit.rmse_history[-1]:.6f} in {sum(fit.accepted)} steps, "
                   f"{fit.n_evals} window evaluations: " + ", ".join(f"{k} = {v:.4g}" for k, v in fit.params.items()))
+        if ens is not None:
+            print(f"  [ensemble] {int(ensemble)} vehicles drawn around the fit, {ens['steps']}-step open-loop rollout of the test split; "
+                  "per state: mean band width (max - min) / share of recorded samples inside the band")
+            print("    " + "  ".join(f"x{i}: {w:.3g} / {100 * s:.0f}%" for i, (w, s) in enumerate(zip(ens["band_width"], ens["inside"]))))
         print("\n[timing] seconds:", {k: round(v, 4) for k, v in t.items()})
     return dict(table=table, timings=t, dt=dt, split=split, model=koop, ranking=np.argsort(np.argsort(table, axis=0), axis=0), rows=ROWS[:len(table)],
-                pinc_weights=pinc, fossen_fitted=None if fitted_row is None else np.array(fitted_row), fossen_fit=fit)
+                pinc_weights=pinc, fossen_fitted=None if fitted_row is None else np.array(fitted_row), fossen_fit=fit, ensemble=ens)
 
 
 if __name__ == "__main__":
@@ -154,8 +179,11 @@ if __name__ == "__main__":
     ap.add_argument("--fit-fossen-bags", nargs="+", default=None, metavar="CSV",
                     help="fit the Fossen model's damping on these recordings instead, each file one bag (no window crosses from one "
                          "file into the next), and print the 'Fossen (fitted)' row")
+    ap.add_argument("--ensemble", type=int, default=0, metavar="N",
+                    help="with --fit-fossen / --fit-fossen-bags: draw N vehicles from the fit's covariance, roll all of them over 500 steps "
+                         "of the test split in one launch and print the band they span per state")
     a = ap.parse_args()
     if sum(v is not None for v in (a.pinc_row, a.pinc_ckpt, a.pinc_train)) > 1:
         ap.error("--pinc-row, --pinc-ckpt and --pinc-train are mutually exclusive")
     compare(a.csv, a.rbfs, a.gamma, a.ridge, "rk4" if a.rk4 else "euler", variant=a.variant, pinc_row=a.pinc_row, pinc=a.pinc_ckpt,
-            pinc_train=a.pinc_train, fit_fossen=a.fit_fossen, fit_fossen_bags=a.fit_fossen_bags)
+            pinc_train=a.pinc_train, fit_fossen=a.fit_fossen, fit_fossen_bags=a.fit_fossen_bags, ensemble=a.ensemble)

@@ -245,6 +245,36 @@ BROV_API int brov_window_endpoint_se_ragged_dev(brov_ctx* ctx, int model, int in
 BROV_API int brov_fd_normal_eq_dev(brov_ctx* ctx, int nx, int m, int64_t W, const double* d_endpoints, const double* d_target,
                           const double* delta_host, const double* weight_host, double* JtJ_host, double* Jtr_host);
 
+/* ---- rollouts over a population of parameter sets, ensemble statistics ------------------------------------------------------
+ * brov_rollout_pop is simulate_physics (training/train_tank_brov2_full_comparison.py:453-466, ..._rk4.py:375-396,
+ * ..._wrench_quat.py:249-266) for P vehicles in one call: candidate j rolls B trajectories of T steps under params[j].  One
+ * derivation pass on the host, one upload of the derived constants, one kernel launch, whatever P is (the candidate is a grid
+ * dimension).  params is a HOST array in both forms; the ctx's own parameters (brov_set_params) are neither read nor written.
+ * Layout BROV_LAYOUT_BTU only.  Inputs are shared by the candidates (inputs_per_candidate = 0: x0 [B][nx], U [B][T][nu], every
+ * vehicle sees the same scenarios) or per candidate (inputs_per_candidate = 1: x0 [P][B][nx], U [P][B][T][nu]).  Outputs are always
+ * per candidate and each may be NULL: traj [P][B][T/traj_stride+1][nx] (every traj_stride-th state including x0), xT [P][B][nx],
+ * lag_io [P][B][8][3] in/out (thruster model; NULL = start from zero lag, no per-thruster bookkeeping).
+ * The kernel always takes the general step (the one brov_rollout_dev takes for a vehicle with a current, xb / yb != 0, a dense
+ * allocation matrix or a lag bank without observer form), so one kernel serves mixed populations.  Candidate j agrees with
+ * brov_rollout_dev after brov_set_params(&params[j]) to rounding; it is not bit-equal to any of brov_rollout_dev's paths (the
+ * specialised step, the two-wave kernel, the one-lane general kernel): those carry sin/cos of the attitude and the
+ * acceleration-space lag from step to step, this kernel re-forms both from (x, lag_io) at every step so that a call can be resumed
+ * exactly (last sentence below).
+ * Models: BROV_THRUSTER_EULER, BROV_WRENCH_EULER, BROV_WRENCH_QUAT (the double-integrator gains are not brov_params:
+ * BROV_ERR_ARG); both integrators and both lag modes; 0 <= P <= 65535, every candidate's mass matrix non-singular.  B = 0 or
+ * P = 0: BROV_OK, nothing touched.  A call of T steps continued by a call from the returned xT and lag_io gives the bits of one
+ * call over both spans. */
+BROV_API int brov_rollout_pop(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                     int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* x0, const double* U,
+                     double* lag_io, double* traj, int64_t traj_stride, double* xT);
+BROV_API int brov_rollout_pop_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                         int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U,
+                         double* d_lag_io, double* d_traj, int64_t traj_stride, double* d_xT);
+/* Reduces a population of results to bands: d_vals [P][M] (for instance traj of brov_rollout_pop_dev, M = B rows nx) ->
+ * d_out [4][M] = mean, sample standard deviation (divisor P - 1; 0 when P = 1), minimum, maximum over the P candidates.  Where any
+ * candidate's value is not finite all four are NaN.  Summed in index order, no atomics: the same bits from run to run.  P >= 1. */
+BROV_API int brov_ensemble_stats_dev(brov_ctx* ctx, int64_t P, int64_t M, const double* d_vals, double* d_out);
+
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
  * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.
