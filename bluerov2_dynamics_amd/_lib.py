@@ -39,6 +39,16 @@ class BrovParams(ctypes.Structure):
     ]
 
 
+class BrovFeedback(ctypes.Structure):
+    """struct brov_feedback (include/brov2.h): the gains and limits of brov_rollout_feedback.  fossen/control.py builds them."""
+    _fields_ = [
+        ("K", (ctypes.c_double * 12) * 8), ("Ki", (ctypes.c_double * 6) * 8),
+        ("u_min", ctypes.c_double * 8), ("u_max", ctypes.c_double * 8),
+        ("z_max", ctypes.c_double * 6),
+        ("hold", ctypes.c_int32), ("_pad", ctypes.c_int32),
+    ]
+
+
 class PincHyper(ctypes.Structure):
     """struct brov_pinc_hyper (include/brov2.h)."""
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -135,6 +145,13 @@ SIGNATURES = {
                                             ctypes.c_int, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64,
                                             c_void_p]),
     "brov_ensemble_stats_dev": (ctypes.c_int, [c_void_p, i64, i64, c_void_p, c_void_p]),
+    "brov_rollout_feedback": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                             ctypes.POINTER(BrovFeedback), ctypes.c_int, i64, i64, ctypes.c_double, c_void_p, c_void_p,
+                                             c_void_p, i64, c_void_p, c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p]),
+    "brov_rollout_feedback_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                                 ctypes.POINTER(BrovFeedback), ctypes.c_int, i64, i64, ctypes.c_double, c_void_p,
+                                                 c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p, i64, c_void_p, c_void_p,
+                                                 c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

@@ -23,6 +23,27 @@ hipError_t launch_rollout(hipStream_t st, const FastParams* d_fp, int model, int
 hipError_t launch_rollout_pop(hipStream_t st, const FastParams* d_fp, int model, int integ, int lag_mode, int P, int per_candidate,
                               int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag, double* traj,
                               int64_t stride, double* xT);
+// Closed-loop form of launch_rollout_pop (feedback.hip): the command of every step comes from a linear feedback law evaluated
+// inside the kernel (include/brov2.h: brov_rollout_feedback).  FeedbackRec is struct brov_feedback byte for byte; d_fb holds one
+// record (fb_per_candidate = 0) or P.  x0 [.][B][nx], u_ff [.][B][T][nu] (nullptr = 0) and ref [.][B][ref_rows][nx] are shared or per
+// candidate together (per_candidate); every output is per candidate and may be nullptr: lag [P][B][24] and z [P][B][6] in / out,
+// traj [P][B][T/stride+1][nx], xT [P][B][nx], u_applied [P][B][T][nu], metrics [P][B][4].
+struct FeedbackRec {
+    double K[8][12], Ki[8][6];
+    double u_min[8], u_max[8];
+    double z_max[6];
+    int32_t hold, pad;
+};
+struct FeedbackArgs {
+    const FastParams* fp;
+    const FeedbackRec* fb;
+    int fb_per_candidate, per_candidate;
+    int64_t B, T, ref_rows, stride;
+    double dt;
+    const double *x0, *u_ff, *ref;
+    double *lag, *z, *traj, *xT, *u_applied, *metrics;
+};
+hipError_t launch_rollout_feedback(hipStream_t st, int model, int integ, int lag_mode, int P, const FeedbackArgs& a);
 // vals [P][M] -> out [4][M]: mean, sample standard deviation, minimum, maximum over the P candidates; NaN where any is non-finite
 hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out);
 // The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major

@@ -1673,6 +1673,128 @@ int brov_rollout_pop(brov_ctx* c, int model, int integ, int lag_mode, int64_t P,
     return BROV_OK;
 }
 
+// ---- closed-loop rollouts (feedback.hip) --------------------------------------------------------------------------------------
+static_assert(sizeof(brov_feedback) == sizeof(FeedbackRec) && sizeof(brov_feedback) == 167 * 8, "FeedbackRec is brov_feedback byte for byte");
+// Everything the host can refuse, and the derived constants of every candidate: nothing has been copied or launched when this fails.
+static int rollout_feedback_prepare(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
+                                    const brov_feedback* fb, int64_t B, int64_t T, double dt, const void* x0, const void* ref,
+                                    int64_t ref_rows, int64_t stride, std::vector<FastParams>& fp) {
+    if (!c) return BROV_ERR_ARG;
+    if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) ||
+        P < 0 || B < 0 || T < 0)
+        return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: bad enum or negative size");
+    if (model_is_di_h(model))
+        return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: the double-integrator gains are not brov_params; thruster and wrench models only");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: P must be <= 65535");
+    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: B must be <= 2^31");
+    if (B == 0 || P == 0) return BROV_OK;
+    if (!params || !x0 || !ref || !fb) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: NULL input");
+    if (nfb != 1 && nfb != P) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: nfb must be 1 or P");
+    if (ref_rows != 1 && ref_rows != T) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: ref_rows must be 1 or T");
+    if (stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: traj_stride must be >= 1");
+    const int nu = NU(model);
+    for (int64_t k = 0; k < nfb; ++k) {
+        const brov_feedback& f = fb[k];
+        const std::string who = "brov_rollout_feedback: fb[" + std::to_string(k) + "]: ";
+        const double* v = &f.K[0][0];
+        for (int i = 0; i < 166; ++i)
+            if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, who + "NaN in the record");
+        if (f.hold < 1) return fail(c, BROV_ERR_ARG, who + "hold must be >= 1");
+        for (int i = 0; i < nu; ++i)
+            if (f.u_min[i] > f.u_max[i]) return fail(c, BROV_ERR_ARG, who + "u_min must be <= u_max");
+        for (int i = 0; i < 6; ++i)
+            if (f.z_max[i] < 0.0) return fail(c, BROV_ERR_ARG, who + "z_max must be >= 0");
+    }
+    std::vector<double> phi;
+    return derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
+}
+// one upload of FastParams[P] and of the feedback records, one launch
+static int rollout_feedback_impl(brov_ctx* c, int model, int integ, int lag_mode, int P, const std::vector<FastParams>& fp, int64_t nfb,
+                                 const brov_feedback* fb, FeedbackArgs args, Arena& a) {
+    FastParams* d_fp = a.take<FastParams>(P);
+    FeedbackRec* d_fb = a.take<FeedbackRec>(nfb);
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    HIPCK(c, h2d_copy(c, d_fb, fb, (size_t)nfb * sizeof(FeedbackRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp is a local, fb the caller's
+    args.fp = d_fp;
+    args.fb = d_fb;
+    args.fb_per_candidate = nfb > 1;
+    CallTimer t(c);
+    HIPCK(c, launch_rollout_feedback(c->stream, model, integ, lag_mode, P, args));
+    return BROV_OK;
+}
+
+int brov_rollout_feedback_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
+                              const brov_feedback* fb, int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* d_x0,
+                              const double* d_u_ff, const double* d_ref, int64_t ref_rows, double* d_lag_io, double* d_z_io,
+                              double* d_traj, int64_t stride, double* d_xT, double* d_u_applied, double* d_metrics) {
+    std::vector<FastParams> fp;
+    int rc = rollout_feedback_prepare(c, model, integ, lag_mode, P, params, nfb, fb, B, T, dt, d_x0, d_ref, ref_rows, stride, fp);
+    if (rc) return rc;
+    if (B == 0 || P == 0) return BROV_OK;
+    DeviceGuard g(c);
+    Arena a(c);
+    rc = a.reserve(Arena::al(P * sizeof(FastParams)) + Arena::al(nfb * sizeof(FeedbackRec)));
+    if (rc) return rc;
+    FeedbackArgs args{};
+    args.per_candidate = inputs_per_candidate != 0;
+    args.B = B; args.T = T; args.ref_rows = ref_rows; args.stride = stride; args.dt = dt;
+    args.x0 = d_x0; args.u_ff = d_u_ff; args.ref = d_ref;
+    args.lag = model == BROV_THRUSTER_EULER ? d_lag_io : nullptr;
+    args.z = d_z_io; args.traj = d_traj; args.xT = d_xT; args.u_applied = d_u_applied; args.metrics = d_metrics;
+    return rollout_feedback_impl(c, model, integ, lag_mode, (int)P, fp, nfb, fb, args, a);
+}
+
+int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
+                          const brov_feedback* fb, int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* x0,
+                          const double* u_ff, const double* ref, int64_t ref_rows, double* lag_io, double* z_io, double* traj,
+                          int64_t stride, double* xT, double* u_applied, double* metrics) {
+    std::vector<FastParams> fp;
+    int rc = rollout_feedback_prepare(c, model, integ, lag_mode, P, params, nfb, fb, B, T, dt, x0, ref, ref_rows, stride, fp);
+    if (rc) return rc;
+    if (B == 0 || P == 0) return BROV_OK;
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
+    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
+    const size_t nin = inputs_per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
+    const size_t n_uff = u_ff ? nin * T * nu : 0, n_ref = nin * ref_rows * nx, n_ua = u_applied ? nout * T * nu : 0;
+    Arena a(c);
+    rc = a.reserve(Arena::al(nin * nx * 8) + Arena::al(n_uff * 8) + Arena::al(n_ref * 8) + Arena::al(nout * nx * 8) +
+                   (lag ? Arena::al(nout * 24 * 8) : 0) + Arena::al(nout * 6 * 8) + Arena::al(nout * rows * nx * 8) + Arena::al(n_ua * 8) +
+                   Arena::al(nout * 4 * 8) + Arena::al(P * sizeof(FastParams)) + Arena::al(nfb * sizeof(FeedbackRec)));
+    if (rc) return rc;
+    double* dx0 = a.take<double>(nin * nx);
+    double* duf = u_ff ? a.take<double>(n_uff) : nullptr;
+    double* dref = a.take<double>(n_ref);
+    double* dxT = a.take<double>(nout * nx);
+    double* dl = lag ? a.take<double>(nout * 24) : nullptr;
+    double* dz = z_io ? a.take<double>(nout * 6) : nullptr;
+    double* dtr = traj ? a.take<double>(nout * rows * nx) : nullptr;
+    double* dua = u_applied ? a.take<double>(n_ua) : nullptr;
+    double* dm = metrics ? a.take<double>(nout * 4) : nullptr;
+    HIPCK(c, h2d_copy(c, dx0, x0, nin * nx * 8));
+    if (n_uff) HIPCK(c, h2d_copy(c, duf, u_ff, n_uff * 8));
+    if (n_ref) HIPCK(c, h2d_copy(c, dref, ref, n_ref * 8));
+    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, nout * 24 * 8));
+    if (z_io) HIPCK(c, h2d_copy(c, dz, z_io, nout * 6 * 8));
+    FeedbackArgs args{};
+    args.per_candidate = inputs_per_candidate != 0;
+    args.B = B; args.T = T; args.ref_rows = ref_rows; args.stride = stride; args.dt = dt;
+    args.x0 = dx0; args.u_ff = T ? duf : nullptr; args.ref = dref;
+    args.lag = dl; args.z = dz; args.traj = dtr; args.xT = dxT; args.u_applied = dua; args.metrics = dm;
+    rc = rollout_feedback_impl(c, model, integ, lag_mode, (int)P, fp, nfb, fb, args, a);
+    if (rc) return rc;
+    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, nout * nx * 8));
+    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, nout * 24 * 8));
+    if (z_io) HIPCK(c, d2h_copy(c, z_io, dz, nout * 6 * 8));
+    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, nout * rows * nx * 8));
+    if (n_ua) HIPCK(c, d2h_copy(c, u_applied, dua, n_ua * 8));
+    if (metrics) HIPCK(c, d2h_copy(c, metrics, dm, nout * 4 * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
 int brov_ensemble_stats_dev(brov_ctx* c, int64_t P, int64_t M, const double* d_vals, double* d_out) {
     if (!c || P < 1 || M < 0 || M > ((int64_t)1 << 38)) return fail(c, BROV_ERR_ARG, "brov_ensemble_stats_dev: need P >= 1 and 0 <= M <= 2^38");
     if (M == 0) return BROV_OK;

@@ -12,6 +12,7 @@
 #include "brov2_device.h"
 #include "brov2_fast.h"
 #include "brov2_kernels.h"
+#include "brov2_rows.h"
 
 namespace brov {
 
@@ -28,30 +29,8 @@ extern "C" __attribute__((visibility("default"))) int brov_debug_clock_stamps(un
 #endif
 
 // ---------------------------------------------------------------------------------------
-// global <-> register movement for one row of NX/NU doubles
+// global <-> register movement for one row of NX/NU doubles (load_row / store_row: brov2_rows.h)
 // ---------------------------------------------------------------------------------------
-template <int N>
-__device__ __forceinline__ void load_row(const double* __restrict__ src, double* r) {
-    if constexpr (N % 2 == 0) {
-        const double2* s2 = reinterpret_cast<const double2*>(src);
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) { double2 v = s2[i]; r[2 * i] = v.x; r[2 * i + 1] = v.y; }
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) r[i] = src[i];
-    }
-}
-template <int N>
-__device__ __forceinline__ void store_row(double* __restrict__ dst, const double* r) {
-    if constexpr (N % 2 == 0) {
-        double2* d2 = reinterpret_cast<double2*>(dst);
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) d2[i] = make_double2(r[2 * i], r[2 * i + 1]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; ++i) dst[i] = r[i];
-    }
-}
 template <int N>
 __device__ __forceinline__ void load_soa(const double* __restrict__ src, int64_t ld, double* r) {
 #pragma unroll

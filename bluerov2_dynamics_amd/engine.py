@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats", "rollout_feedback"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -510,6 +510,79 @@ def rollout_pop(model, integrator, params_list, x0, U, dt, lag=None, lag_mode=LA
                                            float(dt), _dptr(x0), _dptr(U), _dptr(lag_io), _dptr(traj), stride, _dptr(xT)),
               "brov_rollout_pop_dev")
     out = dict(traj=traj, xT=xT, lag=lag_io)
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=None, u_ff=None, lag=None, z=None, lag_mode=LAG_PER_CALL,
+                     stride=1, store=True, want_u=False, want_metrics=True, per_candidate=False, ctx=None):
+    """Closed-loop rollouts of a population of vehicles in one launch: the command of every step comes from a linear feedback law on
+    the tracking error, evaluated inside the kernel (include/brov2.h: brov_rollout_feedback_dev holds the law).
+
+    params_list: sequence of P _lib.BrovParams.  feedback: one _lib.BrovFeedback (one controller for every vehicle) or a sequence of
+    P (candidate j under feedback[j]); fossen/control.py builds them.  Shared inputs (per_candidate=False): x0 [B,nx], ref
+    [B,rows,nx] with rows 1 (a set-point) or T, u_ff [B,T,nu] or None (no feed-forward); per_candidate=True: each with a leading P.
+    T defaults to the rows of ref when it has more than one, else to the rows of u_ff.  lag [P,B,8,3] (thruster model) and z
+    [P,B,6] are the start lag and integral state; None starts from zero and returns None.  Host and device arrays as in rollout_pop.
+    Returns dict(traj [P,B,T//stride+1,nx] | None, xT [P,B,nx], lag | None, z | None, u [P,B,T,nu] | None (want_u), metrics [P,B,4] |
+    None (want_metrics): sum dt |e_pos|^2, sum dt |e_att|^2, sum dt |u|^2, steps with a channel on a limit).  The ctx's own
+    parameters are left alone."""
+    P = len(params_list)
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    fbs = [feedback] if isinstance(feedback, _lib.BrovFeedback) else list(feedback)
+    fa = (_lib.BrovFeedback * max(len(fbs), 1))(*fbs)
+    nx, nu = NX.get(model, 12), NU.get(model, 8)
+    host = isinstance(x0, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x0, ref = as_f64(x0), as_f64(ref)
+        u_ff, lag, z = (None if v is None else as_f64(v) for v in (u_ff, lag, z))
+    else:
+        ctx = _ctx_of(x0, ctx)
+        arr = arrays_of(x0, ctx)
+    arr.bind()
+    lead = (P,) if per_candidate else ()
+    assert len(x0.shape) == len(lead) + 2 and tuple(x0.shape[:len(lead)]) == lead and int(x0.shape[-1]) == nx, \
+        f"x0 must be {'[P,B,nx]' if per_candidate else '[B,nx]'} with nx = {nx}"
+    B = int(x0.shape[-2])
+    assert len(ref.shape) == len(lead) + 3 and tuple(int(v) for v in ref.shape[:-2]) == lead + (B,) and int(ref.shape[-1]) == nx, \
+        f"ref shape {tuple(ref.shape)} != {lead + (B, 'rows', nx)}"
+    ref_rows = int(ref.shape[-2])
+    if T is None:
+        assert ref_rows > 1 or u_ff is not None, "T is needed with a set-point reference and no u_ff"
+        T = ref_rows if ref_rows > 1 else int(u_ff.shape[-2])
+    T = int(T)
+    if u_ff is not None:
+        assert tuple(int(v) for v in u_ff.shape) == lead + (B, T, nu), f"u_ff shape {tuple(u_ff.shape)} != {lead + (B, T, nu)}"
+    track = model == THRUSTER_EULER and lag is not None
+    if track:
+        assert int(np.prod(lag.shape)) == P * B * 24, "lag must be [P,B,8,3]"
+    if z is not None:
+        assert int(np.prod(z.shape)) == P * B * 6, "z must be [P,B,6]"
+
+    def in_out(v, shape):          # in / out in the ABI: work on a copy
+        if v is None:
+            return None
+        if host:
+            return arr.upload(v.reshape(shape))
+        return (v.clone() if _is_torch(v) else arr.upload(v.numpy())).reshape(shape)
+    if host:
+        x0, ref = arr.upload(x0), arr.upload(ref)
+        u_ff = None if u_ff is None else arr.upload(u_ff)
+    lag_io = in_out(lag, (P, B, 8, 3)) if track else None
+    z_io = in_out(z, (P, B, 6))
+    stride = int(stride)
+    traj = arr.empty((P, B, T // stride + 1 if stride >= 1 else 1, nx)) if store else None     # stride < 1: refused by the library
+    xT = arr.empty((P, B, nx))
+    u = arr.empty((P, B, T, nu)) if want_u else None
+    metrics = arr.empty((P, B, 4)) if want_metrics else None
+    ctx.check(ctx.lib.brov_rollout_feedback_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, len(fbs), fa,
+                                                int(bool(per_candidate)), B, T, float(dt), _dptr(x0), _dptr(u_ff), _dptr(ref), ref_rows,
+                                                _dptr(lag_io), _dptr(z_io), _dptr(traj), stride, _dptr(xT), _dptr(u), _dptr(metrics)),
+              "brov_rollout_feedback_dev")
+    out = dict(traj=traj, xT=xT, lag=lag_io, z=z_io, u=u, metrics=metrics)
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out

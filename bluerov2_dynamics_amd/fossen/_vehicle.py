@@ -181,6 +181,31 @@ class VehicleBase:
                                dt, ctx=self._ctx)
         return r["traj"][:, 0]
 
+    def simulate_closed_loop(self, x0, ref, dt, feedback, T=None, params_list=None, integrator="euler", hold=None):
+        """One trajectory under a feedback law evaluated inside the rollout kernel (engine.rollout_feedback; fossen/control.py builds
+        `feedback`): x0 [nx], ref [nx] (a set-point; T required) or [T,nx] (row t tracked at step t).  hold overrides the
+        controller period of `feedback`.  Returns (traj [T+1,nx], u [T,nu] the applied commands, metrics [4]).  With params_list
+        (P _lib.BrovParams) the same controller runs on P vehicles in one launch and every result gains a leading P axis.
+        Starts from zero thruster lag and zero integral state; this object's own lag state is neither read nor changed, and its
+        parameters reach the kernel as arguments (params_of), not through the ctx."""
+        import ctypes
+        from . import identify
+        ref = np.asarray(ref, float)
+        ref = ref[None] if ref.ndim == 1 else ref
+        if T is None and ref.shape[0] == 1:
+            raise ValueError("T is needed with a set-point reference")
+        if hold is not None:
+            fb = _lib.BrovFeedback()
+            ctypes.memmove(ctypes.byref(fb), ctypes.byref(feedback), ctypes.sizeof(fb))
+            fb.hold = int(hold)
+            feedback = fb
+        single = params_list is None
+        ps = [identify.params_of(self)] if single else list(params_list)
+        r = engine.rollout_feedback(self.MODEL, integrator, ps, feedback, np.asarray(x0, float)[None], ref[None], dt, T=T, want_u=True,
+                                    ctx=self._ctx)
+        out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
+        return tuple(v[0] for v in out) if single else out
+
     def one_step_rmse(self, X, U, dt):
         """one_step_rmse_physics (training/train_tank_brov2_koopmanEDMDc.py:237-247): Euler one-step predictions over a
         recording with ONE vehicle object (the lag runs through the whole sequence) == the H = 1 window evaluator."""

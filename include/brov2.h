@@ -275,6 +275,60 @@ BROV_API int brov_rollout_pop_dev(brov_ctx* ctx, int model, int integrator, int 
  * candidate's value is not finite all four are NaN.  Summed in index order, no atomics: the same bits from run to run.  P >= 1. */
 BROV_API int brov_ensemble_stats_dev(brov_ctx* ctx, int64_t P, int64_t M, const double* d_vals, double* d_out);
 
+/* ---- closed-loop rollouts: a feedback law evaluated inside the rollout kernel -----------------------------------------------
+ * brov_rollout_feedback is brov_rollout_pop with the control array replaced by a linear tracking law on the state, which never
+ * leaves the kernel: candidate j rolls B trajectories of T steps under params[j], and at every step the command comes from the
+ * state, a reference and the gains below.  One law serves the wrench models (nu = 6) and the thruster model (nu = 8).
+ *
+ * Ticks and hold.  The law is evaluated at the steps t = 0, hold, 2 hold, ... of a call (hold >= 1) and its command is held in
+ * between (zero-order hold).  Under RK4 the command is constant over the four stages; the thruster lag advances per lag_mode
+ * exactly as in brov_rollout_pop.
+ * Tracking error e[12], from the state x at the start of the step and the reference row r, which has the layout of a state
+ * (nx values):
+ *     e[0:3]  = R(att)^T (r.p - x.p), the position error in the body frame, R the rotation matrix the model itself forms from x
+ *               (the quaternion model normalises q for it, as its dynamics do);
+ *     e[3:6]  = Euler models: r.att - x.att component-wise, wrapped to [-pi, pi] as d - 2 pi rint(d / (2 pi)) (round half to even:
+ *               a difference of exactly an odd multiple of pi keeps the sign rint gives it);
+ *               BROV_WRENCH_QUAT: q_e = conj(x.q) (x) r.q on the quaternions as stored, e = 2 s q_e.xyz with s = +1 when
+ *               q_e.w >= 0 and -1 otherwise (the short way round);
+ *     e[6:12] = r.nu - x.nu.
+ * Command and integral state, at a tick:
+ *     u = clip(u_ff[t] + K e + Ki z, u_min, u_max)            K [nu][12], Ki [nu][6], u_ff the feed-forward row of step t (NULL = 0)
+ *     z <- clip(z + hold dt e[0:6], -z_max, z_max)            after the command is formed: the first tick uses the incoming z,
+ *                                                             and anti-windup is the clamp.
+ * Reference: ref_rows = 1 is a set-point (one row per trajectory), ref_rows = T uses row t at step t.
+ * Metrics [4] per trajectory, accumulated at every step t = 0..T-1 on the state at the start of the step (the error is evaluated
+ * at every step for this, whatever hold is): sum dt |e[0:3]|^2, sum dt |e[3:6]|^2, sum dt |u|^2 of the applied command, and the
+ * number of steps at which at least one channel of the applied command equals its u_min or u_max.
+ *
+ * Arguments as brov_rollout_pop, except: u_ff [.][B][T][nu] is optional; fb is a HOST array of nfb records, nfb = 1 (one
+ * controller for every vehicle: robustness) or nfb = P (candidate j under fb[j]: gain tuning); ref [.][B][ref_rows][nx];
+ * inputs_per_candidate covers x0, u_ff and ref together (0: shared, leading dimension B; 1: leading dimensions [P][B]).  z_io
+ * [P][B][6] in/out (NULL = start from zero, nothing returned).  Optional outputs u_applied [P][B][T][nu] and metrics [P][B][4].
+ * Models, integrators, lag modes and the range of P are those of brov_rollout_pop (double-integrator models: BROV_ERR_ARG); B = 0
+ * or P = 0: BROV_OK, nothing touched.  Refused on the host with BROV_ERR_ARG and a brov_last_error text naming the rule, before
+ * anything is copied or launched: hold < 1, nfb not in {1, P}, ref_rows not in {1, T}, u_min > u_max (channels < nu), a negative
+ * z_max, a NaN anywhere in fb, traj_stride < 1.  The ctx's own parameters are neither read nor written.
+ * Deterministic (no atomics, every lane writes its own outputs): two calls give the same bits.  Resume: a call of T1 steps with
+ * T1 a multiple of hold, continued by a call from the returned (xT, lag_io, z_io) with the remaining rows of u_ff / ref, gives the
+ * bits of one call over both spans in traj, xT, lag_io, z_io and u_applied; the metrics of the two spans add up to those of the
+ * one call to rounding only (the sums are split at T1). */
+typedef struct brov_feedback {
+    double K[8][12], Ki[8][6];      /* rows >= nu ignored */
+    double u_min[8], u_max[8];      /* u_min <= u_max, may be +-inf */
+    double z_max[6];                /* >= 0, may be inf */
+    int32_t hold, _pad;             /* >= 1 */
+} brov_feedback;
+BROV_API int brov_rollout_feedback(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                          int64_t nfb, const brov_feedback* fb /* [nfb], host */, int inputs_per_candidate, int64_t B, int64_t T,
+                          double dt, const double* x0, const double* u_ff, const double* ref, int64_t ref_rows, double* lag_io,
+                          double* z_io, double* traj, int64_t traj_stride, double* xT, double* u_applied, double* metrics);
+BROV_API int brov_rollout_feedback_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                              int64_t nfb, const brov_feedback* fb /* [nfb], host */, int inputs_per_candidate, int64_t B, int64_t T,
+                              double dt, const double* d_x0, const double* d_u_ff, const double* d_ref, int64_t ref_rows,
+                              double* d_lag_io, double* d_z_io, double* d_traj, int64_t traj_stride, double* d_xT,
+                              double* d_u_applied, double* d_metrics);
+
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
  * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.
