@@ -49,6 +49,17 @@ class BrovFeedback(ctypes.Structure):
     ]
 
 
+class BrovMppi(ctypes.Structure):
+    """struct brov_mppi (include/brov2.h): weights, noise, limits and temperature of brov_mppi_step.  fossen/control.py builds it."""
+    _fields_ = [
+        ("q", ctypes.c_double * 12), ("qf", ctypes.c_double * 12),
+        ("r", ctypes.c_double * 8), ("sigma", ctypes.c_double * 8),
+        ("u_min", ctypes.c_double * 8), ("u_max", ctypes.c_double * 8),
+        ("lam", ctypes.c_double), ("gamma", ctypes.c_double),
+        ("hold", ctypes.c_int32), ("_pad", ctypes.c_int32),
+    ]
+
+
 class PincHyper(ctypes.Structure):
     """struct brov_pinc_hyper (include/brov2.h)."""
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -109,6 +120,7 @@ SIGNATURES = {
     "brov_free": (ctypes.c_int, [c_void_p, c_void_p]),
     "brov_memcpy_h2d": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
     "brov_memcpy_d2h": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
+    "brov_memcpy_d2d": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_size_t]),
     "brov_memset": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_size_t]),
     "brov_mem_info": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
     "edmdc_col_stats_dev": (ctypes.c_int, [c_void_p, i64, ctypes.c_int, c_void_p, i64, c_void_p, c_void_p]),
@@ -152,6 +164,12 @@ SIGNATURES = {
                                                  ctypes.POINTER(BrovFeedback), ctypes.c_int, i64, i64, ctypes.c_double, c_void_p,
                                                  c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p, i64, c_void_p, c_void_p,
                                                  c_void_p]),
+    "brov_mppi_step": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.POINTER(BrovParams),
+                                      ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
+                                      i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "brov_mppi_step_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.POINTER(BrovParams),
+                                          ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p,
+                                          c_void_p, i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

@@ -44,6 +44,29 @@ struct FeedbackArgs {
     double *lag, *z, *traj, *xT, *u_applied, *metrics;
 };
 hipError_t launch_rollout_feedback(hipStream_t st, int model, int integ, int lag_mode, int P, const FeedbackArgs& a);
+// One MPPI update for B problems (mppi.hip; include/brov2.h: brov_mppi_step holds the law).  MppiRec is struct brov_mppi byte for
+// byte; rec is ONE device record.  fp holds one parameter set (per_problem = 0) or B.  x [B][nx], lag [B][24] or nullptr (zero), ref
+// [B][ref_total][nx], eps [B][K][M][nu] or nullptr (the seeded stream), U_nom [B][M][nu] in / out, M = ceil(H / hold).  cost [B][K]
+// and U_old [B][M][nu] are never nullptr here (scratch when the caller wants no costs; U_old receives the knots as they came);
+// u_apply [B][hold][nu] and info [B][4] may be.  Two launches, whatever B, K and H are.
+struct MppiRec {
+    double q[12], qf[12];
+    double r[8], sigma[8];
+    double u_min[8], u_max[8];
+    double lambda, gamma;
+    int32_t hold, pad;
+};
+struct MppiArgs {
+    const FastParams* fp;
+    const MppiRec* rec;
+    int per_problem, shift;
+    int64_t K, H, M, ref_total, ref_row0;
+    double dt;
+    uint64_t seed;
+    const double *x, *lag, *ref, *eps;
+    double *U_nom, *U_old, *u_apply, *cost, *info;
+};
+hipError_t launch_mppi_step(hipStream_t st, int model, int integ, int lag_mode, int64_t B, const MppiArgs& a);
 // vals [P][M] -> out [4][M]: mean, sample standard deviation, minimum, maximum over the P candidates; NaN where any is non-finite
 hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out);
 // The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major

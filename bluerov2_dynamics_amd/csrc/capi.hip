@@ -778,6 +778,16 @@ int brov_memcpy_d2h(brov_ctx* c, void* dst, const void* src, size_t bytes) {
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BROV_OK;
 }
+int brov_memcpy_d2d(brov_ctx* c, void* dst, const void* src, size_t bytes) {
+    if (!c || (bytes && (!dst || !src))) return BROV_ERR_ARG;
+    if (bytes == 0) return BROV_OK;
+    const char *d = static_cast<const char*>(dst), *s = static_cast<const char*>(src);
+    if (d < s + bytes && s < d + bytes) return fail(c, BROV_ERR_ARG, "brov_memcpy_d2d: the ranges overlap");
+    DeviceGuard g(c);
+    lift_cache_touch(c, dst);
+    HIPCK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    return BROV_OK;
+}
 int brov_memset(brov_ctx* c, void* dst, int value, size_t bytes) {
     if (!c || (bytes && !dst)) return BROV_ERR_ARG;
     DeviceGuard g(c);
@@ -1791,6 +1801,138 @@ int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64
     if (traj) HIPCK(c, d2h_copy(c, traj, dtr, nout * rows * nx * 8));
     if (n_ua) HIPCK(c, d2h_copy(c, u_applied, dua, n_ua * 8));
     if (metrics) HIPCK(c, d2h_copy(c, metrics, dm, nout * 4 * 8));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return BROV_OK;
+}
+
+// ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------
+static_assert(sizeof(brov_mppi) == sizeof(MppiRec) && sizeof(brov_mppi) == 59 * 8, "MppiRec is brov_mppi byte for byte");
+// Everything the host can refuse, and the derived constants of every parameter set: nothing has been copied or launched when this
+// fails.  *M = the number of knots.
+static int mppi_prepare(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
+                        const brov_mppi* cfg, int64_t K, int64_t H, double dt, const void* x, const void* ref, int64_t ref_total,
+                        int64_t ref_row0, const void* U_nom, std::vector<FastParams>& fp, int64_t* M) {
+    if (!c) return BROV_ERR_ARG;
+    if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) || B < 0)
+        return fail(c, BROV_ERR_ARG, "brov_mppi_step: bad enum or negative size");
+    if (model_is_di_h(model))
+        return fail(c, BROV_ERR_ARG, "brov_mppi_step: the double-integrator gains are not brov_params; thruster and wrench models only");
+    if (B > 65535) return fail(c, BROV_ERR_ARG, "brov_mppi_step: B must be <= 65535");
+    if (B == 0) return BROV_OK;
+    if (K < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be >= 1");
+    if (H < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be >= 1");
+    if (K > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be <= 2^31");
+    if (H > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be <= 2^31");
+    if (!params || !cfg || !x || !ref || !U_nom) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NULL input");
+    if (nparams != 1 && nparams != B) return fail(c, BROV_ERR_ARG, "brov_mppi_step: nparams must be 1 or B");
+    const int nu = NU(model);
+    const double* v = cfg->q;
+    for (int i = 0; i < 58; ++i)
+        if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NaN in the record");
+    if (cfg->hold < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: hold must be >= 1");
+    if (!(cfg->lambda > 0.0)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: lambda must be > 0");
+    if (cfg->gamma < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: gamma must be >= 0");
+    for (int i = 0; i < 12; ++i)
+        if (cfg->q[i] < 0.0 || cfg->qf[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: the weights q and qf must be >= 0");
+    for (int i = 0; i < nu; ++i) {
+        if (cfg->r[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: the weights r must be >= 0");
+        if (cfg->sigma[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: sigma must be >= 0");
+        if (cfg->u_min[i] > cfg->u_max[i]) return fail(c, BROV_ERR_ARG, "brov_mppi_step: u_min must be <= u_max");
+    }
+    if (ref_total == 1 ? ref_row0 != 0 : (ref_total < 1 || ref_row0 < 0 || H >= ref_total || ref_row0 > ref_total - 1 - H))
+        return fail(c, BROV_ERR_ARG, "brov_mppi_step: the reference window ref_row0 .. ref_row0 + H must lie inside ref_total (a set-point: ref_total = 1, ref_row0 = 0)");
+    *M = (H + cfg->hold - 1) / cfg->hold;
+    std::vector<double> phi;
+    return derive_candidates(c, integ, (int)nparams, params, 0, dt, false, fp, phi);
+}
+// one upload of FastParams[nparams] and the record, two launches.  d_cost may be nullptr (arena scratch then).
+static int mppi_impl(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, const std::vector<FastParams>& fp, const brov_mppi* cfg,
+                     MppiArgs args, Arena& a) {
+    const size_t np = fp.size();
+    const int nu = NU(model);
+    char* blob = a.take<char>(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec));
+    args.U_old = a.take<double>((size_t)B * args.M * nu);
+    if (!args.cost) args.cost = a.take<double>((size_t)B * args.K);
+    std::vector<char> host(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec));
+    memcpy(host.data(), fp.data(), np * sizeof(FastParams));
+    memcpy(host.data() + Arena::al(np * sizeof(FastParams)), cfg, sizeof(MppiRec));
+    HIPCK(c, h2d_copy(c, blob, host.data(), host.size()));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // host is a local
+    args.fp = reinterpret_cast<const FastParams*>(blob);
+    args.rec = reinterpret_cast<const MppiRec*>(blob + Arena::al(np * sizeof(FastParams)));
+    args.per_problem = np > 1;
+    CallTimer t(c);
+    HIPCK(c, launch_mppi_step(c->stream, model, integ, lag_mode, B, args));
+    return BROV_OK;
+}
+static size_t mppi_scratch(int64_t B, size_t np, int64_t K, int64_t M, int nu, bool own_cost) {
+    return Arena::al(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec)) + Arena::al((size_t)B * M * nu * 8) +
+           (own_cost ? Arena::al((size_t)B * K * 8) : 0);
+}
+
+int brov_mppi_step_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
+                       const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* d_x, const double* d_lag,
+                       const double* d_ref, int64_t ref_total, int64_t ref_row0, const double* d_eps, double* d_U_nom, int shift,
+                       double* d_u_apply, double* d_cost, double* d_info) {
+    std::vector<FastParams> fp;
+    int64_t M = 0;
+    int rc = mppi_prepare(c, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, d_x, d_ref, ref_total, ref_row0, d_U_nom, fp, &M);
+    if (rc) return rc;
+    if (B == 0) return BROV_OK;
+    DeviceGuard g(c);
+    Arena a(c);
+    rc = a.reserve(mppi_scratch(B, fp.size(), K, M, NU(model), !d_cost));
+    if (rc) return rc;
+    MppiArgs args{};
+    args.shift = shift != 0;
+    args.K = K; args.H = H; args.M = M; args.ref_total = ref_total; args.ref_row0 = ref_row0; args.dt = dt; args.seed = seed;
+    args.x = d_x; args.lag = model == BROV_THRUSTER_EULER ? d_lag : nullptr; args.ref = d_ref; args.eps = d_eps;
+    args.U_nom = d_U_nom; args.u_apply = d_u_apply; args.cost = d_cost; args.info = d_info;
+    return mppi_impl(c, model, integ, lag_mode, B, fp, cfg, args, a);
+}
+
+int brov_mppi_step(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
+                   const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* x, const double* lag,
+                   const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps, double* U_nom, int shift, double* u_apply,
+                   double* cost, double* info) {
+    std::vector<FastParams> fp;
+    int64_t M = 0;
+    int rc = mppi_prepare(c, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, x, ref, ref_total, ref_row0, U_nom, fp, &M);
+    if (rc) return rc;
+    if (B == 0) return BROV_OK;
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const bool has_lag = lag && model == BROV_THRUSTER_EULER;
+    const size_t n_x = (size_t)B * nx, n_ref = (size_t)B * ref_total * nx, n_eps = eps ? (size_t)B * K * M * nu : 0, n_U = (size_t)B * M * nu;
+    const size_t n_ua = u_apply ? (size_t)B * cfg->hold * nu : 0, n_cost = (size_t)B * K;
+    Arena a(c);
+    rc = a.reserve(Arena::al(n_x * 8) + (has_lag ? Arena::al((size_t)B * 24 * 8) : 0) + Arena::al(n_ref * 8) + Arena::al(n_eps * 8) + Arena::al(n_U * 8) +
+                   Arena::al(n_ua * 8) + Arena::al(n_cost * 8) + Arena::al((size_t)B * 4 * 8) + mppi_scratch(B, fp.size(), K, M, nu, false));
+    if (rc) return rc;
+    double* dx = a.take<double>(n_x);
+    double* dl = has_lag ? a.take<double>((size_t)B * 24) : nullptr;
+    double* dref = a.take<double>(n_ref);
+    double* deps = eps ? a.take<double>(n_eps) : nullptr;
+    double* dU = a.take<double>(n_U);
+    double* dua = u_apply ? a.take<double>(n_ua) : nullptr;
+    double* dcost = a.take<double>(n_cost);
+    double* dinfo = info ? a.take<double>((size_t)B * 4) : nullptr;
+    HIPCK(c, h2d_copy(c, dx, x, n_x * 8));
+    if (has_lag) HIPCK(c, h2d_copy(c, dl, lag, (size_t)B * 24 * 8));
+    HIPCK(c, h2d_copy(c, dref, ref, n_ref * 8));
+    if (n_eps) HIPCK(c, h2d_copy(c, deps, eps, n_eps * 8));
+    HIPCK(c, h2d_copy(c, dU, U_nom, n_U * 8));
+    MppiArgs args{};
+    args.shift = shift != 0;
+    args.K = K; args.H = H; args.M = M; args.ref_total = ref_total; args.ref_row0 = ref_row0; args.dt = dt; args.seed = seed;
+    args.x = dx; args.lag = dl; args.ref = dref; args.eps = deps;
+    args.U_nom = dU; args.u_apply = dua; args.cost = dcost; args.info = dinfo;
+    rc = mppi_impl(c, model, integ, lag_mode, B, fp, cfg, args, a);
+    if (rc) return rc;
+    HIPCK(c, d2h_copy(c, U_nom, dU, n_U * 8));
+    if (n_ua) HIPCK(c, d2h_copy(c, u_apply, dua, n_ua * 8));
+    if (cost) HIPCK(c, d2h_copy(c, cost, dcost, n_cost * 8));
+    if (info) HIPCK(c, d2h_copy(c, info, dinfo, (size_t)B * 4 * 8));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return BROV_OK;
 }

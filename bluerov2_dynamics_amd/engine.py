@@ -107,6 +107,12 @@ class DevArray:
             self.ctx.check(self.ctx.lib.brov_memcpy_d2h(self.ctx.h, out.ctypes.data, self.ptr, out.nbytes), "brov_memcpy_d2h")
         return out
 
+    def copy_from_device(self, src):
+        """device-to-device copy of another DevArray of the same size, on the ctx's stream (no host round trip)"""
+        assert src.nbytes == self.nbytes, "size mismatch"
+        self.ctx.check(self.ctx.lib.brov_memcpy_d2d(self.ctx.h, self.ptr, src.ptr, self.nbytes), "brov_memcpy_d2d")
+        return self
+
     def zero_(self):
         self.ctx.check(self.ctx.lib.brov_memset(self.ctx.h, self.ptr, 0, self.nbytes), "brov_memset")
         return self
@@ -583,6 +589,66 @@ def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=No
                                                 _dptr(lag_io), _dptr(z_io), _dptr(traj), stride, _dptr(xT), _dptr(u), _dptr(metrics)),
               "brov_rollout_feedback_dev")
     out = dict(traj=traj, xT=xT, lag=lag_io, z=z_io, u=u, metrics=metrics)
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def mppi_step(model, integrator, params_list, cfg, x, ref, U_nom, dt, K, H=None, lag=None, lag_mode=LAG_PER_CALL, seed=0, eps=None,
+              ref_row0=0, shift=False, want_cost=False, ctx=None):
+    """One sampling-based model-predictive (MPPI) update for B problems: K perturbed command sequences per problem are drawn,
+    rolled out H steps, scored and combined through a soft-min on the device (include/brov2.h: brov_mppi_step_dev holds the law).
+
+    params_list: one _lib.BrovParams (one planning model for every problem) or B.  cfg: a _lib.BrovMppi (fossen/control.py: mppi).
+    x [B,nx], ref [B,rows,nx] (rows = 1: a set-point; else rows ref_row0 .. ref_row0 + H are read), U_nom [B,M,nu] with
+    M = ceil(H / cfg.hold) knots; H defaults to M cfg.hold.  lag [B,8,3] (thruster model) is the start lag, None = zero.  eps
+    [B,K,M,nu] gives the normals explicitly; None draws them from the library's stream at `seed`.  Host arrays are uploaded and the
+    results come back as NumPy arrays; device arrays (DevArray / torch CUDA tensors) are used in place and the results come back
+    as device arrays of the same kind.  Returns dict(U_nom [B,M,nu] the updated (shift: and shifted) knots -- a new array, the
+    argument is not written --, u_apply [B,hold,nu], cost [B,K] | None (want_cost), info [B,4] = S_0, beta, effective sample size,
+    non-finite samples).  The ctx's own parameters are left alone."""
+    ps = [params_list] if isinstance(params_list, _lib.BrovParams) else list(params_list)
+    pa = (_lib.BrovParams * max(len(ps), 1))(*ps)
+    nx, nu = NX.get(model, 12), NU.get(model, 8)
+    host = isinstance(x, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x, ref, U_nom = as_f64(x), as_f64(ref), as_f64(U_nom)
+        lag, eps = (None if v is None else as_f64(v) for v in (lag, eps))
+    else:
+        ctx = _ctx_of(x, ctx)
+        arr = arrays_of(x, ctx)
+    arr.bind()
+    assert len(x.shape) == 2 and int(x.shape[1]) == nx, f"x must be [B,nx] with nx = {nx}"
+    B = int(x.shape[0])
+    assert len(ref.shape) == 3 and int(ref.shape[0]) == B and int(ref.shape[2]) == nx, f"ref shape {tuple(ref.shape)} != {(B, 'rows', nx)}"
+    assert len(U_nom.shape) == 3 and int(U_nom.shape[0]) == B and int(U_nom.shape[2]) == nu, f"U_nom shape {tuple(U_nom.shape)} != {(B, 'M', nu)}"
+    M, hold, K = int(U_nom.shape[1]), int(cfg.hold), int(K)
+    H = M * hold if H is None else int(H)
+    if hold >= 1 and H >= 1:          # otherwise the library refuses the call
+        assert (H + hold - 1) // hold == M, f"U_nom has {M} knots, H = {H} at hold = {hold} needs {(H + hold - 1) // hold}"
+    if lag is not None and model == THRUSTER_EULER:
+        assert int(np.prod(lag.shape)) == B * 24, "lag must be [B,8,3]"
+    else:
+        lag = None
+    if eps is not None:
+        assert tuple(int(v) for v in eps.shape) == (B, K, M, nu), f"eps shape {tuple(eps.shape)} != {(B, K, M, nu)}"
+    if host:
+        x, ref = arr.upload(x), arr.upload(ref)
+        lag = None if lag is None else arr.upload(lag)
+        eps = None if eps is None else arr.upload(eps)
+        U = arr.upload(U_nom)
+    else:                             # in / out in the ABI: work on a copy
+        U = U_nom.clone() if _is_torch(U_nom) else arr.empty(tuple(U_nom.shape)).copy_from_device(U_nom)
+    u_apply = arr.empty((B, max(hold, 1), nu))
+    cost = arr.empty((B, max(K, 1))) if want_cost else None
+    info = arr.empty((B, 4))
+    ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, B, len(ps), pa, ctypes.byref(cfg), K, H, float(dt),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, _dptr(x), _dptr(lag), _dptr(ref), int(ref.shape[1]), int(ref_row0),
+                                         _dptr(eps), _dptr(U), int(bool(shift)), _dptr(u_apply), _dptr(cost), _dptr(info)),
+              "brov_mppi_step_dev")
+    out = dict(U_nom=U, u_apply=u_apply, cost=cost, info=info)
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out

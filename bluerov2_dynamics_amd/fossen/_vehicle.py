@@ -206,6 +206,82 @@ class VehicleBase:
         out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
         return tuple(v[0] for v in out) if single else out
 
+    def simulate_mppi(self, x0, ref, dt, cfg, T, K, H, plant_params=None, integrator="euler", seed=0):
+        """Receding-horizon control of B plants by the sampling-based model-predictive update (engine.mppi_step; fossen/control.py:
+        mppi builds `cfg`), planned with THIS vehicle's parameters.  The loop is device-resident: the state, the thruster lag and
+        the plan never come back to the host between ticks.
+
+        x0 [B,nx] (or [nx], repeated for every plant); ref [nx] or [B,nx] (a set-point) or [B,T+H+1,nx] (row t tracked at step t).
+        T steps, a multiple of cfg.hold.  Tick n starts at step n hold: one update with K samples over a horizon of H steps
+        (shift=True, seed + n, reference rows from n hold), then hold plant steps on the first knot.  plant_params=None: the plants
+        are this vehicle (B from x0); a list of B _lib.BrovParams: plant b runs under plant_params[b] while the planner keeps this
+        vehicle's model -- the model-mismatch case.  Every plant starts from zero thruster lag and a zero plan.
+        Returns dict(traj [B,T+1,nx], u [B,T,nu] the applied commands, info [ticks,B,4], ticks = dict(x [ticks,B,nx], lag
+        [ticks,B,8,3] | None, U_nom [ticks,B,M,nu], seed [ticks], ref_row0 [ticks]): what the planner saw at each tick, before
+        its update)."""
+        import ctypes
+        from . import identify
+        model, ctx = self.MODEL, self._ctx
+        nx, nu = _lib.NX[model], _lib.NU[model]
+        hold, T, K, H = int(cfg.hold), int(T), int(K), int(H)
+        if hold < 1 or H < 1 or K < 1:
+            raise ValueError("hold, H and K must be >= 1")
+        if T < 0 or T % hold:
+            raise ValueError(f"T = {T} must be a multiple of hold = {hold}")
+        plants = None if plant_params is None else list(plant_params)
+        x0 = np.asarray(x0, float)
+        if x0.ndim == 1:
+            x0 = np.repeat(x0[None], len(plants) if plants else 1, axis=0)
+        B = x0.shape[0]
+        if x0.shape != (B, nx) or (plants is not None and len(plants) != B):
+            raise ValueError(f"x0 must be [B,{nx}] with one row per plant")
+        ref = np.asarray(ref, float)
+        if ref.ndim == 1:
+            ref = np.repeat(ref[None, None], B, axis=0)
+        elif ref.ndim == 2:
+            ref = ref[:, None]
+        setpoint = ref.shape[1] == 1
+        if ref.shape[0] != B or ref.shape[2] != nx or not (setpoint or ref.shape[1] >= T + H + 1):
+            raise ValueError(f"ref must be a set-point or [B,T+H+1,{nx}], got {ref.shape}")
+        nt, M = T // hold, (H + hold - 1) // hold
+        integ = engine.INTEGRATORS[integrator]
+        planner = (_lib.BrovParams * 1)(identify.params_of(self))
+        pa = planner if plants is None else (_lib.BrovParams * B)(*plants)
+        P, Bp, per = (1, B, 0) if plants is None else (B, 1, 1)          # [1][B] or [B][1] rows: the same bytes either way
+        ctx.use_null_stream()
+        D = engine.DevArray
+        X = D(ctx, (nt + 1, B, nx))
+        X.rows(0, 1).copy_from_host(x0)
+        d_ref = D.from_host(ctx, ref)
+        thr = model == _lib.THRUSTER_EULER
+        lag = D(ctx, (B, 8, 3)).zero_() if thr else None
+        U = D(ctx, (B, M, nu)).zero_()
+        traj, ua, info = D(ctx, (max(nt, 1), B, hold + 1, nx)), D(ctx, (max(nt, 1), B, hold, nu)), D(ctx, (max(nt, 1), B, 4))
+        rec_lag = D(ctx, (max(nt, 1), B, 8, 3)) if thr else None
+        rec_U = D(ctx, (max(nt, 1), B, M, nu))
+        seeds, rows = [], []
+        p_ = lambda a: None if a is None else a.ptr
+        for n in range(nt):
+            row0 = 0 if setpoint else n * hold
+            seeds.append(int(seed) + n)
+            rows.append(row0)
+            if thr:
+                rec_lag.rows(n, n + 1).copy_from_device(lag)
+            rec_U.rows(n, n + 1).copy_from_device(U)
+            xn = X.rows(n, n + 1)
+            ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, B, 1, planner, ctypes.byref(cfg), K, H, float(dt),
+                                                 seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, p_(lag), d_ref.ptr, ref.shape[1], row0, None, U.ptr, 1,
+                                                 ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "brov_mppi_step_dev")
+            ctx.check(ctx.lib.brov_rollout_pop_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, P, pa, per, Bp, hold, float(dt), xn.ptr,
+                                                   ua.rows(n, n + 1).ptr, p_(lag), traj.rows(n, n + 1).ptr, 1, X.rows(n + 1, n + 2).ptr),
+                      "brov_rollout_pop_dev")
+        tr = traj.numpy()[:nt]                                           # [nt,B,hold+1,nx]: drop every segment's first row but the first's
+        states = np.concatenate([x0[:, None]] + [tr[n][:, 1:] for n in range(nt)], axis=1)
+        u = np.concatenate([ua.numpy()[n] for n in range(nt)], axis=1) if nt else np.zeros((B, 0, nu))
+        ticks = dict(x=X.numpy()[:nt], lag=rec_lag.numpy()[:nt] if thr else None, U_nom=rec_U.numpy()[:nt],
+                     seed=np.array(seeds, dtype=np.int64), ref_row0=np.array(rows, dtype=np.int64))
+        return dict(traj=states, u=u, info=info.numpy()[:nt], ticks=ticks)
+
     def one_step_rmse(self, X, U, dt):
         """one_step_rmse_physics (training/train_tank_brov2_koopmanEDMDc.py:237-247): Euler one-step predictions over a
         recording with ONE vehicle object (the lag runs through the whole sequence) == the H = 1 window evaluator."""

@@ -1,5 +1,6 @@
-"""Feedback laws for the closed-loop rollouts (engine.rollout_feedback, VehicleBase.simulate_closed_loop): builders of
-struct brov_feedback and the tracking error on the host.  include/brov2.h (brov_rollout_feedback) is the specification of the law:
+"""Feedback laws for the closed-loop rollouts (engine.rollout_feedback, VehicleBase.simulate_closed_loop) and the record of the
+model-predictive update (engine.mppi_step, VehicleBase.simulate_mppi): builders of struct brov_feedback and struct brov_mppi, and
+the tracking error on the host.  include/brov2.h (brov_rollout_feedback) is the specification of the law:
 
     e[0:3]  = R(att)^T (p_ref - p)          e[3:6] = attitude error (wrapped Euler difference, or 2 s q_e.xyz)
     e[6:12] = nu_ref - nu
@@ -61,6 +62,49 @@ def feedback(K, Ki=None, u_min=None, u_max=None, z_max=None, hold=1, nu=None):
         fb.z_max[j] = zm[j]
     fb.hold = hold
     return fb
+
+
+def mppi(q, qf=None, r=0.0, sigma=0.1, lam=1.0, gamma=None, u_min=None, u_max=None, hold=1, nu=None):
+    """struct brov_mppi (include/brov2.h: brov_mppi_step) from the stage weights q and terminal weights qf on the tracking error
+    (scalar or [12]; qf=None means q), the command weights r and the noise sigma (scalar or [nu]), the temperature lam, the weight
+    gamma of the importance term (None means lam), limits u_min / u_max (scalar or [nu]; None = -inf / +inf) and hold (steps per
+    knot).  nu (6 or 8) defaults to the length of the first of r, sigma, u_min, u_max given as a vector, else 8.  ValueError where
+    the library would refuse the record: a NaN, a negative weight, sigma or gamma, lam <= 0, u_min > u_max, hold < 1."""
+    if nu is None:
+        nu = next((np.asarray(v).shape[0] for v in (r, sigma, u_min, u_max) if v is not None and np.ndim(v) == 1), 8)
+    nu = int(nu)
+    if nu not in (6, 8):
+        raise ValueError(f"nu must be 6 or 8, got {nu}")
+    q = _vec(q, 12, 0.0, "q")
+    qf = q.copy() if qf is None else _vec(qf, 12, 0.0, "qf")
+    r, sg = _vec(r, nu, 0.0, "r"), _vec(sigma, nu, 0.0, "sigma")
+    lo, hi = _vec(u_min, nu, -np.inf, "u_min"), _vec(u_max, nu, np.inf, "u_max")
+    lam = float(lam)
+    gamma = lam if gamma is None else float(gamma)
+    if isinstance(hold, float) and hold != int(hold):
+        raise ValueError(f"hold must be an integer, got {hold}")
+    hold = int(hold)
+    if hold < 1 or hold >= 2 ** 31:
+        raise ValueError(f"hold must be >= 1, got {hold}")
+    if any(np.isnan(a).any() for a in (q, qf, r, sg, lo, hi)) or np.isnan(lam) or np.isnan(gamma):
+        raise ValueError("NaN in the MPPI record")
+    if np.any(q < 0) or np.any(qf < 0) or np.any(r < 0):
+        raise ValueError("the weights q, qf and r must be >= 0")
+    if np.any(sg < 0):
+        raise ValueError("sigma must be >= 0")
+    if not lam > 0:
+        raise ValueError("lam must be > 0")
+    if gamma < 0:
+        raise ValueError("gamma must be >= 0")
+    if np.any(lo > hi):
+        raise ValueError("u_min must be <= u_max")
+    cfg = _lib.BrovMppi()
+    for i in range(12):
+        cfg.q[i], cfg.qf[i] = q[i], qf[i]
+    for j in range(nu):
+        cfg.r[j], cfg.sigma[j], cfg.u_min[j], cfg.u_max[j] = r[j], sg[j], lo[j], hi[j]
+    cfg.lam, cfg.gamma, cfg.hold = lam, gamma, hold
+    return cfg
 
 
 def _gain6(g, name):

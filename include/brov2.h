@@ -130,6 +130,9 @@ BROV_API int brov_malloc(brov_ctx* ctx, size_t bytes, void** dptr);
 BROV_API int brov_free(brov_ctx* ctx, void* dptr);
 BROV_API int brov_memcpy_h2d(brov_ctx* ctx, void* dst, const void* src, size_t bytes);
 BROV_API int brov_memcpy_d2h(brov_ctx* ctx, void* dst, const void* src, size_t bytes);
+/* device to device on the ctx stream, asynchronous like brov_memset (both ranges on the ctx's device; overlapping ranges:
+ * BROV_ERR_ARG, nothing copied) */
+BROV_API int brov_memcpy_d2d(brov_ctx* ctx, void* dst, const void* src, size_t bytes);
 BROV_API int brov_memset(brov_ctx* ctx, void* dst, int value, size_t bytes);
 /* Free and total bytes of the ctx's device (hipMemGetInfo): lets a caller without HIP / torch decide whether an optional buffer
  * (edmdc_lift_cache) fits. */
@@ -328,6 +331,64 @@ BROV_API int brov_rollout_feedback_dev(brov_ctx* ctx, int model, int integrator,
                               double dt, const double* d_x0, const double* d_u_ff, const double* d_ref, int64_t ref_rows,
                               double* d_lag_io, double* d_z_io, double* d_traj, int64_t traj_stride, double* d_xT,
                               double* d_u_applied, double* d_metrics);
+
+/* ---- model-predictive control: one sampling-based (MPPI) update, sampled, rolled out and scored on the device ---------------------
+ * brov_mppi_step performs one MPPI update for B independent problems (B vehicles, or B draws of a fit).  Problem b has a state
+ * x [nx], for the thruster model optionally a start lag [8][3] (read only; NULL = zero), a reference, and a nominal knot sequence
+ * U_nom [M][nu] with M = ceil(H / hold): step t of the horizon uses knot m(t) = t / hold (the last knot may cover fewer than hold
+ * steps).
+ *
+ * Samples.  Sample 0 is the nominal itself (xi = 0).  For k >= 1 and sigma[j] > 0, xi[k][m][j] is read from the optional eps
+ * [B][K][M][nu] (row k = 0 of eps is ignored, and so are the channels with sigma[j] = 0), or, with eps = NULL, drawn from the
+ * library's counter-based stream: counter c = ((b K + k) M + m) nu + j, second stream s2 = seed ^ 0xA5A5A5A5A5A5A5A5,
+ * xi = sqrt(-2 ln(1 - u1)) cos(2 pi u2) with u1, u2 the uniforms number 2c and 2c + 1 of s2 -- the normal of dist B of
+ * brov_fill_controls_dev.
+ * Sample command and rollout.
+ *     v[k][m][j]     = clip(U_nom[m][j] + sigma[j] xi[k][m][j], u_min[j], u_max[j])        (a NaN xi stays a NaN)
+ *     delta[k][m][j] = v[k][m][j] - U_nom[m][j]                                            the perturbation after the clamp
+ * The rollout of sample k applies v[k][m(t)] at step t, H steps from x (and the lag), with the model, integrator and lag mode of
+ * brov_rollout_pop (the general step, both integrators, both lag modes; the double-integrator models: BROV_ERR_ARG).
+ * Cost.  e_t = the tracking error e[12] of brov_rollout_feedback on the state at the start of step t against reference row
+ * ref_row0 + t:
+ *     S_k = sum_{t<H} dt ( sum_i q[i] e_t[i]^2 + sum_j r[j] v[k][m(t)][j]^2 )
+ *           + sum_i qf[i] e_H[i]^2                                                          the end state against row ref_row0 + H
+ *           + gamma sum_m sum_{j: sigma[j] > 0} U_nom[m][j] delta[k][m][j] / sigma[j]^2     the importance term
+ * Reference: ref [B][ref_total][nx].  ref_total = 1 is a set-point (ref_row0 must be 0); otherwise the call reads the rows
+ * ref_row0 .. ref_row0 + H, which must lie inside ref_total.
+ * Update.  A non-finite S_k is left out (weight 0) and counted.  beta = the minimum over the finite S_k,
+ *     w_k = exp(-(S_k - beta) / lambda),   eta = sum_k w_k,
+ *     U_new[m][j] = clip(U_nom[m][j] + sum_k w_k delta[k][m][j] / eta, u_min[j], u_max[j]).
+ * shift = 0: U_nom <- U_new.  shift = 1: U_nom[m] <- U_new[m + 1], the last knot repeated (the plan of the next controller tick).
+ * Outputs, each optional: u_apply [B][hold][nu] = U_new[0] in hold rows (what brov_rollout_pop_dev takes as U for the plant);
+ * cost [B][K]; info [B][4] = S_0, beta, the effective sample size eta^2 / sum_k w_k^2, the number of non-finite samples.
+ * A problem with no finite sample: its U_nom is left as it came (no shift), u_apply is the clamped first knot, info = (S_0, +inf,
+ * 0, K); the call still returns BROV_OK.
+ *
+ * Arguments.  params is a HOST array of nparams sets, nparams = 1 (one planning model for every problem) or B (one per problem);
+ * the ctx's own parameters are neither read nor written.  cfg is ONE host record.  U_nom [B][M][nu] is in / out.  1 <= B <= 65535,
+ * 1 <= K <= 2^31, 1 <= H <= 2^31; B = 0: BROV_OK, nothing touched.  Refused on the host with BROV_ERR_ARG and a brov_last_error
+ * text naming the rule, before anything is copied or launched: K < 1 or K > 2^31, H < 1 or H > 2^31, hold < 1, lambda <= 0, a
+ * negative weight, sigma or gamma, u_min > u_max (channels < nu), a NaN anywhere in cfg, nparams not in {1, B}, a reference window
+ * outside ref_total, B > 65535, a double-integrator model, a NULL params, cfg, x, ref or U_nom, a dt that is not finite and > 0, a
+ * parameter set with a singular mass matrix.
+ * Deterministic: no atomics, every sum in a fixed order -- two calls with the same arguments give the same bits in every output. */
+typedef struct brov_mppi {
+    double q[12], qf[12];           /* stage / terminal weights on the tracking error e[12] of brov_rollout_feedback, >= 0 */
+    double r[8];                    /* weights on the command, >= 0; entries >= nu ignored */
+    double sigma[8];                /* standard deviation of the perturbation per channel, >= 0 (0: channel not perturbed) */
+    double u_min[8], u_max[8];      /* u_min <= u_max, may be +-inf */
+    double lambda;                  /* temperature, > 0 */
+    double gamma;                   /* weight of the importance term, >= 0 (the usual choice is lambda) */
+    int32_t hold, _pad;             /* >= 1 */
+} brov_mppi;
+BROV_API int brov_mppi_step(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t B, int64_t nparams,
+                   const brov_params* params /* [nparams], host */, const brov_mppi* cfg /* host */, int64_t K, int64_t H, double dt,
+                   uint64_t seed, const double* x, const double* lag, const double* ref, int64_t ref_total, int64_t ref_row0,
+                   const double* eps, double* U_nom, int shift, double* u_apply, double* cost, double* info);
+BROV_API int brov_mppi_step_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t B, int64_t nparams,
+                       const brov_params* params /* [nparams], host */, const brov_mppi* cfg /* host */, int64_t K, int64_t H, double dt,
+                       uint64_t seed, const double* d_x, const double* d_lag, const double* d_ref, int64_t ref_total, int64_t ref_row0,
+                       const double* d_eps, double* d_U_nom, int shift, double* d_u_apply, double* d_cost, double* d_info);
 
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped

@@ -1,0 +1,469 @@
+"""The model-predictive update (brov_mppi_step / engine.mppi_step / simulate_mppi) on the GPU against tests/mppi_ref.py, the NumPy
+restatement of the law of include/brov2.h around the parameterised oracle, at the vehicles of tests/fossen_vehicles.py (one per
+problem: V0, V5, V7).
+
+Recipe of tests/test_feedback_gpu.py: the mixed error max |a-b| / max(1,|b|) formed in long double against TOL_ROLL = 1e-10; every
+comparison also runs the reference in np.longdouble and asserts that fp64 and long double stay within a tenth of the bound, and
+that the wrap margin of feedback_ref.error exceeds 1e-6.  The seeds are chosen so that this holds (checked on the CPU).
+
+Shapes, the smallest that can still go wrong: B = 3 problems; K = 300 samples (one full 256-lane block and a ragged one); H = 7 at
+hold = 3, so M = 3 knots and the last covers one step; ref_total = 12 with ref_row0 = 2; a start lag for the thruster model;
+limits that a few per cent of the sample commands reach (asserted on the reference); one channel with sigma = 0."""
+import ctypes
+import functools
+
+import numpy as np
+import pytest
+
+import fossen_vehicles as fv
+import mppi_ref as mr
+from oracle import fossen_params as fp
+
+pytestmark = pytest.mark.gpu
+
+TOL_ROLL = 1e-10
+MARGIN = 1e-6
+L = np.longdouble
+B, K, H, HOLD, DT = 3, 300, 7, 3, 0.02
+M, REF_TOTAL, ROW0 = 3, 12, 2
+NAMES = ("V0", "V5", "V7")
+INTEG = {"euler": fp.EULER, "rk4": fp.RK4}
+SEED_X = 4102                              # chosen so that the margins below hold for every case of this file (checked on the CPU)
+
+
+def chan_scale(model):
+    """size of a command channel: thruster commands ~1, forces ~10 N, moments ~0.5 N m"""
+    return np.ones(8) if model == 0 else np.array([10.0, 10.0, 10.0, 0.5, 0.5, 0.5])
+
+
+def err(a, b):
+    """max |a-b| / max(1, |b|), formed in long double"""
+    a, b = np.asarray(a, dtype=L), np.asarray(b, dtype=L)
+    return float(np.max(np.abs(a - b) / np.maximum(L(1), np.abs(b)))) if a.size else 0.0
+
+
+def report(what, kernel_err, gap, bound):
+    print(f"{what}: kernel err {kernel_err:.2e}  reference fp64-vs-long-double gap {gap:.2e}  bound {bound:.0e}")
+    assert gap < 0.1 * bound, (what, "inputs too hard for fp64", gap)
+    assert kernel_err < bound, (what, kernel_err)
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from bluerov2_dynamics_amd import engine
+    return engine
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    from bluerov2_dynamics_amd import _lib
+    c = _lib.Context(0)
+    yield c
+    c.close()
+
+
+def _bytes(p):
+    return ctypes.string_at(ctypes.byref(p), ctypes.sizeof(p))
+
+
+# ------------------------------------------------------------------------------------------ shared inputs, records, reference results
+@functools.lru_cache(maxsize=None)
+def inputs(model, k=K):
+    """x [B,nx] and ref [B,REF_TOTAL,nx] in +-0.5 (unit quaternions for model 2), knots U [B,M,nu], start lag [B,8,3], eps [B,k,M,nu]"""
+    rng = np.random.default_rng(SEED_X + model)
+    nx, nu = fp.NX[model], fp.NU[model]
+    X, REF = rng.uniform(-0.5, 0.5, (B, nx)), rng.uniform(-0.5, 0.5, (B, REF_TOTAL, nx))
+    if model == 2:
+        X[:, 3:7] /= np.linalg.norm(X[:, 3:7], axis=1, keepdims=True)
+        REF[:, :, 3:7] /= np.linalg.norm(REF[:, :, 3:7], axis=2, keepdims=True)
+    U = rng.uniform(-0.3, 0.3, (B, M, nu)) * chan_scale(model)
+    lag = rng.uniform(-1, 1, (B, 8, 3))
+    eps = np.random.default_rng(SEED_X + 50 + model).normal(size=(B, K, M, nu))[:, :k].copy()
+    return X, REF, U, lag, eps
+
+
+@functools.lru_cache(maxsize=None)
+def record(model, lam=1.0, plain=False):
+    """random weights; sigma 0.2 x chan_scale with channel 2 unperturbed; per-channel limits 0.5 .. 0.8 x chan_scale, which lie in the
+    tails of the sample commands.  plain: q = qf = 0, gamma = 0, no limits (the cost reads the noise out directly)."""
+    rng = np.random.default_rng(SEED_X + 90 + model)
+    nu, s = fp.NU[model], chan_scale(model)
+    sigma = 0.2 * s
+    sigma[2] = 0.0
+    q, qf, r = rng.uniform(0.5, 2.0, 12), rng.uniform(2.0, 8.0, 12), rng.uniform(0.05, 0.2, nu) / (s * s)
+    if plain:
+        return mr.cfg(nu, q=0.0, qf=0.0, r=r, sigma=sigma, lam=lam, gamma=0.0, hold=HOLD)
+    return mr.cfg(nu, q=q, qf=qf, r=r, sigma=sigma, lam=lam, u_min=-np.linspace(0.8, 0.5, nu) * s, u_max=np.linspace(0.5, 0.8, nu) * s, hold=HOLD)
+
+
+@functools.lru_cache(maxsize=None)
+def reference(model, integ, lag_mode=0, ld=False, lam=1.0, shared=False, k=K, shift=False, seed=None, plain=False):
+    """mppi_ref.step on inputs(model).  shared: one planning vehicle (V7) and a set-point (the first reference row); otherwise one
+    vehicle per problem and the window ROW0 .. ROW0 + H of REF_TOTAL rows.  seed: the seeded stream instead of the explicit eps."""
+    X, REF, U, lag, eps = inputs(model, k)
+    veh = [fv.vehicle("V7")] if shared else [fv.vehicle(n) for n in NAMES]
+    return mr.step(model, INTEG[integ], lag_mode, veh, record(model, lam, plain), X, REF[:, :1] if shared else REF, U, DT, k, H,
+                   lag=lag if model == 0 else None, seed=seed or 0, eps=None if seed is not None else eps, ref_row0=0 if shared else ROW0,
+                   shift=shift, dtype=L if ld else np.float64)
+
+
+def _run(eng, ctx, model, integ, lag_mode=0, lam=1.0, shared=False, k=K, shift=False, seed=None, plain=False, eps=None, x=None, **kw):
+    X, REF, U, lag, e = inputs(model, k)
+    ps = [fv.params("V7")] if shared else [fv.params(n) for n in NAMES]
+    if seed is None and eps is None:
+        eps = e
+    return eng.mppi_step(model, integ, ps, mr.to_struct(record(model, lam, plain)), X if x is None else x, REF[:, :1] if shared else REF, U, DT,
+                         k, H=H, lag=lag if model == 0 else None, lag_mode=lag_mode, seed=seed or 0, eps=eps, ref_row0=0 if shared else ROW0,
+                         shift=shift, want_cost=True, ctx=ctx, **kw)
+
+
+def _limits_reached(model, o):
+    c = record(model)
+    on = (o["v"] == c.u_min) | (o["v"] == c.u_max)
+    frac = on[:, 1:][..., c.sigma > 0].mean()
+    assert 0.01 < frac < 0.2, ("a few per cent of the sample commands must reach a limit", frac)
+
+
+def _check_costs(what, got, model, integ, lag_mode=0, **kw):
+    o, ol = reference(model, integ, lag_mode, **kw), reference(model, integ, lag_mode, ld=True, **kw)
+    assert min(o["wrap_margin"], ol["wrap_margin"]) > MARGIN, o["wrap_margin"]
+    assert got["cost"].shape == o["cost"].shape and np.all(np.isfinite(got["cost"]))
+    report(what, err(got["cost"], o["cost"]), err(o["cost"], ol["cost"]), TOL_ROLL)
+    return o
+
+
+# ------------------------------------------------------------------------------------------ 1. costs with explicit eps
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+@pytest.mark.parametrize("model", [0, 1, 2])
+def test_costs_three_models(eng, ctx, model, integ):
+    """per-problem parameters, the reference window at ROW0, a start lag for the thruster model: cost [B,K] against mppi_ref"""
+    r = _run(eng, ctx, model, integ)
+    nu = fp.NU[model]
+    assert r["cost"].shape == (B, K) and r["U_nom"].shape == (B, M, nu) and r["u_apply"].shape == (B, HOLD, nu) and r["info"].shape == (B, 4)
+    o = _check_costs(f"mppi costs model {model} {integ}", r, model, integ)
+    _limits_reached(model, o)
+
+
+def test_costs_lag_per_step(eng, ctx):
+    r = _run(eng, ctx, 0, "rk4", lag_mode=1)
+    _check_costs("mppi costs LAG_PER_STEP", r, 0, "rk4", 1)
+    assert err(reference(0, "rk4", 1)["cost"], reference(0, "rk4", 0)["cost"]) > 1e3 * TOL_ROLL, "the lag mode must matter"
+
+
+def test_costs_one_planning_model_and_a_set_point(eng, ctx):
+    """nparams = 1 (V7 for every problem), ref_total = 1"""
+    r = _run(eng, ctx, 0, "rk4", shared=True)
+    _check_costs("mppi costs nparams 1, set-point", r, 0, "rk4", shared=True)
+
+
+# ------------------------------------------------------------------------------------------ 2. update
+@functools.lru_cache(maxsize=None)
+def spread_lambda():
+    """a tenth of the reference's cost spread (max - min of a problem's costs, the smallest over the problems)"""
+    S = reference(0, "rk4")["cost"]
+    return float(np.min(S.max(axis=1) - S.min(axis=1))) / 10.0
+
+
+def test_update_from_the_kernels_own_costs(eng, ctx):
+    """(a) U_new and info against the soft-min recomputed in long double from the kernel's OWN returned costs and the reference's
+    delta, at 1e-12: a fixed-order fp64 sum of <= 300 terms errs by <= 300 x 2^-53 = 3e-14 of sum |terms|, so the bound leaves a
+    margin of 30 or more.  S_0, beta and the non-finite count are exact."""
+    lam = spread_lambda()
+    r = _run(eng, ctx, 0, "rk4", lam=lam)
+    ol = reference(0, "rk4", ld=True, lam=lam)
+    c = record(0, lam)
+    e = 0.0
+    for b in range(B):
+        Un, info, w = mr.softmin(c, r["cost"][b], ol["delta"][b], inputs(0)[2][b], dtype=L)
+        e = max(e, err(r["U_nom"][b], Un), err(r["info"][b, 2], info[2]))
+        assert r["info"][b, 0] == r["cost"][b, 0] and r["info"][b, 1] == r["cost"][b].min() and r["info"][b, 3] == 0
+        assert np.array_equal(r["u_apply"][b], np.repeat(r["U_nom"][b, :1], HOLD, axis=0))
+    print(f"mppi update from the kernel's costs: err {e:.2e}  bound 1e-12")
+    assert e < 1e-12
+
+
+@pytest.mark.parametrize("shift", [False, True])
+@pytest.mark.parametrize("model", [1, 2])
+def test_update_six_channels(eng, ctx, model, shift):
+    """the nu = 6 instantiation of the update kernel (wrench and quaternion models), with and without the shift: the plan, u_apply
+    and info against the soft-min recomputed in long double from the kernel's own costs, at the 1e-12 of the test above"""
+    r = _run(eng, ctx, model, "rk4", shift=shift)
+    ol = reference(model, "rk4", ld=True)
+    c = record(model)
+    e = 0.0
+    for b in range(B):
+        Un, info, w = mr.softmin(c, r["cost"][b], ol["delta"][b], inputs(model)[2][b], dtype=L)
+        plan = np.concatenate([Un[1:], Un[-1:]], axis=0) if shift else Un
+        e = max(e, err(r["U_nom"][b], plan), err(r["u_apply"][b], np.repeat(Un[:1], HOLD, axis=0)), err(r["info"][b, 2], info[2]))
+        assert r["info"][b, 0] == r["cost"][b, 0] and r["info"][b, 1] == r["cost"][b].min() and r["info"][b, 3] == 0
+        assert 1.5 < info[2] < K / 2 and err(Un, inputs(model)[2][b]) > 1e-3, "weights neither one-hot nor uniform, and a plan that moves"
+    print(f"mppi update, model {model}, shift {shift}: err {e:.2e}  bound 1e-12")
+    assert e < 1e-12
+
+
+def test_update_end_to_end(eng, ctx):
+    """(b) U_new against mppi_ref at 1e-6.  lambda is a tenth of the reference's cost spread; asserted on the reference: max |S| <=
+    100 x the spread, |delta| <= 2, and an effective sample size between 2 and K / 2 (weights neither uniform nor one-hot).  Then
+    |dU| <= 2 eps_S max|delta| / lambda <= 2 (1e-10 max|S|) 2 / (spread / 10) <= 4e-7."""
+    lam = spread_lambda()
+    r = _run(eng, ctx, 0, "rk4", lam=lam)
+    o, ol = reference(0, "rk4", lam=lam), reference(0, "rk4", ld=True, lam=lam)
+    S = o["cost"]
+    assert np.max(np.abs(S)) <= 100 * 10 * lam and np.max(np.abs(o["delta"])) <= 2.0
+    assert np.all(o["info"][:, 2] >= 2) and np.all(o["info"][:, 2] <= K / 2), o["info"][:, 2]
+    assert np.all(o["info"][:, 3] == 0)
+    e, gap = err(r["U_nom"], o["U_new"]), err(o["U_new"], ol["U_new"])
+    print("effective sample sizes", o["info"][:, 2], "kernel", r["info"][:, 2])
+    report("mppi U_new end to end", e, gap, 1e-6)
+    assert err(r["info"][:, 2], o["info"][:, 2]) < 1e-4                 # the effective sample size moves like U_new, relative to ~K
+    assert err(o["U_new"], inputs(0)[2]) > 1e-3, "the update must move the plan"
+
+
+# ------------------------------------------------------------------------------------------ 3. seeded stream
+def test_seeded_stream_equals_explicit_normals(eng, ctx):
+    """eps = NULL at seed 77 against a second call that passes the oracle-side normals as eps: the device Box-Muller agrees with
+    NumPy to ~6e-15 (csrc/brov2_stream.h), far inside TOL_ROLL on the costs"""
+    a = _run(eng, ctx, 0, "rk4", seed=77)
+    b = _run(eng, ctx, 0, "rk4", eps=mr.normals(77, B, K, M, 8))
+    e = err(a["cost"], b["cost"])
+    print(f"seeded against explicit normals: {e:.2e}")
+    assert e < TOL_ROLL
+    _check_costs("mppi costs, seeded stream", a, 0, "rk4", seed=77)
+    assert err(a["cost"], reference(0, "rk4")["cost"]) > 1e-3, "other normals, other costs"
+
+
+def test_seeded_stream_read_out_directly(eng, ctx):
+    """q = qf = 0, gamma = 0, no limits: S_k = dt sum_t sum_j r_j (U + sigma xi)^2 reads the noise out of the kernel.  Bound 1e-12:
+    7 x 8 fused terms err by <= 56 x 2^-53 = 6e-15 of the sum and the normals by ~6e-15, so the margin is 50 or more."""
+    r = _run(eng, ctx, 0, "rk4", seed=123, plain=True)
+    c, U = record(0, plain=True), inputs(0)[2]
+    xi = mr.normals(123, B, K, M, 8).astype(L)
+    xi[:, 0] = 0
+    xi[..., c.sigma == 0] = 0
+    v = U[:, None].astype(L) + c.sigma.astype(L) * xi                                     # [B,K,M,nu]
+    steps = np.array([min(HOLD, H - m * HOLD) for m in range(M)], dtype=L)                # 3, 3, 1 steps per knot
+    want = L(DT) * np.sum(steps[None, None, :, None] * c.r.astype(L) * v * v, axis=(2, 3))
+    e = err(r["cost"], want)
+    print(f"noise read out through the cost: {e:.2e}")
+    assert e < 1e-12
+    assert len(np.unique(r["cost"][0])) == K, "every sample has its own noise"
+
+
+# ------------------------------------------------------------------------------------------ 4. edges
+def test_one_sample(eng, ctx):
+    """K = 1: the nominal alone.  U_new is the clamped nominal and the effective sample size is 1."""
+    r = _run(eng, ctx, 0, "rk4", k=1)
+    c, U = record(0), inputs(0)[2]
+    assert np.array_equal(r["U_nom"], np.clip(U, c.u_min, c.u_max)) and np.array_equal(r["info"][:, 2], np.ones(B))
+    assert np.array_equal(r["info"][:, 0], r["cost"][:, 0]) and np.array_equal(r["info"][:, 1], r["cost"][:, 0])
+    _check_costs("mppi K = 1", r, 0, "rk4", k=1)
+
+
+def test_64_lane_launch(eng, ctx):
+    r = _run(eng, ctx, 0, "rk4", k=64)
+    _check_costs("mppi K = 64", r, 0, "rk4", k=64)
+    for b in range(B):
+        Un, info, _ = mr.softmin(record(0), r["cost"][b], reference(0, "rk4", ld=True, k=64)["delta"][b], inputs(0)[2][b], dtype=L)
+        assert err(r["U_nom"][b], Un) < 1e-12 and err(r["info"][b, 2], info[2]) < 1e-12
+
+
+def test_shift_and_determinism(eng, ctx):
+    """shift = 1 against shift = 0: the knots move by one and the last is repeated; u_apply is U_new[0] in hold rows either way.
+    Two identical calls give identical bytes in every output."""
+    a, s = _run(eng, ctx, 0, "rk4", seed=5), _run(eng, ctx, 0, "rk4", seed=5, shift=True)
+    assert np.array_equal(s["U_nom"][:, :-1], a["U_nom"][:, 1:]) and np.array_equal(s["U_nom"][:, -1], a["U_nom"][:, -1])
+    assert not np.array_equal(a["U_nom"][:, 0], a["U_nom"][:, 1])
+    for r in (a, s):
+        assert np.array_equal(r["u_apply"], np.repeat(a["U_nom"][:, :1], HOLD, axis=1))
+    assert np.array_equal(a["cost"], s["cost"]) and np.array_equal(a["info"], s["info"])
+    a2 = _run(eng, ctx, 0, "rk4", seed=5)
+    for k in ("U_nom", "u_apply", "cost", "info"):
+        assert a[k].tobytes() == a2[k].tobytes(), k
+
+
+# ------------------------------------------------------------------------------------------ 5. non-finite samples
+def test_nan_in_one_sample(eng, ctx):
+    """one NaN in eps of sample 5 of problem 1: that sample has weight 0 and is counted, the other problems are unaffected"""
+    eps = inputs(0)[4].copy()
+    eps[1, 5, 1, 0] = np.nan
+    good, r = _run(eng, ctx, 0, "rk4"), _run(eng, ctx, 0, "rk4", eps=eps)
+    assert np.isnan(r["cost"][1, 5]) and np.isfinite(np.delete(r["cost"][1], 5)).all()
+    assert list(r["info"][:, 3]) == [0, 1, 0]
+    for b in (0, 2):
+        for k in ("U_nom", "u_apply", "cost", "info"):
+            assert r[k][b].tobytes() == good[k][b].tobytes(), (k, b)
+    Un, info, w = mr.softmin(record(0), r["cost"][1], reference(0, "rk4", ld=True)["delta"][1], inputs(0)[2][1], dtype=L)
+    assert w[5] == 0 and err(r["U_nom"][1], Un) < 1e-12 and err(r["info"][1, 2], info[2]) < 1e-12
+    assert np.isfinite(r["U_nom"]).all() and not np.array_equal(r["U_nom"][1], good["U_nom"][1])
+
+
+def test_no_finite_sample(eng, ctx):
+    """a NaN state in problem 2: its plan comes back byte-identical, u_apply is the clamped first knot, info = (non-finite, inf, 0,
+    K), the call succeeds and the other problems are unaffected"""
+    X, _, U, _, _ = inputs(0)
+    x = X.copy()
+    x[2, 0] = np.nan
+    good, r = _run(eng, ctx, 0, "rk4", shift=True), _run(eng, ctx, 0, "rk4", x=x, shift=True)
+    c = record(0)
+    assert r["U_nom"][2].tobytes() == U[2].tobytes()
+    assert np.array_equal(r["u_apply"][2], np.repeat(np.clip(U[2, :1], c.u_min, c.u_max), HOLD, axis=0))
+    assert not np.isfinite(r["info"][2, 0]) and r["info"][2, 1] == np.inf and r["info"][2, 2] == 0 and r["info"][2, 3] == K
+    assert not np.isfinite(r["cost"][2]).any()
+    for b in (0, 1):
+        for k in ("U_nom", "u_apply", "cost", "info"):
+            assert r[k][b].tobytes() == good[k][b].tobytes(), (k, b)
+
+
+# ------------------------------------------------------------------------------------------ 6. refusals
+def test_host_contract(ctx):
+    """every rule of the header returns BROV_ERR_ARG with a brov_last_error text naming it, and no output buffer is written"""
+    from bluerov2_dynamics_amd import _lib
+    X, REF, U, lag, eps = inputs(0, 8)
+    pa = (_lib.BrovParams * B)(*[fv.params(n) for n in NAMES])
+    PAT = -7.25
+
+    def call(want, model=0, nb=B, nparams=B, k=8, h=H, ref_total=REF_TOTAL, row0=ROW0, edit=None):
+        s = mr.to_struct(record(0))
+        if edit:
+            edit(s)
+        Un = U.copy()
+        ua, cost, info = np.full((B, max(s.hold, 1), 8), PAT), np.full((B, 8), PAT), np.full((B, 4), PAT)
+        rc = ctx.lib.brov_mppi_step(ctx.h, model, _lib.RK4, 0, nb, nparams, pa, ctypes.byref(s), k, h, DT, 0, X.ctypes.data, lag.ctypes.data,
+                                    REF.ctypes.data, ref_total, row0, eps.ctypes.data, Un.ctypes.data, 0, ua.ctypes.data, cost.ctypes.data,
+                                    info.ctypes.data)
+        msg = ctx.lib.brov_last_error(ctx.h)
+        msg = msg.decode() if isinstance(msg, bytes) else msg
+        assert rc == -1 and want in msg, (want, rc, msg)
+        assert np.array_equal(Un, U) and np.all(ua == PAT) and np.all(cost == PAT) and np.all(info == PAT), want
+
+    def setf(name, value, i=None):
+        def edit(s):
+            if i is None:
+                setattr(s, name, value)
+            else:
+                getattr(s, name)[i] = value
+        return edit
+
+    call("K must be >= 1", k=0)
+    call("H must be >= 1", h=0)
+    call("hold must be >= 1", edit=setf("hold", 0))
+    call("lambda must be > 0", edit=setf("lam", 0.0))
+    call("q and qf must be >= 0", edit=setf("q", -1.0, 3))
+    call("q and qf must be >= 0", edit=setf("qf", -1.0, 11))
+    call("r must be >= 0", edit=setf("r", -0.5, 0))
+    call("sigma must be >= 0", edit=setf("sigma", -0.1, 1))
+    call("gamma must be >= 0", edit=setf("gamma", -1.0))
+    call("u_min must be <= u_max", edit=setf("u_min", 2.0, 7))
+    call("NaN in the record", edit=setf("qf", np.nan, 2))
+    call("NaN in the record", edit=setf("lam", np.nan))
+    call("nparams must be 1 or B", nparams=2)
+    call("reference window", row0=REF_TOTAL - H)            # rows 5 .. 12 of 12
+    call("reference window", row0=-1)
+    call("reference window", ref_total=1, row0=1)           # a set-point has one row
+    call("B must be <= 65535", nb=65536)
+    call("K must be <= 2^31", k=2 ** 31 + 1)
+    call("H must be <= 2^31", h=2 ** 31 + 1, ref_total=1, row0=0)
+    call("double-integrator", model=3)
+    # B = 0: BROV_OK, nothing touched
+    Un, cost = U.copy(), np.full((B, 8), PAT)
+    rc = ctx.lib.brov_mppi_step(ctx.h, 0, _lib.RK4, 0, 0, 1, pa, ctypes.byref(mr.to_struct(record(0))), 8, H, DT, 0, X.ctypes.data, None,
+                                REF.ctypes.data, REF_TOTAL, ROW0, None, Un.ctypes.data, 0, None, cost.ctypes.data, None)
+    assert rc == 0 and np.array_equal(Un, U) and np.all(cost == PAT)
+
+
+def test_host_form_equals_device_form(eng, ctx):
+    """brov_mppi_step (host arrays staged by the library) gives the bytes of engine.mppi_step, which calls brov_mppi_step_dev"""
+    from bluerov2_dynamics_amd import _lib
+    X, REF, U, lag, eps = inputs(0)
+    pa = (_lib.BrovParams * B)(*[fv.params(n) for n in NAMES])
+    s = mr.to_struct(record(0))
+    Un, ua, cost, info = U.copy(), np.zeros((B, HOLD, 8)), np.zeros((B, K)), np.zeros((B, 4))
+    rc = ctx.lib.brov_mppi_step(ctx.h, 0, _lib.RK4, 0, B, B, pa, ctypes.byref(s), K, H, DT, 0, X.ctypes.data, lag.ctypes.data, REF.ctypes.data,
+                                REF_TOTAL, ROW0, eps.ctypes.data, Un.ctypes.data, 1, ua.ctypes.data, cost.ctypes.data, info.ctypes.data)
+    assert rc == 0, ctx.lib.brov_last_error(ctx.h)
+    r = _run(eng, ctx, 0, "rk4", shift=True)
+    for got, k in ((Un, "U_nom"), (ua, "u_apply"), (cost, "cost"), (info, "info")):
+        assert got.tobytes() == r[k].tobytes(), k
+
+
+def test_device_to_device_copy(ctx):
+    """brov_memcpy_d2d / DevArray.copy_from_device: the bytes arrive, a view of rows is a valid target, overlapping ranges are refused
+    with nothing copied"""
+    from bluerov2_dynamics_amd import engine
+    a = np.random.default_rng(3).normal(size=(5, 7))
+    src, dst = engine.DevArray.from_host(ctx, a), engine.DevArray(ctx, (2, 5, 7)).zero_()
+    dst.rows(1, 2).copy_from_device(src)
+    got = dst.numpy()
+    assert got[1].tobytes() == a.tobytes() and not got[0].any()
+    rc = ctx.lib.brov_memcpy_d2d(ctx.h, src.ptr + 8, src.ptr, 16)
+    msg = ctx.lib.brov_last_error(ctx.h)
+    msg = msg.decode() if isinstance(msg, bytes) else msg
+    assert rc == -1 and "overlap" in msg and src.numpy().tobytes() == a.tobytes()
+    assert ctx.lib.brov_memcpy_d2d(ctx.h, dst.ptr, src.ptr, 0) == 0
+
+
+# ------------------------------------------------------------------------------------------ 7. the receding-horizon driver
+@pytest.mark.parametrize("mismatch", [False, True])
+def test_simulate_mppi(mismatch):
+    """T = 6 at hold = 2 (three ticks), B = 2, K = 64, H = 4, once with the planner's own vehicle as the plant and once with two
+    differing plants.  Verified tick by tick from what the driver recorded, so that the soft-min's sensitivity does not compound
+    across ticks: each tick's shifted plan and u_apply against mppi_ref fed the recorded (x, lag, U_nom, seed + n) at the 1e-6 of
+    test_update_end_to_end, whose premise 2 (1e-10 max|S|) max|delta| / lambda <= 1e-6 is asserted on the reference at every tick;
+    each plant segment against the oracle from the recorded state and the applied commands at TOL_ROLL; the seed and ref_row0
+    progression exactly."""
+    from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2
+    from bluerov2_dynamics_amd.fossen import control, identify
+    T, hold, nb, k, h, seed = 6, 2, 2, 64, 4, 900
+    rng = np.random.default_rng(SEED_X + 7)
+    x0, ref = rng.uniform(-0.3, 0.3, (nb, 12)), rng.uniform(-0.3, 0.3, (nb, T + h + 1, 12))
+    rov = BlueROV2()
+    c = mr.cfg(8, q=np.linspace(1.0, 2.0, 12), qf=np.linspace(4.0, 6.0, 12), r=0.1, sigma=0.25, lam=0.05, u_min=-0.7, u_max=0.7, hold=hold)
+    cfg = control.mppi(c.q, qf=c.qf, r=c.r, sigma=c.sigma, lam=c.lam, u_min=c.u_min, u_max=c.u_max, hold=hold)
+    assert _bytes(cfg) == _bytes(mr.to_struct(c))
+    plants = [fv.params("V5"), fv.params("V7")] if mismatch else None
+    before = _bytes(identify.params_of(rov))
+    r = rov.simulate_mppi(x0, ref, DT, cfg, T, k, h, plant_params=plants, integrator="rk4", seed=seed)
+    assert _bytes(identify.params_of(rov)) == before
+    tk = r["ticks"]
+    nt, m = T // hold, 2
+    assert r["traj"].shape == (nb, T + 1, 12) and r["u"].shape == (nb, T, 8) and r["info"].shape == (nt, nb, 4)
+    assert tk["x"].shape == (nt, nb, 12) and tk["lag"].shape == (nt, nb, 8, 3) and tk["U_nom"].shape == (nt, nb, m, 8)
+    assert list(tk["seed"]) == [seed + n for n in range(nt)] and list(tk["ref_row0"]) == [n * hold for n in range(nt)]
+    assert np.array_equal(tk["x"][0], x0) and not tk["lag"][0].any() and not tk["U_nom"][0].any()
+    planner = [fp.from_brov_params(identify.params_of(rov))]
+    plant_v = [fp.from_brov_params(p) for p in plants] if mismatch else planner * nb
+    e_plan = g_plan = e_plant = g_plant = 0.0
+    for n in range(nt):
+        kw = dict(lag=tk["lag"][n], seed=seed + n, ref_row0=n * hold, shift=True)
+        o = mr.step(0, fp.RK4, 0, planner, c, tk["x"][n], ref, tk["U_nom"][n], DT, k, h, **kw)
+        ol = mr.step(0, fp.RK4, 0, planner, c, tk["x"][n], ref, tk["U_nom"][n], DT, k, h, dtype=L, **kw)
+        assert min(o["wrap_margin"], ol["wrap_margin"]) > MARGIN
+        assert 2 * TOL_ROLL * max(1.0, np.max(np.abs(o["cost"]))) * np.max(np.abs(o["delta"])) / c.lam <= 1e-6
+        seg = slice(n * hold, (n + 1) * hold)
+        e_plan, g_plan = max(e_plan, err(r["u"][:, seg], o["u_apply"])), max(g_plan, err(o["u_apply"], ol["u_apply"]))
+        if n + 1 < nt:
+            e_plan, g_plan = max(e_plan, err(tk["U_nom"][n + 1], o["U_nom"])), max(g_plan, err(o["U_nom"], ol["U_nom"]))
+            assert np.array_equal(tk["x"][n + 1], r["traj"][:, (n + 1) * hold])
+        assert np.array_equal(r["traj"][:, n * hold], tk["x"][n])
+        for b in range(nb):
+            args = (0, fp.RK4, 0, plant_v[b], tk["x"][n][b:b + 1], r["u"][b:b + 1, seg], DT)
+            p, pl = fp.rollout(*args, lag=tk["lag"][n][b:b + 1]), fp.rollout(*args, lag=tk["lag"][n][b:b + 1], dtype=L)
+            got = r["traj"][b:b + 1, n * hold:(n + 1) * hold + 1]
+            e_plant, g_plant = max(e_plant, err(got, p["traj"])), max(g_plant, err(p["traj"], pl["traj"]))
+            if n + 1 < nt:
+                e_plant, g_plant = max(e_plant, err(tk["lag"][n + 1][b:b + 1], p["lag"])), max(g_plant, err(p["lag"], pl["lag"]))
+    report(f"simulate_mppi plan per tick (mismatch {mismatch})", e_plan, g_plan, 1e-6)
+    report(f"simulate_mppi plant segments (mismatch {mismatch})", e_plant, g_plant, TOL_ROLL)
+    assert np.max(np.abs(r["u"])) <= 0.7 and np.max(np.abs(r["u"])) > 0.01
+
+
+def test_example_runs_small():
+    """examples/mppi_tracking.py at a size of seconds: four plants, one second of simulated time"""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "mppi_tracking.py")
+    spec = importlib.util.spec_from_file_location("mppi_tracking", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    rows = mod.main(["--plants", "4", "--seconds", "1.0", "--samples", "256"])
+    assert set(rows) == {"mppi", "pid"} and all(np.all(np.isfinite(v)) and v.shape == (4,) for v in rows.values())
