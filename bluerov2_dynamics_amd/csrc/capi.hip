@@ -165,15 +165,30 @@ struct CallTimer {
     }
 };
 
-// bump allocator over the ctx scratch arena; grows (after a stream sync) when too small
+// Bump allocator over the ctx scratch arena; grows (after a stream sync) when too small.
+//
+// The EDMDc and k-means code sizes a call by hand: reserve(total), then take<T>(count).
+//
+// The Fossen and PINc entry points declare their buffers once, in a layout function that lay() runs twice: a measuring pass in which
+// take only adds up offsets, then -- the arena grown to exactly that total -- a binding pass that hands the pointers out, so a take
+// cannot leave what was reserved.  A buffer with a host side is declared with in / out / inout.  In a host form (`staged`) it is arena
+// memory and a recorded copy: lay() ends with the uploads, finish() makes the downloads and the one stream synchronisation of the
+// call, both in declaration order.  In a `_dev` form the caller's device pointer passes through and nothing is taken or copied: one
+// body serves both forms of an entry point.
+// The arena ends with the last take (each take is rounded up to 256 bytes, nothing follows): no kernel may rely on slack behind it.
 struct Arena {
     brov_ctx* c;
-    size_t off = 0;
-    std::vector<size_t> wants;
-    explicit Arena(brov_ctx* ctx) : c(ctx) {}
+    const bool staged;
+    size_t off = 0, limit = ~(size_t)0;     // limit: what lay() reserved
+    bool bind = true, fits = true, listed = true;
+    struct Copy { void* dev; void* host; size_t bytes; bool up, down; };
+    static constexpr int MAX_COPIES = 12;    // staged buffers of one call (brov_rollout_feedback has nine)
+    Copy copies[MAX_COPIES];
+    int ncopies = 0;
+    explicit Arena(brov_ctx* ctx, bool staged_ = false) : c(ctx), staged(staged_) {}
     static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-    int reserve(size_t total) {
-        total = al(total) + 4096;
+    int reserve(size_t total) { return grow(al(total) + 4096); }
+    int grow(size_t total) {
         if (total <= c->scratch_cap) return BROV_OK;
         (void)hipStreamSynchronize(c->stream);
         if (c->scratch) (void)hipFree(c->scratch);
@@ -185,9 +200,45 @@ struct Arena {
         return BROV_OK;
     }
     template <typename T> T* take(size_t count) {
-        T* p = reinterpret_cast<T*>(c->scratch + off);
+        const size_t at = off;
         off += al(count * sizeof(T));
-        return p;
+        if (!bind) return nullptr;
+        if (off > limit) { fits = false; return nullptr; }
+        return reinterpret_cast<T*>(c->scratch + at);
+    }
+    template <typename T> T* stage(const T* host, size_t count, bool up, bool down) {
+        if (!staged) return const_cast<T*>(host);
+        T* d = take<T>(count);
+        if (bind && host && count) {
+            if (ncopies == MAX_COPIES) listed = false;
+            else copies[ncopies++] = {d, const_cast<T*>(host), count * sizeof(T), up, down};
+        }
+        return d;
+    }
+    template <typename T> T* in(const T* host, size_t count) { return stage(host, count, true, false); }
+    template <typename T> T* out(T* host, size_t count) { return stage(host, count, false, true); }      // host form: NULL = scratch
+    template <typename T> T* inout(T* host, size_t count) { return stage(host, count, true, true); }
+    template <typename F> int lay(const char* who, F&& layout) {
+        bind = false;
+        layout();
+        limit = off;
+        int rc = grow(limit);
+        if (rc) return rc;
+        bind = true;
+        off = 0;
+        layout();
+        if (!fits) return fail(c, BROV_ERR_NOMEM, std::string(who) + ": the call's buffers do not fit the arena reserved for them");
+        if (!listed) return fail(c, BROV_ERR_NOMEM, std::string(who) + ": more staged buffers than Arena::MAX_COPIES");
+        for (int i = 0; i < ncopies; ++i)
+            if (copies[i].up) HIPCK(c, h2d_copy(c, copies[i].dev, copies[i].host, copies[i].bytes));
+        return BROV_OK;
+    }
+    int finish() {
+        if (!staged) return BROV_OK;
+        for (int i = 0; i < ncopies; ++i)
+            if (copies[i].down) HIPCK(c, d2h_copy(c, copies[i].host, copies[i].dev, copies[i].bytes));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        return BROV_OK;
     }
 };
 
@@ -1060,24 +1111,20 @@ int brov_rhs(brov_ctx* c, int model, int64_t B, const double* x, const double* u
         if (lag) std::memcpy(lag_io, c->h_io + ol, B * 24 * 8);
         return BROV_OK;
     }
-    Arena a(c);
-    rc = a.reserve(Arena::al(B * nx * 8) * 2 + Arena::al(B * nu * 8) + Arena::al(B * 24 * 8));
+    Arena a(c, true);
+    double *dx, *du, *dxd, *dl;
+    rc = a.lay("brov_rhs", [&] {
+        dx = a.in(x, B * nx);
+        du = a.in(u, B * nu);
+        dxd = a.out(xdot, B * nx);
+        dl = lag ? a.inout(lag_io, B * 24) : nullptr;
+    });
     if (rc) return rc;
-    double* dx = a.take<double>(B * nx);
-    double* du = a.take<double>(B * nu);
-    double* dxd = a.take<double>(B * nx);
-    double* dl = lag ? a.take<double>(B * 24) : nullptr;
-    HIPCK(c, h2d_copy(c, dx, x, B * nx * 8));
-    HIPCK(c, h2d_copy(c, du, u, B * nu * 8));
-    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, B * 24 * 8));
     {
         CallTimer t(c);
         HIPCK(c, launch_rhs(c->stream, *dp, model, B, dx, du, dl, dxd));
     }
-    HIPCK(c, d2h_copy(c, xdot, dxd, B * nx * 8));
-    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, B * 24 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 int brov_thruster_forces(brov_ctx* c, int64_t B, const double* u, double dt, double* lag_io, double* tau) {
@@ -1106,22 +1153,19 @@ int brov_thruster_forces(brov_ctx* c, int64_t B, const double* u, double dt, dou
         std::memcpy(lag_io, c->h_io + ol, B * 24 * 8);
         return BROV_OK;
     }
-    Arena a(c);
-    rc = a.reserve(Arena::al(B * 8 * 8) + Arena::al(B * 24 * 8) + Arena::al(B * 6 * 8));
+    Arena a(c, true);
+    double *du, *dtau, *dl;
+    rc = a.lay("brov_thruster_forces", [&] {
+        du = a.in(u, B * 8);
+        dtau = a.out(tau, B * 6);
+        dl = a.inout(lag_io, B * 24);
+    });
     if (rc) return rc;
-    double* du = a.take<double>(B * 8);
-    double* dl = a.take<double>(B * 24);
-    double* dt_ = a.take<double>(B * 6);
-    HIPCK(c, h2d_copy(c, du, u, B * 8 * 8));
-    HIPCK(c, h2d_copy(c, dl, lag_io, B * 24 * 8));
     {
         CallTimer t(c);
-        HIPCK(c, launch_thruster_forces(c->stream, *dp, B, du, dl, dt_));
+        HIPCK(c, launch_thruster_forces(c->stream, *dp, B, du, dl, dtau));
     }
-    HIPCK(c, d2h_copy(c, tau, dt_, B * 6 * 8));
-    HIPCK(c, d2h_copy(c, lag_io, dl, B * 24 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 // ---- rollout -------------------------------------------------------------------------------------
@@ -1185,24 +1229,19 @@ int brov_rollout(brov_ctx* c, int model, int integ, int lag_mode, int layout, in
     const int64_t rows = traj ? T / stride + 1 : 0;
     const int nuw = layout == BROV_LAYOUT_TPB ? (nu + 1) / 2 * 2 : nu;     // TPB pads odd channel counts to pairs
     const int nxw = layout == BROV_LAYOUT_TPB ? (nx + 1) / 2 * 2 : nx;
-    Arena a(c);
-    rc = a.reserve(Arena::al(B * nx * 8) * 2 + Arena::al((size_t)B * T * nuw * 8) + Arena::al(B * 24 * 8) + Arena::al((size_t)B * rows * nxw * 8));
+    Arena a(c, true);
+    double *dx0, *dU, *dxT, *dl, *dtr;
+    rc = a.lay("brov_rollout", [&] {
+        dx0 = a.in(x0, B * nx);
+        dU = a.in(U, (size_t)B * T * nuw);
+        dxT = a.out(xT, B * nx);
+        dl = lag ? a.inout(lag_io, B * 24) : nullptr;
+        dtr = traj ? a.out(traj, (size_t)B * rows * nxw) : nullptr;
+    });
     if (rc) return rc;
-    double* dx0 = a.take<double>(B * nx);
-    double* dU = a.take<double>((size_t)B * T * nuw);
-    double* dxT = a.take<double>(B * nx);
-    double* dl = lag ? a.take<double>(B * 24) : nullptr;
-    double* dtr = traj ? a.take<double>((size_t)B * rows * nxw) : nullptr;
-    HIPCK(c, h2d_copy(c, dx0, x0, B * nx * 8));
-    if (T) HIPCK(c, h2d_copy(c, dU, U, (size_t)B * T * nuw * 8));
-    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, B * 24 * 8));
     rc = brov_rollout_dev(c, model, integ, lag_mode, layout, B, T, dt, dx0, dU, dl, dtr, stride, dxT);
     if (rc) return rc;
-    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, B * nx * 8));
-    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, B * 24 * 8));
-    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, (size_t)B * rows * nxw * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 // ---- sliding-window endpoint error ----------------------------------------------------------------
@@ -1225,95 +1264,6 @@ static void lag_window_phi_pair(const DevParams& dp, int64_t samples, double out
     lag_window_phi(dp, samples * window_scan_chunk(), out18 + 9);
 }
 
-// what window_impl takes from the arena: the pre-scan's arrays (thruster model with carried lag only)
-static size_t window_scratch(int model, int carry, int64_t P, int64_t nwin) {
-    if (model != BROV_THRUSTER_EULER || !carry) return 0;
-    return Arena::al(P * nwin * 18 * 8) + Arena::al(P * window_chunks(nwin) * 18 * 8) + Arena::al(P * 18 * 8);
-}
-// The evaluator for the P parameter sets d_fp [P] (device).  phi [P][18] (host): each candidate's lag_window_phi_pair, read with the
-// thruster model and carried lag only.  host_temps: the caller has uploads from temporaries of its own on the stream.
-static int window_impl(brov_ctx* c, const FastParams* d_fp, const double* phi, bool host_temps, int model, int integ, int P, int64_t N,
-                       int64_t H, double dt, const double* dX, const double* dU, int carry, double* d_se, double* d_total,
-                       double* d_endpoints, Arena& a) {
-    const int64_t nwin = N - H;
-    const bool scan = model == BROV_THRUSTER_EULER && carry;
-    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
-    if (scan) {
-        d_lag = a.take<double>(P * nwin * 18);
-        d_chunk = a.take<double>(P * window_chunks(nwin) * 18);
-        d_phi = a.take<double>(P * 18);
-        HIPCK(c, h2d_copy(c, d_phi, phi, (size_t)P * 18 * 8));
-    }
-    if (scan || host_temps) HIPCK(c, hipStreamSynchronize(c->stream));   // phi and the caller's arrays are temporaries
-    CallTimer t(c);
-    HIPCK(c, launch_window_endpoint(c->stream, d_fp, model, integ, P, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_se, d_total,
-                                    d_endpoints));
-    return BROV_OK;
-}
-
-// one parameter set: the ctx's own
-static int window_dev_impl(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* dX, const double* dU,
-                           int carry, double* d_total, double* d_se, Arena& a) {
-    const DevParams* dp;
-    int rc = get_dp(c, dt, &dp);
-    if (rc) return rc;
-    if (model_is_di_h(model) && !c->di_set) return fail(c, BROV_ERR_ARG, "double-integrator model: call brov_set_di_gains first");
-    double Phi[18];
-    lag_window_phi_pair(*dp, H * (integ == BROV_RK4 ? 4 : 1), Phi);
-    return window_impl(c, model_is_di_h(model) ? c->d_fp_di : c->d_fp, Phi, false, model, integ, 1, N, H, dt, dX, dU, carry, d_se, d_total,
-                       nullptr, a);
-}
-
-int brov_window_endpoint_se_dev(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* d_X,
-                                const double* d_U, int carry_lag, double* d_se_total, double* d_per_window) {
-    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || N < 0 || H < 0 || !d_se_total)
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_dev: bad argument");
-    DeviceGuard g(c);
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
-    if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_dev: NULL array");
-    Arena a(c);
-    int rc = a.reserve(window_scratch(model, carry_lag, 1, nwin));
-    if (rc) return rc;
-    return window_dev_impl(c, model, integ, N, H, dt, d_X, d_U, carry_lag, d_se_total, d_per_window, a);
-}
-
-int brov_window_endpoint_se(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* X, const double* U,
-                            int carry_lag, double* se_total, double* per_window) {
-    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || N < 0 || H < 0 || !se_total)
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se: bad argument");
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { *se_total = 0.0; return BROV_OK; }
-    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se: NULL array");
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    Arena a(c);
-    int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) +
-                       window_scratch(model, carry_lag, 1, nwin));
-    if (rc) return rc;
-    double* dX = a.take<double>(N * nx);
-    double* dU = a.take<double>(N * nu);
-    double* dse = a.take<double>(nwin);
-    double* dtot = a.take<double>(8);
-    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
-    HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
-    rc = window_dev_impl(c, model, integ, N, H, dt, dX, dU, carry_lag, dtot, dse, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, se_total, dtot, 8));
-    if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
-}
-
-// ---- the window evaluator over a population of parameter sets; finite-difference normal equations -----------------
-// (parameter identification: fossen/identify.py).  The ctx's own parameters and their derived cache are not touched.
-static bool pop_args_ok(const brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, const double* se) {
-    return c && (model == BROV_THRUSTER_EULER || model == BROV_WRENCH_EULER || model == BROV_WRENCH_QUAT) &&
-           (integ == BROV_EULER || integ == BROV_RK4) && P >= 1 && P <= 65535 && params && N >= 0 && H >= 0 && se;
-}
-static size_t window_pop_scratch(int model, int carry, int64_t P, int64_t nwin) {
-    return Arena::al(P * sizeof(FastParams)) + Arena::al(P * nwin * 8) + window_scratch(model, carry, P, nwin);
-}
 // derive_fast once per candidate: fp [P], and with `scan` each candidate's lag_window_phi_pair in phi [P][18]
 static int derive_candidates(brov_ctx* c, int integ, int P, const brov_params* params, int64_t H, double dt, bool scan,
                              std::vector<FastParams>& fp, std::vector<double>& phi) {
@@ -1333,60 +1283,7 @@ static int derive_candidates(brov_ctx* c, int integ, int P, const brov_params* p
     }
     return BROV_OK;
 }
-static int window_pop_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, int64_t N, int64_t H, double dt,
-                           const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints, Arena& a) {
-    const int64_t nwin = N - H;
-    // one upload carries the whole FastParams[P] array (and one more the scan matrices)
-    std::vector<FastParams> fp;
-    std::vector<double> phi;
-    int rc = derive_candidates(c, integ, P, params, H, dt, model == BROV_THRUSTER_EULER && carry, fp, phi);
-    if (rc) return rc;
-    FastParams* d_fp = a.take<FastParams>(P);
-    double* d_se = a.take<double>(P * nwin);
-    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
-    return window_impl(c, d_fp, phi.data(), true, model, integ, P, N, H, dt, dX, dU, carry, d_se, d_total, d_endpoints, a);
-}
 
-int brov_window_endpoint_pop_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
-                                 const double* d_X, const double* d_U, int carry_lag, double* d_se, double* d_endpoints) {
-    if (!pop_args_ok(c, model, integ, P, params, N, H, d_se)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_dev: bad argument");
-    DeviceGuard g(c);
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se, 0, (size_t)P * 8, c->stream)); return BROV_OK; }
-    if (!d_X || !d_U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_dev: NULL array");
-    Arena a(c);
-    int rc = a.reserve(window_pop_scratch(model, carry_lag, P, nwin));
-    if (rc) return rc;
-    return window_pop_impl(c, model, integ, (int)P, params, N, H, dt, d_X, d_U, carry_lag, d_se, d_endpoints, a);
-}
-
-int brov_window_endpoint_pop(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
-                             const double* X, const double* U, int carry_lag, double* se, double* endpoints) {
-    if (!pop_args_ok(c, model, integ, P, params, N, H, se)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop: bad argument");
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { for (int64_t j = 0; j < P; ++j) se[j] = 0.0; return BROV_OK; }
-    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop: NULL array");
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    Arena a(c);
-    int rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(P * 8) + (endpoints ? Arena::al(P * nwin * nx * 8) : 0) +
-                       window_pop_scratch(model, carry_lag, P, nwin));
-    if (rc) return rc;
-    double* dX = a.take<double>(N * nx);
-    double* dU = a.take<double>(N * nu);
-    double* dtot = a.take<double>(P);
-    double* dE = endpoints ? a.take<double>(P * nwin * nx) : nullptr;
-    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
-    HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
-    rc = window_pop_impl(c, model, integ, (int)P, params, N, H, dt, dX, dU, carry_lag, dtot, dE, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, se, dtot, (size_t)P * 8));
-    if (endpoints) HIPCK(c, d2h_copy(c, endpoints, dE, (size_t)P * nwin * nx * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
-}
-
-// ---- the window evaluator over several recordings (bags): brov_window_endpoint_{pop,se}_ragged(_dev) ---------------
 // the bag list as the kernels want it: tab = [wpre [nbags + 1] | off [nbags + 1]], wpre[b] = windows before bag b
 struct WindowBags {
     int64_t nbags = 0, rows = 0, nwin = 0;
@@ -1408,165 +1305,170 @@ static int window_bags(brov_ctx* c, int64_t nbags, const int64_t* off, int64_t H
     wb->nwin = wpre[nbags];
     return BROV_OK;
 }
-// the map (table, rows, open bits) and the pre-scan's arrays
-static size_t window_ragged_scratch(int model, int carry, int64_t P, const WindowBags& wb) {
-    return Arena::al(wb.tab.size() * 8) + Arena::al(wb.nwin * 8) + Arena::al(window_chunks(wb.nwin) * 8) +
-           window_scratch(model, carry, P, wb.nwin);
-}
-// window_impl over bags, wb.nwin > 0.  P = 0: d_target alone.
-static int window_ragged_impl(brov_ctx* c, const FastParams* d_fp, const double* phi, int model, int integ, int P, const WindowBags& wb,
-                              int64_t H, double dt, const double* dX, const double* dU, int carry, double* d_se, double* d_total,
-                              double* d_endpoints, double* d_target, Arena& a) {
-    const int64_t nwin = wb.nwin;
-    const bool scan = model == BROV_THRUSTER_EULER && carry && P > 0;
-    int64_t* d_tab = a.take<int64_t>(wb.tab.size());
-    int64_t* d_wrow = a.take<int64_t>(nwin);
-    unsigned long long* d_wopen = a.take<unsigned long long>(window_chunks(nwin));
-    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
-    HIPCK(c, h2d_copy(c, d_tab, wb.tab.data(), wb.tab.size() * 8));
-    if (scan) {
-        d_lag = a.take<double>(P * nwin * 18);
-        d_chunk = a.take<double>(P * window_chunks(nwin) * 18);
-        d_phi = a.take<double>(P * 18);
-        HIPCK(c, h2d_copy(c, d_phi, phi, (size_t)P * 18 * 8));
+
+// One call of the window evaluator, as the eight entry points brov_window_endpoint_{se,pop}[_ragged][_dev] describe it.
+//   WINDOW_HOST  X, U and the outputs are the caller's host arrays, staged through the arena; otherwise device arrays
+//   WINDOW_POP   P candidates `params` (host array in both forms), se [P]; otherwise the ctx's own parameter set (P = 1, se [1])
+//   rows         one recording of N rows, or the recordings bag_offsets [nbags + 1] (host array in both forms)
+// per_window: the `se` forms' second output (required on the device); for brov_window_endpoint_pop_ragged_dev the caller's
+// [P][windows] scratch, in whose place the arena serves.
+enum : int { WINDOW_HOST = 1, WINDOW_POP = 2 };
+struct WindowRows {
+    bool ragged;
+    int64_t N, nbags;
+    const int64_t* bag_offsets;
+    static WindowRows one(int64_t N) { return {false, N, 0, nullptr}; }
+    static WindowRows bags(int64_t nbags, const int64_t* bag_offsets) { return {true, 0, nbags, bag_offsets}; }
+};
+struct WindowCall {
+    const char* who;
+    int form;                  // WINDOW_HOST | WINDOW_POP
+    int model, integ;
+    int64_t P;
+    const brov_params* params;
+    WindowRows rows;
+    int64_t H;
+    double dt;
+    const double *X, *U;
+    int carry;
+    double *se, *per_window, *endpoints, *target;
+};
+// (parameter identification: fossen/identify.py).  With candidates, the ctx's own parameters and their derived cache are not touched.
+static int window_eval(brov_ctx* c, const WindowCall& w) {
+    const bool host = w.form & WINDOW_HOST, pop = w.form & WINDOW_POP, ragged = w.rows.ragged;
+    const int64_t P = w.P, H = w.H;
+    const int model = w.model, integ = w.integ;
+    const bool enums = (integ == BROV_EULER || integ == BROV_RK4) && (ragged || w.rows.N >= 0) && H >= 0;
+    const bool ok = !pop ? model_ok(model) && enums && w.se        // the double-integrator gains are not brov_params: `se` forms only
+                           : (model == BROV_THRUSTER_EULER || model == BROV_WRENCH_EULER || model == BROV_WRENCH_QUAT) && enums &&
+                                 ((P >= 1 && P <= 65535 && w.params && w.se) || (ragged && P == 0 && w.target));
+    if (!c || !ok) return fail(c, BROV_ERR_ARG, std::string(w.who) + ": bad argument");
+    WindowBags wb;
+    if (ragged) {
+        int rc = window_bags(c, w.rows.nbags, w.rows.bag_offsets, H, &wb, w.who);
+        if (rc) return rc;
     }
-    HIPCK(c, hipStreamSynchronize(c->stream));   // the table, phi and the caller's arrays are temporaries
-    CallTimer t(c);
-    HIPCK(c, launch_window_endpoint_ragged(c->stream, d_fp, model, integ, P, wb.nbags, d_tab, nwin, H, dt, dX, dU, carry, d_phi, d_lag,
-                                           d_chunk, d_wrow, d_wopen, d_se, d_total, d_endpoints, d_target));
-    return BROV_OK;
+    const int64_t N = ragged ? wb.rows : w.rows.N, nwin = ragged ? wb.nwin : N - H;
+    if (nwin <= 0) {           // no windows: zeros, and nothing else is touched
+        if (host) { std::fill(w.se, w.se + P, 0.0); return BROV_OK; }
+        DeviceGuard g(c);
+        if (P) HIPCK(c, hipMemsetAsync(w.se, 0, (size_t)P * 8, c->stream));
+        return BROV_OK;
+    }
+    if (!w.X || (P && !w.U) || (!pop && !host && !w.per_window)) return fail(c, BROV_ERR_ARG, std::string(w.who) + ": NULL array");
+    DeviceGuard g(c);
+    const int nx = NX(model), nu = NU(model);
+    const bool scan = model == BROV_THRUSTER_EULER && w.carry && P > 0;     // the pre-scan of the carried thruster lag
+    Arena a(c, host);
+    const double *dX, *dU;
+    double *d_total, *d_se, *dE, *dT, *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    FastParams* d_cand = nullptr;
+    int64_t *d_tab = nullptr, *d_wrow = nullptr;
+    unsigned long long* d_wopen = nullptr;
+    int rc = a.lay(w.who, [&] {
+        dX = a.in(w.X, N * nx);
+        dU = P ? a.in(w.U, N * nu) : nullptr;
+        d_total = a.out(w.se, P);
+        if (!pop) d_se = a.out(w.per_window, nwin);
+        dE = w.endpoints ? a.out(w.endpoints, P * nwin * nx) : nullptr;
+        dT = w.target ? a.out(w.target, nwin * nx) : nullptr;
+        if (pop) {
+            d_cand = a.take<FastParams>(P);
+            d_se = w.per_window ? w.per_window : a.take<double>(P * nwin);
+        }
+        if (ragged) {        // the map: table, rows, open bits
+            d_tab = a.take<int64_t>(wb.tab.size());
+            d_wrow = a.take<int64_t>(nwin);
+            d_wopen = a.take<unsigned long long>(window_chunks(nwin));
+        }
+        if (scan) {
+            d_lag = a.take<double>(P * nwin * 18);
+            d_chunk = a.take<double>(P * window_chunks(nwin) * 18);
+            d_phi = a.take<double>(P * 18);
+        }
+    });
+    if (rc) return rc;
+    // the parameter sets, and with `scan` each one's lag_window_phi_pair (temporaries on the host)
+    std::vector<FastParams> fp;
+    std::vector<double> phi(18);
+    const FastParams* d_fp = d_cand;
+    if (pop) {
+        rc = P ? derive_candidates(c, integ, (int)P, w.params, H, w.dt, scan, fp, phi) : BROV_OK;
+        if (rc) return rc;
+    } else {
+        const DevParams* dp;
+        rc = get_dp(c, w.dt, &dp);
+        if (rc) return rc;
+        if (model_is_di_h(model) && !c->di_set) return fail(c, BROV_ERR_ARG, "double-integrator model: call brov_set_di_gains first");
+        lag_window_phi_pair(*dp, H * (integ == BROV_RK4 ? 4 : 1), phi.data());
+        d_fp = model_is_di_h(model) ? c->d_fp_di : c->d_fp;      // get_dp has made the ctx's own set current
+    }
+    // one upload carries the whole FastParams[P] array, one the bag table, one the scan matrices
+    if (pop && P) HIPCK(c, h2d_copy(c, d_cand, fp.data(), (size_t)P * sizeof(FastParams)));
+    if (ragged) HIPCK(c, h2d_copy(c, d_tab, wb.tab.data(), wb.tab.size() * 8));
+    if (scan) HIPCK(c, h2d_copy(c, d_phi, phi.data(), (size_t)P * 18 * 8));
+    if (pop || ragged || scan) HIPCK(c, hipStreamSynchronize(c->stream));   // fp, the table, phi and a caller's arrays are temporaries
+    {
+        // a one-recording call stays what it is: a one-bag ragged call would add the map kernel and the table upload
+        CallTimer t(c);
+        if (ragged)
+            HIPCK(c, launch_window_endpoint_ragged(c->stream, d_fp, model, integ, (int)P, wb.nbags, d_tab, nwin, H, w.dt, dX, dU, w.carry, d_phi,
+                                                   d_lag, d_chunk, d_wrow, d_wopen, d_se, d_total, dE, dT));
+        else
+            HIPCK(c, launch_window_endpoint(c->stream, d_fp, model, integ, (int)P, N, H, w.dt, dX, dU, w.carry, d_phi, d_lag, d_chunk, d_se,
+                                            d_total, dE));
+    }
+    return a.finish();
 }
 
-static bool pop_ragged_args_ok(const brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t H, const double* se,
-                               const double* target) {
-    return c && (model == BROV_THRUSTER_EULER || model == BROV_WRENCH_EULER || model == BROV_WRENCH_QUAT) &&
-           (integ == BROV_EULER || integ == BROV_RK4) && H >= 0 &&
-           ((P >= 1 && P <= 65535 && params && se) || (P == 0 && target));
+int brov_window_endpoint_se_dev(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* d_X,
+                                const double* d_U, int carry_lag, double* d_se_total, double* d_per_window) {
+    return window_eval(c, {"brov_window_endpoint_se_dev", 0, model, integ, 1, nullptr, WindowRows::one(N), H, dt, d_X, d_U,
+                           carry_lag, d_se_total, d_per_window, nullptr, nullptr});
 }
-static size_t window_pop_ragged_scratch(int model, int carry, int64_t P, const WindowBags& wb, bool own_se) {
-    return Arena::al(P * sizeof(FastParams)) + (own_se ? Arena::al(P * wb.nwin * 8) : 0) + window_ragged_scratch(model, carry, P, wb);
+
+int brov_window_endpoint_se(brov_ctx* c, int model, int integ, int64_t N, int64_t H, double dt, const double* X, const double* U,
+                            int carry_lag, double* se_total, double* per_window) {
+    return window_eval(c, {"brov_window_endpoint_se", WINDOW_HOST, model, integ, 1, nullptr, WindowRows::one(N), H, dt, X, U, carry_lag,
+                           se_total, per_window, nullptr, nullptr});
 }
-static int window_pop_ragged_impl(brov_ctx* c, int model, int integ, int P, const brov_params* params, const WindowBags& wb, int64_t H,
-                                  double dt, const double* dX, const double* dU, int carry, double* d_total, double* d_endpoints,
-                                  double* d_target, double* d_per_window, Arena& a) {
-    std::vector<FastParams> fp;
-    std::vector<double> phi;
-    int rc = P ? derive_candidates(c, integ, P, params, H, dt, model == BROV_THRUSTER_EULER && carry, fp, phi) : BROV_OK;
-    if (rc) return rc;
-    FastParams* d_fp = a.take<FastParams>(P);
-    double* d_se = d_per_window ? d_per_window : a.take<double>(P * wb.nwin);
-    if (P) HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
-    return window_ragged_impl(c, d_fp, phi.data(), model, integ, P, wb, H, dt, dX, dU, carry, d_se, d_total, d_endpoints, d_target, a);
+
+int brov_window_endpoint_pop_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
+                                 const double* d_X, const double* d_U, int carry_lag, double* d_se, double* d_endpoints) {
+    return window_eval(c, {"brov_window_endpoint_pop_dev", WINDOW_POP, model, integ, P, params, WindowRows::one(N), H, dt, d_X, d_U,
+                           carry_lag, d_se, nullptr, d_endpoints, nullptr});
+}
+
+int brov_window_endpoint_pop(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t N, int64_t H, double dt,
+                             const double* X, const double* U, int carry_lag, double* se, double* endpoints) {
+    return window_eval(c, {"brov_window_endpoint_pop", WINDOW_HOST | WINDOW_POP, model, integ, P, params, WindowRows::one(N), H, dt, X, U,
+                           carry_lag, se, nullptr, endpoints, nullptr});
 }
 
 int brov_window_endpoint_pop_ragged_dev(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t nbags,
                                         const int64_t* bag_offsets, int64_t H, double dt, const double* d_X, const double* d_U,
                                         int carry_lag, double* d_se, double* d_endpoints, double* d_target, double* d_per_window) {
-    if (!pop_ragged_args_ok(c, model, integ, P, params, H, d_se, d_target))
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged_dev: bad argument");
-    WindowBags wb;
-    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_pop_ragged_dev");
-    if (rc) return rc;
-    DeviceGuard g(c);
-    if (wb.nwin == 0) { if (P) HIPCK(c, hipMemsetAsync(d_se, 0, (size_t)P * 8, c->stream)); return BROV_OK; }
-    if (!d_X || (P && !d_U)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged_dev: NULL array");
-    Arena a(c);
-    rc = a.reserve(window_pop_ragged_scratch(model, carry_lag, P, wb, !d_per_window));
-    if (rc) return rc;
-    return window_pop_ragged_impl(c, model, integ, (int)P, params, wb, H, dt, d_X, d_U, carry_lag, d_se, d_endpoints, d_target,
-                                  d_per_window, a);
+    return window_eval(c, {"brov_window_endpoint_pop_ragged_dev", WINDOW_POP, model, integ, P, params, WindowRows::bags(nbags, bag_offsets),
+                           H, dt, d_X, d_U, carry_lag, d_se, d_per_window, d_endpoints, d_target});
 }
 
 int brov_window_endpoint_pop_ragged(brov_ctx* c, int model, int integ, int64_t P, const brov_params* params, int64_t nbags,
                                     const int64_t* bag_offsets, int64_t H, double dt, const double* X, const double* U, int carry_lag,
                                     double* se, double* endpoints, double* target) {
-    if (!pop_ragged_args_ok(c, model, integ, P, params, H, se, target))
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged: bad argument");
-    WindowBags wb;
-    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_pop_ragged");
-    if (rc) return rc;
-    if (wb.nwin == 0) { for (int64_t j = 0; j < P; ++j) se[j] = 0.0; return BROV_OK; }
-    if (!X || (P && !U)) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_pop_ragged: NULL array");
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    const int64_t N = wb.rows, nwin = wb.nwin;
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(P * 8) + (endpoints ? Arena::al(P * nwin * nx * 8) : 0) +
-                   (target ? Arena::al(nwin * nx * 8) : 0) + window_pop_ragged_scratch(model, carry_lag, P, wb, true));
-    if (rc) return rc;
-    double* dX = a.take<double>(N * nx);
-    double* dU = a.take<double>(N * nu);
-    double* dtot = a.take<double>(P);
-    double* dE = endpoints ? a.take<double>(P * nwin * nx) : nullptr;
-    double* dT = target ? a.take<double>(nwin * nx) : nullptr;
-    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
-    if (P) HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
-    rc = window_pop_ragged_impl(c, model, integ, (int)P, params, wb, H, dt, dX, dU, carry_lag, dtot, dE, dT, nullptr, a);
-    if (rc) return rc;
-    if (P) HIPCK(c, d2h_copy(c, se, dtot, (size_t)P * 8));
-    if (endpoints) HIPCK(c, d2h_copy(c, endpoints, dE, (size_t)P * nwin * nx * 8));
-    if (target) HIPCK(c, d2h_copy(c, target, dT, (size_t)nwin * nx * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
-}
-
-// one parameter set over bags: the ctx's own
-static int window_ragged_dev_impl(brov_ctx* c, int model, int integ, const WindowBags& wb, int64_t H, double dt, const double* dX,
-                                  const double* dU, int carry, double* d_total, double* d_se, Arena& a) {
-    const DevParams* dp;
-    int rc = get_dp(c, dt, &dp);
-    if (rc) return rc;
-    if (model_is_di_h(model) && !c->di_set) return fail(c, BROV_ERR_ARG, "double-integrator model: call brov_set_di_gains first");
-    double Phi[18];
-    lag_window_phi_pair(*dp, H * (integ == BROV_RK4 ? 4 : 1), Phi);
-    return window_ragged_impl(c, model_is_di_h(model) ? c->d_fp_di : c->d_fp, Phi, model, integ, 1, wb, H, dt, dX, dU, carry, d_se, d_total,
-                              nullptr, nullptr, a);
+    return window_eval(c, {"brov_window_endpoint_pop_ragged", WINDOW_HOST | WINDOW_POP, model, integ, P, params,
+                           WindowRows::bags(nbags, bag_offsets), H, dt, X, U, carry_lag, se, nullptr, endpoints, target});
 }
 
 int brov_window_endpoint_se_ragged_dev(brov_ctx* c, int model, int integ, int64_t nbags, const int64_t* bag_offsets, int64_t H, double dt,
                                        const double* d_X, const double* d_U, int carry_lag, double* d_se_total, double* d_per_window) {
-    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || H < 0 || !d_se_total)
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged_dev: bad argument");
-    WindowBags wb;
-    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_se_ragged_dev");
-    if (rc) return rc;
-    DeviceGuard g(c);
-    if (wb.nwin == 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
-    if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged_dev: NULL array");
-    Arena a(c);
-    rc = a.reserve(window_ragged_scratch(model, carry_lag, 1, wb));
-    if (rc) return rc;
-    return window_ragged_dev_impl(c, model, integ, wb, H, dt, d_X, d_U, carry_lag, d_se_total, d_per_window, a);
+    return window_eval(c, {"brov_window_endpoint_se_ragged_dev", 0, model, integ, 1, nullptr, WindowRows::bags(nbags, bag_offsets), H, dt,
+                           d_X, d_U, carry_lag, d_se_total, d_per_window, nullptr, nullptr});
 }
 
 int brov_window_endpoint_se_ragged(brov_ctx* c, int model, int integ, int64_t nbags, const int64_t* bag_offsets, int64_t H, double dt,
                                    const double* X, const double* U, int carry_lag, double* se_total, double* per_window) {
-    if (!c || !model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || H < 0 || !se_total)
-        return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged: bad argument");
-    WindowBags wb;
-    int rc = window_bags(c, nbags, bag_offsets, H, &wb, "brov_window_endpoint_se_ragged");
-    if (rc) return rc;
-    if (wb.nwin == 0) { *se_total = 0.0; return BROV_OK; }
-    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_window_endpoint_se_ragged: NULL array");
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    const int64_t N = wb.rows, nwin = wb.nwin;
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * nx * 8) + Arena::al(N * nu * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) +
-                   window_ragged_scratch(model, carry_lag, 1, wb));
-    if (rc) return rc;
-    double* dX = a.take<double>(N * nx);
-    double* dU = a.take<double>(N * nu);
-    double* dse = a.take<double>(nwin);
-    double* dtot = a.take<double>(8);
-    HIPCK(c, h2d_copy(c, dX, X, N * nx * 8));
-    HIPCK(c, h2d_copy(c, dU, U, N * nu * 8));
-    rc = window_ragged_dev_impl(c, model, integ, wb, H, dt, dX, dU, carry_lag, dtot, dse, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, se_total, dtot, 8));
-    if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return window_eval(c, {"brov_window_endpoint_se_ragged", WINDOW_HOST, model, integ, 1, nullptr, WindowRows::bags(nbags, bag_offsets), H, dt,
+                           X, U, carry_lag, se_total, per_window, nullptr, nullptr});
 }
 
 int brov_fd_normal_eq_dev(brov_ctx* c, int nx, int m, int64_t W, const double* d_endpoints, const double* d_target, const double* delta,
@@ -1580,23 +1482,24 @@ int brov_fd_normal_eq_dev(brov_ctx* c, int nx, int m, int64_t W, const double* d
     DeviceGuard g(c);
     const int64_t R = W * nx;
     const int nb = fd_normal_blocks(R), npair = (m + 1) * (m + 2) / 2, nout = m * m + m;
-    Arena a(c);
-    int rc = a.reserve(Arena::al((m + nx) * 8) + Arena::al((size_t)nb * npair * 8) + Arena::al(nout * 8) + 4096);
-    if (rc) return rc;
-    double* d_dw = a.take<double>(m + nx);       // [delta | weight]
-    double* d_part = a.take<double>((size_t)nb * npair);
-    double* d_out = a.take<double>(nout);
-    std::vector<double> dw((size_t)(m + nx), 1.0), out((size_t)nout);
+    std::vector<double> dw((size_t)(m + nx), 1.0), out((size_t)nout);        // [delta | weight]; [JtJ | Jtr]
     std::copy(delta, delta + m, dw.begin());
     if (weight) std::copy(weight, weight + nx, dw.begin() + m);
-    HIPCK(c, h2d_copy(c, d_dw, dw.data(), dw.size() * 8));
+    Arena a(c, true);
+    double *d_dw, *d_part, *d_out;
+    int rc = a.lay("brov_fd_normal_eq_dev", [&] {
+        d_dw = a.in(dw.data(), dw.size());
+        d_part = a.take<double>((size_t)nb * npair);
+        d_out = a.out(out.data(), out.size());
+    });
+    if (rc) return rc;
     HIPCK(c, hipStreamSynchronize(c->stream));   // dw is a local
     {
         CallTimer t(c);
         HIPCK(c, launch_fd_normal_eq(c->stream, nx, m, R, d_endpoints, d_target, d_dw, d_dw + m, d_part, d_out));
     }
-    HIPCK(c, d2h_copy(c, out.data(), d_out, out.size() * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
+    rc = a.finish();
+    if (rc) return rc;
     std::copy(out.begin(), out.begin() + m * m, JtJ);
     std::copy(out.begin() + m * m, out.end(), Jtr);
     return BROV_OK;
@@ -1605,104 +1508,95 @@ int brov_fd_normal_eq_dev(brov_ctx* c, int nx, int m, int64_t W, const double* d
 // ---- rollouts over a population of parameter sets; ensemble statistics ------------------------------------------------
 // (many vehicles in one launch: fitted against nominal, draws around a fit, a vehicle per trajectory).  As for the window evaluator
 // above, the ctx's own parameters and their derived cache are not touched.
-static int rollout_pop_args_ok(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t B, int64_t T,
-                               int64_t stride, const void* x0, const void* U, const void* traj) {
+
+// What brov_rollout_pop, brov_rollout_feedback and brov_mppi_step (`who`) refuse first: enums, sizes (a form without P or T passes
+// 1 and 0), the double-integrator models, the limits of the grid.  *empty: nothing to do, BROV_OK.
+static int pop_call_ok(brov_ctx* c, const char* who, int model, int integ, int lag_mode, int64_t P, int64_t B, int64_t T, int64_t Bmax,
+                       bool* empty) {
+    const std::string w = who;
+    *empty = false;
     if (!c) return BROV_ERR_ARG;
     if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) ||
         P < 0 || B < 0 || T < 0)
-        return fail(c, BROV_ERR_ARG, "brov_rollout_pop: bad enum or negative size");
+        return fail(c, BROV_ERR_ARG, w + ": bad enum or negative size");
     if (model_is_di_h(model))
-        return fail(c, BROV_ERR_ARG, "brov_rollout_pop: the double-integrator gains are not brov_params; thruster and wrench models only");
-    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: P must be <= 65535");
-    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: B must be <= 2^31");
-    if (B == 0 || P == 0) return BROV_OK;
-    if (!params || !x0 || (T && !U)) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: NULL input");
-    if (traj && stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: traj_stride must be >= 1");
+        return fail(c, BROV_ERR_ARG, w + ": the double-integrator gains are not brov_params; thruster and wrench models only");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, w + ": P must be <= 65535");
+    if (B > Bmax) return fail(c, BROV_ERR_ARG, w + ": B must be <= " + (Bmax == 65535 ? "65535" : "2^31"));
+    *empty = B == 0 || P == 0;
     return BROV_OK;
 }
-// derive_fast per candidate, one upload of FastParams[P], one launch
-static int rollout_pop_impl(brov_ctx* c, int model, int integ, int lag_mode, int P, const brov_params* params, int per_candidate, int64_t B,
-                            int64_t T, double dt, const double* dx0, const double* dU, double* d_lag, double* d_traj, int64_t stride,
-                            double* d_xT, Arena& a) {
+
+// derive_fast per candidate, one upload of FastParams[P], one launch.  host: the arrays are the caller's host memory.
+static int rollout_pop(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int per_candidate,
+                       int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag_io, double* traj, int64_t stride,
+                       double* xT) {
+    bool empty;
+    int rc = pop_call_ok(c, "brov_rollout_pop", model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
+    if (rc || empty) return rc;
+    if (!params || !x0 || (T && !U)) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: NULL input");
+    if (traj && stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_pop: traj_stride must be >= 1");
+    DeviceGuard g(c);
     std::vector<FastParams> fp;
     std::vector<double> phi;
-    int rc = derive_candidates(c, integ, P, params, 0, dt, false, fp, phi);
+    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
     if (rc) return rc;
-    FastParams* d_fp = a.take<FastParams>(P);
+    const int nx = NX(model), nu = NU(model);
+    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
+    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
+    const size_t nin = per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
+    Arena a(c, host);
+    const double *dx0, *dU;
+    double *dxT, *dl, *dtr;
+    FastParams* d_fp;
+    rc = a.lay("brov_rollout_pop", [&] {
+        dx0 = a.in(x0, nin * nx);
+        dU = a.in(U, nin * T * nu);
+        dxT = a.out(xT, nout * nx);
+        dl = lag ? a.inout(lag_io, nout * 24) : nullptr;
+        dtr = traj ? a.out(traj, nout * rows * nx) : nullptr;
+        d_fp = a.take<FastParams>(P);
+    });
+    if (rc) return rc;
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
     HIPCK(c, hipStreamSynchronize(c->stream));   // fp is a local
-    CallTimer t(c);
-    HIPCK(c, launch_rollout_pop(c->stream, d_fp, model, integ, lag_mode, P, per_candidate, B, T, dt, dx0, dU,
-                                model == BROV_THRUSTER_EULER ? d_lag : nullptr, d_traj, d_traj ? stride : 1, d_xT));
-    return BROV_OK;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_rollout_pop(c->stream, d_fp, model, integ, lag_mode, (int)P, per_candidate, B, T, dt, dx0, dU, dl, dtr, dtr ? stride : 1,
+                                    dxT));
+    }
+    return a.finish();
 }
 
 int brov_rollout_pop_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int inputs_per_candidate,
                          int64_t B, int64_t T, double dt, const double* d_x0, const double* d_U, double* d_lag_io, double* d_traj,
                          int64_t stride, double* d_xT) {
-    int rc = rollout_pop_args_ok(c, model, integ, lag_mode, P, params, B, T, stride, d_x0, d_U, d_traj);
-    if (rc) return rc;
-    if (B == 0 || P == 0) return BROV_OK;
-    DeviceGuard g(c);
-    Arena a(c);
-    rc = a.reserve(Arena::al(P * sizeof(FastParams)));
-    if (rc) return rc;
-    return rollout_pop_impl(c, model, integ, lag_mode, (int)P, params, inputs_per_candidate != 0, B, T, dt, d_x0, d_U, d_lag_io, d_traj, stride,
-                            d_xT, a);
+    return rollout_pop(c, false, model, integ, lag_mode, P, params, inputs_per_candidate != 0, B, T, dt, d_x0, d_U, d_lag_io, d_traj, stride,
+                       d_xT);
 }
 
 int brov_rollout_pop(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int inputs_per_candidate,
                      int64_t B, int64_t T, double dt, const double* x0, const double* U, double* lag_io, double* traj, int64_t stride,
                      double* xT) {
-    int rc = rollout_pop_args_ok(c, model, integ, lag_mode, P, params, B, T, stride, x0, U, traj);
-    if (rc) return rc;
-    if (B == 0 || P == 0) return BROV_OK;
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
-    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
-    const size_t nin = inputs_per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
-    Arena a(c);
-    rc = a.reserve(Arena::al(nin * nx * 8) + Arena::al(nin * T * nu * 8) + Arena::al(nout * nx * 8) + (lag ? Arena::al(nout * 24 * 8) : 0) +
-                   Arena::al(nout * rows * nx * 8) + Arena::al(P * sizeof(FastParams)));
-    if (rc) return rc;
-    double* dx0 = a.take<double>(nin * nx);
-    double* dU = a.take<double>(nin * T * nu);
-    double* dxT = a.take<double>(nout * nx);
-    double* dl = lag ? a.take<double>(nout * 24) : nullptr;
-    double* dtr = traj ? a.take<double>(nout * rows * nx) : nullptr;
-    HIPCK(c, h2d_copy(c, dx0, x0, nin * nx * 8));
-    if (T) HIPCK(c, h2d_copy(c, dU, U, nin * T * nu * 8));
-    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, nout * 24 * 8));
-    rc = rollout_pop_impl(c, model, integ, lag_mode, (int)P, params, inputs_per_candidate != 0, B, T, dt, dx0, dU, dl, dtr, stride, dxT, a);
-    if (rc) return rc;
-    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, nout * nx * 8));
-    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, nout * 24 * 8));
-    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, nout * rows * nx * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return rollout_pop(c, true, model, integ, lag_mode, P, params, inputs_per_candidate != 0, B, T, dt, x0, U, lag_io, traj, stride, xT);
 }
 
 // ---- closed-loop rollouts (feedback.hip) --------------------------------------------------------------------------------------
 static_assert(sizeof(brov_feedback) == sizeof(FeedbackRec) && sizeof(brov_feedback) == 167 * 8, "FeedbackRec is brov_feedback byte for byte");
-// Everything the host can refuse, and the derived constants of every candidate: nothing has been copied or launched when this fails.
-static int rollout_feedback_prepare(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
-                                    const brov_feedback* fb, int64_t B, int64_t T, double dt, const void* x0, const void* ref,
-                                    int64_t ref_rows, int64_t stride, std::vector<FastParams>& fp) {
-    if (!c) return BROV_ERR_ARG;
-    if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) ||
-        P < 0 || B < 0 || T < 0)
-        return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: bad enum or negative size");
-    if (model_is_di_h(model))
-        return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: the double-integrator gains are not brov_params; thruster and wrench models only");
-    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: P must be <= 65535");
-    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: B must be <= 2^31");
-    if (B == 0 || P == 0) return BROV_OK;
+// Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
+// and of the feedback records, one launch.  host: the arrays are the caller's host memory.
+static int rollout_feedback(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
+                            const brov_feedback* fb, int per_candidate, int64_t B, int64_t T, double dt, const double* x0,
+                            const double* u_ff, const double* ref, int64_t ref_rows, double* lag_io, double* z_io, double* traj,
+                            int64_t stride, double* xT, double* u_applied, double* metrics) {
+    bool empty;
+    int rc = pop_call_ok(c, "brov_rollout_feedback", model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
+    if (rc || empty) return rc;
     if (!params || !x0 || !ref || !fb) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: NULL input");
     if (nfb != 1 && nfb != P) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: nfb must be 1 or P");
     if (ref_rows != 1 && ref_rows != T) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: ref_rows must be 1 or T");
     if (stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: traj_stride must be >= 1");
-    const int nu = NU(model);
+    const int nx = NX(model), nu = NU(model);
     for (int64_t k = 0; k < nfb; ++k) {
         const brov_feedback& f = fb[k];
         const std::string who = "brov_rollout_feedback: fb[" + std::to_string(k) + "]: ";
@@ -1715,117 +1609,81 @@ static int rollout_feedback_prepare(brov_ctx* c, int model, int integ, int lag_m
         for (int i = 0; i < 6; ++i)
             if (f.z_max[i] < 0.0) return fail(c, BROV_ERR_ARG, who + "z_max must be >= 0");
     }
+    std::vector<FastParams> fp;
     std::vector<double> phi;
-    return derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
-}
-// one upload of FastParams[P] and of the feedback records, one launch
-static int rollout_feedback_impl(brov_ctx* c, int model, int integ, int lag_mode, int P, const std::vector<FastParams>& fp, int64_t nfb,
-                                 const brov_feedback* fb, FeedbackArgs args, Arena& a) {
-    FastParams* d_fp = a.take<FastParams>(P);
-    FeedbackRec* d_fb = a.take<FeedbackRec>(nfb);
+    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
+    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
+    const size_t nin = per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
+    FeedbackArgs args{};
+    args.per_candidate = per_candidate;
+    args.fb_per_candidate = nfb > 1;
+    args.B = B; args.T = T; args.ref_rows = ref_rows; args.stride = stride; args.dt = dt;
+    FastParams* d_fp;
+    FeedbackRec* d_fb;
+    Arena a(c, host);
+    rc = a.lay("brov_rollout_feedback", [&] {
+        args.x0 = a.in(x0, nin * nx);
+        args.u_ff = u_ff && (T || !host) ? a.in(u_ff, nin * T * nu) : nullptr;       // host form without steps: no buffer
+        args.ref = a.in(ref, nin * ref_rows * nx);
+        args.xT = a.out(xT, nout * nx);
+        args.lag = lag ? a.inout(lag_io, nout * 24) : nullptr;
+        args.z = z_io ? a.inout(z_io, nout * 6) : nullptr;
+        args.traj = traj ? a.out(traj, nout * rows * nx) : nullptr;
+        args.u_applied = u_applied ? a.out(u_applied, nout * T * nu) : nullptr;
+        args.metrics = metrics ? a.out(metrics, nout * 4) : nullptr;
+        d_fp = a.take<FastParams>(P);
+        d_fb = a.take<FeedbackRec>(nfb);
+    });
+    if (rc) return rc;
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
     HIPCK(c, h2d_copy(c, d_fb, fb, (size_t)nfb * sizeof(FeedbackRec)));
     HIPCK(c, hipStreamSynchronize(c->stream));   // fp is a local, fb the caller's
     args.fp = d_fp;
     args.fb = d_fb;
-    args.fb_per_candidate = nfb > 1;
-    CallTimer t(c);
-    HIPCK(c, launch_rollout_feedback(c->stream, model, integ, lag_mode, P, args));
-    return BROV_OK;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_rollout_feedback(c->stream, model, integ, lag_mode, (int)P, args));
+    }
+    return a.finish();
 }
 
 int brov_rollout_feedback_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
                               const brov_feedback* fb, int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* d_x0,
                               const double* d_u_ff, const double* d_ref, int64_t ref_rows, double* d_lag_io, double* d_z_io,
                               double* d_traj, int64_t stride, double* d_xT, double* d_u_applied, double* d_metrics) {
-    std::vector<FastParams> fp;
-    int rc = rollout_feedback_prepare(c, model, integ, lag_mode, P, params, nfb, fb, B, T, dt, d_x0, d_ref, ref_rows, stride, fp);
-    if (rc) return rc;
-    if (B == 0 || P == 0) return BROV_OK;
-    DeviceGuard g(c);
-    Arena a(c);
-    rc = a.reserve(Arena::al(P * sizeof(FastParams)) + Arena::al(nfb * sizeof(FeedbackRec)));
-    if (rc) return rc;
-    FeedbackArgs args{};
-    args.per_candidate = inputs_per_candidate != 0;
-    args.B = B; args.T = T; args.ref_rows = ref_rows; args.stride = stride; args.dt = dt;
-    args.x0 = d_x0; args.u_ff = d_u_ff; args.ref = d_ref;
-    args.lag = model == BROV_THRUSTER_EULER ? d_lag_io : nullptr;
-    args.z = d_z_io; args.traj = d_traj; args.xT = d_xT; args.u_applied = d_u_applied; args.metrics = d_metrics;
-    return rollout_feedback_impl(c, model, integ, lag_mode, (int)P, fp, nfb, fb, args, a);
+    return rollout_feedback(c, false, model, integ, lag_mode, P, params, nfb, fb, inputs_per_candidate != 0, B, T, dt, d_x0, d_u_ff, d_ref,
+                            ref_rows, d_lag_io, d_z_io, d_traj, stride, d_xT, d_u_applied, d_metrics);
 }
 
 int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
                           const brov_feedback* fb, int inputs_per_candidate, int64_t B, int64_t T, double dt, const double* x0,
                           const double* u_ff, const double* ref, int64_t ref_rows, double* lag_io, double* z_io, double* traj,
                           int64_t stride, double* xT, double* u_applied, double* metrics) {
-    std::vector<FastParams> fp;
-    int rc = rollout_feedback_prepare(c, model, integ, lag_mode, P, params, nfb, fb, B, T, dt, x0, ref, ref_rows, stride, fp);
-    if (rc) return rc;
-    if (B == 0 || P == 0) return BROV_OK;
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
-    const size_t rows = traj ? (size_t)(T / stride + 1) : 0;
-    const size_t nin = inputs_per_candidate ? (size_t)P * B : (size_t)B, nout = (size_t)P * B;
-    const size_t n_uff = u_ff ? nin * T * nu : 0, n_ref = nin * ref_rows * nx, n_ua = u_applied ? nout * T * nu : 0;
-    Arena a(c);
-    rc = a.reserve(Arena::al(nin * nx * 8) + Arena::al(n_uff * 8) + Arena::al(n_ref * 8) + Arena::al(nout * nx * 8) +
-                   (lag ? Arena::al(nout * 24 * 8) : 0) + Arena::al(nout * 6 * 8) + Arena::al(nout * rows * nx * 8) + Arena::al(n_ua * 8) +
-                   Arena::al(nout * 4 * 8) + Arena::al(P * sizeof(FastParams)) + Arena::al(nfb * sizeof(FeedbackRec)));
-    if (rc) return rc;
-    double* dx0 = a.take<double>(nin * nx);
-    double* duf = u_ff ? a.take<double>(n_uff) : nullptr;
-    double* dref = a.take<double>(n_ref);
-    double* dxT = a.take<double>(nout * nx);
-    double* dl = lag ? a.take<double>(nout * 24) : nullptr;
-    double* dz = z_io ? a.take<double>(nout * 6) : nullptr;
-    double* dtr = traj ? a.take<double>(nout * rows * nx) : nullptr;
-    double* dua = u_applied ? a.take<double>(n_ua) : nullptr;
-    double* dm = metrics ? a.take<double>(nout * 4) : nullptr;
-    HIPCK(c, h2d_copy(c, dx0, x0, nin * nx * 8));
-    if (n_uff) HIPCK(c, h2d_copy(c, duf, u_ff, n_uff * 8));
-    if (n_ref) HIPCK(c, h2d_copy(c, dref, ref, n_ref * 8));
-    if (lag) HIPCK(c, h2d_copy(c, dl, lag_io, nout * 24 * 8));
-    if (z_io) HIPCK(c, h2d_copy(c, dz, z_io, nout * 6 * 8));
-    FeedbackArgs args{};
-    args.per_candidate = inputs_per_candidate != 0;
-    args.B = B; args.T = T; args.ref_rows = ref_rows; args.stride = stride; args.dt = dt;
-    args.x0 = dx0; args.u_ff = T ? duf : nullptr; args.ref = dref;
-    args.lag = dl; args.z = dz; args.traj = dtr; args.xT = dxT; args.u_applied = dua; args.metrics = dm;
-    rc = rollout_feedback_impl(c, model, integ, lag_mode, (int)P, fp, nfb, fb, args, a);
-    if (rc) return rc;
-    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, nout * nx * 8));
-    if (lag) HIPCK(c, d2h_copy(c, lag_io, dl, nout * 24 * 8));
-    if (z_io) HIPCK(c, d2h_copy(c, z_io, dz, nout * 6 * 8));
-    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, nout * rows * nx * 8));
-    if (n_ua) HIPCK(c, d2h_copy(c, u_applied, dua, n_ua * 8));
-    if (metrics) HIPCK(c, d2h_copy(c, metrics, dm, nout * 4 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return rollout_feedback(c, true, model, integ, lag_mode, P, params, nfb, fb, inputs_per_candidate != 0, B, T, dt, x0, u_ff, ref, ref_rows,
+                            lag_io, z_io, traj, stride, xT, u_applied, metrics);
 }
 
 // ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------
 static_assert(sizeof(brov_mppi) == sizeof(MppiRec) && sizeof(brov_mppi) == 59 * 8, "MppiRec is brov_mppi byte for byte");
-// Everything the host can refuse, and the derived constants of every parameter set: nothing has been copied or launched when this
-// fails.  *M = the number of knots.
-static int mppi_prepare(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
-                        const brov_mppi* cfg, int64_t K, int64_t H, double dt, const void* x, const void* ref, int64_t ref_total,
-                        int64_t ref_row0, const void* U_nom, std::vector<FastParams>& fp, int64_t* M) {
-    if (!c) return BROV_ERR_ARG;
-    if (!model_ok(model) || (integ != BROV_EULER && integ != BROV_RK4) || (lag_mode != BROV_LAG_PER_CALL && lag_mode != BROV_LAG_PER_STEP) || B < 0)
-        return fail(c, BROV_ERR_ARG, "brov_mppi_step: bad enum or negative size");
-    if (model_is_di_h(model))
-        return fail(c, BROV_ERR_ARG, "brov_mppi_step: the double-integrator gains are not brov_params; thruster and wrench models only");
-    if (B > 65535) return fail(c, BROV_ERR_ARG, "brov_mppi_step: B must be <= 65535");
-    if (B == 0) return BROV_OK;
+// Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of
+// FastParams[nparams] and the record, two launches.  host: the arrays are the caller's host memory.
+static int mppi_step(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
+                     const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* x, const double* lag,
+                     const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps, double* U_nom, int shift, double* u_apply,
+                     double* cost, double* info) {
+    bool empty;
+    int rc = pop_call_ok(c, "brov_mppi_step", model, integ, lag_mode, 1, B, 0, 65535, &empty);
+    if (rc || empty) return rc;
     if (K < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be >= 1");
     if (H < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be >= 1");
     if (K > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be <= 2^31");
     if (H > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be <= 2^31");
     if (!params || !cfg || !x || !ref || !U_nom) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NULL input");
     if (nparams != 1 && nparams != B) return fail(c, BROV_ERR_ARG, "brov_mppi_step: nparams must be 1 or B");
-    const int nu = NU(model);
+    const int nx = NX(model), nu = NU(model);
     const double* v = cfg->q;
     for (int i = 0; i < 58; ++i)
         if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NaN in the record");
@@ -1841,100 +1699,63 @@ static int mppi_prepare(brov_ctx* c, int model, int integ, int lag_mode, int64_t
     }
     if (ref_total == 1 ? ref_row0 != 0 : (ref_total < 1 || ref_row0 < 0 || H >= ref_total || ref_row0 > ref_total - 1 - H))
         return fail(c, BROV_ERR_ARG, "brov_mppi_step: the reference window ref_row0 .. ref_row0 + H must lie inside ref_total (a set-point: ref_total = 1, ref_row0 = 0)");
-    *M = (H + cfg->hold - 1) / cfg->hold;
+    const int64_t M = (H + cfg->hold - 1) / cfg->hold;      // knots
+    std::vector<FastParams> fp;
     std::vector<double> phi;
-    return derive_candidates(c, integ, (int)nparams, params, 0, dt, false, fp, phi);
-}
-// one upload of FastParams[nparams] and the record, two launches.  d_cost may be nullptr (arena scratch then).
-static int mppi_impl(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, const std::vector<FastParams>& fp, const brov_mppi* cfg,
-                     MppiArgs args, Arena& a) {
-    const size_t np = fp.size();
-    const int nu = NU(model);
-    char* blob = a.take<char>(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec));
-    args.U_old = a.take<double>((size_t)B * args.M * nu);
-    if (!args.cost) args.cost = a.take<double>((size_t)B * args.K);
-    std::vector<char> host(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec));
-    memcpy(host.data(), fp.data(), np * sizeof(FastParams));
-    memcpy(host.data() + Arena::al(np * sizeof(FastParams)), cfg, sizeof(MppiRec));
-    HIPCK(c, h2d_copy(c, blob, host.data(), host.size()));
-    HIPCK(c, hipStreamSynchronize(c->stream));   // host is a local
-    args.fp = reinterpret_cast<const FastParams*>(blob);
-    args.rec = reinterpret_cast<const MppiRec*>(blob + Arena::al(np * sizeof(FastParams)));
+    rc = derive_candidates(c, integ, (int)nparams, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const size_t np = fp.size(), n_U = (size_t)B * M * nu, n_cost = (size_t)B * K;
+    MppiArgs args{};
+    args.shift = shift != 0;
     args.per_problem = np > 1;
-    CallTimer t(c);
-    HIPCK(c, launch_mppi_step(c->stream, model, integ, lag_mode, B, args));
-    return BROV_OK;
-}
-static size_t mppi_scratch(int64_t B, size_t np, int64_t K, int64_t M, int nu, bool own_cost) {
-    return Arena::al(Arena::al(np * sizeof(FastParams)) + sizeof(MppiRec)) + Arena::al((size_t)B * M * nu * 8) +
-           (own_cost ? Arena::al((size_t)B * K * 8) : 0);
+    args.K = K; args.H = H; args.M = M; args.ref_total = ref_total; args.ref_row0 = ref_row0; args.dt = dt; args.seed = seed;
+    FastParams* d_fp;
+    MppiRec* d_rec;
+    Arena a(c, host);
+    rc = a.lay("brov_mppi_step", [&] {
+        args.x = a.in(x, (size_t)B * nx);
+        args.lag = lag && model == BROV_THRUSTER_EULER ? a.in(lag, (size_t)B * 24) : nullptr;
+        args.ref = a.in(ref, (size_t)B * ref_total * nx);
+        args.eps = eps ? a.in(eps, n_cost * M * nu) : nullptr;
+        args.U_nom = a.inout(U_nom, n_U);
+        args.u_apply = u_apply ? a.out(u_apply, (size_t)B * cfg->hold * nu) : nullptr;
+        args.cost = host || cost ? a.out(cost, n_cost) : a.take<double>(n_cost);     // the kernels need it: scratch when the caller has none
+        args.info = info ? a.out(info, (size_t)B * 4) : nullptr;
+        d_fp = a.take<FastParams>(np);                                                // [FastParams[np] | record]: one upload
+        d_rec = a.take<MppiRec>(1);
+        args.U_old = a.take<double>(n_U);
+    });
+    if (rc) return rc;
+    const size_t rec_at = reinterpret_cast<char*>(d_rec) - reinterpret_cast<char*>(d_fp);
+    std::vector<char> blob(rec_at + sizeof(MppiRec));
+    memcpy(blob.data(), fp.data(), np * sizeof(FastParams));
+    memcpy(blob.data() + rec_at, cfg, sizeof(MppiRec));
+    HIPCK(c, h2d_copy(c, d_fp, blob.data(), blob.size()));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // blob is a local
+    args.fp = d_fp;
+    args.rec = d_rec;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_mppi_step(c->stream, model, integ, lag_mode, B, args));
+    }
+    return a.finish();
 }
 
 int brov_mppi_step_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
                        const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* d_x, const double* d_lag,
                        const double* d_ref, int64_t ref_total, int64_t ref_row0, const double* d_eps, double* d_U_nom, int shift,
                        double* d_u_apply, double* d_cost, double* d_info) {
-    std::vector<FastParams> fp;
-    int64_t M = 0;
-    int rc = mppi_prepare(c, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, d_x, d_ref, ref_total, ref_row0, d_U_nom, fp, &M);
-    if (rc) return rc;
-    if (B == 0) return BROV_OK;
-    DeviceGuard g(c);
-    Arena a(c);
-    rc = a.reserve(mppi_scratch(B, fp.size(), K, M, NU(model), !d_cost));
-    if (rc) return rc;
-    MppiArgs args{};
-    args.shift = shift != 0;
-    args.K = K; args.H = H; args.M = M; args.ref_total = ref_total; args.ref_row0 = ref_row0; args.dt = dt; args.seed = seed;
-    args.x = d_x; args.lag = model == BROV_THRUSTER_EULER ? d_lag : nullptr; args.ref = d_ref; args.eps = d_eps;
-    args.U_nom = d_U_nom; args.u_apply = d_u_apply; args.cost = d_cost; args.info = d_info;
-    return mppi_impl(c, model, integ, lag_mode, B, fp, cfg, args, a);
+    return mppi_step(c, false, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, seed, d_x, d_lag, d_ref, ref_total, ref_row0, d_eps,
+                     d_U_nom, shift, d_u_apply, d_cost, d_info);
 }
 
 int brov_mppi_step(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
                    const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* x, const double* lag,
                    const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps, double* U_nom, int shift, double* u_apply,
                    double* cost, double* info) {
-    std::vector<FastParams> fp;
-    int64_t M = 0;
-    int rc = mppi_prepare(c, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, x, ref, ref_total, ref_row0, U_nom, fp, &M);
-    if (rc) return rc;
-    if (B == 0) return BROV_OK;
-    DeviceGuard g(c);
-    const int nx = NX(model), nu = NU(model);
-    const bool has_lag = lag && model == BROV_THRUSTER_EULER;
-    const size_t n_x = (size_t)B * nx, n_ref = (size_t)B * ref_total * nx, n_eps = eps ? (size_t)B * K * M * nu : 0, n_U = (size_t)B * M * nu;
-    const size_t n_ua = u_apply ? (size_t)B * cfg->hold * nu : 0, n_cost = (size_t)B * K;
-    Arena a(c);
-    rc = a.reserve(Arena::al(n_x * 8) + (has_lag ? Arena::al((size_t)B * 24 * 8) : 0) + Arena::al(n_ref * 8) + Arena::al(n_eps * 8) + Arena::al(n_U * 8) +
-                   Arena::al(n_ua * 8) + Arena::al(n_cost * 8) + Arena::al((size_t)B * 4 * 8) + mppi_scratch(B, fp.size(), K, M, nu, false));
-    if (rc) return rc;
-    double* dx = a.take<double>(n_x);
-    double* dl = has_lag ? a.take<double>((size_t)B * 24) : nullptr;
-    double* dref = a.take<double>(n_ref);
-    double* deps = eps ? a.take<double>(n_eps) : nullptr;
-    double* dU = a.take<double>(n_U);
-    double* dua = u_apply ? a.take<double>(n_ua) : nullptr;
-    double* dcost = a.take<double>(n_cost);
-    double* dinfo = info ? a.take<double>((size_t)B * 4) : nullptr;
-    HIPCK(c, h2d_copy(c, dx, x, n_x * 8));
-    if (has_lag) HIPCK(c, h2d_copy(c, dl, lag, (size_t)B * 24 * 8));
-    HIPCK(c, h2d_copy(c, dref, ref, n_ref * 8));
-    if (n_eps) HIPCK(c, h2d_copy(c, deps, eps, n_eps * 8));
-    HIPCK(c, h2d_copy(c, dU, U_nom, n_U * 8));
-    MppiArgs args{};
-    args.shift = shift != 0;
-    args.K = K; args.H = H; args.M = M; args.ref_total = ref_total; args.ref_row0 = ref_row0; args.dt = dt; args.seed = seed;
-    args.x = dx; args.lag = dl; args.ref = dref; args.eps = deps;
-    args.U_nom = dU; args.u_apply = dua; args.cost = dcost; args.info = dinfo;
-    rc = mppi_impl(c, model, integ, lag_mode, B, fp, cfg, args, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, U_nom, dU, n_U * 8));
-    if (n_ua) HIPCK(c, d2h_copy(c, u_apply, dua, n_ua * 8));
-    if (cost) HIPCK(c, d2h_copy(c, cost, dcost, n_cost * 8));
-    if (info) HIPCK(c, d2h_copy(c, info, dinfo, (size_t)B * 4 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return mppi_step(c, true, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, seed, x, lag, ref, ref_total, ref_row0, eps, U_nom,
+                     shift, u_apply, cost, info);
 }
 
 int brov_ensemble_stats_dev(brov_ctx* c, int64_t P, int64_t M, const double* d_vals, double* d_out) {
@@ -1997,100 +1818,81 @@ int brov_pinc_rollout(brov_ctx* c, int64_t B, int64_t T, double dt, const double
     if (rc || B == 0) return rc;
     DeviceGuard g(c);
     const int64_t rows = traj ? T / stride + 1 : 0;
-    Arena a(c);
-    rc = a.reserve(Arena::al(B * 12 * 8) * 2 + Arena::al((size_t)B * T * 8 * 8) + Arena::al(B * 24 * 8) + Arena::al((size_t)B * rows * 12 * 8));
+    Arena a(c, true);
+    double *dx0, *dU, *dxT, *dl, *dtr;
+    rc = a.lay("brov_pinc_rollout", [&] {
+        dx0 = a.in(x0, B * 12);
+        dU = a.in(U, (size_t)B * T * 8);
+        dxT = a.out(xT, B * 12);
+        dl = lag_io ? a.inout(lag_io, B * 24) : nullptr;
+        dtr = traj ? a.out(traj, (size_t)B * rows * 12) : nullptr;
+    });
     if (rc) return rc;
-    double* dx0 = a.take<double>(B * 12);
-    double* dU = a.take<double>((size_t)B * T * 8);
-    double* dxT = a.take<double>(B * 12);
-    double* dl = lag_io ? a.take<double>(B * 24) : nullptr;
-    double* dtr = traj ? a.take<double>((size_t)B * rows * 12) : nullptr;
-    HIPCK(c, h2d_copy(c, dx0, x0, B * 12 * 8));
-    if (T) HIPCK(c, h2d_copy(c, dU, U, (size_t)B * T * 8 * 8));
-    if (lag_io) HIPCK(c, h2d_copy(c, dl, lag_io, B * 24 * 8));
     rc = brov_pinc_rollout_dev(c, B, T, dt, dx0, dU, dl, dtr, stride, dxT);
     if (rc) return rc;
-    if (xT) HIPCK(c, d2h_copy(c, xT, dxT, B * 12 * 8));
-    if (lag_io) HIPCK(c, d2h_copy(c, lag_io, dl, B * 24 * 8));
-    if (traj) HIPCK(c, d2h_copy(c, traj, dtr, (size_t)B * rows * 12 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
-static size_t pinc_window_scratch(int64_t nwin) {
-    return Arena::al(nwin * 24 * 8) + Arena::al(window_chunks(nwin) * 24 * 8) + Arena::al(18 * 8);
-}
-
-static int pinc_window_impl(brov_ctx* c, int64_t N, int64_t H, double dt, const double* dX, const double* dU, int carry,
-                            double* d_lag_io, double* d_lag_starts, double* d_total, double* d_se, Arena& a) {
-    const DevParams* dp;
-    int rc = get_dp(c, dt, &dp);
+// host: the arrays are the caller's host memory (`who` names the form)
+static int pinc_window(brov_ctx* c, bool host, const char* who, int64_t N, int64_t H, double dt, const double* X, const double* U, int carry,
+                       double* lag_io, double* se_total, double* per_window, double* lag_starts) {
+    if (!c || N < 0 || H < 0 || !se_total) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument");
+    int rc = pinc_ready(c, who);
     if (rc) return rc;
     const int64_t nwin = N - H;
-    double *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    if (nwin <= 0) {
+        if (host) { *se_total = 0.0; return BROV_OK; }
+        DeviceGuard g(c);
+        HIPCK(c, hipMemsetAsync(se_total, 0, 8, c->stream));
+        return BROV_OK;
+    }
+    if (!X || !U || (!host && !per_window)) return fail(c, BROV_ERR_ARG, std::string(who) + ": NULL array");
+    DeviceGuard g(c);
+    const int64_t nu_rows = H > 0 ? N - 1 : 0;             // window k reads U[k .. k+H-1]: the caller's U may end at row N-2
+    const double *dX, *dU;
+    double *d_total, *d_se, *d_lag_io, *d_starts, *d_lag = nullptr, *d_chunk = nullptr, *d_phi = nullptr;
+    Arena a(c, host);
+    rc = a.lay(who, [&] {
+        dX = a.in(X, N * 12);
+        dU = a.in(U, nu_rows * 8);
+        d_total = a.out(se_total, 1);
+        d_se = a.out(per_window, nwin);
+        d_lag_io = carry ? a.inout(lag_io, 24) : a.in(lag_io, 24);
+        d_starts = lag_starts && carry ? a.out(lag_starts, nwin * 24) : nullptr;
+        if (carry) {
+            d_lag = a.take<double>(nwin * 24);                    // responses, then start states
+            d_chunk = a.take<double>(window_chunks(nwin) * 24);
+            d_phi = a.take<double>(18);
+        }
+    });
+    if (rc) return rc;
+    if (host && !lag_io) HIPCK(c, hipMemsetAsync(d_lag_io, 0, 24 * 8, c->stream));   // no lag given: the vehicle starts at rest
+    const DevParams* dp;
+    rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
     if (carry) {
-        d_lag = a.take<double>(nwin * 24);                    // responses, then start states
-        d_chunk = a.take<double>(window_chunks(nwin) * 24);
-        d_phi = a.take<double>(18);
         double Phi[18];                                       // Phi = Ad^H (one lag sample per step), Phi^chunk
         lag_window_phi_pair(*dp, H, Phi);
         HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
         HIPCK(c, hipStreamSynchronize(c->stream));            // Phi is a stack temporary
     }
-    CallTimer t(c);
-    HIPCK(c, launch_pinc_window_endpoint(c->stream, c->d_pinc, *dp, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_lag_io,
-                                         d_lag_starts, d_se, d_total));
-    return BROV_OK;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_pinc_window_endpoint(c->stream, c->d_pinc, *dp, N, H, dt, dX, dU, carry, d_phi, d_lag, d_chunk, d_lag_io, d_starts,
+                                             d_se, d_total));
+    }
+    return a.finish();
 }
 
 int brov_pinc_window_endpoint_se_dev(brov_ctx* c, int64_t N, int64_t H, double dt, const double* d_X, const double* d_U, int carry_lag,
                                      double* d_lag_io, double* d_se_total, double* d_per_window, double* d_lag_starts) {
-    if (!c || N < 0 || H < 0 || !d_se_total) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se_dev: bad argument");
-    int rc = pinc_ready(c, "brov_pinc_window_endpoint_se_dev");
-    if (rc) return rc;
-    DeviceGuard g(c);
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { HIPCK(c, hipMemsetAsync(d_se_total, 0, 8, c->stream)); return BROV_OK; }
-    if (!d_X || !d_U || !d_per_window) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se_dev: NULL array");
-    Arena a(c);
-    rc = a.reserve(pinc_window_scratch(nwin));
-    if (rc) return rc;
-    return pinc_window_impl(c, N, H, dt, d_X, d_U, carry_lag, d_lag_io, d_lag_starts, d_se_total, d_per_window, a);
+    return pinc_window(c, false, "brov_pinc_window_endpoint_se_dev", N, H, dt, d_X, d_U, carry_lag, d_lag_io, d_se_total, d_per_window,
+                       d_lag_starts);
 }
 
 int brov_pinc_window_endpoint_se(brov_ctx* c, int64_t N, int64_t H, double dt, const double* X, const double* U, int carry_lag,
                                  double* lag_io, double* se_total, double* per_window, double* lag_starts) {
-    if (!c || N < 0 || H < 0 || !se_total) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se: bad argument");
-    int rc = pinc_ready(c, "brov_pinc_window_endpoint_se");
-    if (rc) return rc;
-    const int64_t nwin = N - H;
-    if (nwin <= 0) { *se_total = 0.0; return BROV_OK; }
-    if (!X || !U) return fail(c, BROV_ERR_ARG, "brov_pinc_window_endpoint_se: NULL array");
-    DeviceGuard g(c);
-    const bool starts = lag_starts && carry_lag;
-    const int64_t nu_rows = H > 0 ? N - 1 : 0;             // window k reads U[k .. k+H-1]: the caller's U may end at row N-2
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * 12 * 8) + Arena::al(nu_rows * 8 * 8) + Arena::al(nwin * 8) + Arena::al(8 * 8) + Arena::al(24 * 8) +
-                   (starts ? Arena::al(nwin * 24 * 8) : 0) + pinc_window_scratch(nwin));
-    if (rc) return rc;
-    double* dX = a.take<double>(N * 12);
-    double* dU = a.take<double>(nu_rows * 8);
-    double* dse = a.take<double>(nwin);
-    double* dtot = a.take<double>(8);
-    double* dlag = a.take<double>(24);
-    double* dstarts = starts ? a.take<double>(nwin * 24) : nullptr;
-    HIPCK(c, h2d_copy(c, dX, X, N * 12 * 8));
-    if (nu_rows) HIPCK(c, h2d_copy(c, dU, U, nu_rows * 8 * 8));
-    if (lag_io) HIPCK(c, h2d_copy(c, dlag, lag_io, 24 * 8));
-    else HIPCK(c, hipMemsetAsync(dlag, 0, 24 * 8, c->stream));
-    rc = pinc_window_impl(c, N, H, dt, dX, dU, carry_lag, dlag, dstarts, dtot, dse, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, se_total, dtot, 8));
-    if (per_window) HIPCK(c, d2h_copy(c, per_window, dse, nwin * 8));
-    if (lag_io && carry_lag) HIPCK(c, d2h_copy(c, lag_io, dlag, 24 * 8));
-    if (starts) HIPCK(c, d2h_copy(c, lag_starts, dstarts, nwin * 24 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return pinc_window(c, true, "brov_pinc_window_endpoint_se", N, H, dt, X, U, carry_lag, lag_io, se_total, per_window, lag_starts);
 }
 
 // ---- PINc training -----------------------------------------------------------------------------------------
@@ -2213,54 +2015,43 @@ int brov_pinc_train_end(brov_ctx* c) {
     return BROV_OK;
 }
 
-static size_t stream_scratch(int64_t N) {
-    return Arena::al(N * 24 * 8) + Arena::al(window_chunks(N) * 24 * 8) + Arena::al(18 * 8);
-}
-
-static int thruster_stream_impl(brov_ctx* c, int64_t N, const double* dU, double dt, double* d_lag_io, double* d_tau, Arena& a) {
-    const DevParams* dp;
-    int rc = get_dp(c, dt, &dp);
+// host: the arrays are the caller's host memory (`who` names the form)
+static int thruster_stream(brov_ctx* c, bool host, const char* who, int64_t N, const double* U, double dt, double* lag_io, double* tau) {
+    if (!c || N < 0 || (N && (!U || !lag_io || !tau))) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument");
+    if (N == 0) return BROV_OK;
+    DeviceGuard g(c);
+    const double* dU;
+    double *d_tau, *d_lag_io, *d_lag, *d_chunk, *d_phi;
+    Arena a(c, host);
+    int rc = a.lay(who, [&] {
+        dU = a.in(U, N * 8);
+        d_tau = a.out(tau, N * 6);
+        d_lag_io = a.inout(lag_io, 24);
+        d_lag = a.take<double>(N * 24);                       // responses, then start states
+        d_chunk = a.take<double>(window_chunks(N) * 24);
+        d_phi = a.take<double>(18);
+    });
     if (rc) return rc;
-    double* d_lag = a.take<double>(N * 24);                   // responses, then start states
-    double* d_chunk = a.take<double>(window_chunks(N) * 24);
-    double* d_phi = a.take<double>(18);
+    const DevParams* dp;
+    rc = get_dp(c, dt, &dp);
+    if (rc) return rc;
     double Phi[18];                                           // Ad (one lag sample per row), Ad^chunk
     lag_window_phi_pair(*dp, 1, Phi);
     HIPCK(c, h2d_copy(c, d_phi, Phi, sizeof Phi));
     HIPCK(c, hipStreamSynchronize(c->stream));                // Phi is a stack temporary
-    CallTimer t(c);
-    HIPCK(c, launch_thruster_stream(c->stream, *dp, N, dU, d_phi, d_lag, d_chunk, d_lag_io, d_tau));
-    return BROV_OK;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_thruster_stream(c->stream, *dp, N, dU, d_phi, d_lag, d_chunk, d_lag_io, d_tau));
+    }
+    return a.finish();
 }
 
 int brov_thruster_stream_dev(brov_ctx* c, int64_t N, const double* d_U, double dt, double* d_lag_io, double* d_tau) {
-    if (!c || N < 0 || (N && (!d_U || !d_lag_io || !d_tau))) return fail(c, BROV_ERR_ARG, "brov_thruster_stream_dev: bad argument");
-    if (N == 0) return BROV_OK;
-    DeviceGuard g(c);
-    Arena a(c);
-    int rc = a.reserve(stream_scratch(N));
-    if (rc) return rc;
-    return thruster_stream_impl(c, N, d_U, dt, d_lag_io, d_tau, a);
+    return thruster_stream(c, false, "brov_thruster_stream_dev", N, d_U, dt, d_lag_io, d_tau);
 }
 
 int brov_thruster_stream(brov_ctx* c, int64_t N, const double* U, double dt, double* lag_io, double* tau) {
-    if (!c || N < 0 || (N && (!U || !lag_io || !tau))) return fail(c, BROV_ERR_ARG, "brov_thruster_stream: bad argument");
-    if (N == 0) return BROV_OK;
-    DeviceGuard g(c);
-    Arena a(c);
-    int rc = a.reserve(Arena::al(N * 8 * 8) + Arena::al(N * 6 * 8) + Arena::al(24 * 8) + stream_scratch(N));
-    if (rc) return rc;
-    double* dU = a.take<double>(N * 8);
-    double* dtau = a.take<double>(N * 6);
-    double* dlag = a.take<double>(24);
-    HIPCK(c, h2d_copy(c, dU, U, N * 8 * 8));
-    HIPCK(c, h2d_copy(c, dlag, lag_io, 24 * 8));
-    rc = thruster_stream_impl(c, N, dU, dt, dlag, dtau, a);
-    if (rc) return rc;
-    HIPCK(c, d2h_copy(c, tau, dtau, N * 6 * 8));
-    HIPCK(c, d2h_copy(c, lag_io, dlag, 24 * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return thruster_stream(c, true, "brov_thruster_stream", N, U, dt, lag_io, tau);
 }
 
 // ---- synthetic controls -------------------------------------------------------------------------------

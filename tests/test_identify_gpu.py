@@ -298,11 +298,17 @@ def test_argument_rules(eng, ctx):
     call = lambda model, P: lib.brov_window_endpoint_pop_dev(h, model, 0, P, pa, 30, 5, 0.02, Xd.ptr, Ud.ptr, 1, d_se.ptr, None)
     assert call(THR, 2) == 0
     for di in (_lib.DI_THRUSTER_EULER, _lib.DI_WRENCH_EULER, _lib.DI_WRENCH_QUAT):
-        assert call(di, 2) == -1                                            # gains are not brov_params
-    assert call(THR, 0) == -1 and b"bad argument" in lib.brov_last_error(h)
+        assert call(di, 2) == -1 and b"brov_window_endpoint_pop_dev: bad argument" in lib.brov_last_error(h)     # gains are not brov_params
+    assert call(THR, 0) == -1 and b"brov_window_endpoint_pop_dev: bad argument" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_pop_dev(h, THR, 0, 2, pa, 30, 5, 0.02, None, Ud.ptr, 1, d_se.ptr, None) == -1
+    assert b"brov_window_endpoint_pop_dev: NULL array" in lib.brov_last_error(h)
     se_h = np.zeros(2)
     assert lib.brov_window_endpoint_pop(h, _lib.DI_THRUSTER_EULER, 0, 2, pa, 30, 5, 0.02, X.ctypes.data, U.ctypes.data, 1, se_h.ctypes.data, None) == -1
+    assert b"brov_window_endpoint_pop: bad argument" in lib.brov_last_error(h)
     assert lib.brov_window_endpoint_pop(h, THR, 0, 0, pa, 30, 5, 0.02, X.ctypes.data, U.ctypes.data, 1, se_h.ctypes.data, None) == -1
+    assert b"brov_window_endpoint_pop: bad argument" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_pop(h, THR, 0, 2, pa, 30, 5, 0.02, X.ctypes.data, None, 1, se_h.ctypes.data, None) == -1
+    assert b"brov_window_endpoint_pop: NULL array" in lib.brov_last_error(h)
     # the host form gives what the device form gives
     assert lib.brov_window_endpoint_pop(h, THR, 0, 2, pa, 30, 5, 0.02, X.ctypes.data, U.ctypes.data, 1, se_h.ctypes.data, None) == 0
     assert se_h.tobytes() == d_se.numpy().tobytes() and se_h[0] > 0

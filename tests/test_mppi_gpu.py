@@ -384,6 +384,22 @@ def test_host_form_equals_device_form(eng, ctx):
     r = _run(eng, ctx, 0, "rk4", shift=True)
     for got, k in ((Un, "U_nom"), (ua, "u_apply"), (cost, "cost"), (info, "info")):
         assert got.tobytes() == r[k].tobytes(), k
+    # eps = NULL (the seeded stream), and u_apply, cost and info each NULL in turn: a fresh context, whose first call grows the
+    # arena and whose second reuses it; what the host form returns is still the bytes of the device form
+    seeded = _run(eng, ctx, 0, "rk4", shift=True, seed=77)
+    fresh = _lib.Context(0)
+    try:
+        for drop in (None, "u_apply", "cost", "info"):
+            for _ in range(2):
+                out = dict(U_nom=U.copy(), u_apply=np.full((B, HOLD, 8), -7.25), cost=np.full((B, K), -7.25), info=np.full((B, 4), -7.25))
+                ptr = {k: (None if k == drop else v.ctypes.data) for k, v in out.items()}
+                rc = fresh.lib.brov_mppi_step(fresh.h, 0, _lib.RK4, 0, B, B, pa, ctypes.byref(s), K, H, DT, 77, X.ctypes.data, lag.ctypes.data,
+                                              REF.ctypes.data, REF_TOTAL, ROW0, None, ptr["U_nom"], 1, ptr["u_apply"], ptr["cost"], ptr["info"])
+                assert rc == 0, fresh.lib.brov_last_error(fresh.h)
+                for k, got in out.items():
+                    assert np.all(got == -7.25) if k == drop else got.tobytes() == seeded[k].tobytes(), (drop, k)
+    finally:
+        fresh.close()
 
 
 def test_device_to_device_copy(ctx):

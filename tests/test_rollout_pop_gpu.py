@@ -222,14 +222,16 @@ def test_refused_arguments(eng, ctx):
     x0, u = X0[:1], U[:1]
     singular = fv.params("V0")
     singular.m = singular.added_mass[0]
-    cases = [("a double-integrator model", dict(model=_lib.DI_THRUSTER_EULER, params=_params(("V0",)))),
-             ("P = 65536", dict(params=[fv.params("V0")] * 65536)),
-             ("a singular mass matrix", dict(params=[fv.params("V0"), singular])),
-             ("stride = 0 with traj", dict(params=_params(("V0",)), stride=0))]
-    for what, kw in cases:
+    cases = [("a double-integrator model", dict(model=_lib.DI_THRUSTER_EULER, params=_params(("V0",))),
+              "brov_rollout_pop: the double-integrator gains are not brov_params"),
+             ("P = 65536", dict(params=[fv.params("V0")] * 65536), "brov_rollout_pop: P must be <= 65535"),
+             ("a singular mass matrix", dict(params=[fv.params("V0"), singular]), "candidate 1: singular mass matrix"),
+             ("stride = 0 with traj", dict(params=_params(("V0",)), stride=0), "brov_rollout_pop: traj_stride must be >= 1")]
+    for what, kw, text in cases:
         with pytest.raises(_lib.BrovError, match=r"BROV_ERR_ARG: \S") as ei:
             eng.rollout_pop(kw.get("model", 0), "rk4", kw["params"], x0, u, DT, stride=kw.get("stride", 1), ctx=ctx)
         print(what, "->", ei.value)
+        assert text in str(ei.value), (what, ei.value)
     r = eng.rollout_pop(0, "rk4", [], x0, u, DT, ctx=ctx)              # P = 0: nothing to do
     assert r["xT"].shape == (0, 1, 12)
 

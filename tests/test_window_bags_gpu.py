@@ -263,9 +263,19 @@ def test_argument_rules(eng, ctx):
     d_tot, d_per = eng.DevArray(ctx, (1,)), eng.DevArray(ctx, (20,))
     off2 = np.array([0, 12, 30], dtype=np.int64)
     se_dev = lambda off, nb: lib.brov_window_endpoint_se_ragged_dev(h, THR, 0, nb, off.ctypes.data, 5, DT, Xd.ptr, Ud.ptr, 1, d_tot.ptr, d_per.ptr)
-    assert se_dev(off2 + 1, 2) == -1 and se_dev(off2[::-1].copy(), 2) == -1 and se_dev(off2, -1) == -1 and se_dev(off2, 2) == 0
+    assert se_dev(off2 + 1, 2) == -1 and b"brov_window_endpoint_se_ragged_dev: bag_offsets[0] must be 0" in lib.brov_last_error(h)
+    assert se_dev(off2[::-1].copy(), 2) == -1 and b"brov_window_endpoint_se_ragged_dev: bag_offsets[0] must be 0" in lib.brov_last_error(h)
+    assert se_dev(np.array([0, 30, 12], dtype=np.int64), 2) == -1
+    assert b"brov_window_endpoint_se_ragged_dev: bag_offsets must not decrease" in lib.brov_last_error(h)
+    assert se_dev(off2, -1) == -1 and b"brov_window_endpoint_se_ragged_dev: bad bag list" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_se_ragged_dev(h, THR, 0, 2, off2.ctypes.data, 5, DT, Xd.ptr, Ud.ptr, 1, d_tot.ptr, None) == -1
+    assert b"brov_window_endpoint_se_ragged_dev: NULL array" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_se_ragged_dev(h, THR, 0, 2, off2.ctypes.data, 5, DT, Xd.ptr, Ud.ptr, 1, None, d_per.ptr) == -1
+    assert b"brov_window_endpoint_se_ragged_dev: bad argument" in lib.brov_last_error(h)
+    assert se_dev(off2, 2) == 0
     for di in (_lib.DI_THRUSTER_EULER, _lib.DI_WRENCH_EULER, _lib.DI_WRENCH_QUAT):
         assert call([0, 12, 30], model=di) == -1                              # gains are not brov_params
+        assert b"brov_window_endpoint_pop_ragged_dev: bad argument" in lib.brov_last_error(h)
     # W = 0: se = 0, nothing else written; NaN from the engine
     d_se.copy_from_host(np.array([7.0, 7.0]))
     assert call([0, 5, 5, 9], H=5) == 0 and d_se.numpy().tolist() == [0.0, 0.0]
@@ -283,6 +293,13 @@ def test_argument_rules(eng, ctx):
     assert np.float64(tot.value).tobytes() == d_tot.numpy()[0].tobytes() and tot.value > 0
     assert lib.brov_window_endpoint_pop_ragged(h, THR, 0, 2, pa, 2, (off + 1).ctypes.data, 5, DT, X.ctypes.data, U.ctypes.data, 1, se_h.ctypes.data,
                                                None, None) == -1
+    assert b"brov_window_endpoint_pop_ragged: bag_offsets[0] must be 0" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_pop_ragged(h, THR, 0, 2, pa, 2, off.ctypes.data, 5, DT, None, U.ctypes.data, 1, se_h.ctypes.data, None, None) == -1
+    assert b"brov_window_endpoint_pop_ragged: NULL array" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_se_ragged(h, THR, 0, 2, off.ctypes.data, 5, DT, X.ctypes.data, None, 1, ctypes.addressof(tot), None) == -1
+    assert b"brov_window_endpoint_se_ragged: NULL array" in lib.brov_last_error(h)
+    assert lib.brov_window_endpoint_se_ragged(h, THR, 2, 2, off.ctypes.data, 5, DT, X.ctypes.data, U.ctypes.data, 1, ctypes.addressof(tot), None) == -1
+    assert b"brov_window_endpoint_se_ragged: bad argument" in lib.brov_last_error(h)
     # the engine's forms of the same: window_pop / window_rmse over bags, and the target alone
     rm = eng.window_pop(THR, "euler", [_lib.default_params()] * 2, X, U, 5, DT, ctx=ctx, bag_offsets=off)
     assert np.allclose(rm, np.sqrt(good / (20 * 12)), rtol=1e-15, atol=0)
