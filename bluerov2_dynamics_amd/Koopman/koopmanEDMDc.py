@@ -186,6 +186,15 @@ class KoopmanEDMDc:
         U_seq = np.asarray(U_seq, dtype=float).reshape(-1, self.input_dim)
         return engine.simulate_lifted(x0[None], U_seq[None], self.centers_, self.gamma, self.A_, self.B_)[0]
 
+    def mppi_planner(self, H, hold=1, ctx=None):
+        """The fitted model made ready for model-predictive control over a horizon of H steps with `hold` steps per knot
+        (engine.KoopmanPlanner): centres, A, B and the coefficients of the linear-in-the-command predictor are uploaded once.  The
+        model is taken to be fitted at the planning step (one row of the recording per step).  planner.step(cfg, x, ref, U_nom, dt,
+        K) is one update (engine.koopman_mppi_step); VehicleBase.simulate_mppi(..., planner=planner) plans every tick with it."""
+        if self.A_ is None or self.B_ is None or self.centers_ is None:
+            raise ValueError("fit the model first: mppi_planner needs centers_, A_ and B_")
+        return engine.KoopmanPlanner(self.centers_, self.gamma, self.A_, self.B_, H, hold, ctx=ctx)
+
     # ------------------------------------------------------------------ persistence (new: the reference never stores it)
     def save(self, path) -> None:
         np.savez(path, state_dim=self.state_dim, input_dim=self.input_dim, n_rbfs=self.n_rbfs, gamma=self.gamma, ridge=self.ridge,

@@ -170,6 +170,13 @@ SIGNATURES = {
     "brov_mppi_step_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.POINTER(BrovParams),
                                           ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p,
                                           c_void_p, i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "edmdc_mppi_step": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, i64, ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p,
+                                       i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "edmdc_mppi_step_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, i64, ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64,
+                                           c_void_p, c_void_p, i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

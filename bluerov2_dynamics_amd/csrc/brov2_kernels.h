@@ -67,6 +67,23 @@ struct MppiArgs {
     double *U_nom, *U_old, *u_apply, *cost, *info;
 };
 hipError_t launch_mppi_step(hipStream_t st, int model, int integ, int lag_mode, int64_t B, const MppiArgs& a);
+// the second launch alone (nu = 6 or 8): reads rec, K, M, shift, seed, eps, cost, U_old; writes U_nom, u_apply, info
+hipError_t launch_mppi_update(hipStream_t st, int nu, int64_t B, const MppiArgs& a);
+// The same update with an EDMDc model as the planning model (koopman_mppi.hip; include/brov2.h: edmdc_mppi_step holds the law).
+// m: as above, without fp, per_problem and lag; x [B][n], ref [B][ref_total][n].  C [k][n]; P [H+1][n][n+k] and Gc [H+1][M][n][r] are
+// the coefficients of the linear form; F [B][H+1][n] is scratch (the free response), pred [B][K][H+1][n] or nullptr.  n in {12, 13},
+// r in {6, 8}, 0 <= k <= KOOPMAN_MPPI_MAX_K, M r <= KOOPMAN_MPPI_MAX_MNU.  Three launches, whatever B, K and H are.
+constexpr int KOOPMAN_MPPI_MAX_K = 1024;          // the lift of one state lives in LDS
+constexpr int KOOPMAN_MPPI_MAX_MNU = 312;         // a sample's commands live in LDS: 64 lanes x 312 doubles = 156 KB of the 160 KB
+struct KoopmanMppiArgs {
+    MppiArgs m;
+    int n, r, k;
+    double gamma;
+    const double *C, *P, *Gc;
+    double *F, *pred;
+};
+int koopman_mppi_block(int64_t K, int64_t mnu);   // lanes per block of the cost kernel: 256, 128 or 64 as the LDS allows (0: does not fit)
+hipError_t launch_koopman_mppi_step(hipStream_t st, int64_t B, const KoopmanMppiArgs& a);
 // vals [P][M] -> out [4][M]: mean, sample standard deviation, minimum, maximum over the P candidates; NaN where any is non-finite
 hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out);
 // The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major

@@ -182,7 +182,7 @@ struct Arena {
     size_t off = 0, limit = ~(size_t)0;     // limit: what lay() reserved
     bool bind = true, fits = true, listed = true;
     struct Copy { void* dev; void* host; size_t bytes; bool up, down; };
-    static constexpr int MAX_COPIES = 12;    // staged buffers of one call (brov_rollout_feedback has nine)
+    static constexpr int MAX_COPIES = 12;    // staged buffers of one call (edmdc_mppi_step has eleven)
     Copy copies[MAX_COPIES];
     int ncopies = 0;
     explicit Arena(brov_ctx* ctx, bool staged_ = false) : c(ctx), staged(staged_) {}
@@ -1668,6 +1668,33 @@ int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64
 
 // ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------
 static_assert(sizeof(brov_mppi) == sizeof(MppiRec) && sizeof(brov_mppi) == 59 * 8, "MppiRec is brov_mppi byte for byte");
+// What brov_mppi_step and edmdc_mppi_step (`who`) refuse of the sample count and the horizon ...
+static int mppi_sizes_ok(brov_ctx* c, const std::string& w, int64_t K, int64_t H) {
+    if (K < 1) return fail(c, BROV_ERR_ARG, w + ": K must be >= 1");
+    if (H < 1) return fail(c, BROV_ERR_ARG, w + ": H must be >= 1");
+    if (K > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, w + ": K must be <= 2^31");
+    if (H > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, w + ": H must be <= 2^31");
+    return BROV_OK;
+}
+// ... and of the record (channels < nu) and the reference window
+static int mppi_record_ok(brov_ctx* c, const std::string& w, const brov_mppi* cfg, int nu, int64_t H, int64_t ref_total, int64_t ref_row0) {
+    const double* v = cfg->q;
+    for (int i = 0; i < 58; ++i)
+        if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, w + ": NaN in the record");
+    if (cfg->hold < 1) return fail(c, BROV_ERR_ARG, w + ": hold must be >= 1");
+    if (!(cfg->lambda > 0.0)) return fail(c, BROV_ERR_ARG, w + ": lambda must be > 0");
+    if (cfg->gamma < 0.0) return fail(c, BROV_ERR_ARG, w + ": gamma must be >= 0");
+    for (int i = 0; i < 12; ++i)
+        if (cfg->q[i] < 0.0 || cfg->qf[i] < 0.0) return fail(c, BROV_ERR_ARG, w + ": the weights q and qf must be >= 0");
+    for (int i = 0; i < nu; ++i) {
+        if (cfg->r[i] < 0.0) return fail(c, BROV_ERR_ARG, w + ": the weights r must be >= 0");
+        if (cfg->sigma[i] < 0.0) return fail(c, BROV_ERR_ARG, w + ": sigma must be >= 0");
+        if (cfg->u_min[i] > cfg->u_max[i]) return fail(c, BROV_ERR_ARG, w + ": u_min must be <= u_max");
+    }
+    if (ref_total == 1 ? ref_row0 != 0 : (ref_total < 1 || ref_row0 < 0 || H >= ref_total || ref_row0 > ref_total - 1 - H))
+        return fail(c, BROV_ERR_ARG, w + ": the reference window ref_row0 .. ref_row0 + H must lie inside ref_total (a set-point: ref_total = 1, ref_row0 = 0)");
+    return BROV_OK;
+}
 // Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of
 // FastParams[nparams] and the record, two launches.  host: the arrays are the caller's host memory.
 static int mppi_step(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t B, int64_t nparams, const brov_params* params,
@@ -1677,28 +1704,13 @@ static int mppi_step(brov_ctx* c, bool host, int model, int integ, int lag_mode,
     bool empty;
     int rc = pop_call_ok(c, "brov_mppi_step", model, integ, lag_mode, 1, B, 0, 65535, &empty);
     if (rc || empty) return rc;
-    if (K < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be >= 1");
-    if (H < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be >= 1");
-    if (K > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: K must be <= 2^31");
-    if (H > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: H must be <= 2^31");
+    rc = mppi_sizes_ok(c, "brov_mppi_step", K, H);
+    if (rc) return rc;
     if (!params || !cfg || !x || !ref || !U_nom) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NULL input");
     if (nparams != 1 && nparams != B) return fail(c, BROV_ERR_ARG, "brov_mppi_step: nparams must be 1 or B");
     const int nx = NX(model), nu = NU(model);
-    const double* v = cfg->q;
-    for (int i = 0; i < 58; ++i)
-        if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, "brov_mppi_step: NaN in the record");
-    if (cfg->hold < 1) return fail(c, BROV_ERR_ARG, "brov_mppi_step: hold must be >= 1");
-    if (!(cfg->lambda > 0.0)) return fail(c, BROV_ERR_ARG, "brov_mppi_step: lambda must be > 0");
-    if (cfg->gamma < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: gamma must be >= 0");
-    for (int i = 0; i < 12; ++i)
-        if (cfg->q[i] < 0.0 || cfg->qf[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: the weights q and qf must be >= 0");
-    for (int i = 0; i < nu; ++i) {
-        if (cfg->r[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: the weights r must be >= 0");
-        if (cfg->sigma[i] < 0.0) return fail(c, BROV_ERR_ARG, "brov_mppi_step: sigma must be >= 0");
-        if (cfg->u_min[i] > cfg->u_max[i]) return fail(c, BROV_ERR_ARG, "brov_mppi_step: u_min must be <= u_max");
-    }
-    if (ref_total == 1 ? ref_row0 != 0 : (ref_total < 1 || ref_row0 < 0 || H >= ref_total || ref_row0 > ref_total - 1 - H))
-        return fail(c, BROV_ERR_ARG, "brov_mppi_step: the reference window ref_row0 .. ref_row0 + H must lie inside ref_total (a set-point: ref_total = 1, ref_row0 = 0)");
+    rc = mppi_record_ok(c, "brov_mppi_step", cfg, nu, H, ref_total, ref_row0);
+    if (rc) return rc;
     const int64_t M = (H + cfg->hold - 1) / cfg->hold;      // knots
     std::vector<FastParams> fp;
     std::vector<double> phi;
@@ -1756,6 +1768,87 @@ int brov_mppi_step(brov_ctx* c, int model, int integ, int lag_mode, int64_t B, i
                    double* cost, double* info) {
     return mppi_step(c, true, model, integ, lag_mode, B, nparams, params, cfg, K, H, dt, seed, x, lag, ref, ref_total, ref_row0, eps, U_nom,
                      shift, u_apply, cost, info);
+}
+
+// ---- the same update planned with an EDMDc model (koopman_mppi.hip) ---------------------------------------------------------------
+// Everything the host can refuse comes first.  Then one upload of the record, three launches.  A and B define the model whose
+// coefficients P and Gc are: they are required and not read.
+static int koopman_mppi_step(brov_ctx* c, bool host, int n, int r, int k, double gamma, const double* C, const double* A, const double* Bm,
+                             const double* P, const double* Gc, int64_t B, const brov_mppi* cfg, int64_t K, int64_t H, double dt,
+                             uint64_t seed, const double* x, const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps,
+                             double* U_nom, int shift, double* u_apply, double* cost, double* info, double* pred) {
+    const std::string w = "edmdc_mppi_step";
+    if (!c) return BROV_ERR_ARG;
+    if (n != 12 && n != 13) return fail(c, BROV_ERR_ARG, w + ": n must be 12 (Euler angles) or 13 (quaternion)");
+    if (r != 6 && r != 8) return fail(c, BROV_ERR_ARG, w + ": r must be 6 or 8");
+    if (k < 0) return fail(c, BROV_ERR_ARG, w + ": k must be >= 0");
+    if (k > KOOPMAN_MPPI_MAX_K) return fail(c, BROV_ERR_ARG, w + ": k must be <= " + std::to_string(KOOPMAN_MPPI_MAX_K));
+    if (B < 0) return fail(c, BROV_ERR_ARG, w + ": negative size");
+    if (B > 65535) return fail(c, BROV_ERR_ARG, w + ": B must be <= 65535");
+    if (B == 0) return BROV_OK;
+    int rc = mppi_sizes_ok(c, w, K, H);
+    if (rc) return rc;
+    if (!cfg || !x || !ref || !U_nom) return fail(c, BROV_ERR_ARG, w + ": NULL input");
+    if (!A || !Bm || !P || !Gc) return fail(c, BROV_ERR_ARG, w + ": NULL A, B, P or Gc");
+    if (k > 0 && !C) return fail(c, BROV_ERR_ARG, w + ": NULL C with k > 0");
+    if (std::isnan(gamma)) return fail(c, BROV_ERR_ARG, w + ": NaN gamma");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, BROV_ERR_ARG, w + ": dt must be finite and > 0");
+    rc = mppi_record_ok(c, w, cfg, r, H, ref_total, ref_row0);
+    if (rc) return rc;
+    const int64_t M = (H + cfg->hold - 1) / cfg->hold;      // knots
+    if (M * r > KOOPMAN_MPPI_MAX_MNU)
+        return fail(c, BROV_ERR_ARG, w + ": M nu = " + std::to_string(M * r) + " must be <= " + std::to_string(KOOPMAN_MPPI_MAX_MNU) +
+                                         " (a sample's commands are held in LDS)");
+    DeviceGuard g(c);
+    const size_t n_U = (size_t)B * M * r, n_cost = (size_t)B * K, d = (size_t)n + k;
+    KoopmanMppiArgs args{};
+    MppiArgs& m = args.m;
+    m.shift = shift != 0;
+    m.K = K; m.H = H; m.M = M; m.ref_total = ref_total; m.ref_row0 = ref_row0; m.dt = dt; m.seed = seed;
+    args.n = n; args.r = r; args.k = k; args.gamma = gamma;
+    MppiRec* d_rec;
+    Arena a(c, host);
+    rc = a.lay("edmdc_mppi_step", [&] {
+        m.x = a.in(x, (size_t)B * n);
+        m.ref = a.in(ref, (size_t)B * ref_total * n);
+        m.eps = eps ? a.in(eps, n_cost * M * r) : nullptr;
+        m.U_nom = a.inout(U_nom, n_U);
+        m.u_apply = u_apply ? a.out(u_apply, (size_t)B * cfg->hold * r) : nullptr;
+        m.cost = host || cost ? a.out(cost, n_cost) : a.take<double>(n_cost);        // the kernels need it: scratch when the caller has none
+        m.info = info ? a.out(info, (size_t)B * 4) : nullptr;
+        args.pred = pred ? a.out(pred, n_cost * (H + 1) * n) : nullptr;
+        args.C = k ? a.in(C, (size_t)k * n) : nullptr;
+        args.P = a.in(P, (size_t)(H + 1) * n * d);
+        args.Gc = a.in(Gc, (size_t)(H + 1) * M * n * r);
+        d_rec = a.take<MppiRec>(1);
+        m.U_old = a.take<double>(n_U);
+        args.F = a.take<double>((size_t)B * (H + 1) * n);
+    });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_rec, cfg, sizeof(MppiRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // cfg is the caller's
+    m.rec = d_rec;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_koopman_mppi_step(c->stream, B, args));
+    }
+    return a.finish();
+}
+
+int edmdc_mppi_step_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, const double* d_A, const double* d_B,
+                        const double* d_P, const double* d_Gc, int64_t nb, const brov_mppi* cfg, int64_t K, int64_t H, double dt,
+                        uint64_t seed, const double* d_x, const double* d_ref, int64_t ref_total, int64_t ref_row0, const double* d_eps,
+                        double* d_U_nom, int shift, double* d_u_apply, double* d_cost, double* d_info, double* d_pred) {
+    return koopman_mppi_step(c, false, n, r, k, gamma, d_C, d_A, d_B, d_P, d_Gc, nb, cfg, K, H, dt, seed, d_x, d_ref, ref_total, ref_row0,
+                             d_eps, d_U_nom, shift, d_u_apply, d_cost, d_info, d_pred);
+}
+
+int edmdc_mppi_step(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const double* A, const double* B, const double* P,
+                    const double* Gc, int64_t nb, const brov_mppi* cfg, int64_t K, int64_t H, double dt, uint64_t seed, const double* x,
+                    const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps, double* U_nom, int shift, double* u_apply,
+                    double* cost, double* info, double* pred) {
+    return koopman_mppi_step(c, true, n, r, k, gamma, C, A, B, P, Gc, nb, cfg, K, H, dt, seed, x, ref, ref_total, ref_row0, eps, U_nom, shift,
+                             u_apply, cost, info, pred);
 }
 
 int brov_ensemble_stats_dev(brov_ctx* c, int64_t P, int64_t M, const double* d_vals, double* d_out) {

@@ -20,43 +20,11 @@
 #include "brov2_error.h"
 #include "brov2_fast.h"
 #include "brov2_kernels.h"
+#include "brov2_mppi.h"
 #include "brov2_rows.h"
 #include "brov2_stream.h"
 
 namespace brov {
-
-typedef const MppiRec __attribute__((address_space(4)))* CMR;
-typedef const double __attribute__((address_space(4)))* CDP;
-__device__ __forceinline__ CMR as_constant_mr(const MppiRec* g) { return (CMR)(unsigned long long)g; }
-__device__ __forceinline__ CDP as_constant_d(const double* g) { return (CDP)(unsigned long long)g; }
-// make the compiler re-issue the scalar loads behind the pointer here (relaunder in brov2_fast.h)
-__device__ __forceinline__ CMR relaunder_mr(CMR f) {
-    asm volatile("" : "+s"(f));
-    return f;
-}
-__device__ __forceinline__ CDP relaunder_d(CDP f) {
-    asm volatile("" : "+s"(f));
-    return f;
-}
-
-// a clamp that lets a NaN through (fmin / fmax would return the limit): a NaN perturbation must reach the cost
-__device__ __forceinline__ double clip_keep_nan(double v, double lo, double hi) {
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
-
-// The command of sample k at one (knot, channel): clip(U + sigma xi, lo, hi) with xi = 0 for the nominal sample (k = 0) and for an
-// unperturbed channel (sigma = 0; neither eps nor the stream is touched), else eps[c] or the normal number c of the second stream.
-// c = ((b K + k) M + m) nu + j is both the index into eps and the counter.  Both kernels call this: the same bits in both.
-__device__ __forceinline__ double mppi_command(double U, double sg, double lo, double hi, const double* __restrict__ eps, uint64_t s2,
-                                               uint64_t c, bool nominal) {
-    double xi = 0.0;
-    if (sg > 0.0) {                     // wave-uniform
-        const double n = eps ? eps[c] : box_muller(uniform01_at(s2, 2ull * c), uniform01_at(s2, 2ull * c + 1ull));
-        xi = nominal ? 0.0 : n;
-    }
-    return clip_keep_nan(fma(sg, xi, U), lo, hi);
-}
 
 template <int MODEL, int INTEG, int LAGMODE>
 __global__ void __launch_bounds__(256) mppi_cost_kernel(const MppiArgs a) {
@@ -273,14 +241,20 @@ __global__ void __launch_bounds__(256) mppi_update_kernel(const MppiArgs a) {
 // ---------------------------------------------------------------------------------------
 // launch: cost grid (blocks of K, B) with 64-lane blocks when K <= 64, as launch_rollout_pop; update grid (M, B)
 // ---------------------------------------------------------------------------------------
+// the update alone (grid (M, B)): what follows any cost kernel that has filled a.cost and a.U_old (koopman_mppi.hip calls it too)
+hipError_t launch_mppi_update(hipStream_t st, int nu, int64_t B, const MppiArgs& a) {
+    if (nu == 8) hipLaunchKernelGGL((mppi_update_kernel<8>), dim3((unsigned)a.M, (unsigned)B), dim3(256), 0, st, a);
+    else if (nu == 6) hipLaunchKernelGGL((mppi_update_kernel<6>), dim3((unsigned)a.M, (unsigned)B), dim3(256), 0, st, a);
+    else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
 template <int MODEL, int INTEG, int LAGMODE>
 static hipError_t launch_mppi_t(hipStream_t st, int64_t B, const MppiArgs& a) {
     const int bs = a.K <= 64 ? 64 : 256;
     hipLaunchKernelGGL((mppi_cost_kernel<MODEL, INTEG, LAGMODE>), dim3((unsigned)((a.K + bs - 1) / bs), (unsigned)B), dim3(bs), 0, st, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((mppi_update_kernel<Dims<MODEL>::NU>), dim3((unsigned)a.M, (unsigned)B), dim3(256), 0, st, a);
-    return hipGetLastError();
+    return launch_mppi_update(st, Dims<MODEL>::NU, B, a);
 }
 template <int MODEL>
 static hipError_t launch_mppi_m(hipStream_t st, int integ, int lag_mode, int64_t B, const MppiArgs& a) {

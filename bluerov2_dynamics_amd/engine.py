@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats", "rollout_feedback"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats", "rollout_feedback", "koopman_markov", "koopman_mppi_step", "KoopmanPlanner"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -652,6 +652,109 @@ def mppi_step(model, integrator, params_list, cfg, x, ref, U_nom, dt, K, H=None,
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out
+
+
+def _to_host(v):
+    """NumPy copy of a host or device array"""
+    if isinstance(v, DevArray):
+        return v.numpy()
+    return v.cpu().numpy() if _is_torch(v) else as_f64(v)
+
+
+def koopman_mppi_step(C, gamma, A, B, cfg, x, ref, U_nom, dt, K, H=None, seed=0, eps=None, ref_row0=0, shift=False, want_cost=False,
+                      want_pred=False, coeffs=None, ctx=None):
+    """mppi_step with a Koopman EDMDc model (centres C [k,n], gamma, A [d,d], B [d,r]; d = n + k) as the planning model: the samples are
+    predicted by KoopmanEDMDc.simulate's recursion, evaluated in its linear form on the device (include/brov2.h: edmdc_mppi_step_dev
+    holds the law).  n in {12, 13} and r in {6, 8} come from x and U_nom; dt is the step of the stage cost, as in mppi_step (the
+    model's own sampling time is in A and B).
+
+    x [nb,n], ref [nb,rows,n], U_nom [nb,M,r], eps [nb,K,M,r] | None, cfg, K, H, seed, ref_row0, shift as in mppi_step.  Host arrays
+    are uploaded and the results come back as NumPy arrays; device arrays (DevArray / torch CUDA tensors) are used in place and the
+    results come back as device arrays of the same kind.  C, A and B may be host or device arrays either way.  coeffs: the
+    device-resident (P, Gc) of koopman_markov(A, B, n, H, cfg.hold), so that a receding-horizon loop uploads them once
+    (KoopmanPlanner does); None forms and uploads them here.
+    Returns dict(U_nom, u_apply, cost | None, info) as mppi_step, and pred [nb,K,H+1,n] | None (want_pred): the predicted states of
+    every sample."""
+    host = isinstance(x, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x, ref, U_nom = as_f64(x), as_f64(ref), as_f64(U_nom)
+        eps = None if eps is None else as_f64(eps)
+    else:
+        ctx = _ctx_of(x, ctx)
+        arr = arrays_of(x, ctx)
+    arr.bind()
+    assert len(x.shape) == 2 and len(U_nom.shape) == 3, "x must be [nb,n] and U_nom [nb,M,r]"
+    nb, n = int(x.shape[0]), int(x.shape[1])
+    M, r = int(U_nom.shape[1]), int(U_nom.shape[2])
+    d = int(A.shape[0])
+    k = d - n
+    assert tuple(int(v) for v in A.shape) == (d, d) and tuple(int(v) for v in B.shape) == (d, r), f"A must be [d,d] and B [d,{r}]"
+    assert (k == 0 and (C is None or int(C.shape[0]) == 0)) or tuple(int(v) for v in C.shape) == (k, n), f"C must be [{k},{n}]"
+    assert len(ref.shape) == 3 and int(ref.shape[0]) == nb and int(ref.shape[2]) == n, f"ref shape {tuple(ref.shape)} != {(nb, 'rows', n)}"
+    assert int(U_nom.shape[0]) == nb, f"U_nom shape {tuple(U_nom.shape)} != {(nb, 'M', r)}"
+    hold, K = int(cfg.hold), int(K)
+    H = M * hold if H is None else int(H)
+    if hold < 1 or H < 1:
+        raise ValueError("H and cfg.hold must be >= 1")
+    assert (H + hold - 1) // hold == M, f"U_nom has {M} knots, H = {H} at hold = {hold} needs {(H + hold - 1) // hold}"
+    if eps is not None:
+        assert tuple(int(v) for v in eps.shape) == (nb, K, M, r), f"eps shape {tuple(eps.shape)} != {(nb, K, M, r)}"
+    dev = lambda v: arr.upload(as_f64(v)) if isinstance(v, (np.ndarray, list, tuple)) else v
+    if coeffs is None:
+        coeffs = koopman_markov(_to_host(A), _to_host(B), n, H, hold)
+    P, Gc = (dev(v) for v in coeffs)
+    assert tuple(int(v) for v in P.shape) == (H + 1, n, d) and tuple(int(v) for v in Gc.shape) == (H + 1, M, n, r), \
+        f"coeffs must be P {(H + 1, n, d)} and Gc {(H + 1, M, n, r)}"
+    C, A, B = (None if k == 0 else dev(C)), dev(A), dev(B)
+    if host:
+        x, ref = arr.upload(x), arr.upload(ref)
+        eps = None if eps is None else arr.upload(eps)
+        U = arr.upload(U_nom)
+    else:                             # in / out in the ABI: work on a copy
+        U = U_nom.clone() if _is_torch(U_nom) else arr.empty(tuple(U_nom.shape)).copy_from_device(U_nom)
+    u_apply = arr.empty((nb, max(hold, 1), r))
+    cost = arr.empty((nb, max(K, 1))) if want_cost else None
+    info = arr.empty((nb, 4))
+    pred = arr.empty((nb, max(K, 1), H + 1, n)) if want_pred else None
+    ctx.check(ctx.lib.edmdc_mppi_step_dev(ctx.h, n, r, k, float(gamma), _dptr(C), _dptr(A), _dptr(B), _dptr(P), _dptr(Gc), nb, ctypes.byref(cfg),
+                                          K, H, float(dt), int(seed) & 0xFFFFFFFFFFFFFFFF, _dptr(x), _dptr(ref), int(ref.shape[1]),
+                                          int(ref_row0), _dptr(eps), _dptr(U), int(bool(shift)), _dptr(u_apply), _dptr(cost), _dptr(info),
+                                          _dptr(pred)), "edmdc_mppi_step_dev")
+    out = dict(U_nom=U, u_apply=u_apply, cost=cost, info=info, pred=pred)
+    if host:
+        out = {key: (None if v is None else arr.download(v)) for key, v in out.items()}
+    return out
+
+
+class KoopmanPlanner:
+    """An EDMDc model made ready for planning over H steps at `hold` steps per knot: the model's arrays and the coefficients
+    (P, Gc) of koopman_markov live on the device, uploaded once.  KoopmanEDMDc.mppi_planner builds one; step() is
+    koopman_mppi_step on them; VehicleBase.simulate_mppi(planner=...) plans every tick with it."""
+
+    def __init__(self, C, gamma, A, B, H, hold, ctx=None):
+        A, B = as_f64(A), as_f64(B)
+        self.H, self.hold, self.gamma = int(H), int(hold), float(gamma)
+        if self.H < 1 or self.hold < 1:
+            raise ValueError("H and hold must be >= 1")
+        self.d, self.r = int(A.shape[0]), int(B.shape[1])
+        self.k = 0 if C is None else int(np.shape(C)[0])
+        self.n = self.d - self.k
+        self.M = (self.H + self.hold - 1) // self.hold
+        if A.shape != (self.d, self.d) or B.shape[0] != self.d or (self.k and np.shape(C) != (self.k, self.n)):
+            raise ValueError("need C [k,n], A [n+k,n+k] and B [n+k,r]")
+        P, Gc = koopman_markov(A, B, self.n, self.H, self.hold)
+        self.ctx = ctx or default_context()
+        self.ctx.use_null_stream()
+        up = lambda v: DevArray.from_host(self.ctx, v)
+        self.C = up(as_f64(C)) if self.k else None
+        self.A, self.B, self.P, self.Gc = up(A), up(B), up(P), up(Gc)
+
+    def step(self, cfg, x, ref, U_nom, dt, K, **kw):
+        assert int(cfg.hold) == self.hold, f"the planner was built for hold = {self.hold}"
+        return koopman_mppi_step(self.C, self.gamma, self.A, self.B, cfg, x, ref, U_nom, dt, K, H=self.H, coeffs=(self.P, self.Gc),
+                                 ctx=self.ctx, **kw)
 
 
 def ensemble_stats(vals, ctx=None):
@@ -1461,6 +1564,29 @@ def linear_coefficients(A, B, n, H):
         Gt[H - 1 - j] = (R @ B).T
         R = R @ A
     return np.ascontiguousarray(R.T), Gt
+
+
+def koopman_markov(A, B, n, H, hold):
+    """(P [H+1, n, d], Gc [H+1, M, n, r]) of koopman_mppi_step (include/brov2.h: edmdc_mppi_step), M = ceil(H / hold): with E the first n
+    rows of the identity, P[0] = E, P[t+1] = P[t] A;  G[j] = P[j] B;  Gc[t][m] = the sum of G[t-1-s] over the steps s < t held by knot
+    m (s // hold == m), in ascending s -- zero where m hold >= t.  The state predicted for step t under the knots v [M, r] is
+    P[t] phi(x) + sum_m Gc[t][m] v[m].  H products of an n x d block by A on the host (NumPy)."""
+    A, B = as_f64(A), as_f64(B)
+    d, r = A.shape[0], B.shape[1]
+    H, hold = int(H), int(hold)
+    assert H >= 1 and hold >= 1 and 0 < n <= d and A.shape == (d, d) and B.shape[0] == d
+    M = (H + hold - 1) // hold
+    P = np.zeros((H + 1, n, d))
+    P[0, :, :n] = np.eye(n)
+    G = np.empty((H, n, r))
+    for t in range(H):
+        G[t] = P[t] @ B
+        P[t + 1] = P[t] @ A
+    Gc = np.zeros((H + 1, M, n, r))
+    for t in range(1, H + 1):
+        for s_ in range(t):
+            Gc[t, s_ // hold] += G[t - 1 - s_]
+    return P, Gc
 
 
 def multistep_se_linear(X, U, C, gamma, A, B, H, want_xhat=False, ctx=None):

@@ -206,7 +206,7 @@ class VehicleBase:
         out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
         return tuple(v[0] for v in out) if single else out
 
-    def simulate_mppi(self, x0, ref, dt, cfg, T, K, H, plant_params=None, integrator="euler", seed=0):
+    def simulate_mppi(self, x0, ref, dt, cfg, T, K, H, plant_params=None, integrator="euler", seed=0, planner=None):
         """Receding-horizon control of B plants by the sampling-based model-predictive update (engine.mppi_step; fossen/control.py:
         mppi builds `cfg`), planned with THIS vehicle's parameters.  The loop is device-resident: the state, the thruster lag and
         the plan never come back to the host between ticks.
@@ -216,6 +216,9 @@ class VehicleBase:
         (shift=True, seed + n, reference rows from n hold), then hold plant steps on the first knot.  plant_params=None: the plants
         are this vehicle (B from x0); a list of B _lib.BrovParams: plant b runs under plant_params[b] while the planner keeps this
         vehicle's model -- the model-mismatch case.  Every plant starts from zero thruster lag and a zero plan.
+        planner=None plans with this vehicle's Fossen model.  An engine.KoopmanPlanner (KoopmanEDMDc.mppi_planner(H, cfg.hold)) plans
+        every tick with that learned model instead (edmdc_mppi_step_dev) while the plants stay Fossen vehicles as above: the planner
+        sees the state alone, never the thruster lag.
         Returns dict(traj [B,T+1,nx], u [B,T,nu] the applied commands, info [ticks,B,4], ticks = dict(x [ticks,B,nx], lag
         [ticks,B,8,3] | None, U_nom [ticks,B,M,nu], seed [ticks], ref_row0 [ticks]): what the planner saw at each tick, before
         its update)."""
@@ -245,8 +248,12 @@ class VehicleBase:
             raise ValueError(f"ref must be a set-point or [B,T+H+1,{nx}], got {ref.shape}")
         nt, M = T // hold, (H + hold - 1) // hold
         integ = engine.INTEGRATORS[integrator]
-        planner = (_lib.BrovParams * 1)(identify.params_of(self))
-        pa = planner if plants is None else (_lib.BrovParams * B)(*plants)
+        if planner is not None and (planner.n, planner.r, planner.H, planner.hold) != (nx, nu, H, hold):
+            raise ValueError(f"the planner is for n = {planner.n}, r = {planner.r}, H = {planner.H}, hold = {planner.hold}; this call needs {(nx, nu, H, hold)}")
+        if planner is not None and planner.ctx.device != ctx.device:
+            raise ValueError("the planner's arrays live on another device than this vehicle's")
+        plan_params = (_lib.BrovParams * 1)(identify.params_of(self))          # the Fossen planning model: this vehicle
+        pa = plan_params if plants is None else (_lib.BrovParams * B)(*plants)
         P, Bp, per = (1, B, 0) if plants is None else (B, 1, 1)          # [1][B] or [B][1] rows: the same bytes either way
         ctx.use_null_stream()
         D = engine.DevArray
@@ -269,9 +276,15 @@ class VehicleBase:
                 rec_lag.rows(n, n + 1).copy_from_device(lag)
             rec_U.rows(n, n + 1).copy_from_device(U)
             xn = X.rows(n, n + 1)
-            ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, B, 1, planner, ctypes.byref(cfg), K, H, float(dt),
-                                                 seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, p_(lag), d_ref.ptr, ref.shape[1], row0, None, U.ptr, 1,
-                                                 ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "brov_mppi_step_dev")
+            if planner is None:
+                ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, B, 1, plan_params, ctypes.byref(cfg), K, H, float(dt),
+                                                     seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, p_(lag), d_ref.ptr, ref.shape[1], row0, None, U.ptr, 1,
+                                                     ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "brov_mppi_step_dev")
+            else:
+                ctx.check(ctx.lib.edmdc_mppi_step_dev(ctx.h, planner.n, planner.r, planner.k, planner.gamma, p_(planner.C), planner.A.ptr, planner.B.ptr, planner.P.ptr, planner.Gc.ptr, B,
+                                                      ctypes.byref(cfg), K, H, float(dt), seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, d_ref.ptr,
+                                                      ref.shape[1], row0, None, U.ptr, 1, ua.rows(n, n + 1).ptr, None,
+                                                      info.rows(n, n + 1).ptr, None), "edmdc_mppi_step_dev")
             ctx.check(ctx.lib.brov_rollout_pop_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, P, pa, per, Bp, hold, float(dt), xn.ptr,
                                                    ua.rows(n, n + 1).ptr, p_(lag), traj.rows(n, n + 1).ptr, 1, X.rows(n + 1, n + 2).ptr),
                       "brov_rollout_pop_dev")

@@ -8,7 +8,13 @@ damping and added-mass terms), or, with --current, the nominal vehicle in N diff
 PID law of examples/closed_loop_ensemble.py (engine.rollout_feedback), and the four closed-loop metrics of brov_rollout_feedback --
 sum dt |e_pos|^2, sum dt |e_att|^2, sum dt |u|^2, steps with a channel on a limit -- are printed side by side, averaged over the plants.
 
-    python examples/mppi_tracking.py [--plants 16 --seconds 6 --samples 1024 --horizon 25 --hold 5 --current 0.2]
+--planner koopman plans with a learned model instead: a Koopman EDMDc model (KoopmanEDMDc.fit_multi) fitted here on a short simulated
+recording of the NOMINAL vehicle (on-device AR(1) commands, as examples/sim_koopman.py makes them) and handed to the same update
+through model.mppi_planner (engine.koopman_mppi_step: the learned model is linear in the command, so a sample costs a block
+convolution, not a rollout).  The plants, the seeds and the cost stay the same; the learned model never sees the thruster lag.
+--planner both prints a column per planner.
+
+    python examples/mppi_tracking.py [--plants 16 --seconds 6 --samples 1024 --horizon 25 --hold 5 --current 0.2 --planner both]
 """
 import argparse
 import os
@@ -18,12 +24,14 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from bluerov2_dynamics_amd import engine                             # noqa: E402
+from bluerov2_dynamics_amd import _lib, engine                       # noqa: E402
+from bluerov2_dynamics_amd.Koopman.koopmanEDMDc import KoopmanEDMDc   # noqa: E402
 from bluerov2_dynamics_amd.fossen import control, identify           # noqa: E402
 from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2             # noqa: E402
 
 SPREAD = ("Xu", "Yv", "Zw", "Nr", "Xu_abs", "Yv_abs", "Zw_abs", "Nr_abs", "Xu_dot", "Yv_dot", "Zw_dot", "Nr_dot")
 NAMES = ("sum dt |e_pos|^2", "sum dt |e_att|^2", "sum dt |u|^2", "steps on a limit")
+LABEL = {"mppi": "fossen", "koopman": "koopman"}
 
 
 def drawn_plants(base, n, seed, rel_std=0.05):
@@ -54,8 +62,29 @@ def metrics_of(model, traj, u, ref, dt, lo, hi):
                      on.sum(axis=1).astype(float)], axis=1)
 
 
-def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, current=0.0, integrator="rk4", seed=0, verbose=True):
-    """Returns dict(mppi [N,4], pid [N,4]): the closed-loop metrics of every plant under the two controllers"""
+def fit_koopman(rov, x0, dt, rollouts=64, steps=300, n_rbfs=64, gamma=1.0, ridge=1e-3, seed=0xED3D):
+    """A KoopmanEDMDc model of the nominal vehicle at step dt: `rollouts` recordings of `steps` steps under AR(1) commands, simulated on
+    the device from starts spread around x0 (depth and heading over the range of the move), fitted with fit_multi"""
+    ctx = rov._ctx
+    ctx.use_null_stream()
+    rng = np.random.default_rng(seed)
+    starts = np.repeat(x0[None], rollouts, axis=0)
+    starts[:, 2] += rng.uniform(-0.5, 1.5, rollouts)
+    starts[:, 5] += rng.uniform(-0.3, 0.8, rollouts)
+    U = engine.DevArray(ctx, (rollouts, steps, 8))
+    engine.fill_controls_dev(U, "btu", "ar1", seed=seed, ctx=ctx)
+    X = engine.DevArray(ctx, (rollouts, steps + 1, 12))
+    engine.rollout_dev(_lib.THRUSTER_EULER, "euler", engine.DevArray.from_host(ctx, starts), U, dt, traj=X, layout="btu", ctx=ctx)
+    Xh, Uh = X.numpy(), U.numpy()
+    model = KoopmanEDMDc(state_dim=12, input_dim=8, n_rbfs=n_rbfs, gamma=gamma, ridge=ridge)
+    model.fit_multi([Xh[b] for b in range(rollouts)], [np.vstack([Uh[b], np.zeros((1, 8))]) for b in range(rollouts)])
+    return model
+
+
+def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, current=0.0, integrator="rk4", seed=0, verbose=True,
+        planner="fossen", fit_rollouts=64, fit_steps=300, n_rbfs=64):
+    """Returns dict(mppi [N,4] (planner fossen / both), koopman [N,4] (planner koopman / both), pid [N,4]): the closed-loop metrics of
+    every plant under the controllers"""
     rov = BlueROV2(dt=dt)
     base = identify.params_of(rov)
     n = int(plants)
@@ -72,21 +101,32 @@ def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, curre
     REF = np.repeat(ref[None], n, axis=0)
     cfg = control.mppi(q=[40.0, 40.0, 60.0, 4.0, 4.0, 6.0, 2.0, 2.0, 3.0, 0.2, 0.2, 0.4], qf=[80.0, 80.0, 120.0, 8.0, 8.0, 12.0, 4.0, 4.0, 6.0, 0.4, 0.4, 0.8],
                        r=0.05, sigma=0.15, lam=0.2, u_min=-1.0, u_max=1.0, hold=hold, nu=8)
-    r = rov.simulate_mppi(np.repeat(x0[None], n, axis=0), REF, dt, cfg, T, int(samples), int(horizon), plant_params=ps, integrator=integrator,
-                          seed=seed)
-    m_mppi = metrics_of(rov.MODEL, r["traj"], r["u"], REF[:, :T], dt, -1.0, 1.0)
+    out, info = {}, {}
+    for key, label in (("mppi", "fossen"), ("koopman", "koopman")):
+        if planner not in (label, "both"):
+            continue
+        kp = None
+        if label == "koopman":
+            kp = fit_koopman(rov, x0, dt, fit_rollouts, fit_steps, n_rbfs).mppi_planner(int(horizon), hold, ctx=rov._ctx)
+        r = rov.simulate_mppi(np.repeat(x0[None], n, axis=0), REF, dt, cfg, T, int(samples), int(horizon), plant_params=ps,
+                              integrator=integrator, seed=seed, planner=kp)
+        out[key] = metrics_of(rov.MODEL, r["traj"], r["u"], REF[:, :T], dt, -1.0, 1.0)
+        info[key] = r["info"]
     fb = control.pid_thrusters(rov, [40.0, 40.0, 60.0, 4.0, 4.0, 6.0], [20.0, 20.0, 30.0, 1.0, 1.0, 2.0], [4.0, 4.0, 6.0, 0.4, 0.4, 0.6],
                                z_max=2.0, hold=hold)
     p = engine.rollout_feedback(rov.MODEL, integrator, ps, fb, x0[None], ref[None, :T], dt, store=False, ctx=rov._ctx)
-    m_pid = p["metrics"][:, 0]
+    out["pid"] = p["metrics"][:, 0]
     if verbose:
         what = f"in currents of {current} m/s" if current > 0 else "drawn around the nominal vehicle"
-        print(f"{n} plants {what}, {T} steps of {dt} s, hold {hold}; MPPI: {samples} samples over {horizon} steps per tick, "
-              f"effective sample size {r['info'][:, :, 2].mean():.1f}, {int(r['info'][:, :, 3].sum())} non-finite samples")
-        print(f"{'mean over the plants':<22}{'MPPI':>14}{'PID':>14}")
+        for key, i in info.items():
+            print(f"{n} plants {what}, {T} steps of {dt} s, hold {hold}; MPPI{'' if planner == 'fossen' else ' (' + LABEL[key] + ' model)'}: "
+                  f"{samples} samples over {horizon} steps per tick, effective sample size {i[:, :, 2].mean():.1f}, "
+                  f"{int(i[:, :, 3].sum())} non-finite samples")
+        cols = [(k, "MPPI" if planner == "fossen" else "MPPI " + LABEL[k]) for k in info] + [("pid", "PID")]
+        print(f"{'mean over the plants':<22}" + "".join(f"{label:>14}" for _, label in cols))
         for i, name in enumerate(NAMES):
-            print(f"{name:<22}{m_mppi[:, i].mean():>14.5g}{m_pid[:, i].mean():>14.5g}")
-    return dict(mppi=m_mppi, pid=m_pid)
+            print(f"{name:<22}" + "".join(f"{out[k][:, i].mean():>14.5g}" for k, _ in cols))
+    return out
 
 
 def main(argv=None):
@@ -99,9 +139,14 @@ def main(argv=None):
     ap.add_argument("--current", type=float, default=0.0)
     ap.add_argument("--euler", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--planner", choices=["fossen", "koopman", "both"], default="fossen")
+    ap.add_argument("--fit-rollouts", type=int, default=64, help="koopman: simulated recordings of the nominal vehicle")
+    ap.add_argument("--fit-steps", type=int, default=300, help="koopman: steps per recording")
+    ap.add_argument("--rbfs", type=int, default=64, help="koopman: RBF centres")
     a = ap.parse_args(argv)
     out = run(a.plants, a.seconds, samples=a.samples, horizon=a.horizon, hold=a.hold, current=a.current,
-              integrator="euler" if a.euler else "rk4", seed=a.seed)
+              integrator="euler" if a.euler else "rk4", seed=a.seed, planner=a.planner, fit_rollouts=a.fit_rollouts, fit_steps=a.fit_steps,
+              n_rbfs=a.rbfs)
     return {k: v.mean(axis=0) for k, v in out.items()}
 
 

@@ -390,6 +390,43 @@ BROV_API int brov_mppi_step_dev(brov_ctx* ctx, int model, int integrator, int la
                        uint64_t seed, const double* d_x, const double* d_lag, const double* d_ref, int64_t ref_total, int64_t ref_row0,
                        const double* d_eps, double* d_U_nom, int shift, double* d_u_apply, double* d_cost, double* d_info);
 
+/* ---- model-predictive control planned with a Koopman EDMDc model -------------------------------------------------------------------
+ * edmdc_mppi_step performs one MPPI update for nb problems with an EDMDc model as the planning model: n in {12, 13} states,
+ * r = nu in {6, 8} inputs, k >= 0 centres C [k][n], gamma, A [d][d], B [d][r] with d = n + k (what KoopmanEDMDc.fit returns).
+ * Everything that does not concern the prediction is the law of brov_mppi_step, word for word: the brov_mppi record, the knots
+ * (M = ceil(H / hold)), sample 0 is the nominal, the counter c = ((b K + k) M + m) nu + j on the second stream or the explicit eps
+ * [nb][K][M][nu], the clamp that keeps a NaN and delta, the importance term, the treatment of non-finite costs, the soft-min,
+ * shift, u_apply, cost and info, the no-finite-sample rule, and determinism.  The same seed gives the same v[k][m][j] as
+ * brov_mppi_step does.
+ * Prediction.  z_0 = phi(x) = [x, exp(-gamma (|x|^2 + |c_i|^2 - 2 x.c_i))], the lift as edmdc_lift computes it;
+ * z_{t+1} = A z_t + B v[k][m(t)];  x_hat_t = z_t[0:n], with no re-lifting: KoopmanEDMDc.simulate applied to the sample's command
+ * sequence.  The call evaluates this in the linear form
+ *     x_hat_t = P[t] phi(x) + sum_{m : m hold < t} Gc[t][m] v[k][m]            (m ascending, then the channels ascending)
+ * from two coefficient arrays that the caller passes, formed with E = the first n rows of the identity as
+ *     P[0] = E,  P[t+1] = P[t] A                                               P [H+1][n][d]
+ *     G[j] = P[j] B                                                            (n x r)
+ *     Gc[t][m] = sum_{s : m(s) = m, s < t} G[t-1-s]   in ascending s           Gc [H+1][M][n][r], zero where m hold >= t
+ * (m(s) = s / hold; entries with m hold >= t are never read).  A and B are required as the model the coefficients belong to; the
+ * call itself reads P and Gc only.  The linear form agrees with the iterated recursion to rounding amplified by |E A^t|.
+ * Cost.  e_t = the tracking error e[12] of brov_rollout_feedback on x_hat_t against reference row ref_row0 + t: n = 12 with the
+ * Euler-angle error, n = 13 with the quaternion error on the predicted quaternion as it stands (x_hat is not normalised; the
+ * rotation normalises its copy as the quaternion model does).  S_k is then brov_mppi_step's expression.  x [nb][n], ref
+ * [nb][ref_total][n], U_nom [nb][M][nu] in / out.
+ * One more optional output: pred [nb][K][H+1][n], the predicted states of every sample (row 0 = x); NULL = no stores.
+ * Refused on the host with BROV_ERR_ARG and a brov_last_error text naming the rule, before anything is copied or launched: what
+ * brov_mppi_step refuses of K, H, the record, the reference window, nb > 65535 and dt; n or r outside the sets above; k < 0 or
+ * k > 1024; a NULL cfg, x, ref, U_nom, A, B, P or Gc; a NULL C with k > 0; a NaN gamma; M nu > 312 (a sample's commands live in
+ * the 160 KB of LDS of one 64-lane block).  nb = 0: BROV_OK, nothing touched. */
+BROV_API int edmdc_mppi_step(brov_ctx* ctx, int n, int r, int k, double gamma, const double* C, const double* A, const double* B,
+                    const double* P, const double* Gc, int64_t nb, const brov_mppi* cfg /* host */, int64_t K, int64_t H, double dt,
+                    uint64_t seed, const double* x, const double* ref, int64_t ref_total, int64_t ref_row0, const double* eps,
+                    double* U_nom, int shift, double* u_apply, double* cost, double* info, double* pred);
+BROV_API int edmdc_mppi_step_dev(brov_ctx* ctx, int n, int r, int k, double gamma, const double* d_C, const double* d_A, const double* d_B,
+                        const double* d_P, const double* d_Gc, int64_t nb, const brov_mppi* cfg /* host */, int64_t K, int64_t H,
+                        double dt, uint64_t seed, const double* d_x, const double* d_ref, int64_t ref_total, int64_t ref_row0,
+                        const double* d_eps, double* d_U_nom, int shift, double* d_u_apply, double* d_cost, double* d_info,
+                        double* d_pred);
+
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
  * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.
