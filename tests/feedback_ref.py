@@ -8,7 +8,9 @@ header comment, with the oracle's own rotation matrices.
 Besides the results, rollout() returns two margins that say whether its discontinuous branches are well-posed for the inputs:
   wrap_margin  the smallest | |att_ref - att| - pi | before wrapping over all steps (Euler models; the distance to the nearest
                odd multiple of pi), and for the quaternion model the smallest |q_e.w| (the sign of the short way round);
-  sat_margin   the smallest |u_raw - limit| over channels, finite limits and ticks (u_raw: the command before the clamp)."""
+  sat_margin   the smallest |u_raw - limit| over channels, finite limits and ticks (u_raw: the command before the clamp).
+wrap_margin_lane / sat_margin_lane [B] hold the same per trajectory, so that a sweep over many shapes can leave out the one
+trajectory that sits on a branch; the two scalars are their minima."""
 import dataclasses
 
 import numpy as np
@@ -56,6 +58,12 @@ def _pi(dtype):
 
 def error(model, x, r, dtype=np.float64):
     """(e [B,12], margin): the tracking error of states x [B,nx] against reference rows r [B,nx]"""
+    e, lanes = error_lanes(model, x, r, dtype)
+    return e, (float(np.min(lanes)) if lanes.size else np.inf)
+
+
+def error_lanes(model, x, r, dtype=np.float64):
+    """(e [B,12], margin [B]): error() with the wrap margin of every row"""
     x, r = np.asarray(x, dtype=dtype), np.asarray(r, dtype=dtype)
     nx = fp.NX[model]
     e = np.zeros((x.shape[0], 12), dtype=dtype)
@@ -70,13 +78,13 @@ def error(model, x, r, dtype=np.float64):
                        qw * rz - qx * ry + qy * rx - qz * rw], -1)
         s = np.where(we >= 0, dtype(1), dtype(-1))
         e[:, 3:6] = dtype(2) * s[:, None] * ve
-        margin = float(np.min(np.abs(we))) if we.size else np.inf
+        margin = np.abs(we)
     else:
         R = fp._rotation(x[:, 3], x[:, 4], x[:, 5])
         d = r[:, 3:6] - x[:, 3:6]
         two_pi = dtype(2) * _pi(dtype)
         e[:, 3:6] = d - two_pi * np.rint(d / two_pi)
-        margin = float(np.min(np.abs(np.mod(np.abs(d), two_pi) - _pi(dtype)))) if d.size else np.inf
+        margin = np.min(np.abs(np.mod(np.abs(d), two_pi) - _pi(dtype)), axis=1)
     dp = r[:, 0:3] - x[:, 0:3]
     for i in range(3):
         e[:, i] = R[:, 0, i] * dp[:, 0] + R[:, 1, i] * dp[:, 1] + R[:, 2, i] * dp[:, 2]
@@ -86,7 +94,7 @@ def error(model, x, r, dtype=np.float64):
 
 def rollout(model, integ, lag_mode, v, l, x0, ref, dt, T=None, u_ff=None, lag=None, z=None, sub=1, dtype=np.float64):
     """x0 [B,nx], ref [B,rows,nx] (rows 1 or T), u_ff [B,T,nu] | None, lag [B,8,3] | None, z [B,6] | None ->
-    dict(traj [B,T//sub+1,nx], xT, lag, z, u [B,T,nu], metrics [B,4], wrap_margin, sat_margin)"""
+    dict(traj [B,T//sub+1,nx], xT, lag, z, u [B,T,nu], metrics [B,4], wrap_margin, sat_margin, wrap_margin_lane [B], sat_margin_lane [B])"""
     c = fp._Prep(v, dt, dtype)
     nu = fp.NU[model]
     ref = np.asarray(ref, dtype=dtype)
@@ -101,10 +109,12 @@ def rollout(model, integ, lag_mode, v, l, x0, ref, dt, T=None, u_ff=None, lag=No
     traj, us = [x.copy()], []
     metrics = np.zeros((B, 4), dtype=dtype)
     wrap_margin = sat_margin = np.inf
+    wrap_lane, sat_lane = np.full(B, np.inf, dtype=dtype), np.full(B, np.inf, dtype=dtype)
     u = np.zeros((B, nu), dtype=dtype)
     for t in range(T):
-        e, m = error(model, x, ref[:, t if rows > 1 else 0], dtype)
-        wrap_margin = min(wrap_margin, m)
+        e, ml = error_lanes(model, x, ref[:, t if rows > 1 else 0], dtype)
+        wrap_lane = np.minimum(wrap_lane, ml)
+        wrap_margin = min(wrap_margin, float(np.min(ml)) if ml.size else np.inf)
         if t % l.hold == 0:
             raw = np.zeros((B, nu), dtype=dtype) if u_ff is None else np.asarray(u_ff, dtype=dtype)[:, t].copy()
             for j in range(12):
@@ -115,6 +125,7 @@ def rollout(model, integ, lag_mode, v, l, x0, ref, dt, T=None, u_ff=None, lag=No
                 fin = np.isfinite(lim)
                 if fin.any():
                     sat_margin = min(sat_margin, float(np.min(np.abs(raw[:, fin] - lim[fin]))))
+                    sat_lane = np.minimum(sat_lane, np.min(np.abs(raw[:, fin] - lim[fin]), axis=1))
             u = np.minimum(np.maximum(raw, lo), hi)
             z = np.minimum(np.maximum(z + (dtype(l.hold) * h) * e[:, 0:6], -zm), zm)
         metrics[:, 0] += h * np.sum(e[:, 0:3] ** 2, axis=1)
@@ -126,4 +137,4 @@ def rollout(model, integ, lag_mode, v, l, x0, ref, dt, T=None, u_ff=None, lag=No
         if (t + 1) % sub == 0:
             traj.append(x.copy())
     return dict(traj=np.stack(traj, axis=1), xT=x, lag=lag, z=z, u=np.stack(us, axis=1) if us else np.zeros((B, 0, nu), dtype=dtype),
-                metrics=metrics, wrap_margin=wrap_margin, sat_margin=sat_margin)
+                metrics=metrics, wrap_margin=wrap_margin, sat_margin=sat_margin, wrap_margin_lane=wrap_lane, sat_margin_lane=sat_lane)

@@ -40,20 +40,26 @@ def predict(C, gamma, A, B, x, cmd, H, hold, dtype=np.float64):
 def costs(c, pred, ref_rows, U, cmd, delta, dt, H, dtype=np.float64):
     """(S [K], wrap margin) of one problem from its predicted states pred [K,H+1,n], reference rows [H+1,n], knots U [M,r] and
     commands cmd / delta [K,M,r]: mppi_ref.costs with the plant replaced by the prediction"""
+    S, lanes = costs_lanes(c, pred, ref_rows, U, cmd, delta, dt, H, dtype)
+    return S, min(np.inf, float(np.min(lanes)))
+
+
+def costs_lanes(c, pred, ref_rows, U, cmd, delta, dt, H, dtype=np.float64):
+    """costs() with the wrap margin of every sample [K]"""
     K, n = pred.shape[0], pred.shape[2]
     model = ERROR_MODEL[n]
     q, qf, r, sg = c.q.astype(dtype), c.qf.astype(dtype), c.r.astype(dtype), c.sigma.astype(dtype)
     h = dtype(dt)
     S = np.zeros(K, dtype=dtype)
-    margin = np.inf
+    margin = np.full(K, np.inf, dtype=dtype)
     ref_rows = np.asarray(ref_rows, dtype=dtype)
     for t in range(H):
-        e, m = fr.error(model, pred[:, t], np.repeat(ref_rows[t][None], K, axis=0), dtype)
-        margin = min(margin, m)
+        e, m = fr.error_lanes(model, pred[:, t], np.repeat(ref_rows[t][None], K, axis=0), dtype)
+        margin = np.minimum(margin, m)
         u = cmd[:, t // c.hold]
         S = S + h * (np.sum(q * e * e, axis=1) + np.sum(r * u * u, axis=1))
-    e, m = fr.error(model, pred[:, H], np.repeat(ref_rows[H][None], K, axis=0), dtype)
-    margin = min(margin, m)
+    e, m = fr.error_lanes(model, pred[:, H], np.repeat(ref_rows[H][None], K, axis=0), dtype)
+    margin = np.minimum(margin, m)
     S = S + np.sum(qf * e * e, axis=1)
     on = c.sigma > 0
     Ud = np.asarray(U, dtype=dtype)
@@ -63,20 +69,21 @@ def costs(c, pred, ref_rows, U, cmd, delta, dt, H, dtype=np.float64):
 
 def step(C, gamma, A, B, c, x, ref, U_nom, dt, K, H, seed=0, eps=None, ref_row0=0, shift=False, dtype=np.float64):
     """One update for nb problems: x [nb,n], ref [nb,rows,n], U_nom [nb,M,r], eps [nb,K,M,r] | None -> dict(cost [nb,K], pred
-    [nb,K,H+1,n], U_new, U_nom (after the shift), u_apply [nb,hold,r], info [nb,4], xi, v, delta [nb,K,M,r], w [nb,K], wrap_margin)"""
+    [nb,K,H+1,n], U_new, U_nom (after the shift), u_apply [nb,hold,r], info [nb,4], xi, v, delta [nb,K,M,r], w [nb,K], wrap_margin, wrap_margin_lane [nb,K])"""
     x, ref, U_nom = np.asarray(x), np.asarray(ref), np.asarray(U_nom)
     nb, M, r = U_nom.shape
     assert M == mr.knots(H, c.hold) and r == np.shape(B)[1]
     rows = ref.shape[1]
     assert (rows == 1 and ref_row0 == 0) or (ref_row0 >= 0 and ref_row0 + H <= rows - 1)
     xi = mr.normals(seed, nb, K, M, r) if eps is None else np.asarray(eps, dtype=np.float64)
-    out = dict(cost=[], pred=[], U_new=[], U_nom=[], u_apply=[], info=[], v=[], delta=[], w=[], xi=xi, wrap_margin=np.inf)
+    out = dict(cost=[], pred=[], U_new=[], U_nom=[], u_apply=[], info=[], v=[], delta=[], w=[], wrap_margin_lane=[], xi=xi, wrap_margin=np.inf)
     lo, hi = c.u_min.astype(dtype), c.u_max.astype(dtype)
     for b in range(nb):
         v, d = mr.commands(c, U_nom[b], xi[b], dtype)
         rr = np.repeat(ref[b, :1], H + 1, axis=0) if rows == 1 else ref[b, ref_row0:ref_row0 + H + 1]
         pred = predict(C, gamma, A, B, x[b], v, H, c.hold, dtype)
-        S, margin = costs(c, pred, rr, U_nom[b], v, d, dt, H, dtype)
+        S, lanes = costs_lanes(c, pred, rr, U_nom[b], v, d, dt, H, dtype)
+        margin = min(np.inf, float(np.min(lanes)))
         U_new, info, w = mr.softmin(c, S, d, U_nom[b], dtype)
         if w is None:               # no finite sample: the plan stays, the command is the clamped first knot
             Un = np.asarray(U_nom[b], dtype=dtype).copy()
@@ -87,6 +94,6 @@ def step(C, gamma, A, B, c, x, ref, U_nom, dt, K, H, seed=0, eps=None, ref_row0=
             first = U_new[0]
         out["wrap_margin"] = min(out["wrap_margin"], margin)
         for key, val in (("cost", S), ("pred", pred), ("U_new", U_new), ("U_nom", Un), ("u_apply", np.repeat(first[None], c.hold, axis=0)),
-                         ("info", info), ("v", v), ("delta", d), ("w", w)):
+                         ("info", info), ("v", v), ("delta", d), ("w", w), ("wrap_margin_lane", lanes)):
             out[key].append(val)
     return {k: (np.stack(val) if isinstance(val, list) else val) for k, val in out.items()}

@@ -92,6 +92,12 @@ def softmin(c, S, delta, U, dtype=np.float64):
 def costs(model, integ, lag_mode, v, c, x, ref_rows, U, cmd, delta, dt, H, lag=None, dtype=np.float64):
     """S [K] of one problem: vehicle v, state x [nx], reference rows ref_rows [H+1,nx] (a set-point: the row repeated), commands
     cmd / delta [K,M,nu].  Also returns the smallest wrap margin of feedback_ref.error over the steps."""
+    S, lanes = costs_lanes(model, integ, lag_mode, v, c, x, ref_rows, U, cmd, delta, dt, H, lag, dtype)
+    return S, min(np.inf, float(np.min(lanes)))
+
+
+def costs_lanes(model, integ, lag_mode, v, c, x, ref_rows, U, cmd, delta, dt, H, lag=None, dtype=np.float64):
+    """costs() with the wrap margin of every sample [K]"""
     pc = fp._Prep(v, dt, dtype)
     K = cmd.shape[0]
     nu = fp.NU[model]
@@ -100,16 +106,16 @@ def costs(model, integ, lag_mode, v, c, x, ref_rows, U, cmd, delta, dt, H, lag=N
     q, qf, r, sg = c.q.astype(dtype), c.qf.astype(dtype), c.r.astype(dtype), c.sigma.astype(dtype)
     h = dtype(dt)
     S = np.zeros(K, dtype=dtype)
-    margin = np.inf
+    margin = np.full(K, np.inf, dtype=dtype)
     ref_rows = np.asarray(ref_rows, dtype=dtype)
     for t in range(H):
-        e, m = fr.error(model, xs, np.repeat(ref_rows[t][None], K, axis=0), dtype)
-        margin = min(margin, m)
+        e, m = fr.error_lanes(model, xs, np.repeat(ref_rows[t][None], K, axis=0), dtype)
+        margin = np.minimum(margin, m)
         u = cmd[:, t // c.hold]
         S = S + h * (np.sum(q * e * e, axis=1) + np.sum(r * u * u, axis=1))
         xs, lg = fp._step(pc, model, integ, lag_mode, dt, xs, u, lg)
-    e, m = fr.error(model, xs, np.repeat(ref_rows[H][None], K, axis=0), dtype)
-    margin = min(margin, m)
+    e, m = fr.error_lanes(model, xs, np.repeat(ref_rows[H][None], K, axis=0), dtype)
+    margin = np.minimum(margin, m)
     S = S + np.sum(qf * e * e, axis=1)
     on = c.sigma > 0
     Ud = np.asarray(U, dtype=dtype)
@@ -121,20 +127,21 @@ def step(model, integ, lag_mode, vehicles, c, x, ref, U_nom, dt, K, H, lag=None,
          dtype=np.float64):
     """One update for B problems: vehicles (1 or B oracle Vehicles), x [B,nx], ref [B,rows,nx], U_nom [B,M,nu], lag [B,8,3] | None,
     eps [B,K,M,nu] | None -> dict(cost [B,K], U_new, U_nom (after the shift), u_apply [B,hold,nu], info [B,4], xi, v, delta
-    [B,K,M,nu], w [B,K], wrap_margin)"""
+    [B,K,M,nu], w [B,K], wrap_margin, wrap_margin_lane [B,K]: the margin of every sample)"""
     x, ref, U_nom = np.asarray(x), np.asarray(ref), np.asarray(U_nom)
     B, M, nu = U_nom.shape
     assert M == knots(H, c.hold) and nu == fp.NU[model]
     rows = ref.shape[1]
     assert (rows == 1 and ref_row0 == 0) or (ref_row0 >= 0 and ref_row0 + H <= rows - 1)
     xi = normals(seed, B, K, M, nu) if eps is None else np.asarray(eps, dtype=np.float64)
-    out = dict(cost=[], U_new=[], U_nom=[], u_apply=[], info=[], v=[], delta=[], w=[], xi=xi, wrap_margin=np.inf)
+    out = dict(cost=[], U_new=[], U_nom=[], u_apply=[], info=[], v=[], delta=[], w=[], wrap_margin_lane=[], xi=xi, wrap_margin=np.inf)
     lo, hi = c.u_min.astype(dtype), c.u_max.astype(dtype)
     for b in range(B):
         veh = vehicles[b if len(vehicles) > 1 else 0]
         v, d = commands(c, U_nom[b], xi[b], dtype)
         rr = np.repeat(ref[b, :1], H + 1, axis=0) if rows == 1 else ref[b, ref_row0:ref_row0 + H + 1]
-        S, margin = costs(model, integ, lag_mode, veh, c, x[b], rr, U_nom[b], v, d, dt, H, None if lag is None else lag[b], dtype)
+        S, lanes = costs_lanes(model, integ, lag_mode, veh, c, x[b], rr, U_nom[b], v, d, dt, H, None if lag is None else lag[b], dtype)
+        margin = min(np.inf, float(np.min(lanes)))
         U_new, info, w = softmin(c, S, d, U_nom[b], dtype)
         if w is None:               # no finite sample: the plan stays, the command is the clamped first knot
             Un = np.asarray(U_nom[b], dtype=dtype).copy()
@@ -145,6 +152,6 @@ def step(model, integ, lag_mode, vehicles, c, x, ref, U_nom, dt, K, H, lag=None,
             first = U_new[0]
         out["wrap_margin"] = min(out["wrap_margin"], margin)
         for key, val in (("cost", S), ("U_new", U_new), ("U_nom", Un), ("u_apply", np.repeat(first[None], c.hold, axis=0)), ("info", info),
-                         ("v", v), ("delta", d), ("w", w)):
+                         ("v", v), ("delta", d), ("w", w), ("wrap_margin_lane", lanes)):
             out[key].append(val)
     return {k: (np.stack(val) if isinstance(val, list) else val) for k, val in out.items()}

@@ -3,7 +3,7 @@
 strides, bag structures and chunk sizes through the C ABI against the oracle.  Prints the worst relative error per family
 and exits non-zero on the first violation.
 
-    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp,pinc]
+    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp,pinc,rollout_pop,feedback,mppi,koopman_mppi,window_pop]
 
 Lives under tests/ because it checks against oracle/ (test infrastructure); tests/test_gpu_parity.py runs a short sweep."""
 import os, sys, time
@@ -437,8 +437,33 @@ def pinc():
     print(f"pinc       : {n} cases, worst mixed err " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()), flush=True)
 
 
+def family_sweep(name):
+    """The five newer families (population rollouts, closed-loop rollouts, Fossen and Koopman MPPI, population window evaluator with
+    fd_normal_eq): random cases from the generators of tests/sweep_cases.py against the references and bounds of tests/sweep_run.py,
+    which tests/test_family_sweeps_gpu.py runs on a fixed list.  A case whose reference is not well-posed (more than 2 % of its lanes
+    off the float64 / long double condition) is skipped and counted."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import sweep_cases, sweep_run
+    ctx = _lib.default_context()
+    draw = getattr(sweep_cases, "draw_" + name)
+    worst, second, n, skipped, t0 = 0.0, 0.0, 0, 0, time.time()
+    while time.time() - t0 < budget:
+        case = draw(rng)
+        ref = sweep_run.PREPARE[name](case)
+        try:
+            sweep_run.well_posed(case, ref)
+        except AssertionError:
+            skipped += 1
+            continue
+        e, e2, _, _ = sweep_run.sweep_one(engine, ctx, case, ref)
+        worst, second, n = max(worst, e), max(second, e2), n + 1
+    print(f"{name:11s}: {n} cases, worst mixed err {worst:.2e}, update / normal equations {second:.2e}, {skipped} ill-posed draws skipped", flush=True)
+
+
 if __name__ == "__main__":
-    fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp, pinc=pinc)
+    import functools
+    fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp, pinc=pinc,
+                **{f: functools.partial(family_sweep, f) for f in ("rollout_pop", "feedback", "mppi", "koopman_mppi", "window_pop")})
     for name in (sys.argv[3].split(",") if len(sys.argv) > 3 else list(fams)):
         fams[name]()
     print("stress parity: ok")

@@ -1,0 +1,295 @@
+"""Case lists of the shape sweeps over the population-rollout, closed-loop, MPPI, Koopman-MPPI and population-window kernels.
+Not collected; pure NumPy; imports no GPU code.
+
+One generator per family: NAME(seed) returns an ordered list of plain dicts (ints, bools, strings and lists of them), the
+hand-written corner list first, then seeded random draws from the family's value sets.  The lists depend on the seed alone, never on
+a clock: tests/test_sweep_cases_cpu.py pins a hash of each.  A case holds shapes, switches, vehicle names and the seed of its data;
+tests/sweep_run.py turns it into arrays, runs the reference and compares.  draw_NAME(rng, names...) is one random case, which
+tests/stress_parity.py calls with its own generator.
+
+The value sets are the smallest shapes at which the kernels' grid rules, knot arithmetic, counter addressing and reductions can go
+wrong: both sides of every block edge (64 lanes when B or K <= 64, 256 otherwise; 64 / 128 / 256 lanes by M nu in the Koopman cost
+kernel), partial and full last knots, hold >= H, a set-point against a reference window, more than one trip of the 256-wide
+strided loops (K = 513), the 64-window chunks of the lag scan."""
+import hashlib
+import json
+
+import numpy as np
+
+NAMES = ("V0", "V1", "V2", "V3", "V4", "V5", "V6", "V7", "V8")      # tests/fossen_vehicles.py: NAMES
+WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/fossen_vehicles.py: WRENCH_NAMES
+N_CASES = 48                                                        # per family: four slices of 12
+SEED = 2024
+
+SETS = dict(
+    rollout_pop=dict(model=(0, 1, 2), integ=("euler", "rk4"), lag_mode=(0, 1), P=(1, 2, 5), B=(1, 2, 63, 64, 65, 255, 256, 257, 300),
+                     T=(0, 1, 2, 3, 7, 65), stride=("1", "2", "T", "T+1"), store=(True, False), per_candidate=(True, False),
+                     lag=(True, False)),
+    feedback=dict(model=(0, 1, 2), integ=("euler", "rk4"), lag_mode=(0, 1), P=(1, 2, 5), B=(1, 2, 63, 64, 65, 255, 256, 257, 300),
+                  T=(0, 1, 2, 3, 7, 24, 65, 130), hold=("1", "2", "3", "5", "T+1"), ref=("set", "T"), u_ff=(True, False), z=(True, False),
+                  lag=(True, False), gain_sets=(True, False), stride=("1", "2", "T", "T+1"), store=(True, False)),
+    mppi=dict(model=(0, 1, 2), integ=("euler", "rk4"), lag_mode=(0, 1), B=(1, 2, 3), nparams=("1", "B"),
+              K=(1, 2, 63, 64, 65, 255, 256, 257, 300, 513), H=(1, 2, 5, 7, 12), hold=("1", "2", "3", "H", "H+2"), rows=("1", "H+1", "H+4"),
+              shift=(True, False), eps=(True, False)),
+    koopman_mppi=dict(n=(12, 13), r=(6, 8), k=(0, 5, 20), Mr=(6, 8, 36, 40, 42, 72, 78, 80, 84),
+                      K=(1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 300), B=(1, 2, 3), rows=("1", "H+1", "H+4"), shift=(True, False),
+                      eps=(True, False)),
+    window_pop=dict(model=(0, 1, 2), integ=("euler", "rk4"), carry=(True, False), P=(1, 2, 9), H=(1, 2, 5, 12),
+                    nwin=(1, 2, 63, 64, 65, 127, 128, 129, 257), nbags=(1, 2, 3, 4, 5), short_u=(True, False)),
+)
+
+
+def _sym(v, **names):
+    """the number behind a symbolic value such as "T+1" or "H" """
+    return int(eval(v, {"__builtins__": {}}, names)) if isinstance(v, str) else int(v)
+
+
+def _pick(rng, values):
+    return values[int(rng.integers(0, len(values)))]
+
+
+def _vehicles(rng, model, P):
+    pool = NAMES if model == 0 else WRENCH_NAMES
+    return [pool[int(i)] for i in rng.integers(0, len(pool), P)]
+
+
+def digest(cases):
+    """hash of a case list: what tests/test_sweep_cases_cpu.py pins"""
+    return hashlib.sha256(json.dumps(cases, sort_keys=True).encode()).hexdigest()[:16]
+
+
+# ------------------------------------------------------------------------------------------ population rollouts
+def _rollout_pop(rng, model, integ, lag_mode, P, B, T, stride, store, per_candidate, lag):
+    """stride as a symbol of T; lag_mode 1 is the thruster model's under RK4 only, a lag the thruster model's only"""
+    T = int(T)
+    return dict(family="rollout_pop", model=model, integ=integ, lag_mode=lag_mode if (model == 0 and integ == "rk4") else 0, P=P, B=B, T=T,
+                stride=max(_sym(stride, T=T), 1), stride_as=stride, store=bool(store), per_candidate=bool(per_candidate),
+                lag=bool(lag and model == 0), names=_vehicles(rng, model, P), seed=int(rng.integers(0, 1 << 30)))
+
+
+ROLLOUT_POP_CORNERS = (
+    # model integ  lag_mode P  B    T   stride store  per_candidate lag
+    (0, "rk4", 0, 5, 64, 7, "1", True, True, True),            # B = 64 (the 64-lane blocks) with P = 5 and per-candidate inputs
+    (0, "rk4", 1, 2, 65, 7, "T+1", True, False, True),         # B = 65 (the 256-lane blocks) with a stride past the horizon
+    (0, "euler", 0, 2, 63, 0, "1", True, False, True),         # an empty horizon with a start lag
+    (1, "rk4", 0, 1, 1, 1, "1", True, False, False),
+    (2, "euler", 0, 2, 2, 2, "T", True, True, False),
+    (0, "euler", 0, 1, 255, 3, "2", False, False, False),
+    (1, "euler", 0, 5, 256, 3, "T", True, False, False),
+    (2, "rk4", 0, 2, 257, 2, "T+1", True, True, False),
+    (0, "rk4", 0, 1, 300, 65, "2", True, False, True),
+    (0, "rk4", 1, 2, 64, 65, "T", False, True, False),
+    (1, "rk4", 0, 5, 1, 7, "T", True, True, False),
+    (2, "rk4", 0, 1, 65, 1, "2", False, False, False),
+)
+
+
+def draw_rollout_pop(rng):
+    s = SETS["rollout_pop"]
+    T = _pick(rng, s["T"])
+    return _rollout_pop(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["lag_mode"]), _pick(rng, s["P"]), _pick(rng, s["B"]),
+                        T, _pick(rng, s["stride"]) if T else "1", _pick(rng, s["store"]), _pick(rng, s["per_candidate"]), _pick(rng, s["lag"]))
+
+
+# ------------------------------------------------------------------------------------------ closed-loop rollouts
+def _feedback(rng, model, integ, lag_mode, P, B, T, hold, ref, u_ff, z, lag, gain_sets, stride, store):
+    """hold and stride as symbols of T; T = 0 takes a set-point (ref_rows must be 1 or T)"""
+    T = int(T)
+    return dict(family="feedback", model=model, integ=integ, lag_mode=lag_mode if (model == 0 and integ == "rk4") else 0, P=P, B=B, T=T,
+                hold=_sym(hold, T=T), hold_as=hold, ref="set" if T == 0 else ref, u_ff=bool(u_ff), z=bool(z), lag=bool(lag and model == 0),
+                gain_sets=bool(gain_sets), stride=max(_sym(stride, T=T), 1), stride_as=stride, store=bool(store),
+                names=_vehicles(rng, model, P), seed=int(rng.integers(0, 1 << 30)))
+
+
+FEEDBACK_CORNERS = (
+    # model integ lag_mode P  B    T    hold   ref    u_ff   z      lag    gain_sets stride store
+    (0, "rk4", 0, 5, 64, 7, "5", "T", True, True, True, True, "1", True),
+    (0, "rk4", 1, 2, 65, 24, "T+1", "set", False, False, False, False, "T+1", True),
+    (0, "euler", 0, 2, 63, 0, "1", "set", False, True, True, False, "1", True),
+    (1, "rk4", 0, 1, 1, 1, "1", "T", True, False, False, False, "1", True),
+    (2, "euler", 0, 2, 2, 2, "2", "set", True, True, False, True, "T", True),
+    (0, "euler", 0, 1, 255, 3, "3", "T", False, True, True, False, "2", False),
+    (1, "euler", 0, 5, 256, 3, "T+1", "T", True, True, False, True, "T", True),
+    (2, "rk4", 0, 2, 257, 65, "5", "T", True, False, False, False, "T+1", True),
+    (0, "rk4", 0, 1, 300, 130, "3", "T", True, True, True, False, "2", True),
+    (0, "rk4", 1, 2, 64, 65, "2", "set", True, True, False, True, "T", False),
+    (1, "rk4", 0, 5, 1, 7, "T+1", "set", False, False, False, True, "T", True),
+    (2, "rk4", 0, 1, 65, 24, "5", "T", True, True, False, False, "2", False),
+)
+
+
+def draw_feedback(rng):
+    s = SETS["feedback"]
+    T = _pick(rng, s["T"])
+    return _feedback(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["lag_mode"]), _pick(rng, s["P"]), _pick(rng, s["B"]), T,
+                     _pick(rng, s["hold"]), _pick(rng, s["ref"]), _pick(rng, s["u_ff"]), _pick(rng, s["z"]), _pick(rng, s["lag"]),
+                     _pick(rng, s["gain_sets"]), _pick(rng, s["stride"]) if T else "1", _pick(rng, s["store"]))
+
+
+# ------------------------------------------------------------------------------------------ MPPI with the Fossen model
+def _window(rng, rows, H):
+    """(reference rows, ref_row0): a set-point, or a window drawn over its whole legal range 0 .. rows - 1 - H"""
+    n = _sym(rows, H=H)
+    return n, (0 if n == 1 else int(rng.integers(0, n - H)))
+
+
+def _mppi(rng, model, integ, lag_mode, B, nparams, K, H, hold, rows, shift, eps):
+    hold_n = _sym(hold, H=H)
+    rows_n, row0 = _window(rng, rows, H)
+    nu = 8 if model == 0 else 6
+    return dict(family="mppi", model=model, integ=integ, lag_mode=lag_mode if (model == 0 and integ == "rk4") else 0, B=B,
+                nparams=_sym(nparams, B=B), K=K, H=H, hold=hold_n, hold_as=hold, M=(H + hold_n - 1) // hold_n, rows=rows_n, rows_as=rows,
+                row0=row0, shift=bool(shift), eps=bool(eps), stream_seed=int(rng.integers(0, 1 << 40)), sigma0=int(rng.integers(0, nu)),
+                names=_vehicles(rng, model, _sym(nparams, B=B)), seed=int(rng.integers(0, 1 << 30)))
+
+
+MPPI_CORNERS = (
+    # model integ lag_mode B nparams K    H   hold   rows    shift  eps
+    (0, "rk4", 0, 2, "B", 300, 7, "H", "H+4", True, True),       # M = 1 with the shift
+    (0, "rk4", 1, 3, "B", 513, 5, "2", "H+1", False, False),     # three trips of the update's stride loop, the seeded stream, B = 3
+    (0, "euler", 0, 3, "1", 64, 12, "3", "1", True, True),       # K = 64 and 65 under Euler: both block sizes
+    (1, "euler", 0, 2, "B", 65, 12, "H+2", "H+4", True, False),
+    (2, "rk4", 0, 1, "1", 1, 1, "1", "1", False, True),
+    (1, "rk4", 0, 2, "1", 2, 2, "2", "H+1", True, True),
+    (2, "euler", 0, 3, "B", 63, 2, "1", "H+4", False, False),
+    (0, "rk4", 0, 1, "B", 255, 5, "3", "H+1", True, False),
+    (1, "rk4", 0, 3, "B", 256, 7, "2", "1", False, True),
+    (2, "rk4", 0, 2, "B", 257, 5, "H+2", "H+4", True, False),
+    (0, "euler", 0, 2, "1", 513, 1, "H", "H+1", True, True),
+    (0, "rk4", 1, 3, "B", 65, 7, "3", "H+4", False, True),
+)
+
+
+def draw_mppi(rng):
+    s = SETS["mppi"]
+    return _mppi(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["lag_mode"]), _pick(rng, s["B"]), _pick(rng, s["nparams"]),
+                 _pick(rng, s["K"]), _pick(rng, s["H"]), _pick(rng, s["hold"]), _pick(rng, s["rows"]), _pick(rng, s["shift"]), _pick(rng, s["eps"]))
+
+
+# ------------------------------------------------------------------------------------------ MPPI with a Koopman model
+# (H, hold) for every M: full last knots and partial ones
+KOOPMAN_KNOTS = {1: ((1, 1), (3, 5)), 5: ((5, 1), (9, 2)), 6: ((6, 1), (11, 2)), 7: ((7, 1), (13, 2)), 9: ((9, 1), (17, 2)),
+                 10: ((10, 1), (28, 3)), 12: ((12, 1), (23, 2)), 13: ((13, 1), (25, 2)), 14: ((14, 1), (27, 2))}
+
+
+def _koopman_mppi(rng, n, r, k, Mr, K, B, rows, shift, eps, partial):
+    """Mr = M r picks the number of knots; partial: the (H, hold) whose last knot is cut short"""
+    assert Mr % r == 0, (Mr, r)
+    M = Mr // r
+    H, hold = KOOPMAN_KNOTS[M][1 if partial else 0]
+    rows_n, row0 = _window(rng, rows, H)
+    return dict(family="koopman_mppi", n=n, r=r, k=k, Mr=Mr, M=M, H=H, hold=hold, K=K, B=B, rows=rows_n, rows_as=rows, row0=row0,
+                shift=bool(shift), eps=bool(eps), stream_seed=int(rng.integers(0, 1 << 40)), sigma0=int(rng.integers(0, r)),
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+KOOPMAN_MPPI_CORNERS = (
+    # n   r  k   Mr  K    B  rows    shift  eps    partial
+    (12, 6, 0, 6, 1, 1, "1", True, True, False),                  # M = 1 with the shift, one sample
+    (13, 8, 5, 8, 63, 2, "H+1", False, False, True),
+    (12, 6, 20, 36, 300, 3, "H+4", True, False, False),           # 256 lanes, the seeded stream, B = 3
+    (13, 8, 20, 40, 65, 2, "H+4", False, True, True),             # M r = 40: 128 lanes
+    (13, 6, 5, 42, 127, 3, "H+1", True, True, False),
+    (12, 8, 0, 72, 128, 1, "1", False, False, True),
+    (13, 6, 20, 78, 129, 2, "H+4", True, True, True),             # M r = 78: the last of the 128-lane sizes
+    (12, 8, 5, 80, 255, 3, "H+1", False, True, False),            # M r = 80: 64 lanes at K > 64, dynamic LDS
+    (13, 6, 0, 84, 256, 2, "1", True, False, True),
+    (12, 6, 5, 72, 257, 1, "H+4", False, True, False),
+    (13, 8, 0, 80, 64, 3, "H+1", True, True, True),               # K = 64: 64 lanes whatever M r
+    (12, 6, 20, 78, 300, 2, "H+1", False, False, False),
+)
+
+
+def draw_koopman_mppi(rng):
+    s = SETS["koopman_mppi"]
+    r = _pick(rng, s["r"])
+    return _koopman_mppi(rng, _pick(rng, s["n"]), r, _pick(rng, s["k"]), _pick(rng, [v for v in s["Mr"] if v % r == 0]), _pick(rng, s["K"]),
+                         _pick(rng, s["B"]), _pick(rng, s["rows"]), _pick(rng, s["shift"]), _pick(rng, s["eps"]), bool(rng.integers(0, 2)))
+
+
+# ------------------------------------------------------------------------------------------ population window evaluator
+def _window_pop(rng, model, integ, carry, P, H, lens, bags, short_u):
+    """lens: rows per bag (symbols of H); bags False: one recording through the plain entry point.  The windows of a bag number
+    max(L - H, 0), counted bag after bag."""
+    L = [_sym(v, H=H) for v in lens]
+    assert bags or len(L) == 1
+    pool = NAMES if model == 0 else WRENCH_NAMES
+    first = int(rng.integers(0, len(pool)))
+    return dict(family="window_pop", model=model, integ=integ, carry=bool(carry), P=P, H=H, lens=L, nwin=sum(max(v - H, 0) for v in L),
+                bags=bool(bags), short_u=bool(short_u), names=[pool[(first + j) % len(pool)] for j in range(P)],
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+WINDOW_POP_CORNERS = (
+    # model integ carry P  H   lens                                  bags   short_u
+    (0, "rk4", True, 2, 5, ("H+64", "0", "H+1"), True, False),                 # a join on the edge of a scan chunk, an empty bag: 65 windows
+    (0, "euler", True, 9, 1, ("H+1",), False, True),                           # one window
+    (0, "rk4", False, 1, 2, ("H+2",), True, False),                            # one bag through the ragged entry point: 2 windows
+    (1, "rk4", True, 2, 12, ("H+63",), False, False),
+    (2, "euler", False, 9, 5, ("H+64",), False, True),
+    (0, "rk4", True, 1, 12, ("1", "H", "H+65", "H+62", "0"), True, True),      # bags without a window first: 127 windows in five bags
+    (0, "euler", True, 2, 2, ("H+128",), False, False),
+    (0, "rk4", True, 2, 1, ("H+64", "H+65"), True, True),                      # 129 windows, the join on a chunk edge
+    (0, "rk4", True, 2, 5, ("H+257",), False, False),
+    (1, "euler", True, 1, 2, ("H+1", "H", "H+64", "H+63"), True, False),       # 128 windows in four bags
+    (2, "rk4", True, 2, 12, ("H+65", "H+64", "H+128"), True, True),            # 257 windows, joins at 65 and 129
+    (0, "rk4", True, 9, 5, ("H+63", "H+1"), True, False),                      # 64 windows, a join inside the first chunk
+)
+
+WINDOW_BAG_LENS = ("0", "1", "H", "H+1", "H+2", "H+63", "H+64", "H+65")
+
+
+def draw_window_pop(rng):
+    s = SETS["window_pop"]
+    H = _pick(rng, s["H"])
+    bags = bool(rng.integers(0, 2))
+    if bags:
+        lens = [_pick(rng, WINDOW_BAG_LENS) for _ in range(_pick(rng, s["nbags"]))]
+        if all(_sym(v, H=H) <= H for v in lens):
+            lens[int(rng.integers(0, len(lens)))] = "H+64"                     # a case keeps at least one window
+    else:
+        lens = ["H+%d" % _pick(rng, s["nwin"])]
+    return _window_pop(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["carry"]), _pick(rng, s["P"]), H, lens, bags,
+                       _pick(rng, s["short_u"]))
+
+
+# ------------------------------------------------------------------------------------------ the lists
+_MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
+             mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
+             window_pop=(_window_pop, WINDOW_POP_CORNERS, draw_window_pop))
+FAMILIES = tuple(_MAKE)
+
+
+def corners(family, seed=SEED):
+    make, rows, _ = _MAKE[family]
+    rng = np.random.default_rng([seed, FAMILIES.index(family), 0])
+    return [make(rng, *row) for row in rows]
+
+
+def cases(family, seed=SEED, n=N_CASES):
+    """the corner list, then seeded draws up to n cases"""
+    out = corners(family, seed)
+    rng = np.random.default_rng([seed, FAMILIES.index(family), 1])
+    while len(out) < n:
+        out.append(_MAKE[family][2](rng))
+    return out
+
+
+def rollout_pop(seed=SEED):
+    return cases("rollout_pop", seed)
+
+
+def feedback(seed=SEED):
+    return cases("feedback", seed)
+
+
+def mppi(seed=SEED):
+    return cases("mppi", seed)
+
+
+def koopman_mppi(seed=SEED):
+    return cases("koopman_mppi", seed)
+
+
+def window_pop(seed=SEED):
+    return cases("window_pop", seed)
