@@ -1,5 +1,5 @@
-"""Case lists of the shape sweeps over the population-rollout, closed-loop, MPPI, Koopman-MPPI and population-window kernels.
-Not collected; pure NumPy; imports no GPU code.
+"""Case lists of the shape sweeps over the population-rollout, closed-loop, MPPI, Koopman-MPPI and population-window kernels, and over
+the EDMDc kernels (lift, Gram, pinv_apply, the two multistep evaluators, simulate).  Not collected; pure NumPy; imports no GPU code.
 
 One generator per family: NAME(seed) returns an ordered list of plain dicts (ints, bools, strings and lists of them), the
 hand-written corner list first, then seeded random draws from the family's value sets.  The lists depend on the seed alone, never on
@@ -10,7 +10,9 @@ tests/stress_parity.py calls with its own generator.
 The value sets are the smallest shapes at which the kernels' grid rules, knot arithmetic, counter addressing and reductions can go
 wrong: both sides of every block edge (64 lanes when B or K <= 64, 256 otherwise; 64 / 128 / 256 lanes by M nu in the Koopman cost
 kernel), partial and full last knots, hold >= H, a set-point against a reference window, more than one trip of the 256-wide
-strided loops (K = 513), the 64-window chunks of the lag scan."""
+strided loops (K = 513), the 64-window chunks of the lag scan.  The EDMDc families (second half of the file) add the 64-row / 256-centre
+blocks of the lift, every tile count of the Gram's task packing, bags and chunk edges, the 192-row unit of the apply pass, window
+blocks of 128 with the two-stream split from 16 blocks on, and both parities of the propagation's K-steps."""
 import hashlib
 import json
 
@@ -19,6 +21,7 @@ import numpy as np
 NAMES = ("V0", "V1", "V2", "V3", "V4", "V5", "V6", "V7", "V8")      # tests/fossen_vehicles.py: NAMES
 WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/fossen_vehicles.py: WRENCH_NAMES
 N_CASES = 48                                                        # per family: four slices of 12
+N_CASES_EDMDC = 32                                                  # per EDMDc family: four slices of 8 (corner lists of 12 to 24)
 SEED = 2024
 
 SETS = dict(
@@ -36,6 +39,16 @@ SETS = dict(
                       eps=(True, False)),
     window_pop=dict(model=(0, 1, 2), integ=("euler", "rk4"), carry=(True, False), P=(1, 2, 9), H=(1, 2, 5, 12),
                     nwin=(1, 2, 63, 64, 65, 127, 128, 129, 257), nbags=(1, 2, 3, 4, 5), short_u=(True, False)),
+    lift=dict(N=(1, 63, 64, 65, 130), k=(1, 255, 256, 257, 513), n=(1, 5, 12, 13, 16), gamma=(0.3, 3.0), scale=(0.5, 3.0, 12.0)),
+    gram=dict(nr=((12, 8), (13, 8), (12, 10), (13, 6), (9, 4), (5, 2), (12, 0), (12, 1)),
+              k=(1, 15, 16, 17, 31, 32, 33, 48, 64, 80, 96, 112, 160, 257, 512, 513), gamma=(0.3, 1.0, 3.0),
+              form=("host", "ragged_dev", "uniform_dev"), gty=(True, False), chunk=(64, 100, 257, 0), short_u=(True, False)),
+    pinv_apply=dict(nr=((12, 8), (12, 6), (13, 6), (9, 4), (5, 2), (13, 8)), k=(1, 7, 16, 17, 48, 64, 80, 96, 100, 160, 257, 512, 530),
+                    gamma=(0.3, 1.0, 3.0), form=("host", "ragged_dev", "uniform_dev"), chunk=(64, 192, 257)),
+    multistep=dict(shape=((1, 1, 1), (2, 3, 3), (12, 35, 8), (12, 36, 9), (13, 36, 6), (12, 83, 8), (13, 84, 8), (12, 8, 0), (5, 8, 2), (9, 4, 6)),
+                   nw=(0, 1, 127, 128, 129, 255, 256, 257, 1920, 1921, 2176), H=(0, 1, 2, 3, 7), short_u=(True, False)),
+    simulate=dict(shape=((1, 1, 1), (2, 3, 3), (12, 35, 8), (12, 36, 9), (13, 36, 6), (12, 83, 8), (13, 84, 8), (12, 8, 0), (5, 8, 2), (9, 4, 6)),
+                  nb=(1, 2, 127, 128, 129, 255, 256, 257, 300), T=(0, 1, 2, 3, 7, 50)),
 )
 
 
@@ -253,11 +266,243 @@ def draw_window_pop(rng):
                        _pick(rng, s["short_u"]))
 
 
+# ------------------------------------------------------------------------------------------ EDMDc: lift
+def _lift(rng, N, k, n, gamma, scale):
+    """scale: the rows are uniform in +- scale; 12 puts every row far from every centre (|x_j| in 6 .. 12, the centres in +-0.5)"""
+    return dict(family="lift", N=N, k=k, n=n, gamma=gamma, scale=scale, seed=int(rng.integers(0, 1 << 30)))
+
+
+LIFT_CORNERS = (
+    # N   k    n   gamma scale
+    (1, 1, 1, 0.3, 0.5),
+    (63, 255, 5, 3.0, 0.5),                # below both block edges; the runtime-n instantiation
+    (64, 256, 12, 0.3, 0.5),               # one block each way, <12>
+    (65, 257, 13, 3.0, 0.5),               # two blocks each way, <13>
+    (130, 513, 16, 0.3, 0.5),              # three blocks each way, n = LIFT_NMAX
+    (130, 257, 12, 3.0, 12.0),             # far from every centre: the clamped ldexp of exp_fast
+    (65, 513, 13, 0.3, 3.0),               # values down to the denormals
+    (1, 513, 12, 3.0, 0.5),
+    (130, 1, 5, 0.3, 3.0),
+    (64, 255, 16, 3.0, 3.0),
+    (63, 256, 1, 3.0, 12.0),
+    (65, 257, 12, 0.3, 0.5),
+)
+
+
+def draw_lift(rng):
+    """one row against one centre is a single value, whose float64-to-long-double gap says nothing about the size of the error at its
+    exponent (it can be 0 by chance) although the relative bound is a multiple of it: that draw takes 63 rows.  The corner list keeps
+    N = k = n = 1 at scale 0.5, where the exponent is below 0.3 and the 2^-50 of the bound covers any rounding of it."""
+    s = SETS["lift"]
+    N, k = _pick(rng, s["N"]), _pick(rng, s["k"])
+    return _lift(rng, 63 if N * k == 1 else N, k, _pick(rng, s["n"]), _pick(rng, s["gamma"]), _pick(rng, s["scale"]))
+
+
+# ------------------------------------------------------------------------------------------ EDMDc: Gram and pinv_apply
+def tiles(n, r, k):
+    """(nt = lifted-row width / 16, xplus) of csrc/brov2_kernels.h: edmdc_shape -- what the task packing depends on"""
+    tailp = (n + r + 15) // 16 * 16
+    return ((k + 15) // 16 * 16 + tailp) // 16, int(n + r + n <= tailp)
+
+
+def chunk_rows(chunk, lens, xpad=0):
+    """the rows per lifted chunk that gram_core / apply_core use: the setting rounded up to 4, at most the rows that can start a pair"""
+    rows = sum(lens) + xpad * (len(lens) - 1)
+    top = max((max(rows - 1, 0) + 3) // 4 * 4, 4)
+    return min((chunk + 3) // 4 * 4, top) if chunk else top
+
+
+def bag_ends(lens):
+    """row index one past the last row of every bag that has a row"""
+    return [e for e, m in zip(np.cumsum(lens).tolist(), lens) if m]
+
+
+def _bags(rng, family, n, r, k, gamma, form, gty, lens, xpad, upad, chunk, short_u, split):
+    """lens: state rows per bag (uniform_dev: all equal, L + 1); xpad / upad: rows between the bags of the uniform layout beyond L + 1 / L;
+    chunk: edmdc_set_chunk_rows (0 = the default); short_u: the inputs of the last bag one row shorter than its states (list forms);
+    split: bags in the first of two accumulate calls (device forms of the Gram; 0 = one call)"""
+    lens = [int(v) for v in lens]
+    uniform = form == "uniform_dev"
+    assert not uniform or (len(set(lens)) == 1 and lens[0] >= 1), lens
+    assert 0 <= split < max(len(lens), 1) and (split == 0 or (form != "host" and family == "gram"))
+    nt, xplus = tiles(n, r, k)
+    return dict(family=family, n=n, r=r, k=k, gamma=gamma, form=form, gty=bool(gty or form == "host" or family == "pinv_apply"), lens=lens,
+                xpad=xpad if uniform else 0, upad=upad if uniform else 0, chunk=chunk, short_u=bool(short_u and not uniform and lens[-1] >= 1),
+                split=split, pairs=sum(max(v - 1, 0) for v in lens), nt=nt, xplus=xplus, seed=int(rng.integers(0, 1 << 30)))
+
+
+def _gram(rng, n, r, k, gamma, form, gty, lens, xpad, upad, chunk, short_u, split):
+    return _bags(rng, "gram", n, r, k, gamma, form, gty, lens, xpad, upad, chunk, short_u, split)
+
+
+GRAM_CORNERS = (
+    # n   r   k    gamma form          gty    lens                             xpad upad chunk short_u split
+    (12, 8, 1, 1.0, "host", True, (0, 5, 1, 2, 3), 0, 0, 0, False, 0),                  # bags of 0 .. 3 rows first, last, in the middle
+    (13, 8, 15, 0.3, "host", True, (1, 4, 0, 3, 2), 0, 0, 64, True, 0),
+    (12, 10, 16, 3.0, "ragged_dev", True, (2, 6, 3, 0, 1), 0, 0, 100, False, 2),
+    (13, 6, 17, 1.0, "ragged_dev", False, (3, 2, 7, 1, 0), 0, 0, 257, False, 0),        # G^T G alone over a ragged list
+    (9, 4, 31, 0.3, "uniform_dev", True, (9,) * 4, 0, 0, 0, False, 2),                  # strides L + 1 / L, two halves
+    (5, 2, 32, 3.0, "uniform_dev", True, (9,) * 5, 3, 2, 64, False, 2),                 # larger strides, uneven halves
+    (12, 0, 33, 1.0, "host", True, (20, 1, 13), 0, 0, 0, False, 0),                     # r = 0
+    (12, 1, 48, 0.3, "uniform_dev", False, (17,) * 3, 2, 0, 64, False, 0),              # r = 1; G^T G alone over a uniform layout
+    (12, 8, 64, 1.0, "host", True, (64, 63, 66, 5), 0, 0, 64, False, 0),                # bags ending on, one before, one after a chunk's last row
+    (13, 8, 80, 3.0, "host", True, (5,) + (1,) * 130 + (7,), 0, 0, 64, False, 0),       # a chunk that holds no pair
+    (12, 10, 96, 0.3, "ragged_dev", True, (65, 36), 0, 0, 64, True, 1),                 # a pair across the chunk edge; a short U
+    (13, 6, 112, 1.0, "ragged_dev", False, (100, 1, 0, 99), 0, 0, 100, False, 0),       # bags of 1 and 0 rows behind a chunk edge
+    (9, 4, 160, 3.0, "host", True, (40, 30), 0, 0, 0, True, 0),
+    (5, 2, 257, 0.3, "host", True, (30, 25), 0, 0, 0, False, 0),
+    (12, 8, 512, 1.0, "uniform_dev", True, (12,) * 2, 0, 0, 0, False, 1),
+    (13, 8, 513, 3.0, "host", True, (14, 9), 0, 0, 64, False, 0),
+    (12, 8, 16, 1.0, "host", True, (2,), 0, 0, 0, False, 0),                            # one pair: fewer rows than K-slabs
+    (13, 6, 17, 0.3, "ragged_dev", True, (2, 0, 2), 0, 0, 64, False, 0),                # two pairs
+    (9, 4, 1, 3.0, "uniform_dev", True, (2,) * 3, 1, 1, 0, False, 1),                   # three pairs
+    (12, 10, 512, 0.3, "ragged_dev", False, (10, 11), 0, 0, 0, False, 0),
+    (13, 8, 257, 1.0, "uniform_dev", False, (8,) * 3, 0, 3, 0, False, 0),
+    (12, 8, 33, 1.0, "host", True, (63, 1, 0, 64, 0, 1, 66), 0, 0, 64, True, 0),        # bags of 0 and 1 rows on both sides of chunk edges
+    (5, 2, 48, 1.0, "host", True, (260, 259, 262, 4), 0, 0, 257, False, 0),             # chunk 257 (260 rows): on, before, after
+    (13, 6, 64, 0.3, "ragged_dev", True, (100, 99, 102, 4), 0, 0, 100, False, 3),       # chunk 100: on, before, after
+)
+
+GRAM_LENS = (0, 1, 2, 3, 5, 33, 63, 64, 65, 100)
+
+
+def _draw_bags(rng, k, form, lens_set):
+    """a bag list whose long-double reference stays cheap: few rows where k is large"""
+    small = tuple(v for v in lens_set if v <= 12)
+    if form == "uniform_dev":
+        lens = [_pick(rng, [v for v in (small if k > 160 else lens_set) if v >= 2])] * int(rng.integers(1, 6))
+    else:
+        lens = [_pick(rng, small if k > 160 else lens_set) for _ in range(int(rng.integers(1, 6)))]
+        if max(lens) < 2:
+            lens[int(rng.integers(0, len(lens)))] = 5
+    return lens
+
+
+def draw_gram(rng):
+    s = SETS["gram"]
+    (n, r), k, form = _pick(rng, s["nr"]), _pick(rng, s["k"]), _pick(rng, s["form"])
+    lens = _draw_bags(rng, k, form, GRAM_LENS)
+    split = int(rng.integers(0, len(lens))) if form != "host" else 0
+    return _gram(rng, n, r, k, _pick(rng, s["gamma"]), form, _pick(rng, s["gty"]), lens, int(rng.integers(0, 4)), int(rng.integers(0, 4)),
+                 _pick(rng, s["chunk"]), _pick(rng, s["short_u"]), split)
+
+
+def _pinv_apply(rng, n, r, k, gamma, form, lens, xpad, upad, chunk):
+    return _bags(rng, "pinv_apply", n, r, k, gamma, form, True, lens, xpad, upad, chunk, False, 0)
+
+
+PINV_APPLY_CORNERS = (
+    # n   r  k    gamma form          lens              xpad upad chunk
+    (12, 8, 1, 1.0, "host", (2, 3), 0, 0, 64),
+    (12, 6, 7, 0.3, "host", (192,), 0, 0, 192),                    # one 192-row unit, one chunk
+    (13, 6, 16, 3.0, "ragged_dev", (193, 2), 0, 0, 192),
+    (9, 4, 17, 1.0, "uniform_dev", (193,) * 2, 0, 0, 64),
+    (5, 2, 48, 0.3, "uniform_dev", (3,) * 3, 2, 1, 257),
+    (13, 8, 64, 3.0, "host", (257, 3), 0, 0, 64),
+    (12, 8, 80, 1.0, "ragged_dev", (192, 193), 0, 0, 257),
+    (12, 6, 96, 0.3, "host", (3, 2, 12), 0, 0, 192),
+    (13, 6, 100, 3.0, "uniform_dev", (12,) * 2, 0, 3, 64),
+    (9, 4, 160, 1.0, "host", (2, 12, 3), 0, 0, 257),
+    (5, 2, 257, 0.3, "ragged_dev", (12, 3), 0, 0, 64),
+    (13, 8, 512, 3.0, "host", (12,), 0, 0, 192),
+    (12, 8, 530, 1.0, "uniform_dev", (3,) * 4, 0, 0, 257),
+    (12, 8, 17, 1.0, "host", (257, 192, 2), 0, 0, 192),
+)
+
+PINV_APPLY_LENS = (2, 3, 12, 192, 193, 257)
+
+
+def draw_pinv_apply(rng):
+    s = SETS["pinv_apply"]
+    (n, r), k, form = _pick(rng, s["nr"]), _pick(rng, s["k"]), _pick(rng, s["form"])
+    lens = _draw_bags(rng, k, form, PINV_APPLY_LENS)[:3]
+    return _pinv_apply(rng, n, r, k, _pick(rng, s["gamma"]), form, lens, int(rng.integers(0, 4)), int(rng.integers(0, 4)), _pick(rng, s["chunk"]))
+
+
+# ------------------------------------------------------------------------------------------ EDMDc: multistep evaluators and simulate
+def _prop(n, k, r):
+    """(d, K-steps of propagate_kernel = ceil((n + k + r) / 4))"""
+    return n + k, (n + k + r + 3) // 4
+
+
+def _multistep(rng, shape, nw, H, short_u):
+    """nw windows of horizon H over N = nw + H rows; nw = 0: H >= N (three rows at most), where the evaluators return 0"""
+    n, k, r = shape
+    H = max(H, 1) if nw == 0 else H
+    d, ksteps = _prop(n, k, r)
+    return dict(family="multistep", n=n, k=k, r=r, d=d, ksteps=ksteps, nw=nw, H=H, N=nw + H if nw else min(H, 3), short_u=bool(short_u),
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+MULTISTEP_CORNERS = (
+    # (n, k, r)     nw    H  short_u
+    ((1, 1, 1), 1, 0, False),              # one K-step, H = 0, one window
+    ((2, 3, 3), 127, 1, True),             # two K-steps
+    ((12, 35, 8), 128, 2, False),          # d = 47
+    ((12, 36, 9), 129, 3, True),           # d = 48, 15 K-steps: the odd tail
+    ((13, 36, 6), 255, 7, False),          # d = 49
+    ((12, 83, 8), 256, 2, False),          # d = 95
+    ((13, 84, 8), 257, 3, True),           # d = 97, 27 K-steps
+    ((12, 8, 0), 129, 7, False),           # r = 0
+    ((5, 8, 2), 1920, 7, False),           # 15 window blocks: one stream
+    ((9, 4, 6), 1921, 2, True),            # 16 blocks: two streams; odd K-steps, even H
+    ((5, 8, 2), 2176, 3, False),           # 17 blocks: 8 + 9; even K-steps, odd H
+    ((9, 4, 6), 0, 7, False),              # H >= N
+    ((1, 1, 1), 2176, 2, True),            # one K-step on two streams
+    ((12, 8, 0), 1, 1, True),
+)
+
+
+def draw_multistep(rng):
+    s = SETS["multistep"]
+    shape, nw = _pick(rng, s["shape"]), _pick(rng, s["nw"])
+    if nw > 257 and shape[0] + shape[1] > 20:                      # the long-double reference: many windows go with a small d
+        shape = (5, 8, 2)
+    return _multistep(rng, shape, nw, _pick(rng, s["H"]), _pick(rng, s["short_u"]))
+
+
+def _simulate(rng, shape, nb, T):
+    n, k, r = shape
+    d, ksteps = _prop(n, k, r)
+    return dict(family="simulate", n=n, k=k, r=r, d=d, ksteps=ksteps, nb=nb, T=T, seed=int(rng.integers(0, 1 << 30)))
+
+
+SIMULATE_CORNERS = (
+    # (n, k, r)     nb   T
+    ((1, 1, 1), 1, 0),
+    ((2, 3, 3), 2, 1),
+    ((12, 35, 8), 127, 2),
+    ((12, 36, 9), 128, 3),
+    ((13, 36, 6), 129, 7),
+    ((12, 83, 8), 255, 2),
+    ((13, 84, 8), 256, 3),
+    ((12, 8, 0), 257, 7),                  # r = 0, a third block
+    ((5, 8, 2), 300, 50),
+    ((9, 4, 6), 257, 50),
+    ((12, 8, 0), 300, 1),
+    ((1, 1, 1), 129, 50),
+)
+
+
+def draw_simulate(rng):
+    s = SETS["simulate"]
+    shape, T = _pick(rng, s["shape"]), _pick(rng, s["T"])
+    if T == 50 and shape[0] + shape[1] > 20:                       # the long-double reference: a long horizon goes with a small d
+        T = 7
+    return _simulate(rng, shape, _pick(rng, s["nb"]), T)
+
+
 # ------------------------------------------------------------------------------------------ the lists
 _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
              mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
-             window_pop=(_window_pop, WINDOW_POP_CORNERS, draw_window_pop))
-FAMILIES = tuple(_MAKE)
+             window_pop=(_window_pop, WINDOW_POP_CORNERS, draw_window_pop),
+             lift=(_lift, LIFT_CORNERS, draw_lift), gram=(_gram, GRAM_CORNERS, draw_gram),
+             pinv_apply=(_pinv_apply, PINV_APPLY_CORNERS, draw_pinv_apply), multistep=(_multistep, MULTISTEP_CORNERS, draw_multistep),
+             simulate=(_simulate, SIMULATE_CORNERS, draw_simulate))
+FAMILIES = tuple(_MAKE)                                             # the order is part of the seeds: new families go last
+EDMDC_FAMILIES = ("lift", "gram", "pinv_apply", "multistep", "simulate")
+N_CORNERS = {f: len(_MAKE[f][1]) for f in FAMILIES}                 # 12 for the five older families
+N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES for f in FAMILIES}
 
 
 def corners(family, seed=SEED):
@@ -266,8 +511,9 @@ def corners(family, seed=SEED):
     return [make(rng, *row) for row in rows]
 
 
-def cases(family, seed=SEED, n=N_CASES):
-    """the corner list, then seeded draws up to n cases"""
+def cases(family, seed=SEED, n=None):
+    """the corner list, then seeded draws up to n cases (N_CASES_OF[family] unless given)"""
+    n = N_CASES_OF[family] if n is None else n
     out = corners(family, seed)
     rng = np.random.default_rng([seed, FAMILIES.index(family), 1])
     while len(out) < n:
@@ -293,3 +539,23 @@ def koopman_mppi(seed=SEED):
 
 def window_pop(seed=SEED):
     return cases("window_pop", seed)
+
+
+def lift(seed=SEED):
+    return cases("lift", seed)
+
+
+def gram(seed=SEED):
+    return cases("gram", seed)
+
+
+def pinv_apply(seed=SEED):
+    return cases("pinv_apply", seed)
+
+
+def multistep(seed=SEED):
+    return cases("multistep", seed)
+
+
+def simulate(seed=SEED):
+    return cases("simulate", seed)

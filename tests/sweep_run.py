@@ -12,13 +12,17 @@ The recipe is that of the families' own test files: the mixed error max |a-b| / 
 TOL_ROLL = 1e-10; a lane is compared if the reference's own float64-to-long-double gap on it is below a tenth of the bound and
 its wrap and saturation margins exceed 1e-6 (conditions on the inputs, not measurements of the kernel).  Counts are exact.  The
 soft-min update is checked against a long-double soft-min of the kernel's OWN costs at 1e-12: a fixed-order sum of K <= 513 terms
-errs by at most 513 x 2^-53 = 6e-14 of sum |terms|.  Every assertion message carries the case dict."""
+errs by at most 513 x 2^-53 = 6e-14 of sum |terms|.  Every assertion message carries the case dict.
+
+The EDMDc families (lift, gram, pinv_apply, multistep, simulate) have their prepare / run / compare in tests/sweep_edmdc.py, with
+their own measures and bounds (a reference states its own gap condition as ref["gap_bound"]); PREPARE and sweep_one here cover them."""
 import numpy as np
 
 import feedback_ref as fr
 import fossen_vehicles as fv
 import koopman_mppi_ref as kr
 import mppi_ref as mr
+import sweep_edmdc as se
 from oracle import fossen_params as fp
 
 TOL_ROLL = 1e-10
@@ -68,7 +72,7 @@ def well_posed(case, ref):
     out = int(keep.size - keep.sum())
     assert keep.size > 0 and keep.any(), ("no lane left to compare", case)
     assert out <= CAP * keep.size, (f"{out} of {keep.size} lanes left out: inputs too hard for fp64", ref["gap_all"], case)
-    assert ref["gap"] < 0.1 * TOL_ROLL, ("reference gap on the compared lanes", ref["gap"], case)
+    assert ref["gap"] < ref.get("gap_bound", 0.1 * TOL_ROLL), ("reference gap on the compared lanes", ref["gap"], case)
     return out
 
 
@@ -393,15 +397,18 @@ def compare_window_pop(case, ref, got):
 
 
 PREPARE = dict(rollout_pop=prepare_rollout_pop, feedback=prepare_feedback, mppi=prepare_mppi, koopman_mppi=prepare_koopman_mppi,
-               window_pop=prepare_window_pop)
+               window_pop=prepare_window_pop, **se.PREPARE)
 
 
 def sweep_one(eng, ctx, case, ref=None):
-    """one case end to end: (worst kernel error, second figure: update / normal-equation error or 0, lanes left out, reference gap)"""
+    """one case end to end: (worst kernel error, second figure: update / normal-equation error or 0 -- for the EDMDc families what
+    sweep_edmdc.sweep_one says --, lanes left out, reference gap)"""
     fam = case["family"]
     ref = PREPARE[fam](case) if ref is None else ref
     out = well_posed(case, ref)
-    if fam == "rollout_pop":
+    if fam in se.PREPARE:
+        e, e2 = se.sweep_one(eng, ctx, case, ref)
+    elif fam == "rollout_pop":
         e, e2 = compare_rollout_pop(case, ref, run_rollout_pop(eng, ctx, case, ref)), 0.0
     elif fam == "feedback":
         e, e2 = compare_feedback(case, ref, run_feedback(eng, ctx, case, ref)), 0.0

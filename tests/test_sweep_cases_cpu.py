@@ -1,14 +1,28 @@
-"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the five families' value sets occurs in
+"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the ten families' value sets occurs in
 the hand-written corner list, by name, so that a list cannot shrink silently; (b) for every case the reference alone meets the
 conditions of tests/sweep_run.py (float64 against long double below a tenth of the bound on the compared lanes, at most 2 % of the
 lanes left out, never all), so that tests/test_family_sweeps_gpu.py can fail only because of a kernel; (c) the lists are a function
-of the seed alone and their hashes are pinned.  The vehicles come from tests/fossen_vehicles.py, which needs the built library."""
+of the seed alone and their hashes are pinned.  The vehicles come from tests/fossen_vehicles.py, which needs the built library.
+The EDMDc families' reference is oracle/edmdc_numpy.py restated with a dtype (tests/sweep_edmdc.py): (d) its float64 form is the
+oracle's bit for bit."""
+import numpy as np
 import pytest
 
 import sweep_cases as sc
 
 SLICES = 4
-PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52")
+PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52",
+              lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921")
+CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12)
+
+
+def _value(c, key):
+    """the value a case holds for a key of its family's value set"""
+    if key == "nr":
+        return (c["n"], c["r"])
+    if key == "shape":
+        return (c["n"], c["k"], c["r"])
+    return c.get(key + "_as", c.get(key))
 
 
 def _seen(family, key):
@@ -17,13 +31,14 @@ def _seen(family, key):
         return {len(c["lens"]) for c in cs}
     if family in ("mppi",) and key == "nparams":
         return {"1" if c["nparams"] == 1 and c["B"] > 1 else "B" if c["nparams"] == c["B"] and c["B"] > 1 else None for c in cs} - {None}
-    return {c.get(key + "_as", c.get(key)) for c in cs}
+    return {_value(c, key) for c in cs}
 
 
 # ------------------------------------------------------------------------------------------ (a) coverage
 @pytest.mark.parametrize("family", sc.FAMILIES)
 def test_every_value_is_in_the_corner_list(family):
-    assert len(sc.corners(family)) == 12 and len(sc.cases(family)) == sc.N_CASES
+    assert len(sc.corners(family)) == CORNERS[family] == sc.N_CORNERS[family], (family, len(sc.corners(family)))
+    assert len(sc.cases(family)) == (sc.N_CASES_EDMDC if family in sc.EDMDC_FAMILIES else sc.N_CASES)
     for key, values in sc.SETS[family].items():
         missing = set(values) - _seen(family, key)
         assert not missing, (family, key, "not in the corner list", missing)
@@ -32,7 +47,7 @@ def test_every_value_is_in_the_corner_list(family):
             if family == "window_pop" and key in ("nbags", "nwin"):      # a bag list: up to five bags of up to H + 65 rows each
                 assert (len(c["lens"]) in sc.SETS[family]["nbags"] and c["nwin"] <= 5 * 65) if c["bags"] else c["nwin"] in sc.SETS[family]["nwin"], c
             elif not (family == "mppi" and key == "nparams"):
-                assert c.get(key + "_as", c.get(key)) in values, (family, key, c)
+                assert _value(c, key) in values, (family, key, c)
 
 
 def _has(family, **want):
@@ -63,6 +78,75 @@ def test_corner_pairs():
     assert any(c["bags"] for c in w) and any(not c["bags"] for c in w)
 
 
+def _chunk_edges(c):
+    """(bag ends on a chunk's last row, one row before it, one row after it, chunks that hold no pair) of a list-form case"""
+    ch, lens = sc.chunk_rows(c["chunk"], c["lens"]), c["lens"]
+    ends = sc.bag_ends(lens)
+    starts = np.concatenate([[0], np.cumsum(lens)])[:-1]
+    pair = np.zeros(sum(lens), dtype=bool)                  # rows that start a pair
+    for a, m in zip(starts, lens):
+        pair[a:a + max(m - 1, 0)] = True
+    nchunks = -(-max(sum(lens) - 1, 0) // ch)
+    empty = sum(1 for i in range(nchunks) if not pair[i * ch:(i + 1) * ch].any())
+    at = lambda off: any(e > ch and (e + off) % ch == 0 for e in ends) or any(e + off == ch for e in ends)
+    return at(0), at(1), at(-1), empty
+
+
+def test_edmdc_corner_pairs():
+    """the edges the EDMDc corner lists must contain, by name"""
+    # lift: every instantiation, both block edges, the far corner
+    assert _has("lift", N=65, k=257, n=13) and _has("lift", N=64, k=256, n=12) and _has("lift", N=130, k=513, n=16) and _has("lift", n=5)
+    far = [c for c in sc.corners("lift") if c["scale"] == 12.0 and c["gamma"] == 3.0 and c["n"] == 12]
+    assert far, "rows far from every centre"
+    import sweep_edmdc as se
+    ref = se.prepare_lift(far[0])
+    assert ref["far"].all() and np.all(ref["o"][:, 12:] == 0.0) and float(ref["ol"][:, 12:].max()) < 1e-300, "the float64 reference is exactly 0"
+    assert float(np.log(ref["ol"][:, 12:].max())) < -1000, "exponents far beyond float64's underflow: the clamped ldexp of exp_fast"
+    # gram: the three forms, G^T G alone on both layouts, both strides, both xplus, r = 0 and 1, tile counts, bags, chunk edges
+    g = sc.corners("gram")
+    assert _has("gram", form="host") and _has("gram", form="ragged_dev", gty=False) and _has("gram", form="uniform_dev", gty=False)
+    assert any(c["form"] == "uniform_dev" and c["split"] and c["xpad"] == 0 and c["upad"] == 0 for c in g), "strides L + 1 / L, two halves"
+    assert any(c["form"] == "uniform_dev" and c["split"] and c["xpad"] > 0 and c["upad"] > 0 for c in g), "larger strides, two halves"
+    assert any(c["form"] == "ragged_dev" and c["split"] for c in g)
+    assert {(c["n"], c["r"]): c["xplus"] for c in g} == {(12, 8): 1, (13, 8): 0, (12, 10): 0, (13, 6): 1, (9, 4): 0, (5, 2): 1, (12, 0): 0, (12, 1): 0}
+    assert {c["nt"] for c in g} >= {2, 3, 4, 5, 6, 7, 8, 9, 11, 18, 34, 35}, sorted({c["nt"] for c in g})
+    assert {c["nt"] for c in g if not c["gty"]} >= {4, 9, 34} and {c["xplus"] for c in g if not c["gty"]} == {0, 1}
+    lists = [c for c in g if c["form"] != "uniform_dev"]
+    for m in (0, 1, 2, 3):
+        assert any(c["lens"][0] == m for c in lists) and any(c["lens"][-1] == m for c in lists) and any(m in c["lens"][1:-1] for c in lists), ("bag of rows", m)
+    for chunk in (64, 100, 257):
+        edges = [_chunk_edges(c) for c in lists if c["chunk"] == chunk]
+        assert any(e[0] for e in edges) and any(e[1] for e in edges) and any(e[2] for e in edges), ("bag ends on / before / after a chunk's last row", chunk)
+    assert any(_chunk_edges(c)[3] for c in lists if c["chunk"] == 64), "a chunk that holds no pair"
+    assert {c["pairs"] for c in g if c["k"] <= 17} >= {1, 2, 3}, "fewer pairs than K-slabs"
+    assert any(c["short_u"] and c["form"] == "host" for c in g) and any(c["short_u"] and c["form"] == "ragged_dev" for c in g)
+    assert any(c["chunk"] == 0 for c in g)
+    hard = [c for c in lists if c["chunk"] == 64 and (0 in c["lens"] or 1 in c["lens"])]
+    assert any(any(e % 64 in (0, 1, 63) for e in sc.bag_ends(c["lens"])) for c in hard), "bags of 0 or 1 rows next to a chunk edge"
+    # pinv_apply: the forms, the 192-row unit, every chunk size
+    a = sc.corners("pinv_apply")
+    assert {c["form"] for c in a} == {"host", "ragged_dev", "uniform_dev"} and {c["chunk"] for c in a} == {64, 192, 257}
+    assert {m for c in a for m in c["lens"]} >= {2, 3, 192, 193, 257}
+    assert {c["nt"] % 6 for c in a} == {0, 1, 2, 3, 4, 5}, "every nt mod 6 of the W-rows plan"
+    assert any(c["form"] == "uniform_dev" and c["xpad"] and c["upad"] for c in a) and any(c["form"] == "uniform_dev" and not c["xpad"] and not c["upad"] for c in a)
+    # multistep: window blocks, the two-stream edge, K-step parities, d around 48 and 96, r = 0, H >= N
+    m = sc.corners("multistep")
+    assert any(c["nw"] == 1920 and c["H"] > 1 for c in m) and any(c["nw"] == 1921 and c["H"] > 1 for c in m) and any(c["nw"] == 2176 and c["H"] > 1 for c in m)
+    two = [c for c in m if c["nw"] >= 1921 and c["H"] > 1]
+    assert {c["ksteps"] % 2 for c in two} == {0, 1} and {c["H"] % 2 for c in two} == {0, 1} and any(c["ksteps"] == 1 for c in two)
+    assert all(c["d"] <= 20 for c in m if c["nw"] >= 1920), "a small d for the long lists"
+    for fam in ("multistep", "simulate"):
+        cs = sc.corners(fam)
+        assert {c["ksteps"] for c in cs} >= {1, 2} and any(c["ksteps"] % 2 and c["ksteps"] > 2 for c in cs) and any(c["ksteps"] % 2 == 0 and c["ksteps"] > 2 for c in cs), fam
+        assert {c["d"] for c in cs} >= {47, 48, 49, 95, 97} and any(c["r"] == 0 for c in cs), fam
+        assert all(c["ksteps"] == (c["n"] + c["k"] + c["r"] + 3) // 4 and c["d"] == c["n"] + c["k"] for c in sc.cases(fam)), fam
+    assert _has("multistep", n=1, k=1, r=1, ksteps=1) and any(c["nw"] == 0 and c["H"] >= c["N"] for c in m)
+    assert any(c["r"] == 0 and c["H"] == 0 for c in m) or (any(c["H"] == 0 for c in m) and any(c["r"] == 0 for c in m))
+    assert any(c["short_u"] for c in m) and any(not c["short_u"] for c in m)
+    s = sc.corners("simulate")
+    assert any(c["r"] == 0 and c["nb"] > 256 for c in s) and any(c["r"] > 0 and c["nb"] > 256 and c["T"] == 50 for c in s) and _has("simulate", T=0)
+
+
 # ------------------------------------------------------------------------------------------ (b) well-posedness
 @pytest.mark.parametrize("part", range(SLICES))
 @pytest.mark.parametrize("family", sc.FAMILIES)
@@ -79,6 +163,27 @@ def test_reference_alone_meets_the_conditions(family, part):
         if ref["keep"].size == 1:
             assert ref["keep"].all(), ("a case with one lane must keep it", c)
     print(f"{family} slice {part}: {len(cases)} cases, {lanes} lanes, {left} left out, worst reference gap on the compared lanes {gap:.2e}")
+
+
+# ------------------------------------------------------------------------------------------ (d) the restated reference
+def test_restated_reference_is_the_oracle_in_float64():
+    import sweep_edmdc as se
+    from oracle import edmdc_numpy as ek
+    rng = np.random.default_rng(7)
+    X, C = rng.uniform(-0.5, 0.5, (70, 13)), rng.uniform(-0.5, 0.5, (33, 13))
+    assert np.array_equal(se.lift(X, C, 3.0), ek.lift(X, C, 3.0)) and se.lift(X, C, 3.0, np.longdouble).dtype == np.longdouble
+    c = sc.corners("gram")[0]
+    ref = se.prepare_gram(c)
+    GtG, GtY, npairs = ek.gram(ref["Xs"], ref["Us"], ref["C"], c["gamma"])
+    assert npairs == ref["pairs"] and np.allclose(GtG, ref["o"][0], rtol=0, atol=1e-13) and np.allclose(GtY, ref["o"][1], rtol=0, atol=1e-13)
+    c = sc.corners("multistep")[2]
+    ref = se.prepare_multistep(c)
+    rmse = ek.multistep_rmse(ref["X"], ref["U"], ref["C"], ref["gamma"], ref["A"], ref["B"], c["H"])
+    assert rmse == float(np.sqrt(np.mean((ref["X"][c["H"]:] - ref["o"]) ** 2)))
+    c = sc.corners("simulate")[3]
+    ref = se.prepare_simulate(c)
+    one = ek.simulate(ref["x0"][5], ref["U"][5], ref["C"], ref["gamma"], ref["A"], ref["B"])
+    assert np.allclose(one, ref["o"][5], rtol=0, atol=1e-14)       # A @ z per trajectory there, Z @ A^T batched here
 
 
 # ------------------------------------------------------------------------------------------ (c) byte stability
