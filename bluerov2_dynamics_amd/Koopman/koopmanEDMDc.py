@@ -195,6 +195,16 @@ class KoopmanEDMDc:
             raise ValueError("fit the model first: mppi_planner needs centers_, A_ and B_")
         return engine.KoopmanPlanner(self.centers_, self.gamma, self.A_, self.B_, H, hold, ctx=ctx)
 
+    def lmpc_planner(self, H, cfg, dt, ctx=None):
+        """The fitted model made ready for LINEAR model-predictive control (engine.KoopmanLmpc): the tracking problem over H steps of
+        dt under the record cfg (fossen/control.py: lmpc) is a box-constrained QP in the knots, whose matrix is condensed and
+        inverted once here; planner.step(x, ref, U_nom, y) solves it for a batch of states (engine.koopman_lmpc_step);
+        VehicleBase.simulate_lmpc(..., planner=planner) plans every tick with it.  ValueError when the weights leave the QP
+        without a unique minimum."""
+        if self.A_ is None or self.B_ is None or self.centers_ is None:
+            raise ValueError("fit the model first: lmpc_planner needs centers_, A_ and B_")
+        return engine.KoopmanLmpc(self.centers_, self.gamma, self.A_, self.B_, H, cfg, dt, ctx=ctx)
+
     # ------------------------------------------------------------------ persistence (new: the reference never stores it)
     def save(self, path) -> None:
         np.savez(path, state_dim=self.state_dim, input_dim=self.input_dim, n_rbfs=self.n_rbfs, gamma=self.gamma, ridge=self.ridge,

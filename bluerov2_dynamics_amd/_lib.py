@@ -60,6 +60,20 @@ class BrovMppi(ctypes.Structure):
     ]
 
 
+class BrovLmpc(ctypes.Structure):
+    """struct brov_lmpc (include/brov2.h): weights, limits and ADMM settings of edmdc_lmpc_step.  fossen/control.py builds it."""
+    _fields_ = [
+        ("q", ctypes.c_double * 13), ("qf", ctypes.c_double * 13),
+        ("r", ctypes.c_double * 8),
+        ("u_min", ctypes.c_double * 8), ("u_max", ctypes.c_double * 8),
+        ("rho", ctypes.c_double), ("tol", ctypes.c_double),
+        ("hold", ctypes.c_int32), ("iters", ctypes.c_int32),
+    ]
+
+
+assert ctypes.sizeof(BrovLmpc) == 53 * 8      # sizeof(brov_lmpc), asserted in csrc/capi.hip
+
+
 class PincHyper(ctypes.Structure):
     """struct brov_pinc_hyper (include/brov2.h)."""
     _fields_ = [("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
@@ -177,6 +191,13 @@ SIGNATURES = {
                                            c_void_p, c_void_p, i64, ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64,
                                            c_void_p, c_void_p, i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "edmdc_lmpc_step": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [c_void_p] * 6 +
+                        [i64, ctypes.POINTER(BrovLmpc), i64, ctypes.c_double, c_void_p, c_void_p, i64, i64, c_void_p, c_void_p, ctypes.c_int,
+                         c_void_p, c_void_p, c_void_p]),
+    "edmdc_lmpc_step_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double] + [c_void_p] * 6 +
+                            [i64, ctypes.POINTER(BrovLmpc), i64, ctypes.c_double, c_void_p, c_void_p, i64, i64, c_void_p, c_void_p,
+                             ctypes.c_int, c_void_p, c_void_p, c_void_p]),
+    "edmdc_lmpc_block_lds": (ctypes.c_int, [i64, ctypes.POINTER(ctypes.c_int)]),
     "brov_pinc_set_weights": (ctypes.c_int, [c_void_p, c_void_p, i64]),
     "brov_pinc_forward_dev": (ctypes.c_int, [c_void_p, i64, c_void_p, c_void_p]),
     "brov_pinc_rollout": (ctypes.c_int, [c_void_p, i64, i64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p, i64, c_void_p]),

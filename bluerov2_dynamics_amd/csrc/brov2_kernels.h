@@ -84,6 +84,28 @@ struct KoopmanMppiArgs {
 };
 int koopman_mppi_block(int64_t K, int64_t mnu);   // lanes per block of the cost kernel: 256, 128 or 64 as the LDS allows (0: does not fit)
 hipError_t launch_koopman_mppi_step(hipStream_t st, int64_t B, const KoopmanMppiArgs& a);
+// the first launch alone, F [B][H+1][n] = P[t] phi(x_b): reads n, k, gamma, C, P, m.x, m.H; writes F
+hipError_t launch_koopman_free(hipStream_t st, int64_t B, const KoopmanMppiArgs& a);
+// The linear MPC on the same coefficients: a box-constrained QP per problem, solved by ADMM (koopman_qp.hip; include/brov2.h:
+// edmdc_lmpc_step holds the law).  LmpcRec is struct brov_lmpc byte for byte; rec is ONE device record.  f: the arguments of
+// launch_koopman_free (f.F is scratch) and f.m.ref, ref_total, ref_row0, dt, M, shift, U_nom, u_apply, info [B][6]; f.pred [B][H+1][n] or
+// nullptr.  W [Nv][Nv], y [B][Nv] or nullptr, g [B][Nv] and c0 [B] scratch.  Three launches, whatever B, H and iters are.
+struct LmpcRec {
+    double q[13], qf[13];
+    double r[8];
+    double u_min[8], u_max[8];
+    double rho, tol;
+    int32_t hold, iters;
+};
+struct KoopmanQpArgs {
+    KoopmanMppiArgs f;
+    const LmpcRec* rec;
+    const double* W;
+    double *y, *g, *c0;
+};
+constexpr int KOOPMAN_QP_WAVES = 4;               // problems (waves) per block of the solve kernel
+size_t koopman_qp_block(int64_t nv, bool* w_in_lds);   // dynamic LDS bytes of a solve block; *w_in_lds: W is staged into them
+hipError_t launch_koopman_qp_step(hipStream_t st, int64_t B, const KoopmanQpArgs& a);
 // vals [P][M] -> out [4][M]: mean, sample standard deviation, minimum, maximum over the P candidates; NaN where any is non-finite
 hipError_t launch_ensemble_stats(hipStream_t st, int64_t P, int64_t M, const double* vals, double* out);
 // The sliding-window evaluator for P parameter sets at once (d_fp [P], candidate = blockIdx.y; P = 1: one set).  Candidate-major

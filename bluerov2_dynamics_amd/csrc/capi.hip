@@ -1851,6 +1851,116 @@ int edmdc_mppi_step(brov_ctx* c, int n, int r, int k, double gamma, const double
                              u_apply, cost, info, pred);
 }
 
+// ---- linear MPC on the same coefficients: a box-constrained QP per problem (koopman_qp.hip) -----------------------------------------
+static_assert(sizeof(brov_lmpc) == sizeof(LmpcRec) && sizeof(brov_lmpc) == 53 * 8, "LmpcRec is brov_lmpc byte for byte");
+// Everything the host can refuse comes first.  Then one upload of the record, three launches.  A and B define the model whose
+// coefficients P, Gc and W are: they are required and not read.
+static int koopman_lmpc_step(brov_ctx* c, bool host, int n, int r, int k, double gamma, const double* C, const double* A, const double* Bm,
+                             const double* P, const double* Gc, const double* W, int64_t B, const brov_lmpc* cfg, int64_t H, double dt,
+                             const double* x, const double* ref, int64_t ref_total, int64_t ref_row0, double* U_nom, double* y_io, int shift,
+                             double* u_apply, double* pred, double* info) {
+    const std::string w = "edmdc_lmpc_step";
+    if (!c) return BROV_ERR_ARG;
+    if (n != 12 && n != 13) return fail(c, BROV_ERR_ARG, w + ": n must be 12 (Euler angles) or 13 (quaternion)");
+    if (r != 6 && r != 8) return fail(c, BROV_ERR_ARG, w + ": r must be 6 or 8");
+    if (k < 0) return fail(c, BROV_ERR_ARG, w + ": k must be >= 0");
+    if (k > KOOPMAN_MPPI_MAX_K) return fail(c, BROV_ERR_ARG, w + ": k must be <= " + std::to_string(KOOPMAN_MPPI_MAX_K));
+    if (B < 0) return fail(c, BROV_ERR_ARG, w + ": negative size");
+    if (B > 65535) return fail(c, BROV_ERR_ARG, w + ": B must be <= 65535");
+    if (B == 0) return BROV_OK;
+    int rc = mppi_sizes_ok(c, w, 1, H);
+    if (rc) return rc;
+    if (!cfg || !x || !ref || !U_nom) return fail(c, BROV_ERR_ARG, w + ": NULL input");
+    if (!A || !Bm || !P || !Gc) return fail(c, BROV_ERR_ARG, w + ": NULL A, B, P or Gc");
+    if (!W) return fail(c, BROV_ERR_ARG, w + ": NULL W");
+    if (k > 0 && !C) return fail(c, BROV_ERR_ARG, w + ": NULL C with k > 0");
+    if (std::isnan(gamma)) return fail(c, BROV_ERR_ARG, w + ": NaN gamma");
+    if (!(dt > 0.0) || !std::isfinite(dt)) return fail(c, BROV_ERR_ARG, w + ": dt must be finite and > 0");
+    {
+        double v[52];                   // the doubles of the record: q, qf, r, u_min, u_max, rho, tol
+        static_assert(offsetof(brov_lmpc, hold) == sizeof v, "the record's doubles come first");
+        memcpy(v, cfg, sizeof v);
+        for (double e : v)
+            if (std::isnan(e)) return fail(c, BROV_ERR_ARG, w + ": NaN in the record");
+    }
+    if (cfg->hold < 1) return fail(c, BROV_ERR_ARG, w + ": hold must be >= 1");
+    if (cfg->iters < 0 || cfg->iters > 1000000) return fail(c, BROV_ERR_ARG, w + ": iters must be 0 .. 1 000 000");
+    if (!(cfg->rho > 0.0) || !std::isfinite(cfg->rho)) return fail(c, BROV_ERR_ARG, w + ": rho must be finite and > 0");
+    if (cfg->tol < 0.0) return fail(c, BROV_ERR_ARG, w + ": tol must be >= 0");
+    for (int i = 0; i < n; ++i)
+        if (cfg->q[i] < 0.0 || cfg->qf[i] < 0.0) return fail(c, BROV_ERR_ARG, w + ": the weights q and qf must be >= 0");
+    for (int i = 0; i < r; ++i) {
+        if (cfg->r[i] < 0.0) return fail(c, BROV_ERR_ARG, w + ": the weights r must be >= 0");
+        if (cfg->u_min[i] > cfg->u_max[i]) return fail(c, BROV_ERR_ARG, w + ": u_min must be <= u_max");
+    }
+    if (ref_total == 1 ? ref_row0 != 0 : (ref_total < 1 || ref_row0 < 0 || H >= ref_total || ref_row0 > ref_total - 1 - H))
+        return fail(c, BROV_ERR_ARG, w + ": the reference window ref_row0 .. ref_row0 + H must lie inside ref_total (a set-point: ref_total = 1, ref_row0 = 0)");
+    const int64_t M = (H + cfg->hold - 1) / cfg->hold;      // knots
+    if (M * r > KOOPMAN_MPPI_MAX_MNU)
+        return fail(c, BROV_ERR_ARG, w + ": M nu = " + std::to_string(M * r) + " must be <= " + std::to_string(KOOPMAN_MPPI_MAX_MNU) +
+                                         " (a lane of the solver owns at most five rows)");
+    DeviceGuard g(c);
+    const size_t nv = (size_t)M * r, n_U = (size_t)B * nv, d = (size_t)n + k;
+    KoopmanQpArgs args{};
+    KoopmanMppiArgs& f = args.f;
+    MppiArgs& m = f.m;
+    m.shift = shift != 0;
+    m.K = 1; m.H = H; m.M = M; m.ref_total = ref_total; m.ref_row0 = ref_row0; m.dt = dt;
+    f.n = n; f.r = r; f.k = k; f.gamma = gamma;
+    LmpcRec* d_rec;
+    Arena a(c, host);
+    rc = a.lay("edmdc_lmpc_step", [&] {
+        m.x = a.in(x, (size_t)B * n);
+        m.ref = a.in(ref, (size_t)B * ref_total * n);
+        m.U_nom = a.inout(U_nom, n_U);
+        args.y = y_io ? a.inout(y_io, n_U) : nullptr;
+        m.u_apply = u_apply ? a.out(u_apply, (size_t)B * cfg->hold * r) : nullptr;
+        f.pred = pred ? a.out(pred, (size_t)B * (H + 1) * n) : nullptr;
+        m.info = info ? a.out(info, (size_t)B * 6) : nullptr;
+        f.C = k ? a.in(C, (size_t)k * n) : nullptr;
+        f.P = a.in(P, (size_t)(H + 1) * n * d);
+        f.Gc = a.in(Gc, (size_t)(H + 1) * M * n * r);
+        args.W = a.in(W, nv * nv);
+        d_rec = a.take<LmpcRec>(1);
+        f.F = a.take<double>((size_t)B * (H + 1) * n);
+        args.g = a.take<double>(n_U);
+        args.c0 = a.take<double>((size_t)B);
+    });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_rec, cfg, sizeof(LmpcRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // cfg is the caller's
+    args.rec = d_rec;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_koopman_qp_step(c->stream, B, args));
+    }
+    return a.finish();
+}
+
+int edmdc_lmpc_block_lds(int64_t nv, int* w_in_lds) {
+    if (nv < 1 || nv > KOOPMAN_MPPI_MAX_MNU) return -1;
+    bool w;
+    const size_t bytes = koopman_qp_block(nv, &w);
+    if (w_in_lds) *w_in_lds = w ? 1 : 0;
+    return (int)bytes;
+}
+
+int edmdc_lmpc_step_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, const double* d_A, const double* d_B,
+                        const double* d_P, const double* d_Gc, const double* d_W, int64_t nb, const brov_lmpc* cfg, int64_t H, double dt,
+                        const double* d_x, const double* d_ref, int64_t ref_total, int64_t ref_row0, double* d_U_nom, double* d_y_io,
+                        int shift, double* d_u_apply, double* d_pred, double* d_info) {
+    return koopman_lmpc_step(c, false, n, r, k, gamma, d_C, d_A, d_B, d_P, d_Gc, d_W, nb, cfg, H, dt, d_x, d_ref, ref_total, ref_row0, d_U_nom,
+                             d_y_io, shift, d_u_apply, d_pred, d_info);
+}
+
+int edmdc_lmpc_step(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const double* A, const double* B, const double* P,
+                    const double* Gc, const double* W, int64_t nb, const brov_lmpc* cfg, int64_t H, double dt, const double* x,
+                    const double* ref, int64_t ref_total, int64_t ref_row0, double* U_nom, double* y_io, int shift, double* u_apply,
+                    double* pred, double* info) {
+    return koopman_lmpc_step(c, true, n, r, k, gamma, C, A, B, P, Gc, W, nb, cfg, H, dt, x, ref, ref_total, ref_row0, U_nom, y_io, shift,
+                             u_apply, pred, info);
+}
+
 int brov_ensemble_stats_dev(brov_ctx* c, int64_t P, int64_t M, const double* d_vals, double* d_out) {
     if (!c || P < 1 || M < 0 || M > ((int64_t)1 << 38)) return fail(c, BROV_ERR_ARG, "brov_ensemble_stats_dev: need P >= 1 and 0 <= M <= 2^38");
     if (M == 0) return BROV_OK;

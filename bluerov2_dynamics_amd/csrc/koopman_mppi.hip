@@ -6,7 +6,8 @@
 //
 // koopman_free_kernel: F[b][t] = P[t] phi(x_b), once per problem.  Block = (chunk of 4 steps, problem); the lift is written once into
 // LDS (the code of edmdc_lift: the same bits), then a wave per output row, lanes across the d columns, a fixed shuffle tree.  P is
-// re-read from L2 by the B blocks of a chunk; this kernel is not the hot one.
+// re-read from L2 by the B blocks of a chunk; this kernel is not the hot one.  launch_koopman_free launches it alone: the linear MPC of
+// koopman_qp.hip starts from the same free response.
 //
 // koopman_cost_kernel: one lane per sample k, problem = blockIdx.y, as mppi_cost_kernel.  The lane forms its M nu commands once with
 // mppi_command (the code and so the bits of mppi.hip; the command cost and the importance term in its order) and keeps them
@@ -200,16 +201,24 @@ static hipError_t launch_koopman_cost(hipStream_t st, int64_t B, const KoopmanMp
     return hipGetLastError();
 }
 
+hipError_t launch_koopman_free(hipStream_t st, int64_t B, const KoopmanMppiArgs& a) {
+    if (B <= 0) return hipSuccess;
+    const MppiArgs& m = a.m;
+    if (B > 65535 || m.H < 1 || a.k < 0 || a.k > KOOPMAN_MPPI_MAX_K || (a.n != 12 && a.n != 13) || (m.H + FREE_TCHUNK) / FREE_TCHUNK > 0x7fffffff)
+        return hipErrorInvalidValue;
+    const dim3 fgrid((unsigned)((m.H + FREE_TCHUNK) / FREE_TCHUNK), (unsigned)B);       // ceil((H + 1) / chunk)
+    if (a.n == 12) hipLaunchKernelGGL(koopman_free_kernel<12>, fgrid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(koopman_free_kernel<13>, fgrid, dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
 hipError_t launch_koopman_mppi_step(hipStream_t st, int64_t B, const KoopmanMppiArgs& a) {
     if (B <= 0) return hipSuccess;
     const MppiArgs& m = a.m;
     if (B > 65535 || m.K < 1 || m.H < 1 || m.M < 1 || m.M > 0x7fffffff || (m.K + 63) / 64 > 0x7fffffff || a.k < 0 || a.k > KOOPMAN_MPPI_MAX_K ||
         (a.n != 12 && a.n != 13) || (a.r != 6 && a.r != 8) || (m.H + FREE_TCHUNK) / FREE_TCHUNK > 0x7fffffff)
         return hipErrorInvalidValue;
-    const dim3 fgrid((unsigned)((m.H + FREE_TCHUNK) / FREE_TCHUNK), (unsigned)B);       // ceil((H + 1) / chunk)
-    if (a.n == 12) hipLaunchKernelGGL(koopman_free_kernel<12>, fgrid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(koopman_free_kernel<13>, fgrid, dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_koopman_free(st, B, a);
     if (e != hipSuccess) return e;
     if (a.n == 12) e = a.r == 8 ? launch_koopman_cost<12, 8>(st, B, a) : launch_koopman_cost<12, 6>(st, B, a);
     else e = a.r == 8 ? launch_koopman_cost<13, 8>(st, B, a) : launch_koopman_cost<13, 6>(st, B, a);

@@ -20,7 +20,7 @@ from ._lib import (EULER, RK4, LAG_PER_CALL, LAG_PER_STEP, LAYOUT_BTU, LAYOUT_TU
                    WRENCH_QUAT, DIST_IID_UNIFORM, DIST_AR1, NX, NU, as_f64, _hptr, default_context)
 
 __all__ = ["rhs", "thruster_forces", "rollout", "window_endpoint_se", "window_rmse", "rollout_dev", "fill_controls_dev",
-           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats", "rollout_feedback", "koopman_markov", "koopman_mppi_step", "KoopmanPlanner"]
+           "window_endpoint_se_dev", "lift", "gram", "gram_dev", "gram_ragged_dev", "pinv_apply_ragged_dev", "upload_bags", "BagTable", "solve_AB", "solve_AB_fit_order", "pinv_apply", "pinv_apply_dev", "fit_dev", "apply_decomposition", "gtg_decomposition", "kmeans_lloyd", "kmeans_centers", "kmeans_centers_dev", "multistep_se", "multistep_se_linear", "simulate_lifted", "DevArray", "col_stats_dev", "pinc_forward_dev", "pinc_rollout_dev", "pinc_window_endpoint_se_dev", "thruster_stream", "pinc_loss_grad_dev", "pinc_adamw_step_dev", "window_pop", "window_target", "window_count", "fd_normal_eq", "rollout_pop", "ensemble_stats", "rollout_feedback", "koopman_markov", "koopman_mppi_step", "KoopmanPlanner", "koopman_qp_condense", "koopman_lmpc_step", "KoopmanLmpc"]
 
 INTEGRATORS = {"euler": EULER, "rk4": RK4, EULER: EULER, RK4: RK4}
 LAYOUTS = {"btu": LAYOUT_BTU, "tub": LAYOUT_TUB, "tpb": LAYOUT_TPB, LAYOUT_BTU: LAYOUT_BTU, LAYOUT_TUB: LAYOUT_TUB, LAYOUT_TPB: LAYOUT_TPB}
@@ -755,6 +755,145 @@ class KoopmanPlanner:
         assert int(cfg.hold) == self.hold, f"the planner was built for hold = {self.hold}"
         return koopman_mppi_step(self.C, self.gamma, self.A, self.B, cfg, x, ref, U_nom, dt, K, H=self.H, coeffs=(self.P, self.Gc),
                                  ctx=self.ctx, **kw)
+
+
+def koopman_qp_condense(Gc, cfg, dt, H):
+    """(Hq [Nv,Nv], steps [M]) of the QP of koopman_lmpc_step (include/brov2.h: edmdc_lmpc_step) from the coefficients Gc
+    [H+1,M,n,r] of koopman_markov and the record cfg (_lib.BrovLmpc), Nv = M r with column m r + j for knot m, channel j:
+    Hq = 2 sum_t w_t Gc[t]' diag(Q_t) Gc[t] + 2 diag(dt r[j] steps[m]), w_t = dt and Q_t = q for t < H, w_H = 1 and Q_H = qf;
+    steps[m] = the horizon steps knot m holds.  NumPy, on the host."""
+    Gc = as_f64(Gc)
+    H, hold, dt = int(H), int(cfg.hold), float(dt)
+    assert Gc.ndim == 4 and Gc.shape[0] == H + 1 and hold >= 1 and H >= 1
+    M, n, r = Gc.shape[1:]
+    assert M == (H + hold - 1) // hold, f"Gc has {M} knots, H = {H} at hold = {hold} needs {(H + hold - 1) // hold}"
+    q, qf, rr = np.array(cfg.q[:n]), np.array(cfg.qf[:n]), np.array(cfg.r[:r])
+    G = Gc.transpose(0, 2, 1, 3).reshape(H + 1, n, M * r)
+    wq = np.repeat((dt * q)[None], H + 1, axis=0)
+    wq[H] = qf
+    steps = np.minimum(hold, H - hold * np.arange(M)).astype(np.int64)
+    Hq = 2.0 * np.einsum("tia,ti,tib->ab", G, wq, G) + 2.0 * np.diag(dt * np.outer(steps, rr).ravel())
+    return 0.5 * (Hq + Hq.T), steps
+
+
+def _qp_rho(Hq):
+    """sqrt(lambda_min lambda_max) of a positive definite Hq; ValueError otherwise"""
+    ev = np.linalg.eigvalsh(Hq)
+    if not (np.all(np.isfinite(ev)) and ev[0] > 0.0):
+        raise ValueError(f"the condensed matrix Hq is not positive definite (smallest eigenvalue {ev[0]:.3e}): give every knot a "
+                         "weight through q, qf or r")
+    return float(np.sqrt(ev[0] * ev[-1]))
+
+
+def _qp_inverse(Hq, rho):
+    """W = (Hq + rho I)^-1, symmetric"""
+    W = np.linalg.inv(Hq + rho * np.eye(Hq.shape[0]))
+    return np.ascontiguousarray(0.5 * (W + W.T))
+
+
+def koopman_lmpc_step(C, gamma, A, B, cfg, x, ref, U_nom, dt, H=None, y=None, ref_row0=0, shift=False, want_pred=False, coeffs=None,
+                      ctx=None):
+    """Linear model-predictive control with a Koopman EDMDc model (centres C [k,n], gamma, A [d,d], B [d,r]): for every one of nb
+    states the tracking problem over H steps is the box-constrained QP min 1/2 v' Hq v + g' v, u_min <= v <= u_max in the knots,
+    solved by ADMM on the device in one launch (include/brov2.h: edmdc_lmpc_step_dev holds the law).  cfg: a _lib.BrovLmpc
+    (fossen/control.py: lmpc) with rho set.
+
+    x [nb,n], ref [nb,rows,n] (rows = 1: a set-point; else rows ref_row0 .. ref_row0 + H are read), U_nom [nb,M,r] the warm start
+    (clipped), y [nb,M,r] | None the scaled dual variable (None: zero, and none is returned); H defaults to M cfg.hold.  Host arrays
+    are uploaded and the results come back as NumPy arrays; device arrays (DevArray / torch CUDA tensors) are used in place and the
+    results come back as device arrays of the same kind.  coeffs: the device-resident (P, Gc, W) -- P, Gc of koopman_markov and
+    W = (Hq + rho I)^-1 with Hq of koopman_qp_condense -- so that a receding-horizon loop uploads them once (KoopmanLmpc does);
+    None forms and uploads them here.
+    Returns dict(U_nom [nb,M,r] = z (shift: moved one knot forward) -- a new array, the argument is not written --, y likewise | None,
+    u_apply [nb,hold,r], info [nb,6] = J(z), J(z0), r_prim, r_dual, iterations, entries at a limit, pred [nb,H+1,n] | None)."""
+    host = isinstance(x, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x, ref, U_nom = as_f64(x), as_f64(ref), as_f64(U_nom)
+        y = None if y is None else as_f64(y)
+    else:
+        ctx = _ctx_of(x, ctx)
+        arr = arrays_of(x, ctx)
+    arr.bind()
+    assert len(x.shape) == 2 and len(U_nom.shape) == 3, "x must be [nb,n] and U_nom [nb,M,r]"
+    nb, n = int(x.shape[0]), int(x.shape[1])
+    M, r = int(U_nom.shape[1]), int(U_nom.shape[2])
+    d = int(A.shape[0])
+    k = d - n
+    assert tuple(int(v) for v in A.shape) == (d, d) and tuple(int(v) for v in B.shape) == (d, r), f"A must be [d,d] and B [d,{r}]"
+    assert (k == 0 and (C is None or int(C.shape[0]) == 0)) or tuple(int(v) for v in C.shape) == (k, n), f"C must be [{k},{n}]"
+    assert len(ref.shape) == 3 and int(ref.shape[0]) == nb and int(ref.shape[2]) == n, f"ref shape {tuple(ref.shape)} != {(nb, 'rows', n)}"
+    assert int(U_nom.shape[0]) == nb, f"U_nom shape {tuple(U_nom.shape)} != {(nb, 'M', r)}"
+    assert y is None or tuple(int(v) for v in y.shape) == (nb, M, r), f"y must be {(nb, M, r)}"
+    hold = int(cfg.hold)
+    H = M * hold if H is None else int(H)
+    if hold < 1 or H < 1:
+        raise ValueError("H and cfg.hold must be >= 1")
+    assert (H + hold - 1) // hold == M, f"U_nom has {M} knots, H = {H} at hold = {hold} needs {(H + hold - 1) // hold}"
+    dev = lambda v: arr.upload(as_f64(v)) if isinstance(v, (np.ndarray, list, tuple)) else v
+    if coeffs is None:
+        P, Gc = koopman_markov(_to_host(A), _to_host(B), n, H, hold)
+        coeffs = (P, Gc, _qp_inverse(koopman_qp_condense(Gc, cfg, dt, H)[0], float(cfg.rho)))
+    P, Gc, W = (dev(v) for v in coeffs)
+    assert tuple(int(v) for v in P.shape) == (H + 1, n, d) and tuple(int(v) for v in Gc.shape) == (H + 1, M, n, r) and \
+        tuple(int(v) for v in W.shape) == (M * r, M * r), f"coeffs must be P {(H + 1, n, d)}, Gc {(H + 1, M, n, r)} and W {(M * r, M * r)}"
+    C, A, B = (None if k == 0 else dev(C)), dev(A), dev(B)
+    copy = lambda v: v.clone() if _is_torch(v) else arr.empty(tuple(v.shape)).copy_from_device(v)     # in / out in the ABI: work on a copy
+    if host:
+        x, ref = arr.upload(x), arr.upload(ref)
+        U, Y = arr.upload(U_nom), (None if y is None else arr.upload(y))
+    else:
+        U, Y = copy(U_nom), (None if y is None else copy(y))
+    u_apply = arr.empty((nb, hold, r))
+    info = arr.empty((nb, 6))
+    pred = arr.empty((nb, H + 1, n)) if want_pred else None
+    ctx.check(ctx.lib.edmdc_lmpc_step_dev(ctx.h, n, r, k, float(gamma), _dptr(C), _dptr(A), _dptr(B), _dptr(P), _dptr(Gc), _dptr(W), nb,
+                                          ctypes.byref(cfg), H, float(dt), _dptr(x), _dptr(ref), int(ref.shape[1]), int(ref_row0), _dptr(U),
+                                          _dptr(Y), int(bool(shift)), _dptr(u_apply), _dptr(pred), _dptr(info)), "edmdc_lmpc_step_dev")
+    out = dict(U_nom=U, y=Y, u_apply=u_apply, info=info, pred=pred)
+    if host:
+        out = {key: (None if v is None else arr.download(v)) for key, v in out.items()}
+    return out
+
+
+class KoopmanLmpc:
+    """An EDMDc model made ready for linear model-predictive control over H steps of dt under one record: the model's arrays, the
+    coefficients (P, Gc) of koopman_markov and W = (Hq + rho I)^-1 live on the device, uploaded once; Hq (NumPy) stays here for
+    callers who want to check a result.  A record without rho (fossen/control.py: lmpc(rho=None)) gets rho = sqrt(lambda_min
+    lambda_max) of Hq.  ValueError when Hq is not positive definite.  KoopmanEDMDc.lmpc_planner builds one; step() is
+    koopman_lmpc_step on them; VehicleBase.simulate_lmpc plans every tick with it."""
+
+    def __init__(self, C, gamma, A, B, H, cfg, dt, ctx=None):
+        A, B = as_f64(A), as_f64(B)
+        self.H, self.hold, self.gamma, self.dt = int(H), int(cfg.hold), float(gamma), float(dt)
+        if self.H < 1 or self.hold < 1:
+            raise ValueError("H and cfg.hold must be >= 1")
+        if not (self.dt > 0 and np.isfinite(self.dt)):
+            raise ValueError("dt must be finite and > 0")
+        self.d, self.r = int(A.shape[0]), int(B.shape[1])
+        self.k = 0 if C is None else int(np.shape(C)[0])
+        self.n = self.d - self.k
+        self.M = (self.H + self.hold - 1) // self.hold
+        if A.shape != (self.d, self.d) or B.shape[0] != self.d or (self.k and np.shape(C) != (self.k, self.n)):
+            raise ValueError("need C [k,n], A [n+k,n+k] and B [n+k,r]")
+        P, Gc = koopman_markov(A, B, self.n, self.H, self.hold)
+        self.Hq, self.steps = koopman_qp_condense(Gc, cfg, self.dt, self.H)
+        rho = _qp_rho(self.Hq)
+        self.cfg = _lib.BrovLmpc()
+        ctypes.memmove(ctypes.byref(self.cfg), ctypes.byref(cfg), ctypes.sizeof(cfg))
+        if not self.cfg.rho > 0.0:
+            self.cfg.rho = rho
+        self.rho = float(self.cfg.rho)
+        self.ctx = ctx or default_context()
+        self.ctx.use_null_stream()
+        up = lambda v: DevArray.from_host(self.ctx, v)
+        self.C = up(as_f64(C)) if self.k else None
+        self.A, self.B, self.P, self.Gc, self.W = up(A), up(B), up(P), up(Gc), up(_qp_inverse(self.Hq, self.rho))
+
+    def step(self, x, ref, U_nom, y=None, **kw):
+        return koopman_lmpc_step(self.C, self.gamma, self.A, self.B, self.cfg, x, ref, U_nom, self.dt, H=self.H, y=y,
+                                 coeffs=(self.P, self.Gc, self.W), ctx=self.ctx, **kw)
 
 
 def ensemble_stats(vals, ctx=None):

@@ -224,11 +224,47 @@ class VehicleBase:
         its update)."""
         import ctypes
         from . import identify
-        model, ctx = self.MODEL, self._ctx
-        nx, nu = _lib.NX[model], _lib.NU[model]
         hold, T, K, H = int(cfg.hold), int(T), int(K), int(H)
         if hold < 1 or H < 1 or K < 1:
             raise ValueError("hold, H and K must be >= 1")
+        s = self._receding_setup(x0, ref, T, H, hold, plant_params, integrator)
+        model, ctx, B, nx, nu = s.model, s.ctx, s.B, s.nx, s.nu
+        if planner is not None and (planner.n, planner.r, planner.H, planner.hold) != (nx, nu, H, hold):
+            raise ValueError(f"the planner is for n = {planner.n}, r = {planner.r}, H = {planner.H}, hold = {planner.hold}; this call needs {(nx, nu, H, hold)}")
+        if planner is not None and planner.ctx.device != ctx.device:
+            raise ValueError("the planner's arrays live on another device than this vehicle's")
+        plan_params = (_lib.BrovParams * 1)(identify.params_of(self))          # the Fossen planning model: this vehicle
+        self._receding_device_state(s)
+        D = engine.DevArray
+        U = D(ctx, (B, s.M, nu)).zero_()
+        info = D(ctx, (max(s.nt, 1), B, 4))
+        rec_U = D(ctx, (max(s.nt, 1), B, s.M, nu))
+        seeds = []
+        p_ = lambda a: None if a is None else a.ptr
+        for n in range(s.nt):
+            row0, xn = self._receding_tick_begin(s, n)
+            seeds.append(int(seed) + n)
+            rec_U.rows(n, n + 1).copy_from_device(U)
+            if planner is None:
+                ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, s.integ, _lib.LAG_PER_CALL, B, 1, plan_params, ctypes.byref(cfg), K, H, float(dt),
+                                                     seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, p_(s.lag), s.d_ref.ptr, s.ref.shape[1], row0, None, U.ptr, 1,
+                                                     s.ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "brov_mppi_step_dev")
+            else:
+                ctx.check(ctx.lib.edmdc_mppi_step_dev(ctx.h, planner.n, planner.r, planner.k, planner.gamma, p_(planner.C), planner.A.ptr, planner.B.ptr, planner.P.ptr, planner.Gc.ptr, B,
+                                                      ctypes.byref(cfg), K, H, float(dt), seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, s.d_ref.ptr,
+                                                      s.ref.shape[1], row0, None, U.ptr, 1, s.ua.rows(n, n + 1).ptr, None,
+                                                      info.rows(n, n + 1).ptr, None), "edmdc_mppi_step_dev")
+            self._receding_plant_tick(s, n, dt)
+        return self._receding_results(s, info, dict(U_nom=rec_U.numpy()[:s.nt], seed=np.array(seeds, dtype=np.int64)))
+
+    # What simulate_mppi and simulate_lmpc share: the arguments, the device-resident state of the plants, the plant part of a tick and
+    # the assembly of the results.  The planners differ in what they carry from tick to tick, which stays with each of them.
+    def _receding_setup(self, x0, ref, T, H, hold, plant_params, integrator):
+        import types
+        from . import identify
+        s = types.SimpleNamespace(model=self.MODEL, ctx=self._ctx, hold=hold, H=H)
+        s.nx, s.nu = _lib.NX[s.model], _lib.NU[s.model]
+        nx = s.nx
         if T < 0 or T % hold:
             raise ValueError(f"T = {T} must be a multiple of hold = {hold}")
         plants = None if plant_params is None else list(plant_params)
@@ -243,57 +279,91 @@ class VehicleBase:
             ref = np.repeat(ref[None, None], B, axis=0)
         elif ref.ndim == 2:
             ref = ref[:, None]
-        setpoint = ref.shape[1] == 1
-        if ref.shape[0] != B or ref.shape[2] != nx or not (setpoint or ref.shape[1] >= T + H + 1):
+        s.setpoint = ref.shape[1] == 1
+        if ref.shape[0] != B or ref.shape[2] != nx or not (s.setpoint or ref.shape[1] >= T + H + 1):
             raise ValueError(f"ref must be a set-point or [B,T+H+1,{nx}], got {ref.shape}")
-        nt, M = T // hold, (H + hold - 1) // hold
-        integ = engine.INTEGRATORS[integrator]
-        if planner is not None and (planner.n, planner.r, planner.H, planner.hold) != (nx, nu, H, hold):
-            raise ValueError(f"the planner is for n = {planner.n}, r = {planner.r}, H = {planner.H}, hold = {planner.hold}; this call needs {(nx, nu, H, hold)}")
-        if planner is not None and planner.ctx.device != ctx.device:
-            raise ValueError("the planner's arrays live on another device than this vehicle's")
-        plan_params = (_lib.BrovParams * 1)(identify.params_of(self))          # the Fossen planning model: this vehicle
-        pa = plan_params if plants is None else (_lib.BrovParams * B)(*plants)
-        P, Bp, per = (1, B, 0) if plants is None else (B, 1, 1)          # [1][B] or [B][1] rows: the same bytes either way
+        s.x0, s.ref, s.B, s.T = x0, ref, B, T
+        s.nt, s.M = T // hold, (H + hold - 1) // hold
+        s.integ = engine.INTEGRATORS[integrator]
+        s.pa = (_lib.BrovParams * 1)(identify.params_of(self)) if plants is None else (_lib.BrovParams * B)(*plants)
+        s.P, s.Bp, s.per = (1, B, 0) if plants is None else (B, 1, 1)          # [1][B] or [B][1] rows: the same bytes either way
+        return s
+
+    def _receding_device_state(self, s):
+        ctx, B, nx, nu, nt, hold = s.ctx, s.B, s.nx, s.nu, s.nt, s.hold
         ctx.use_null_stream()
         D = engine.DevArray
-        X = D(ctx, (nt + 1, B, nx))
-        X.rows(0, 1).copy_from_host(x0)
-        d_ref = D.from_host(ctx, ref)
-        thr = model == _lib.THRUSTER_EULER
-        lag = D(ctx, (B, 8, 3)).zero_() if thr else None
-        U = D(ctx, (B, M, nu)).zero_()
-        traj, ua, info = D(ctx, (max(nt, 1), B, hold + 1, nx)), D(ctx, (max(nt, 1), B, hold, nu)), D(ctx, (max(nt, 1), B, 4))
-        rec_lag = D(ctx, (max(nt, 1), B, 8, 3)) if thr else None
-        rec_U = D(ctx, (max(nt, 1), B, M, nu))
-        seeds, rows = [], []
-        p_ = lambda a: None if a is None else a.ptr
-        for n in range(nt):
-            row0 = 0 if setpoint else n * hold
-            seeds.append(int(seed) + n)
-            rows.append(row0)
-            if thr:
-                rec_lag.rows(n, n + 1).copy_from_device(lag)
-            rec_U.rows(n, n + 1).copy_from_device(U)
-            xn = X.rows(n, n + 1)
-            if planner is None:
-                ctx.check(ctx.lib.brov_mppi_step_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, B, 1, plan_params, ctypes.byref(cfg), K, H, float(dt),
-                                                     seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, p_(lag), d_ref.ptr, ref.shape[1], row0, None, U.ptr, 1,
-                                                     ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "brov_mppi_step_dev")
-            else:
-                ctx.check(ctx.lib.edmdc_mppi_step_dev(ctx.h, planner.n, planner.r, planner.k, planner.gamma, p_(planner.C), planner.A.ptr, planner.B.ptr, planner.P.ptr, planner.Gc.ptr, B,
-                                                      ctypes.byref(cfg), K, H, float(dt), seeds[-1] & 0xFFFFFFFFFFFFFFFF, xn.ptr, d_ref.ptr,
-                                                      ref.shape[1], row0, None, U.ptr, 1, ua.rows(n, n + 1).ptr, None,
-                                                      info.rows(n, n + 1).ptr, None), "edmdc_mppi_step_dev")
-            ctx.check(ctx.lib.brov_rollout_pop_dev(ctx.h, model, integ, _lib.LAG_PER_CALL, P, pa, per, Bp, hold, float(dt), xn.ptr,
-                                                   ua.rows(n, n + 1).ptr, p_(lag), traj.rows(n, n + 1).ptr, 1, X.rows(n + 1, n + 2).ptr),
-                      "brov_rollout_pop_dev")
-        tr = traj.numpy()[:nt]                                           # [nt,B,hold+1,nx]: drop every segment's first row but the first's
-        states = np.concatenate([x0[:, None]] + [tr[n][:, 1:] for n in range(nt)], axis=1)
-        u = np.concatenate([ua.numpy()[n] for n in range(nt)], axis=1) if nt else np.zeros((B, 0, nu))
-        ticks = dict(x=X.numpy()[:nt], lag=rec_lag.numpy()[:nt] if thr else None, U_nom=rec_U.numpy()[:nt],
-                     seed=np.array(seeds, dtype=np.int64), ref_row0=np.array(rows, dtype=np.int64))
+        s.X = D(ctx, (nt + 1, B, nx))
+        s.X.rows(0, 1).copy_from_host(s.x0)
+        s.d_ref = D.from_host(ctx, s.ref)
+        s.thr = s.model == _lib.THRUSTER_EULER
+        s.lag = D(ctx, (B, 8, 3)).zero_() if s.thr else None
+        s.traj, s.ua = D(ctx, (max(nt, 1), B, hold + 1, nx)), D(ctx, (max(nt, 1), B, hold, nu))
+        s.rec_lag = D(ctx, (max(nt, 1), B, 8, 3)) if s.thr else None
+        s.rows = []
+
+    def _receding_tick_begin(self, s, n):
+        """records what the planner sees at tick n; returns (first reference row, the state of the tick)"""
+        row0 = 0 if s.setpoint else n * s.hold
+        s.rows.append(row0)
+        if s.thr:
+            s.rec_lag.rows(n, n + 1).copy_from_device(s.lag)
+        return row0, s.X.rows(n, n + 1)
+
+    def _receding_plant_tick(self, s, n, dt):
+        """hold plant steps on the command the planner left in ua[n]"""
+        ctx = s.ctx
+        ctx.check(ctx.lib.brov_rollout_pop_dev(ctx.h, s.model, s.integ, _lib.LAG_PER_CALL, s.P, s.pa, s.per, s.Bp, s.hold, float(dt),
+                                               s.X.rows(n, n + 1).ptr, s.ua.rows(n, n + 1).ptr, None if s.lag is None else s.lag.ptr,
+                                               s.traj.rows(n, n + 1).ptr, 1, s.X.rows(n + 1, n + 2).ptr), "brov_rollout_pop_dev")
+
+    def _receding_results(self, s, info, planner_ticks):
+        nt = s.nt
+        tr = s.traj.numpy()[:nt]                                         # [nt,B,hold+1,nx]: drop every segment's first row but the first's
+        states = np.concatenate([s.x0[:, None]] + [tr[n][:, 1:] for n in range(nt)], axis=1)
+        u = np.concatenate([s.ua.numpy()[n] for n in range(nt)], axis=1) if nt else np.zeros((s.B, 0, s.nu))
+        ticks = dict(x=s.X.numpy()[:nt], lag=s.rec_lag.numpy()[:nt] if s.thr else None, **planner_ticks,
+                     ref_row0=np.array(s.rows, dtype=np.int64))
         return dict(traj=states, u=u, info=info.numpy()[:nt], ticks=ticks)
+
+    def simulate_lmpc(self, x0, ref, dt, planner, T, plant_params=None, integrator="euler"):
+        """Receding-horizon control of B plants by LINEAR model-predictive control with a learned Koopman model: every tick solves
+        the box-constrained QP of an engine.KoopmanLmpc (KoopmanEDMDc.lmpc_planner(H, cfg, dt); edmdc_lmpc_step_dev) from the
+        measured state, while the plants are Fossen vehicles as in simulate_mppi: this vehicle, or plant_params[b] for plant b -- the
+        model-mismatch case.  The planner sees the state alone, never the thruster lag.  The loop is device-resident: the state, the
+        lag, the plan z and the scaled dual variable y never come back to the host between ticks; (z, y) are carried from tick to
+        tick, moved one knot forward.
+
+        x0, ref and T as in simulate_mppi with H = planner.H and hold = planner.hold; dt must be the planner's.  Every plant starts
+        from zero thruster lag, a zero plan and y = 0.
+        Returns dict(traj [B,T+1,nx], u [B,T,nu] the applied commands, info [ticks,B,6] (edmdc_lmpc_step's), ticks = dict(x
+        [ticks,B,nx], lag [ticks,B,8,3] | None, U_nom [ticks,B,M,nu], y [ticks,B,M,nu], ref_row0 [ticks]): what the planner saw at
+        each tick, before its update)."""
+        import ctypes
+        hold, H, T = int(planner.hold), int(planner.H), int(T)
+        s = self._receding_setup(x0, ref, T, H, hold, plant_params, integrator)
+        ctx, B, nu = s.ctx, s.B, s.nu
+        if (planner.n, planner.r) != (s.nx, nu):
+            raise ValueError(f"the planner is for n = {planner.n}, r = {planner.r}; this vehicle needs {(s.nx, nu)}")
+        if float(dt) != planner.dt:
+            raise ValueError(f"the planner was condensed for dt = {planner.dt}, not {dt}")
+        if planner.ctx.device != ctx.device:
+            raise ValueError("the planner's arrays live on another device than this vehicle's")
+        self._receding_device_state(s)
+        D = engine.DevArray
+        U, Y = D(ctx, (B, s.M, nu)).zero_(), D(ctx, (B, s.M, nu)).zero_()
+        info = D(ctx, (max(s.nt, 1), B, 6))
+        rec_U, rec_Y = D(ctx, (max(s.nt, 1), B, s.M, nu)), D(ctx, (max(s.nt, 1), B, s.M, nu))
+        for n in range(s.nt):
+            row0, xn = self._receding_tick_begin(s, n)
+            rec_U.rows(n, n + 1).copy_from_device(U)
+            rec_Y.rows(n, n + 1).copy_from_device(Y)
+            ctx.check(ctx.lib.edmdc_lmpc_step_dev(ctx.h, planner.n, planner.r, planner.k, planner.gamma, None if planner.C is None else planner.C.ptr,
+                                                  planner.A.ptr, planner.B.ptr, planner.P.ptr, planner.Gc.ptr, planner.W.ptr, B,
+                                                  ctypes.byref(planner.cfg), H, float(dt), xn.ptr, s.d_ref.ptr, s.ref.shape[1], row0, U.ptr, Y.ptr, 1,
+                                                  s.ua.rows(n, n + 1).ptr, None, info.rows(n, n + 1).ptr), "edmdc_lmpc_step_dev")
+            self._receding_plant_tick(s, n, dt)
+        return self._receding_results(s, info, dict(U_nom=rec_U.numpy()[:s.nt], y=rec_Y.numpy()[:s.nt]))
 
     def one_step_rmse(self, X, U, dt):
         """one_step_rmse_physics (training/train_tank_brov2_koopmanEDMDc.py:237-247): Euler one-step predictions over a

@@ -1,5 +1,6 @@
 """Feedback laws for the closed-loop rollouts (engine.rollout_feedback, VehicleBase.simulate_closed_loop) and the record of the
-model-predictive update (engine.mppi_step, VehicleBase.simulate_mppi): builders of struct brov_feedback and struct brov_mppi, and
+model-predictive updates (engine.mppi_step, VehicleBase.simulate_mppi; engine.koopman_lmpc_step, VehicleBase.simulate_lmpc): builders of
+struct brov_feedback, struct brov_mppi and struct brov_lmpc, and
 the tracking error on the host.  include/brov2.h (brov_rollout_feedback) is the specification of the law:
 
     e[0:3]  = R(att)^T (p_ref - p)          e[3:6] = attitude error (wrapped Euler difference, or 2 s q_e.xyz)
@@ -104,6 +105,52 @@ def mppi(q, qf=None, r=0.0, sigma=0.1, lam=1.0, gamma=None, u_min=None, u_max=No
     for j in range(nu):
         cfg.r[j], cfg.sigma[j], cfg.u_min[j], cfg.u_max[j] = r[j], sg[j], lo[j], hi[j]
     cfg.lam, cfg.gamma, cfg.hold = lam, gamma, hold
+    return cfg
+
+
+def lmpc(q, qf=None, r=0.0, u_min=None, u_max=None, hold=1, iters=200, tol=0.0, rho=None, nu=None, n=12):
+    """struct brov_lmpc (include/brov2.h: edmdc_lmpc_step) from the stage weights q and terminal weights qf on the linear error
+    (scalar or [n]; qf=None means q), the command weights r (scalar or [nu]), limits u_min / u_max (scalar or [nu]; None = -inf /
+    +inf), hold (steps per knot), the iteration limit, the stop tolerance (0: always `iters` iterations) and the ADMM penalty rho.
+    rho=None leaves the field 0, which the library refuses: engine.KoopmanLmpc fills it with sqrt(lambda_min lambda_max) of the
+    condensed matrix.  n (12 or 13) is the state size, nu (6 or 8) defaults to the length of the first of r, u_min, u_max given as a
+    vector, else 8.  ValueError where the library would refuse the record: a NaN, a negative weight or tol, u_min > u_max, hold < 1,
+    iters outside 0 .. 1 000 000, a rho that is not finite and > 0."""
+    if nu is None:
+        nu = next((np.asarray(v).shape[0] for v in (r, u_min, u_max) if v is not None and np.ndim(v) == 1), 8)
+    nu, n = int(nu), int(n)
+    if nu not in (6, 8):
+        raise ValueError(f"nu must be 6 or 8, got {nu}")
+    if n not in (12, 13):
+        raise ValueError(f"n must be 12 or 13, got {n}")
+    q = _vec(q, n, 0.0, "q")
+    qf = q.copy() if qf is None else _vec(qf, n, 0.0, "qf")
+    r = _vec(r, nu, 0.0, "r")
+    lo, hi = _vec(u_min, nu, -np.inf, "u_min"), _vec(u_max, nu, np.inf, "u_max")
+    for name, v in (("hold", hold), ("iters", iters)):
+        if isinstance(v, float) and v != int(v):
+            raise ValueError(f"{name} must be an integer, got {v}")
+    hold, iters, tol = int(hold), int(iters), float(tol)
+    if hold < 1 or hold >= 2 ** 31:
+        raise ValueError(f"hold must be >= 1, got {hold}")
+    if not 0 <= iters <= 1000000:
+        raise ValueError(f"iters must be 0 .. 1 000 000, got {iters}")
+    if any(np.isnan(a).any() for a in (q, qf, r, lo, hi)) or np.isnan(tol) or (rho is not None and np.isnan(rho)):
+        raise ValueError("NaN in the linear-MPC record")
+    if np.any(q < 0) or np.any(qf < 0) or np.any(r < 0):
+        raise ValueError("the weights q, qf and r must be >= 0")
+    if tol < 0:
+        raise ValueError("tol must be >= 0")
+    if rho is not None and not (rho > 0 and np.isfinite(rho)):
+        raise ValueError("rho must be finite and > 0")
+    if np.any(lo > hi):
+        raise ValueError("u_min must be <= u_max")
+    cfg = _lib.BrovLmpc()
+    for i in range(n):
+        cfg.q[i], cfg.qf[i] = q[i], qf[i]
+    for j in range(nu):
+        cfg.r[j], cfg.u_min[j], cfg.u_max[j] = r[j], lo[j], hi[j]
+    cfg.rho, cfg.tol, cfg.hold, cfg.iters = (0.0 if rho is None else float(rho)), tol, hold, iters
     return cfg
 
 

@@ -12,7 +12,10 @@ sum dt |e_pos|^2, sum dt |e_att|^2, sum dt |u|^2, steps with a channel on a limi
 recording of the NOMINAL vehicle (on-device AR(1) commands, as examples/sim_koopman.py makes them) and handed to the same update
 through model.mppi_planner (engine.koopman_mppi_step: the learned model is linear in the command, so a sample costs a block
 convolution, not a rollout).  The plants, the seeds and the cost stay the same; the learned model never sees the thruster lag.
---planner both prints a column per planner.
+--planner koopman-qp plans with the same learned model but without samples: the model is linear in the command, so with a linear
+error the tracking problem of a tick is a box-constrained QP in the knots, solved on the device by ADMM (model.lmpc_planner,
+rov.simulate_lmpc: engine.koopman_lmpc_step) -- same weights, limits, horizon and plants.
+--planner both (or all) prints a column per planner: Fossen-MPPI, Koopman-MPPI and Koopman-QP ranked by the same realised metrics.
 
     python examples/mppi_tracking.py [--plants 16 --seconds 6 --samples 1024 --horizon 25 --hold 5 --current 0.2 --planner both]
 """
@@ -31,7 +34,8 @@ from bluerov2_dynamics_amd.fossen.BlueROV2 import BlueROV2             # noqa: E
 
 SPREAD = ("Xu", "Yv", "Zw", "Nr", "Xu_abs", "Yv_abs", "Zw_abs", "Nr_abs", "Xu_dot", "Yv_dot", "Zw_dot", "Nr_dot")
 NAMES = ("sum dt |e_pos|^2", "sum dt |e_att|^2", "sum dt |u|^2", "steps on a limit")
-LABEL = {"mppi": "fossen", "koopman": "koopman"}
+LABEL = {"mppi": "fossen", "koopman": "koopman", "koopman_qp": "koopman-qp"}
+HEAD = {"mppi": "MPPI fossen", "koopman": "MPPI koopman", "koopman_qp": "QP koopman"}
 
 
 def drawn_plants(base, n, seed, rel_std=0.05):
@@ -82,9 +86,9 @@ def fit_koopman(rov, x0, dt, rollouts=64, steps=300, n_rbfs=64, gamma=1.0, ridge
 
 
 def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, current=0.0, integrator="rk4", seed=0, verbose=True,
-        planner="fossen", fit_rollouts=64, fit_steps=300, n_rbfs=64):
-    """Returns dict(mppi [N,4] (planner fossen / both), koopman [N,4] (planner koopman / both), pid [N,4]): the closed-loop metrics of
-    every plant under the controllers"""
+        planner="fossen", fit_rollouts=64, fit_steps=300, n_rbfs=64, qp_iters=200):
+    """Returns dict(mppi [N,4] (planner fossen / both), koopman [N,4] (planner koopman / both), koopman_qp [N,4] (planner koopman-qp /
+    both), pid [N,4]): the closed-loop metrics of every plant under the controllers ("all" is "both")"""
     rov = BlueROV2(dt=dt)
     base = identify.params_of(rov)
     n = int(plants)
@@ -101,15 +105,19 @@ def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, curre
     REF = np.repeat(ref[None], n, axis=0)
     cfg = control.mppi(q=[40.0, 40.0, 60.0, 4.0, 4.0, 6.0, 2.0, 2.0, 3.0, 0.2, 0.2, 0.4], qf=[80.0, 80.0, 120.0, 8.0, 8.0, 12.0, 4.0, 4.0, 6.0, 0.4, 0.4, 0.8],
                        r=0.05, sigma=0.15, lam=0.2, u_min=-1.0, u_max=1.0, hold=hold, nu=8)
-    out, info = {}, {}
-    for key, label in (("mppi", "fossen"), ("koopman", "koopman")):
-        if planner not in (label, "both"):
+    out, info, model = {}, {}, None
+    for key, label in LABEL.items():
+        if planner not in (label, "both", "all"):
             continue
-        kp = None
-        if label == "koopman":
-            kp = fit_koopman(rov, x0, dt, fit_rollouts, fit_steps, n_rbfs).mppi_planner(int(horizon), hold, ctx=rov._ctx)
-        r = rov.simulate_mppi(np.repeat(x0[None], n, axis=0), REF, dt, cfg, T, int(samples), int(horizon), plant_params=ps,
-                              integrator=integrator, seed=seed, planner=kp)
+        if label != "fossen" and model is None:
+            model = fit_koopman(rov, x0, dt, fit_rollouts, fit_steps, n_rbfs)
+        X0 = np.repeat(x0[None], n, axis=0)
+        if label == "koopman-qp":
+            qp = control.lmpc(q=list(cfg.q), qf=list(cfg.qf), r=0.05, u_min=-1.0, u_max=1.0, hold=hold, iters=int(qp_iters), nu=8)
+            r = rov.simulate_lmpc(X0, REF, dt, model.lmpc_planner(int(horizon), qp, dt, ctx=rov._ctx), T, plant_params=ps, integrator=integrator)
+        else:
+            kp = model.mppi_planner(int(horizon), hold, ctx=rov._ctx) if label == "koopman" else None
+            r = rov.simulate_mppi(X0, REF, dt, cfg, T, int(samples), int(horizon), plant_params=ps, integrator=integrator, seed=seed, planner=kp)
         out[key] = metrics_of(rov.MODEL, r["traj"], r["u"], REF[:, :T], dt, -1.0, 1.0)
         info[key] = r["info"]
     fb = control.pid_thrusters(rov, [40.0, 40.0, 60.0, 4.0, 4.0, 6.0], [20.0, 20.0, 30.0, 1.0, 1.0, 2.0], [4.0, 4.0, 6.0, 0.4, 0.4, 0.6],
@@ -119,10 +127,14 @@ def run(plants=16, seconds=6.0, dt=0.02, samples=1024, horizon=25, hold=5, curre
     if verbose:
         what = f"in currents of {current} m/s" if current > 0 else "drawn around the nominal vehicle"
         for key, i in info.items():
+            if key == "koopman_qp":
+                print(f"{n} plants {what}, {T} steps of {dt} s, hold {hold}; QP (koopman model): {qp_iters} ADMM iterations over {horizon} steps "
+                      f"per tick, last residuals {i[:, :, 2].max():.1e} / {i[:, :, 3].max():.1e}, {i[:, :, 5].mean():.1f} knot entries at a limit")
+                continue
             print(f"{n} plants {what}, {T} steps of {dt} s, hold {hold}; MPPI{'' if planner == 'fossen' else ' (' + LABEL[key] + ' model)'}: "
                   f"{samples} samples over {horizon} steps per tick, effective sample size {i[:, :, 2].mean():.1f}, "
                   f"{int(i[:, :, 3].sum())} non-finite samples")
-        cols = [(k, "MPPI" if planner == "fossen" else "MPPI " + LABEL[k]) for k in info] + [("pid", "PID")]
+        cols = [(k, "MPPI" if planner == "fossen" else HEAD[k]) for k in info] + [("pid", "PID")]
         print(f"{'mean over the plants':<22}" + "".join(f"{label:>14}" for _, label in cols))
         for i, name in enumerate(NAMES):
             print(f"{name:<22}" + "".join(f"{out[k][:, i].mean():>14.5g}" for k, _ in cols))
@@ -139,14 +151,15 @@ def main(argv=None):
     ap.add_argument("--current", type=float, default=0.0)
     ap.add_argument("--euler", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--planner", choices=["fossen", "koopman", "both"], default="fossen")
+    ap.add_argument("--planner", choices=["fossen", "koopman", "koopman-qp", "both", "all"], default="fossen")
+    ap.add_argument("--qp-iters", type=int, default=200, help="koopman-qp: ADMM iterations per tick")
     ap.add_argument("--fit-rollouts", type=int, default=64, help="koopman: simulated recordings of the nominal vehicle")
     ap.add_argument("--fit-steps", type=int, default=300, help="koopman: steps per recording")
     ap.add_argument("--rbfs", type=int, default=64, help="koopman: RBF centres")
     a = ap.parse_args(argv)
     out = run(a.plants, a.seconds, samples=a.samples, horizon=a.horizon, hold=a.hold, current=a.current,
               integrator="euler" if a.euler else "rk4", seed=a.seed, planner=a.planner, fit_rollouts=a.fit_rollouts, fit_steps=a.fit_steps,
-              n_rbfs=a.rbfs)
+              n_rbfs=a.rbfs, qp_iters=a.qp_iters)
     return {k: v.mean(axis=0) for k, v in out.items()}
 
 

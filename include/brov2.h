@@ -427,6 +427,62 @@ BROV_API int edmdc_mppi_step_dev(brov_ctx* ctx, int n, int r, int k, double gamm
                         const double* d_eps, double* d_U_nom, int shift, double* d_u_apply, double* d_cost, double* d_info,
                         double* d_pred);
 
+/* ---- linear model-predictive control with a Koopman EDMDc model: a batched box-constrained QP ---------------------------------------
+ * edmdc_lmpc_step solves, for nb problems, the convex QP that the EDMDc model makes of the tracking problem of edmdc_mppi_step: the
+ * prediction is linear in the knots v [M][nu], the error is taken linear too, so the cost is a quadratic with ONE matrix Hq for
+ * every problem and a vector g per problem.  The model arguments n, r = nu, k, gamma, C, A, B, P, Gc, the knots (M = ceil(H / hold),
+ * Nv = M nu <= 312) and the reference window (ref_total, ref_row0; one row = a set-point) are those of edmdc_mppi_step.
+ * Prediction.  x_hat_t = F[t] + sum_{m : m hold < t} Gc[t][m] v[m], F[t] = P[t] phi(x): the bits of edmdc_mppi_step's prediction.
+ * Linear error.  e_t = rt_t - x_hat_t, plain component differences, where rt_t is reference row ref_row0 + t adjusted ONCE against the
+ * measured state x (never against the prediction):
+ *     n = 12: rt_t[i] = r_t[i] - 2 pi rint((r_t[i] - x[i]) / (2 pi)) for the angles i = 3, 4, 5; the other entries as they are
+ *     n = 13: entries 3..6 of r_t times -1 when sum_i x[3+i] r_t[3+i] < 0 (the short way round); the other entries as they are
+ * Objective.  brov_mppi_step's cost with this error and no importance term:
+ *     J(v) = sum_{t<H} dt ( sum_i q[i] e_t[i]^2 + sum_j r[j] v[m(t)][j]^2 ) + sum_i qf[i] e_H[i]^2              i < n
+ *          = 1/2 v' Hq v + g' v + c,   with w_t = dt, Q_t = q for t < H, w_H = 1, Q_H = qf, e0_t = F[t] - rt_t:
+ *     Hq = 2 sum_t w_t Gc[t]' diag(Q_t) Gc[t] + 2 diag(dt r[j] steps(m))        steps(m) = the horizon steps knot m holds
+ *     g  = 2 sum_t w_t Gc[t]' diag(Q_t) e0_t                                    (t ascending, then i ascending, one sum per column)
+ *     c  = J(0)
+ * Gc[t] is the n x Nv matrix [Gc[t][0] .. Gc[t][M-1]] (zero where m hold >= t).  Hq depends on the model, the record, H and dt only.
+ * The caller passes W [Nv][Nv] = (Hq + rho I)^-1, symmetric, as it passes P and Gc; the call reads W as given and needs Hq nowhere.
+ * Iteration.  Scaled ADMM from z = clip(U_nom, u_min, u_max) and y = y_io (NULL: 0):
+ *     v+ = W (rho (z - y) - g)            (row i: the sum over j ascending of W[j][i] s_j)
+ *     z+ = clip(v+ + y, u_min, u_max),    y+ = (y + v+) - z+
+ *     r_prim = max |v+ - z+|,   r_dual = rho max |z+ - z|
+ * A problem stops after the first iteration at which r_prim <= tol and r_dual <= tol (tol = 0: no test), or after `iters`; the
+ * problems stop independently.  With iters = 0 there is no residual: both are reported as +inf.
+ * In / out: U_nom [nb][M][nu] receives z; y_io [nb][M][nu] (optional) receives y; shift = 1 moves both one knot forward, the last knot
+ * repeated.  Outputs, each optional: u_apply [nb][hold][nu] = the first knot of z (before the shift) in hold rows; pred [nb][H+1][n] =
+ * x_hat under z; info [nb][6] = J(z), J(clip(U_nom)), r_prim, r_dual, the iterations done, the number of entries of z equal to a
+ * limit.  J is evaluated from the prediction, never from W: a W that belongs to another record shows as a J that does not fall.
+ * A problem whose g or c is not finite: U_nom and y_io are left as they came (no shift), u_apply is the clamped first knot, info =
+ * (+inf, +inf, +inf, +inf, 0, 0), pred is NaN; the call still returns BROV_OK.
+ * Refused on the host with BROV_ERR_ARG and a brov_last_error text naming the rule, before anything is copied or launched: what
+ * edmdc_mppi_step refuses of n, r, k, H, M nu, nb, dt, gamma, the reference window and NULL arrays; a NULL W; hold < 1; iters outside
+ * 0 .. 1 000 000; rho not finite and > 0; tol negative; a negative weight; u_min > u_max (channels < nu); a NaN anywhere in the
+ * record.  nb = 0: BROV_OK, nothing touched.
+ * Deterministic: no atomics, every sum in a fixed order -- two calls with the same arguments give the same bits in every output. */
+typedef struct brov_lmpc {
+    double q[13], qf[13];           /* stage / terminal weights on the linear error, >= 0; entry 12 ignored for n = 12 */
+    double r[8];                    /* weights on the command, >= 0; entries >= nu ignored.  (q, qf, r) must make Hq positive definite */
+    double u_min[8], u_max[8];      /* u_min <= u_max, may be +-inf */
+    double rho;                     /* ADMM penalty, finite and > 0: the rho of W */
+    double tol;                     /* >= 0; 0 = always `iters` iterations */
+    int32_t hold, iters;            /* hold >= 1; 0 <= iters <= 1 000 000 */
+} brov_lmpc;
+BROV_API int edmdc_lmpc_step(brov_ctx* ctx, int n, int r, int k, double gamma, const double* C, const double* A, const double* B,
+                    const double* P, const double* Gc, const double* W, int64_t nb, const brov_lmpc* cfg /* host */, int64_t H, double dt,
+                    const double* x, const double* ref, int64_t ref_total, int64_t ref_row0, double* U_nom, double* y_io, int shift,
+                    double* u_apply, double* pred, double* info);
+BROV_API int edmdc_lmpc_step_dev(brov_ctx* ctx, int n, int r, int k, double gamma, const double* d_C, const double* d_A, const double* d_B,
+                        const double* d_P, const double* d_Gc, const double* d_W, int64_t nb, const brov_lmpc* cfg /* host */, int64_t H,
+                        double dt, const double* d_x, const double* d_ref, int64_t ref_total, int64_t ref_row0, double* d_U_nom,
+                        double* d_y_io, int shift, double* d_u_apply, double* d_pred, double* d_info);
+/* The LDS bytes of one block of the solver (four problems) at Nv = M nu variables, and in *w_in_lds (optional) whether W is staged
+ * into them (1) or read from global memory (0): staged while two blocks fit the 160 KB of a compute unit together.  Needs no device.
+ * -1 for nv outside 1 .. 312. */
+BROV_API int edmdc_lmpc_block_lds(int64_t nv, int* w_in_lds);
+
 /* ---- PINc residual network (inference) ----------------------------------------------------
  * The reference's PINcNet (training/train_tank_brov2_full_comparison.py:648-721) with the architecture of its shipped
  * checkpoint: z = [x9, u4, dt] (14) -> 4 x (Linear, AdaptiveSoftplus, LayerNorm(64)) -> Linear(64 -> 9), fp32.
