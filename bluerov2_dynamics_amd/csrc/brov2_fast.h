@@ -70,6 +70,7 @@ struct HotConstsT {
     static constexpr bool RESIDENT = RES;
     double E[12], db[6];
     double da[6], G[5], ld[4], al4[3];     // RESIDENT only
+    double tk[2];                          // RESIDENT only, VGPRs: the constant the sin / cos kernels of trig_delta share (see there)
 };
 typedef HotConstsT<false> HotConsts;
 typedef HotConstsT<true> HotConstsResident;
@@ -82,6 +83,8 @@ typedef HotConstsT<true> HotConstsResident;
 #endif
 #define BROV_PIN_V(x) asm volatile("" : "+v"(x))
 #define BROV_PIN_S(x) asm volatile("" : "+s"(x))
+// r is formed HERE, not wherever its first reader sits: the values it was formed from die here and can be changed in place afterwards
+#define BROV_FORM_HERE(r) asm volatile("" : "+v"(r))
 #define BROV_SC(h, p, f) (HC::RESIDENT ? (h).f : (p)->f)
 
 template <bool RES>
@@ -100,7 +103,16 @@ __device__ __forceinline__ void load_hot(CFP pp, HotConstsT<RES>& h) {
         for (int i = 0; i < 4; ++i) { h.ld[i] = p.ld[i]; BROV_PIN_S(h.ld[i]); }
 #pragma unroll
         for (int i = 0; i < 3; ++i) { h.al4[i] = p.al4[i]; BROV_PIN_S(h.al4[i]); }
+        h.tk[0] = -1.98412698298579493134e-04; BROV_PIN_V(h.tk[0]);
+        h.tk[1] = 2.48015872894767294178e-05;  BROV_PIN_V(h.tk[1]);
     }
+}
+
+// the pinned sin / cos constants of a RESIDENT kernel for the reference vehicle (nullptr: literals.  load_hot pins them for every RESIDENT kernel;
+// the GENERIC body wave, which is short of VGPRs, never reads them, so there the two pairs are free again right after the pin)
+template <bool GENERIC, class HC>
+__device__ __forceinline__ const double* trig_consts(const HC& h) {
+    if constexpr (HC::RESIDENT && !GENERIC) return h.tk; else return nullptr;
 }
 
 // pointer laundering: makes the compiler re-issue the (scalar) loads behind `p` at this point
@@ -113,7 +125,8 @@ __device__ __forceinline__ CFP relaunder(CFP p) {
 // ---- sin / cos --------------------------------------------------------------------------------
 // Valid (<= ~1 ulp) for |x| < 2^31 pi/2 ~ 3.4e9 rad; NaN/inf give NaN like np.sin/np.cos.  Beyond that
 // range the quadrant index saturates (a vehicle attitude angle never gets there).
-__device__ __forceinline__ void sincos_fast(double x, double& s, double& c, const double2* __restrict__ qt) {
+__device__ __forceinline__ void sincos_fast(double x, double& s, double& c, const double2* __restrict__ qt, const double* kv = nullptr) {
+    const double S7 = kv ? kv[0] : -1.98412698298579493134e-04, C8 = kv ? kv[1] : 2.48015872894767294178e-05;     // see trig_delta
     const double kf = rint(x * 6.36619772367581382433e-01);
     double r = fma(-kf, 1.57079632673412561417e+00, x);      // pio2_1  (33 bits)
     r = fma(-kf, 6.07710050630396597660e-11, r);             // pio2_2  (33 bits)
@@ -122,13 +135,13 @@ __device__ __forceinline__ void sincos_fast(double x, double& s, double& c, cons
     const double z = r * r;
     double ps = fma(z, 1.58969099521155010221e-10, -2.50507602534068634195e-08);
     ps = fma(z, ps, 2.75573137070700676789e-06);
-    ps = fma(z, ps, -1.98412698298579493134e-04);
+    ps = fma(z, ps, S7);
     ps = fma(z, ps, 8.33333333332248946124e-03);
     ps = fma(z, ps, -1.66666666666666324348e-01);
     const double sr = fma(z * r, ps, r);
     double pc = fma(z, -1.13596475577881948265e-11, 2.08757232129817482790e-09);
     pc = fma(z, pc, -2.75573143513906633035e-07);
-    pc = fma(z, pc, 2.48015872894767294178e-05);
+    pc = fma(z, pc, C8);
     pc = fma(z, pc, -1.38888888888741095749e-03);
     pc = fma(z, pc, 4.16666666666666019037e-02);
     const double cr = fma(z * z, pc, fma(-0.5, z, 1.0));
@@ -151,10 +164,10 @@ __device__ __forceinline__ void init_quadrant_table(double2* qt) {
 // sin/cos of the three attitude angles of one dynamics() call
 struct Trig { double sphi, cphi, sth, cth, spsi, cpsi; };
 
-__device__ __forceinline__ void trig_full(const double* ang, Trig& t, const double2* __restrict__ qt) {
-    sincos_fast(ang[0], t.sphi, t.cphi, qt);
-    sincos_fast(ang[1], t.sth, t.cth, qt);
-    sincos_fast(ang[2], t.spsi, t.cpsi, qt);
+__device__ __forceinline__ void trig_full(const double* ang, Trig& t, const double2* __restrict__ qt, const double* kv = nullptr) {
+    sincos_fast(ang[0], t.sphi, t.cphi, qt, kv);
+    sincos_fast(ang[1], t.sth, t.cth, qt, kv);
+    sincos_fast(ang[2], t.spsi, t.cpsi, qt, kv);
 }
 
 // RK4 stages 2-4 evaluate the RHS at angles a + d with a = the angles at the start of the step (whose sin/cos the
@@ -172,17 +185,31 @@ __device__ __forceinline__ void trig_full(const double* ang, Trig& t, const doub
 // SHORT (BROV_TRIG_SHORT, round 5): the half-step stages' increments are half the full step's, so their kernels stop one term earlier
 // and the direct range is |d| <= 1/16 -- dropped terms d^9 / 9! and d^10 / 10! are < 4e-17 and < 3e-19 ABSOLUTE there, against the
 // O(1) sines and cosines the increment is combined with; the share of wave-steps that take the halving path stays what it is.
-template <bool SHORT = false>
-__device__ __forceinline__ void trig_delta(const Trig& b, const double d[3], Trig& t, double* dpsi = nullptr) {
-    double dd[3] = {d[0], d[1], d[2]};
+// LEAN (the body wave of rollout_pair_kernel, reference vehicle): the common path carries nothing for the rare one.  d is scaled IN PLACE (the
+// caller passes a temporary that is dead afterwards), the halving count is derived again from m inside the second rare region, and both
+// regions hang on the one lane mask of the range test -- no copy of d, no k = 0 and no second compare per call.  The two constants every
+// kernel length uses in a Horner step next to another literal (-1/7!, 1/8! as fdlibm has them) come from VGPRs there (kv): a VALU
+// instruction reads one scalar operand, and with both literals in SGPRs the compiler copies one into a VGPR at every call.
+// Only for kernels that keep everything in registers: with two regions on one mask the compiler has been seen to place a register spill
+// at the join of the second region AHEAD of the instruction that restores exec, where a wave that skipped the region runs it with exec = 0
+// and loses the value (one-lane RK4 kernel, GENERIC, 256 VGPRs + AGPRs).  The other kernels keep the form with a copy and a count.
+template <bool SHORT = false, bool LEAN = false>
+__device__ __forceinline__ void trig_delta(const Trig& b, double d[3], Trig& t, double* dpsi = nullptr, const double* kv = nullptr) {
+    constexpr int K0 = SHORT ? 4 : 3;
+    const double S7 = kv ? kv[0] : -1.98412698298579493134e-04, C8 = kv ? kv[1] : 2.48015872894767294178e-05;
+    double dcopy[3] = {d[0], d[1], d[2]};                    // dcopy and k serve the form with a copy and a count only: dead when LEAN
+    double* dd = LEAN ? d : dcopy;
     int k = 0;
     const double m = fmax(fmax(fabs(d[0]), fabs(d[1])), fabs(d[2]));
-    if (!(m <= (SHORT ? 0.0625 : 0.125))) {                  // also NaN
+    const bool far = !(m <= (SHORT ? 0.0625 : 0.125));       // also NaN
+    if (far) {
+        double mf = m;
+        if constexpr (LEAN) asm volatile("; trig_delta range extension, rare" : "+v"(mf));      // not speculatable: the block stays behind a branch of its own
         int e;
-        (void)frexp(m, &e);                                  // m < 2^e
-        k = e + (SHORT ? 4 : 3);
+        (void)frexp(mf, &e);                                 // m < 2^e
+        k = e + K0;
         double sc = ldexp(1.0, -k);
-        if (!(m < 0x1p37)) { sc = __builtin_nan(""); k = 0; }
+        if (!(mf < 0x1p37)) { sc = __builtin_nan(""); k = 0; }
 #pragma unroll
         for (int i = 0; i < 3; ++i) dd[i] *= sc;
     }
@@ -192,12 +219,12 @@ __device__ __forceinline__ void trig_delta(const Trig& b, const double d[3], Tri
         const double z = dd[i] * dd[i];
         double ps, pc;
         if constexpr (SHORT) {
-            ps = fma(z, -1.98412698298579493134e-04, 8.33333333332248946124e-03);
-            pc = fma(z, 2.48015872894767294178e-05, -1.38888888888741095749e-03);
+            ps = fma(z, S7, 8.33333333332248946124e-03);
+            pc = fma(z, C8, -1.38888888888741095749e-03);
         } else {
-            ps = fma(z, 2.75573137070700676789e-06, -1.98412698298579493134e-04);
+            ps = fma(z, 2.75573137070700676789e-06, S7);
             ps = fma(z, ps, 8.33333333332248946124e-03);
-            pc = fma(z, -2.75573143513906633035e-07, 2.48015872894767294178e-05);
+            pc = fma(z, -2.75573143513906633035e-07, C8);
             pc = fma(z, pc, -1.38888888888741095749e-03);
         }
         ps = fma(z, ps, -1.66666666666666324348e-01);
@@ -206,15 +233,26 @@ __device__ __forceinline__ void trig_delta(const Trig& b, const double d[3], Tri
         pc = fma(z, pc, -0.5);
         cm[i] = z * pc;                                      // cos d - 1
     }
-    for (int j = 0; j < k; ++j) {                            // lane-varying trip count, almost always 0
+    auto doubling = [&](int n) {                             // lane-varying trip count, almost always 0
+        for (int j = 0; j < n; ++j) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const double t2 = sd[i] + sd[i];
-            const double s2 = fma(t2, cm[i], t2);
-            cm[i] = -(t2 * sd[i]);
-            sd[i] = s2;
+            for (int i = 0; i < 3; ++i) {
+                const double t2 = sd[i] + sd[i];
+                const double s2 = fma(t2, cm[i], t2);
+                cm[i] = -(t2 * sd[i]);
+                sd[i] = s2;
+            }
         }
-    }
+    };
+    if constexpr (LEAN) {
+        if (far) {
+            double mf = m;
+            asm volatile("; trig_delta doubling, rare" : "+v"(mf));
+            int e;
+            (void)frexp(mf, &e);
+            doubling((mf < 0x1p37) ? e + K0 : 0);
+        }
+    } else doubling(k);
     t.sphi = fma(b.cphi, sd[0], fma(b.sphi, cm[0], b.sphi)); t.cphi = fma(-b.sphi, sd[0], fma(b.cphi, cm[0], b.cphi));
     t.sth = fma(b.cth, sd[1], fma(b.sth, cm[1], b.sth));     t.cth = fma(-b.sth, sd[1], fma(b.cth, cm[1], b.cth));
     t.spsi = fma(b.cpsi, sd[2], fma(b.spsi, cm[2], b.spsi)); t.cpsi = fma(-b.spsi, sd[2], fma(b.cpsi, cm[2], b.cpsi));
@@ -304,18 +342,21 @@ __device__ __forceinline__ void rhs_fast_euler(const HC& h, CFP p, const double 
         }
         xd[2] = z2;
     }
-    double cc = cth;
     // fossen/BlueROV2.py:52-54.  As plain code the compiler turns the clamp into nine select / convert instructions per stage;
-    // behind a wave-level test (is ANY lane that close to the singularity?) the common path pays one compare and a scalar branch
+    // behind a wave-level test (is ANY lane that close to the singularity?) the common path pays one compare and a scalar branch.
+    // The common path takes the reciprocal of cth itself; the rare block forms it again from the clamped value for its lanes, so no
+    // copy of cth is made for the block to modify.
 #if BROV_CLAMP_BRANCH
-    if (__builtin_amdgcn_ballot_w64(fabs(cc) < 1e-7) != 0) {
+    double ic = recip_fast(cth);
+    if (__builtin_amdgcn_ballot_w64(fabs(cth) < 1e-7) != 0) {
         asm volatile("; cos(theta) clamp, rare" ::: "memory");      // not speculatable: keeps the block behind its branch
-        if (fabs(cc) < 1e-7) cc = 1e-7 * ((cc > 0.0) - (cc < 0.0));
+        if (fabs(cth) < 1e-7) ic = recip_fast(1e-7 * ((cth > 0.0) - (cth < 0.0)));
     }
 #else
+    double cc = cth;
     if (fabs(cc) < 1e-7) cc = 1e-7 * ((cc > 0.0) - (cc < 0.0));
-#endif
     const double ic = recip_fast(cc);
+#endif
     const double m = fma(sphi, nu[4], cphi * nu[5]);   // sin(phi) q + cos(phi) r
     xd[3] = fma(sth * ic, m, nu[3]);
     xd[4] = fma(cphi, nu[4], -(sphi * nu[5]));
@@ -544,11 +585,12 @@ __device__ __forceinline__ void integrate_fast(const HC& h, CFP p, double dt, do
                                                const double2* qt, Trig* carry, bool refresh) {
     constexpr int NX = Dims<MODEL>::NX;
     constexpr bool ANG = !model_is_quat(MODEL);          // x[3..5] are Euler angles
+    constexpr bool LEAN = HC::RESIDENT && !GENERIC;      // trig_delta without its copies (see there)
     double a[6];
     Trig tb, ts;
     const bool CARRY = ANG && carry != nullptr;
     if constexpr (ANG) {
-        if (!CARRY || refresh) trig_full(x + 3, tb, qt);
+        if (!CARRY || refresh) trig_full(x + 3, tb, qt, trig_consts<GENERIC>(h));
         else tb = *carry;
     }
     double dang[3];          // angle increment of the whole step (carry only)
@@ -559,8 +601,12 @@ __device__ __forceinline__ void integrate_fast(const HC& h, CFP p, double dt, do
         if (CARRY) {
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
-                if (i >= 3 && i < 6) { dang[i - 3] = dt * k[i]; x[i] += dang[i - 3]; }
-                else x[i] = fma(dt, k[i], x[i]);
+                if (i >= 3 && i < 6) {
+                    if constexpr (LEAN) {
+#pragma clang fp contract(off)                           // as before the angle sum was pinned in front of trig_delta: the increment rounded, then added
+                        dang[i - 3] = dt * k[i]; x[i] += dang[i - 3]; BROV_FORM_HERE(x[i]);
+                    } else { dang[i - 3] = dt * k[i]; x[i] += dang[i - 3]; }
+                } else x[i] = fma(dt, k[i], x[i]);
             }
         } else {
 #pragma unroll
@@ -583,7 +629,7 @@ __device__ __forceinline__ void integrate_fast(const HC& h, CFP p, double dt, do
                 if (ANG && i >= 3 && i < 6) dl[i - 3] = c * k[i];
                 else xs[i] = fma(c, k[i], x[i]);
             }
-            if constexpr (ANG) trig_delta<BROV_TRIG_SHORT && decltype(HALF)::value>(tb, dl, ts, PSIF ? dps : nullptr);
+            if constexpr (ANG) trig_delta<BROV_TRIG_SHORT && decltype(HALF)::value, LEAN>(tb, dl, ts, PSIF ? dps : nullptr, trig_consts<GENERIC>(h));
         };
         // horizontal position increment of a later stage: turn its p_dot by the stage's yaw increment, then weight it
         auto add_turned = [&](double w) {
@@ -620,7 +666,7 @@ __device__ __forceinline__ void integrate_fast(const HC& h, CFP p, double dt, do
         if (CARRY) {
 #pragma unroll
             for (int i = PSIF ? 2 : 0; i < NX; ++i) {
-                if (i >= 3 && i < 6) { dang[i - 3] = fma(h6, k[i], xn[i]); x[i] += dang[i - 3]; }
+                if (i >= 3 && i < 6) { dang[i - 3] = fma(h6, k[i], xn[i]); x[i] += dang[i - 3]; if constexpr (LEAN) BROV_FORM_HERE(x[i]); }
                 else x[i] = fma(h6, k[i], xn[i]);
             }
         } else {
@@ -628,7 +674,7 @@ __device__ __forceinline__ void integrate_fast(const HC& h, CFP p, double dt, do
             for (int i = PSIF ? 2 : 0; i < NX; ++i) x[i] = fma(h6, k[i], xn[i]);
         }
     }
-    if constexpr (ANG) { if (CARRY) trig_delta(tb, dang, *carry); }
+    if constexpr (ANG) { if (CARRY) trig_delta<false, LEAN>(tb, dang, *carry, nullptr, trig_consts<GENERIC>(h)); }
     if constexpr (model_is_quat(MODEL)) quat_normalize(x + 3);
 }
 
