@@ -60,6 +60,17 @@ class BrovMppi(ctypes.Structure):
     ]
 
 
+class BrovUkf(ctypes.Structure):
+    """struct brov_ukf (include/brov2.h): the noise model and sigma-point settings of brov_ukf_filter.  fossen/estimate.py builds it."""
+    _fields_ = [
+        ("q", ctypes.c_double * 12), ("r", ctypes.c_double * 12),
+        ("alpha", ctypes.c_double), ("beta", ctypes.c_double), ("kappa", ctypes.c_double),
+    ]
+
+
+assert ctypes.sizeof(BrovUkf) == 27 * 8       # sizeof(brov_ukf), asserted in csrc/capi.hip
+
+
 class BrovLmpc(ctypes.Structure):
     """struct brov_lmpc (include/brov2.h): weights, limits and ADMM settings of edmdc_lmpc_step.  fossen/control.py builds it."""
     _fields_ = [
@@ -178,6 +189,10 @@ SIGNATURES = {
                                                  ctypes.POINTER(BrovFeedback), ctypes.c_int, i64, i64, ctypes.c_double, c_void_p,
                                                  c_void_p, c_void_p, i64, c_void_p, c_void_p, c_void_p, i64, c_void_p, c_void_p,
                                                  c_void_p]),
+    "brov_ukf_filter": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                       ctypes.POINTER(BrovUkf), i64, i64, ctypes.c_double] + [c_void_p] * 11),
+    "brov_ukf_filter_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                           ctypes.POINTER(BrovUkf), i64, i64, ctypes.c_double] + [c_void_p] * 11),
     "brov_mppi_step": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.POINTER(BrovParams),
                                       ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
                                       i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),

@@ -44,6 +44,26 @@ struct FeedbackArgs {
     double *lag, *z, *traj, *xT, *u_applied, *metrics;
 };
 hipError_t launch_rollout_feedback(hipStream_t st, int model, int integ, int lag_mode, int P, const FeedbackArgs& a);
+// Unscented Kalman filter on the 12-state models (ukf.hip; include/brov2.h: brov_ukf_filter holds the law): candidate j filters B
+// recordings of T rows.  UkfRec is what the host derives from one struct brov_ukf (c = sqrt(n + lambda), the centre weight of the
+// covariance and the weight of the other 24 points); d_rec holds one record (rec_per_candidate = 0) or P.  x0 [B][12], P0
+// [B][12][12], U [B][T][nu] and Y [B][T][12] are shared by the candidates; every output is per candidate and may be nullptr: lag
+// [P][B][24] in / out, xf, pstd, innov [P][B][T][12], xT [P][B][12], PT [P][B][144], info [P][B][4].  One launch; T >= 1.
+struct UkfRec {
+    double q[12], r[12];
+    double c, wc0, wi, pad;
+};
+struct UkfArgs {
+    const FastParams* fp;
+    const UkfRec* rec;
+    int rec_per_candidate, pad;
+    int64_t B, T;
+    double dt;
+    const double *x0, *P0, *U, *Y;
+    double *lag, *xf, *pstd, *innov, *xT, *PT, *info;
+};
+int ukf_waves_per_block();      // recordings per block of the filter kernel
+hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a);
 // One MPPI update for B problems (mppi.hip; include/brov2.h: brov_mppi_step holds the law).  MppiRec is struct brov_mppi byte for
 // byte; rec is ONE device record.  fp holds one parameter set (per_problem = 0) or B.  x [B][nx], lag [B][24] or nullptr (zero), ref
 // [B][ref_total][nx], eps [B][K][M][nu] or nullptr (the seeded stream), U_nom [B][M][nu] in / out, M = ceil(H / hold).  cost [B][K]

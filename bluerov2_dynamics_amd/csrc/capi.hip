@@ -1666,6 +1666,97 @@ int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64
                             lag_io, z_io, traj, stride, xT, u_applied, metrics);
 }
 
+// ---- state estimation: the unscented Kalman filter (ukf.hip) -----------------------------------------------------------------------
+static_assert(sizeof(brov_ukf) == 27 * 8 && sizeof(UkfRec) == 28 * 8, "brov_ukf: 27 doubles; UkfRec: the variances and three derived weights");
+// Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
+// and of the derived records, one launch.  host: the arrays are the caller's host memory.
+static int ukf_filter(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
+                      const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
+                      const double* Y, double* lag_io, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
+    bool empty;
+    int rc = pop_call_ok(c, "brov_ukf_filter", model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
+    if (rc) return rc;
+    if (model != BROV_THRUSTER_EULER && model != BROV_WRENCH_EULER)
+        return fail(c, BROV_ERR_ARG, "brov_ukf_filter: the 12-state Euler models only (BROV_THRUSTER_EULER, BROV_WRENCH_EULER)");
+    if (empty) return BROV_OK;
+    if (T < 1) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: T must be >= 1");
+    if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: NULL input");
+    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: nrec must be 1 or P");
+    std::vector<UkfRec> rec((size_t)nrec);
+    for (int64_t k = 0; k < nrec; ++k) {
+        const brov_ukf& u = ukf[k];
+        const std::string who = "brov_ukf_filter: ukf[" + std::to_string(k) + "]: ";
+        if (!std::isfinite(u.alpha) || !(u.alpha > 0.0)) return fail(c, BROV_ERR_ARG, who + "alpha must be finite and > 0");
+        const double n = 12.0, lambda = u.alpha * u.alpha * (n + u.kappa) - n, nl = n + lambda;
+        if (!(nl > 0.0) || !std::isfinite(nl) || !std::isfinite(u.beta))
+            return fail(c, BROV_ERR_ARG, who + "n + lambda must be finite and > 0 (and beta finite)");
+        for (int i = 0; i < 12; ++i) {
+            if (!(u.q[i] >= 0.0) || std::isinf(u.q[i])) return fail(c, BROV_ERR_ARG, who + "q must be finite and >= 0");
+            if (!(u.r[i] >= 0.0)) return fail(c, BROV_ERR_ARG, who + "r must be >= 0 (+inf: never measured)");
+            rec[k].q[i] = u.q[i];
+            rec[k].r[i] = u.r[i];
+        }
+        rec[k].c = std::sqrt(nl);
+        rec[k].wc0 = lambda / nl + 1.0 - u.alpha * u.alpha + u.beta;
+        rec[k].wi = 1.0 / (2.0 * nl);
+        rec[k].pad = 0.0;
+    }
+    std::vector<FastParams> fp;
+    std::vector<double> phi;
+    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const int nu = NU(model);
+    const bool lag = lag_io && model == BROV_THRUSTER_EULER;
+    const size_t nin = (size_t)B, nout = (size_t)P * B;
+    UkfArgs args{};
+    args.rec_per_candidate = nrec > 1;
+    args.B = B; args.T = T; args.dt = dt;
+    FastParams* d_fp;
+    UkfRec* d_rec;
+    Arena a(c, host);
+    rc = a.lay("brov_ukf_filter", [&] {
+        args.x0 = a.in(x0, nin * 12);
+        args.P0 = a.in(P0, nin * 144);
+        args.U = a.in(U, nin * T * nu);
+        args.Y = a.in(Y, nin * T * 12);
+        args.lag = lag ? a.inout(lag_io, nout * 24) : nullptr;
+        args.xf = xf ? a.out(xf, nout * T * 12) : nullptr;
+        args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
+        args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
+        args.xT = xT ? a.out(xT, nout * 12) : nullptr;
+        args.PT = PT ? a.out(PT, nout * 144) : nullptr;
+        args.info = info ? a.out(info, nout * 4) : nullptr;
+        d_fp = a.take<FastParams>(P);
+        d_rec = a.take<UkfRec>(nrec);
+    });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
+    args.fp = d_fp;
+    args.rec = d_rec;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, args));
+    }
+    return a.finish();
+}
+
+int brov_ukf_filter_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
+                        const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U,
+                        const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
+                        double* d_info) {
+    return ukf_filter(c, false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf, d_pstd, d_innov,
+                      d_xT, d_PT, d_info);
+}
+
+int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
+                    int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
+                    double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
+    return ukf_filter(c, true, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
+}
+
 // ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------
 static_assert(sizeof(brov_mppi) == sizeof(MppiRec) && sizeof(brov_mppi) == 59 * 8, "MppiRec is brov_mppi byte for byte");
 // What brov_mppi_step and edmdc_mppi_step (`who`) refuse of the sample count and the horizon ...

@@ -1,0 +1,294 @@
+// ukf.hip -- unscented Kalman filter on the Fossen model: candidate j filters B noisy recordings of T rows under params[j]
+// (include/brov2.h: brov_ukf_filter, which is the specification of the law).
+//
+// One wave per (candidate, recording): candidate = blockIdx.y with the vehicle constants through as_constant(fp + blockIdx.y) as in
+// rollout_feedback_kernel, UKF_WAVES recordings per block, the time loop inside the kernel.  The wave's (x, P), the Cholesky factor,
+// the 25 propagated deviations and their mean live in the wave's own LDS image between the phases of a row:
+//   update    12 scalar Kalman updates in order.  Lanes 0..11 form the gain column k = P[:, i] / s and update x; every lane owns one
+//             entry of the lower triangle of P (lanes 0..13 a second one: 78 entries on 64 lanes), keeps it in a register over the
+//             row and writes it to both triangles of the image, so the image stays bit-symmetric.
+//   Cholesky  one lane per row, the rows in registers, column by column; the pivot row is read from the image, into which every lane
+//             writes its entry of a column as soon as it has it, and the pivot itself travels through v_readlane.
+//   sigma     lanes 0..24 build their point from x and a column of L, lanes 25..63 repeat point 0 (all 64 lanes stay active, so
+//             the cross-lane reads never meet an inactive lane) and every lane takes the step of rollout_pop_kernel: the GENERIC
+//             step_fast, and with TRACK the acceleration-space bank re-formed from the per-thruster state, which every lane carries
+//             (the lag depends on the commands alone, so the 64 copies are equal and lane 0 stores its own).
+//   moments   lanes 0..11 sum the mean of the deviations in index order, then every lane sums its entries of P over the 25 points
+//             in index order.  No atomics: two calls give the same bits.
+// Synchronisation: a wave is the only reader and writer of its image and never leaves its own program order, and the LDS serves a
+// wave's accesses in issue order.  So wave_sync() -- a scheduling barrier for the compiler and a wait for the wave's outstanding
+// LDS accesses -- is all that a phase needs before it reads what other lanes of the wave wrote; no workgroup barrier is used after
+// the quadrant table is set up, which lets a wave leave (ragged block, or a filter that failed) without the others noticing.
+// Rows of the image have a stride of 13 doubles: lanes that walk down a column (D[i][a] over i, L[r][col] over col, P[lane][i])
+// then start on 26-dword steps, which are distinct even banks within a 32-lane half, so no phase piles onto one bank.
+#include "brov2_device.h"
+#include "brov2_fast.h"
+#include "brov2_kernels.h"
+#include "brov2_rows.h"
+
+namespace brov {
+
+constexpr int UKF_WAVES = 4;            // recordings (waves) per block
+constexpr int UKF_LD = 13;              // row stride of the LDS matrices, in doubles
+constexpr int UKF_NS = 25;              // sigma points of the 12-state model
+
+struct UkfLds {
+    double D[UKF_NS][UKF_LD];           // deviations of the propagated points from point 0 (attitude wrapped)
+    double P[12][UKF_LD];               // covariance, both triangles
+    double L[12][UKF_LD];               // its lower Cholesky factor
+    double x[12], m[12], c0[12], k[12]; // mean, mean deviation, propagated point 0, gain column
+};
+
+typedef const UkfRec __attribute__((address_space(4)))* CUK;
+__device__ __forceinline__ CUK as_constant_uk(const UkfRec* g) { return (CUK)(unsigned long long)g; }
+
+// LDS written by some lanes of a wave is read by others: order the two
+__device__ __forceinline__ void ukf_wave_sync() {
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+}
+// the value of lane l (a constant) / of the first lane, as a wave-uniform scalar
+__device__ __forceinline__ double ukf_lane(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
+}
+__device__ __forceinline__ double ukf_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+__device__ __forceinline__ double ukf_wrap(double d) {      // the rule of the feedback law (brov2_error.h)
+    return fma(-6.28318530717958647692e+00, rint(d * 1.59154943091895335769e-01), d);
+}
+// entry e of the lower triangle, row by row: e = a (a + 1) / 2 + b, b <= a
+__device__ __forceinline__ void ukf_entry(int e, int& a, int& b) {
+    a = 0;
+    while ((a + 1) * (a + 2) / 2 <= e) ++a;
+    b = e - a * (a + 1) / 2;
+}
+
+template <int MODEL, int INTEG, int LAGMODE, bool TRACK>
+__global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArgs a) {
+    constexpr int NU = Dims<MODEL>::NU;
+    static_assert(Dims<MODEL>::NX == 12, "the filter's state is the 12-state Euler model");
+    __shared__ double2 qt[4];
+    __shared__ UkfLds lds[UKF_WAVES];
+    init_quadrant_table(qt);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t B = a.B, T = a.T;
+    const int64_t b = (int64_t)blockIdx.x * UKF_WAVES + wave;
+    if (b >= B) return;                                       // a whole wave: no workgroup barrier follows
+    UkfLds& S = lds[wave];
+    const int64_t row = (int64_t)blockIdx.y * B + b;          // recording b of candidate blockIdx.y in the outputs
+    const CFP p = as_constant(a.fp + blockIdx.y);
+    const CUK f = as_constant_uk(a.rec + (a.rec_per_candidate ? blockIdx.y : 0));
+    HotConsts h;
+    load_hot(p, h);
+    const double dt = a.dt;
+    const double NaN = __builtin_nan(""), INF = __builtin_inf();
+    // the entries of P this lane owns
+    int a0, b0, a1, b1;
+    ukf_entry(lane, a0, b0);
+    const bool two = lane + 64 < 78;
+    ukf_entry(two ? lane + 64 : lane, a1, b1);
+    // the sigma point of this lane: x + sc L[:, col]
+    const bool point = lane >= 1 && lane < UKF_NS;
+    const int col = point ? (lane - 1) % 12 : 0;
+    const double cw = f->c;
+    const double sc = point ? (lane <= 12 ? cw : -cw) : 0.0;
+    const int lr = lane < 12 ? lane : 11;                     // the row of this lane in the per-row phases (lanes >= 12 repeat row 11)
+
+    LagZ lz;
+    double Xl[8][3];
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if constexpr (TRACK) load_row<24>(a.lag + row * 24, &Xl[0][0]);
+        else lz.zero();
+    }
+    double p0 = a.P0[b * 144 + a0 * 12 + b0], p1 = a.P0[b * 144 + a1 * 12 + b1];
+    S.P[a0][b0] = p0;
+    S.P[b0][a0] = p0;
+    if (two) { S.P[a1][b1] = p1; S.P[b1][a1] = p1; }
+    if (lane < 12) S.x[lane] = a.x0[b * 12 + lane];
+    ukf_wave_sync();
+
+    const double* up = a.U + b * T * NU;
+    const double* yp = a.Y + b * T * 12;
+    double* xfp = a.xf ? a.xf + row * T * 12 + lr : nullptr;
+    double* psp = a.pstd ? a.pstd + row * T * 12 + lr : nullptr;
+    double* inp = a.innov ? a.innov + row * T * 12 + lr : nullptr;
+    double ell = 0.0, nupd = 0.0, minpiv = INF;
+    int64_t t = 0, failed = -1, nan_from = T;
+    for (; t < T; ++t) {
+        // ---- 1. update with row t -------------------------------------------------------------------------------------------
+        double y[12];
+        load_row<12>(yp + t * 12, y);
+        double inn = NaN;
+        bool bad = false;
+#pragma unroll
+        for (int i = 0; i < 12; ++i) {
+            const double yi = ukf_uniform(y[i]), ri = f->r[i];
+            if (bad || yi != yi || ri == INF) continue;                // wave-uniform
+            const double s = ukf_uniform(S.P[i][i]) + ri;
+            if (!(s > 0.0) || s == INF) { bad = true; continue; }
+            double v = yi - ukf_uniform(S.x[i]);
+            if (i >= 3 && i < 6) v = ukf_wrap(v);
+            if (lane < 12) {
+                const double k = S.P[lane][i] / s;
+                S.k[lane] = k;
+                S.x[lane] += k * v;
+            }
+            ell -= 0.5 * (log(6.28318530717958647692e+00 * s) + v * v / s);
+            nupd += 1.0;
+            if (lane == i) inn = v / sqrt(s);
+            ukf_wave_sync();                                           // k, x written; every read of column i of P done
+            p0 -= S.k[a0] * S.k[b0] * s;
+            S.P[a0][b0] = p0;
+            S.P[b0][a0] = p0;
+            if (two) {
+                p1 -= S.k[a1] * S.k[b1] * s;
+                S.P[a1][b1] = p1;
+                S.P[b1][a1] = p1;
+            }
+            ukf_wave_sync();                                           // P written
+        }
+        if (bad) { failed = t; nan_from = t; break; }
+        if (lane < 12) {
+            if (xfp) xfp[t * 12] = S.x[lane];
+            if (psp) psp[t * 12] = sqrt(S.P[lane][lane]);
+            if (inp) inp[t * 12] = inn;
+        }
+        // ---- 2. predict with U[t] -------------------------------------------------------------------------------------------
+        // Cholesky, one lane per row, column by column: s_i = P[i][j] - sum_k L[i][k] L[j][k].  Lane j's own s is the pivot argument;
+        // row j, which the other lanes need for column j, is in the image since its last entry was written at column j - 1.
+        double Lr[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) Lr[k] = S.P[lr][k];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            double s = Lr[j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
+            const double piv = ukf_lane(s, j);
+            double d = 1.0;
+            if (!bad) {
+                if (!(piv > 0.0) || piv == INF) bad = true;
+                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
+            }
+            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
+            if (lane < 12) S.L[lane][j] = Lr[j];
+            ukf_wave_sync();                                           // column j of L written
+        }
+        if (bad) { failed = t; nan_from = t + 1; break; }
+        double x[12], u[NU];
+#pragma unroll
+        for (int r = 0; r < 12; ++r) x[r] = S.x[r] + sc * S.L[r][col];
+        load_row<NU>(up + t * NU, u);
+        // the per-thruster state is the lag state, as in rollout_pop_kernel
+        if constexpr (MODEL == MODEL_THRUSTER_EULER && TRACK) lz.from_thrusters(relaunder(p), Xl);
+        step_fast<MODEL, INTEG, LAGMODE, TRACK, true>(h, p, dt, x, u, lz, Xl, qt);
+        if (lane == 0) {
+#pragma unroll
+            for (int r = 0; r < 12; ++r) S.c0[r] = x[r];
+        }
+        ukf_wave_sync();                                               // c0 written
+#pragma unroll
+        for (int r = 0; r < 12; ++r) {
+            double d = x[r] - S.c0[r];
+            if (r >= 3 && r < 6) d = ukf_wrap(d);
+            if (lane < UKF_NS) S.D[lane][r] = d;
+        }
+        ukf_wave_sync();                                               // D written
+        const double wi = f->wi;
+        bool finite = true;
+        if (lane < 12) {
+            double m = 0.0;
+#pragma unroll
+            for (int i = 1; i < UKF_NS; ++i) m = fma(wi, S.D[i][lane], m);
+            const double xn = S.c0[lane] + m;
+            S.m[lane] = m;
+            S.x[lane] = xn;
+            finite = fabs(xn) < INF;
+        }
+        const bool allfinite = __ballot(!finite) == 0;
+        ukf_wave_sync();                                               // m, x written
+        if (!allfinite) { failed = t; nan_from = t + 1; break; }
+        {
+            const double wc0 = f->wc0;
+            const double ma = S.m[a0], mb = S.m[b0];
+            double acc = wc0 * (ma * mb);
+#pragma unroll
+            for (int i = 1; i < UKF_NS; ++i) acc = fma(wi, (S.D[i][a0] - ma) * (S.D[i][b0] - mb), acc);
+            if (a0 == b0) acc += f->q[a0];
+            p0 = acc;
+            S.P[a0][b0] = p0;
+            S.P[b0][a0] = p0;
+            if (two) {
+                const double na = S.m[a1], nb = S.m[b1];
+                double acc1 = wc0 * (na * nb);
+#pragma unroll
+                for (int i = 1; i < UKF_NS; ++i) acc1 = fma(wi, (S.D[i][a1] - na) * (S.D[i][b1] - nb), acc1);
+                if (a1 == b1) acc1 += f->q[a1];
+                p1 = acc1;
+                S.P[a1][b1] = p1;
+                S.P[b1][a1] = p1;
+            }
+        }
+        ukf_wave_sync();                                               // P written
+    }
+    // ---- outputs -------------------------------------------------------------------------------------------------------------
+    const bool ok = failed < 0;
+    if (!ok && lane < 12) {
+        for (int64_t s = nan_from; s < T; ++s) {
+            if (xfp) xfp[s * 12] = NaN;
+            if (psp) psp[s * 12] = NaN;
+            if (inp) inp[s * 12] = NaN;
+        }
+    }
+    if (a.xT && lane < 12) a.xT[row * 12 + lane] = ok ? S.x[lane] : NaN;
+    if (a.PT) {
+        for (int e = lane; e < 144; e += 64) a.PT[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
+    }
+    if (a.info && lane == 0) {
+        const double v[4] = {ok ? ell : -INF, nupd, (double)failed, minpiv};
+        store_row<4>(a.info + row * 4, v);
+    }
+    if constexpr (MODEL == MODEL_THRUSTER_EULER && TRACK) {
+        if (ok && lane == 0) store_row<24>(a.lag + row * 24, &Xl[0][0]);      // a failed filter leaves its lag_io as it came
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// launch: grid (blocks of UKF_WAVES recordings, P)
+// ---------------------------------------------------------------------------------------
+int ukf_waves_per_block() { return UKF_WAVES; }
+
+template <int MODEL, int INTEG, int LAGMODE>
+static hipError_t launch_ukf_t(hipStream_t st, int P, const UkfArgs& a) {
+    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (a.lag) {
+            hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, true>), grid, dim3(64 * UKF_WAVES), 0, st, a);
+            return hipGetLastError();
+        }
+    }
+    hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, false>), grid, dim3(64 * UKF_WAVES), 0, st, a);
+    return hipGetLastError();
+}
+template <int MODEL>
+static hipError_t launch_ukf_m(hipStream_t st, int integ, int lag_mode, int P, const UkfArgs& a) {
+    if (integ == INTEG_EULER) return launch_ukf_t<MODEL, INTEG_EULER, 0>(st, P, a);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (lag_mode == 1) return launch_ukf_t<MODEL, INTEG_RK4, 1>(st, P, a);
+    }
+    return launch_ukf_t<MODEL, INTEG_RK4, 0>(st, P, a);
+}
+hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a0) {
+    if (a0.B <= 0 || P <= 0) return hipSuccess;
+    UkfArgs a = a0;
+    if (model != MODEL_THRUSTER_EULER) a.lag = nullptr;
+    switch (model) {
+        case MODEL_THRUSTER_EULER: return launch_ukf_m<MODEL_THRUSTER_EULER>(st, integ, lag_mode, P, a);
+        case MODEL_WRENCH_EULER: return launch_ukf_m<MODEL_WRENCH_EULER>(st, integ, lag_mode, P, a);
+        default: return hipErrorInvalidValue;     // a manifold mean for the quaternion model is another feature
+    }
+}
+
+}  // namespace brov

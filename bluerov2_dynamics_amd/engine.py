@@ -594,6 +594,62 @@ def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=No
     return out
 
 
+UKF_OUTPUTS = ("xf", "pstd", "innov", "xT", "PT", "info")
+
+
+def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL, want=UKF_OUTPUTS, ctx=None):
+    """Unscented Kalman filter on the Fossen model for P vehicles x B recordings in one launch (include/brov2.h:
+    brov_ukf_filter_dev holds the law): candidate j filters the noisy state rows Y under params_list[j].
+
+    params_list: sequence of P _lib.BrovParams.  cfg: one _lib.BrovUkf (one noise model for every candidate) or a sequence of P
+    (fossen/estimate.py: ukf builds them).  Shared by the candidates: x0 [B,12], P0 [B,12,12] (lower triangle read), U [B,T,nu],
+    Y [B,T,12] with NaN where a component was not measured.  lag [P,B,8,3] (thruster model) is the start lag; None starts from
+    zero and returns None.  want: the outputs to compute, any of UKF_OUTPUTS.  Host and device arrays as in rollout_pop.
+    Returns dict(xf, pstd, innov [P,B,T,12], xT [P,B,12], PT [P,B,12,12], info [P,B,4] = log-likelihood, scalar updates applied,
+    first failed step (-1: none), smallest Cholesky pivot; lag | None), with None for what was not wanted.  Models THRUSTER_EULER
+    and WRENCH_EULER.  The ctx's own parameters are left alone."""
+    P = len(params_list)
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
+    ca = (_lib.BrovUkf * max(len(cfgs), 1))(*cfgs)
+    want = tuple(want)
+    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
+    nu = NU.get(model, 8)
+    host = isinstance(x0, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x0, P0, U, Y = as_f64(x0), as_f64(P0), as_f64(U), as_f64(Y)
+        lag = None if lag is None else as_f64(lag)
+    else:
+        ctx = _ctx_of(x0, ctx)
+        arr = arrays_of(x0, ctx)
+    arr.bind()
+    assert len(U.shape) == 3 and int(U.shape[2]) == nu, f"U must be [B,T,nu] with nu = {nu}"
+    B, T = int(U.shape[0]), int(U.shape[1])
+    for name, v, shape in (("x0", x0, (B, 12)), ("P0", P0, (B, 12, 12)), ("Y", Y, (B, T, 12))):
+        assert tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
+    track = model == THRUSTER_EULER and lag is not None
+    if track:
+        assert int(np.prod(lag.shape)) == P * B * 24, "lag must be [P,B,8,3]"
+    lag_io = None
+    if host:
+        x0, P0, U, Y = arr.upload(x0), arr.upload(P0), arr.upload(U), arr.upload(Y)
+        if track:
+            lag_io = arr.upload(lag.reshape(P, B, 8, 3))
+    elif track:          # in / out in the ABI: work on a copy
+        lag_io = (lag.clone() if _is_torch(lag) else arr.upload(lag.numpy())).reshape(P, B, 8, 3)
+    shapes = dict(xf=(P, B, T, 12), pstd=(P, B, T, 12), innov=(P, B, T, 12), xT=(P, B, 12), PT=(P, B, 12, 12), info=(P, B, 4))
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
+    ctx.check(ctx.lib.brov_ukf_filter_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, len(cfgs), ca, B, T, float(dt), _dptr(x0),
+                                          _dptr(P0), _dptr(U), _dptr(Y), _dptr(lag_io), *(_dptr(out[k]) for k in UKF_OUTPUTS)),
+              "brov_ukf_filter_dev")
+    out["lag"] = lag_io
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
 def mppi_step(model, integrator, params_list, cfg, x, ref, U_nom, dt, K, H=None, lag=None, lag_mode=LAG_PER_CALL, seed=0, eps=None,
               ref_row0=0, shift=False, want_cost=False, ctx=None):
     """One sampling-based model-predictive (MPPI) update for B problems: K perturbed command sequences per problem are drawn,

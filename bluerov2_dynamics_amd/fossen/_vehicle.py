@@ -206,6 +206,46 @@ class VehicleBase:
         out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
         return tuple(v[0] for v in out) if single else out
 
+    def filter_states(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler"):
+        """Unscented Kalman filter over noisy recordings of the state (engine.ukf_filter; fossen/estimate.py: ukf builds `cfg`;
+        include/brov2.h: brov_ukf_filter holds the law).  Y [T,12] or [B,T,12]: the measured state rows, NaN where a component was
+        not measured; U [T,nu] or [B,T,nu] the commands.  x0 / P0 default to estimate.default_start: the first fully measured row
+        and diag(4 r), with estimate.P0_STAND_IN where r is infinite.  params: a _lib.BrovParams to filter under instead of this
+        vehicle's own.  Returns dict(x [.,T,12] the filtered means, std [.,T,12], innov [.,T,12] the normalised innovations (NaN
+        where nothing was measured), xT, PT, loglik, n_updates, failed_step (-1: none), min_pivot), without the leading B when Y
+        was one recording.  Thruster and Euler-wrench vehicles; starts from zero thruster lag; this object's own lag state is
+        neither read nor changed, and its parameters reach the kernel as arguments."""
+        from . import estimate, identify
+        Y, U = np.asarray(Y, float), np.asarray(U, float)
+        single = Y.ndim == 2
+        if single:
+            Y, U = Y[None], U[None]
+        if x0 is None or P0 is None:
+            dx0, dP0 = estimate.default_start(Y, cfg)
+        x0 = dx0 if x0 is None else np.asarray(x0, float).reshape(Y.shape[0], 12)
+        P0 = dP0 if P0 is None else np.asarray(P0, float).reshape(Y.shape[0], 12, 12)
+        p = identify.params_of(self) if params is None else params
+        r = engine.ukf_filter(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, ctx=self._ctx)
+        out = dict(x=r["xf"][0], std=r["pstd"][0], innov=r["innov"][0], xT=r["xT"][0], PT=r["PT"][0], loglik=r["info"][0, :, 0],
+                   n_updates=r["info"][0, :, 1].astype(np.int64), failed_step=r["info"][0, :, 2].astype(np.int64), min_pivot=r["info"][0, :, 3])
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def log_likelihood_population(self, params_list, Y, U, dt, cfg, x0=None, P0=None, integrator="euler"):
+        """Which of P vehicles explains noisy recordings best: the innovation log-likelihood of filter_states for every candidate
+        of params_list (P _lib.BrovParams, e.g. identify.sample_parameters' draws) in one launch.  Y [B,T,12] (or [T,12]), U, cfg,
+        x0, P0 as in filter_states.  Returns l [P,B]; -inf where a filter failed.  Unlike the window evaluator's endpoint error this
+        does not take the measured rows as truth: noise, dropouts and never-measured components are part of the model."""
+        from . import estimate
+        Y, U = np.asarray(Y, float), np.asarray(U, float)
+        if Y.ndim == 2:
+            Y, U = Y[None], U[None]
+        if x0 is None or P0 is None:
+            dx0, dP0 = estimate.default_start(Y, cfg)
+        x0 = dx0 if x0 is None else np.asarray(x0, float).reshape(Y.shape[0], 12)
+        P0 = dP0 if P0 is None else np.asarray(P0, float).reshape(Y.shape[0], 12, 12)
+        r = engine.ukf_filter(self.MODEL, integrator, list(params_list), cfg, x0, P0, U, Y, dt, want=("info",), ctx=self._ctx)
+        return r["info"][:, :, 0]
+
     def simulate_mppi(self, x0, ref, dt, cfg, T, K, H, plant_params=None, integrator="euler", seed=0, planner=None):
         """Receding-horizon control of B plants by the sampling-based model-predictive update (engine.mppi_step; fossen/control.py:
         mppi builds `cfg`), planned with THIS vehicle's parameters.  The loop is device-resident: the state, the thruster lag and

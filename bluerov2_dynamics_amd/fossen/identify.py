@@ -287,7 +287,8 @@ def sample_parameters(result, n, seed=0, bounds=None):
     """n vehicles drawn around a fit: a list of BrovParams whose free parameters are theta_hat + L z, z standard normal from
     np.random.default_rng(seed), L L^T = result.covariance (symmetric eigendecomposition, negative eigenvalues clipped to 0), each
     clipped to bounds {name: (lo, hi)}; every other field is copied from result.brov_params.  Feed the list to engine.rollout_pop
-    or rov.simulate_population.  ValueError when the fit was made without covariance=True."""
+    or rov.simulate_population; rov.log_likelihood_population ranks the draws against a noisy recording (the innovation
+    likelihood of an unscented Kalman filter under each draw).  ValueError when the fit was made without covariance=True."""
     if result.covariance is None:
         raise ValueError("the fit carries no covariance: call fit_parameters(..., covariance=True)")
     names = tuple(result.params)

@@ -332,6 +332,70 @@ BROV_API int brov_rollout_feedback_dev(brov_ctx* ctx, int model, int integrator,
                               double* d_lag_io, double* d_z_io, double* d_traj, int64_t traj_stride, double* d_xT,
                               double* d_u_applied, double* d_metrics);
 
+/* ---- state estimation: an unscented Kalman filter on the Fossen model ---------------------------------------------------------
+ * brov_ukf_filter turns noisy, gappy recordings of the state into estimates with error bars, for P vehicles at once: candidate j
+ * (params[j], a HOST array as in brov_rollout_pop) filters B recordings of T rows each, in one launch whatever P, B and T are.
+ * info[0], the innovation log-likelihood, says which candidate explains a recording best.
+ * Models BROV_THRUSTER_EULER and BROV_WRENCH_EULER (n = 12 states, 2 n + 1 = 25 sigma points); both integrators and both lag
+ * modes.  The quaternion model (its mean lives on a manifold) and the double-integrator models: BROV_ERR_ARG.  The thruster lag
+ * depends on the commands only, never on the state, so all sigma points share one lag bank and the filter's state stays at 12.
+ * The measurements are components of the state and R is diagonal, so the measurement update is a sequence of scalar Kalman
+ * updates: exact, no unscented transform, no matrix inverse, and per-component dropouts come for free.
+ *
+ * Inputs, shared by the candidates: x0 [B][12]; P0 [B][12][12], of which the lower triangle is read and taken as symmetric;
+ * U [B][T][nu]; Y [B][T][12], the measured state rows, where a NaN means "this component was not measured at this row";
+ * lag_io [P][B][8][3] optional, in/out (thruster model; NULL = start from zero lag, nothing returned).
+ * Record brov_ukf: q[12] the per-step process variances (>= 0, finite), r[12] the measurement variances (>= 0; +inf = never
+ * measured), alpha, beta, kappa.  ukf is a HOST array of nrec records: nrec = 1 (one noise model for all candidates) or nrec = P
+ * (candidate j under ukf[j]).  Derived, with n = 12:
+ *     lambda = alpha^2 (n + kappa) - n,  c = sqrt(n + lambda),
+ *     Wm_0 = lambda / (n + lambda),  Wc_0 = Wm_0 + 1 - alpha^2 + beta,  W_i = 1 / (2 (n + lambda))  for i = 1 .. 2 n.
+ * A small alpha makes the centre weight huge (alpha = 1e-3: Wm_0 ~ -1.2e7) and costs digits in any arithmetic: in fp64 against
+ * long double the filtered states then differ by ~2e-10 instead of ~1e-15.  That is a property of the method, not of this kernel;
+ * alpha in [0.5, 1] is the tested range.
+ *
+ * For t = 0 .. T-1, starting from (x, P) = (x0, P0), which is the estimate of row 0 BEFORE its measurement:
+ *   1. Update with row t.  For i = 0 .. 11 in this order, skipped when Y[t][i] is NaN or r[i] = +inf:
+ *          v = Y[t][i] - x[i]; for i in {3, 4, 5} wrapped as d - 2 pi rint(d / (2 pi)), the rule of brov_rollout_feedback
+ *          s = P[i][i] + r[i],  k = P[:, i] / s,  x += k v,  P[a][b] -= k[a] k[b] s for all a, b
+ *          l -= (ln(2 pi s) + v^2 / s) / 2;  the normalised innovation is v / sqrt(s).
+ *      The same expression serves both triangles, so P stays bit-symmetric; a later component sees the x and P the earlier ones
+ *      left.  Outputs of row t: the filtered mean xf[t], pstd[t][i] = sqrt(P[i][i]), innov[t][i] (NaN where skipped).
+ *   2. Predict with U[t].  P = L L^T (lower Cholesky); chi_0 = x, chi_i = x + c L[:, i-1], chi_{i+n} = x - c L[:, i-1] (i = 1 .. n).
+ *      Every chi advances one step through the general step of brov_rollout_pop with the same lag bank, which advances once, exactly
+ *      as that kernel advances it.  d_i = chi_i' - chi_0' with components 3 .. 5 wrapped;  m = sum_{i>=1} W_i d_i;  x = chi_0' + m
+ *      (the attitude of x is not wrapped: it stays continuous);  e_i = d_i - m, e_0 = -m;
+ *      P = Wc_0 e_0 e_0^T + sum_{i>=1} W_i e_i e_i^T + diag(q), every sum in index order.
+ * After T steps (xT, PT) is the estimate of row T before its measurement, so a call continued from (xT, PT, lag_io) with the
+ * remaining rows gives the bits of the unbroken call in every per-row output, in xT, PT and lag_io; l adds up to rounding.
+ *
+ * Outputs, per candidate, each may be NULL: xf, pstd, innov [P][B][T][12]; xT [P][B][12]; PT [P][B][12][12] (full, symmetric);
+ * info [P][B][4] = l, the number of scalar updates applied, the first failed step (-1: none), the smallest Cholesky pivot
+ * L[j][j] seen.
+ * Failure is a numerical condition of one (candidate, recording), handled in the kernel: s <= 0 or not finite in stage 1 of row
+ * t, a pivot argument <= 0 or not finite in stage 2, or a non-finite predicted mean.  The filter stops there for that problem
+ * only: per-row outputs after the failing stage are NaN (stage 1: row t and later; stage 2: row t is kept, its update was
+ * complete), xT and PT are NaN, info = (-inf, updates so far, t, smallest pivot so far), lag_io is left as it came.  The call
+ * returns BROV_OK and no other problem is touched.
+ * Refused on the host with BROV_ERR_ARG and a brov_last_error text naming the rule, before anything is copied or launched: a
+ * model other than the two above, nrec not in {1, P}, alpha not finite or <= 0, n + lambda <= 0 or not finite, a negative or NaN
+ * q or r, an infinite q, T < 1, P > 65535, a NULL params, ukf, x0, P0, U or Y, dt not finite and > 0, a singular mass matrix.
+ * B = 0 or P = 0: BROV_OK, nothing touched.  The ctx's own parameters are neither read nor written.
+ * Deterministic (no atomics, fixed summation orders): two calls give the same bits. */
+typedef struct brov_ukf {
+    double q[12];                   /* per-step process variance, >= 0 */
+    double r[12];                   /* measurement variance, >= 0; +inf: never measured */
+    double alpha, beta, kappa;      /* alpha > 0 and 12 + lambda > 0 */
+} brov_ukf;
+BROV_API int brov_ukf_filter(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                    int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0,
+                    const double* P0, const double* U, const double* Y, double* lag_io, double* xf, double* pstd, double* innov,
+                    double* xT, double* PT, double* info);
+BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                        int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                        const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
+                        double* d_innov, double* d_xT, double* d_PT, double* d_info);
+
 /* ---- model-predictive control: one sampling-based (MPPI) update, sampled, rolled out and scored on the device ---------------------
  * brov_mppi_step performs one MPPI update for B independent problems (B vehicles, or B draws of a fit).  Problem b has a state
  * x [nx], for the thruster model optionally a start lag [8][3] (read only; NULL = zero), a reference, and a nominal knot sequence
