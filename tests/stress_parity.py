@@ -3,7 +3,7 @@
 strides, bag structures and chunk sizes through the C ABI against the oracle.  Prints the worst relative error per family
 and exits non-zero on the first violation.
 
-    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp,pinc,rollout_pop,feedback,mppi,koopman_mppi,window_pop,lift,gram,pinv_apply,multistep_sweep,simulate]
+    python tests/stress_parity.py [seconds per family = 40] [seed = 0] [families, comma separated: copies,linear_multistep,applies,lloyds,lloyds_list,rollouts,windows,grams,multistep,kmeanspp,pinc,rollout_pop,feedback,mppi,koopman_mppi,window_pop,lift,gram,pinv_apply,multistep_sweep,simulate,ukf,lmpc]
 
 Lives under tests/ because it checks against oracle/ (test infrastructure); tests/test_gpu_parity.py runs a short sweep."""
 import os, sys, time
@@ -440,7 +440,8 @@ def pinc():
 def family_sweep(name):
     """The five newer families (population rollouts, closed-loop rollouts, Fossen and Koopman MPPI, population window evaluator with
     fd_normal_eq) and the EDMDc families of tests/sweep_edmdc.py (lift, gram, pinv_apply, multistep -- here `multistep_sweep`, next to
-    the older `multistep` above --, simulate; their second figure is sweep_edmdc.sweep_one's): random cases from the generators of tests/sweep_cases.py against the references and bounds of tests/sweep_run.py,
+    the older `multistep` above --, simulate; their second figure is sweep_edmdc.sweep_one's), the unscented Kalman filter (ukf) and the QP of the
+    Koopman linear MPC (lmpc; tests/sweep_ukf_lmpc.py): random cases from the generators of tests/sweep_cases.py against the references and bounds of tests/sweep_run.py,
     which tests/test_family_sweeps_gpu.py runs on a fixed list.  A case whose reference is not well-posed (more than 2 % of its lanes
     off the float64 / long double condition) is skipped and counted."""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -465,7 +466,7 @@ def family_sweep(name):
 if __name__ == "__main__":
     import functools
     fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp, pinc=pinc,
-                **{f: functools.partial(family_sweep, f) for f in ("rollout_pop", "feedback", "mppi", "koopman_mppi", "window_pop", "lift", "gram", "pinv_apply", "multistep_sweep", "simulate")})
+                **{f: functools.partial(family_sweep, f) for f in ("rollout_pop", "feedback", "mppi", "koopman_mppi", "window_pop", "lift", "gram", "pinv_apply", "multistep_sweep", "simulate", "ukf", "lmpc")})
     for name in (sys.argv[3].split(",") if len(sys.argv) > 3 else list(fams)):
         fams[name]()
     print("stress parity: ok")

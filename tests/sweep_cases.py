@@ -1,5 +1,6 @@
-"""Case lists of the shape sweeps over the population-rollout, closed-loop, MPPI, Koopman-MPPI and population-window kernels, and over
-the EDMDc kernels (lift, Gram, pinv_apply, the two multistep evaluators, simulate).  Not collected; pure NumPy; imports no GPU code.
+"""Case lists of the shape sweeps over the population-rollout, closed-loop, MPPI, Koopman-MPPI and population-window kernels, over
+the EDMDc kernels (lift, Gram, pinv_apply, the two multistep evaluators, simulate), and over the UKF and Koopman-QP kernels.  Not
+collected; pure NumPy; imports no GPU code.
 
 One generator per family: NAME(seed) returns an ordered list of plain dicts (ints, bools, strings and lists of them), the
 hand-written corner list first, then seeded random draws from the family's value sets.  The lists depend on the seed alone, never on
@@ -12,7 +13,13 @@ wrong: both sides of every block edge (64 lanes when B or K <= 64, 256 otherwise
 kernel), partial and full last knots, hold >= H, a set-point against a reference window, more than one trip of the 256-wide
 strided loops (K = 513), the 64-window chunks of the lag scan.  The EDMDc families (second half of the file) add the 64-row / 256-centre
 blocks of the lift, every tile count of the Gram's task packing, bags and chunk edges, the 192-row unit of the apply pass, window
-blocks of 128 with the two-stream split from 16 blocks on, and both parities of the propagation's K-steps."""
+blocks of 128 with the two-stream split from 16 blocks on, and both parities of the propagation's K-steps.  The last two families are
+the unscented Kalman filter (ukf: the eight instantiations of csrc/ukf.hip, each with a full block of UKF_WAVES = 4 recordings and
+with a ragged one, B = 1 .. 9, T = 1 .. 12, one noise record or one per candidate, rows with every component measured and recordings
+with none, components with r = +inf, process variances of 0, the yaw through pi) and the QP of the Koopman linear MPC (lmpc: Nv on
+both sides of every rows-per-lane step of csrc/koopman_qp.hip and of its LDS / global switch, a non-zero Nv % 8 at every step, H + 1
+on both sides of the 64-lane trips of the epilogue, hold r on both sides of the 64-lane trip of the u_apply loop, short last knots,
+iters 0 .. 40 and a residual stop at two, three and five rows per lane)."""
 import hashlib
 import json
 
@@ -22,6 +29,7 @@ NAMES = ("V0", "V1", "V2", "V3", "V4", "V5", "V6", "V7", "V8")      # tests/foss
 WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/fossen_vehicles.py: WRENCH_NAMES
 N_CASES = 48                                                        # per family: four slices of 12
 N_CASES_EDMDC = 32                                                  # per EDMDc family: four slices of 8 (corner lists of 12 to 24)
+N_CASES_FILTER = 32                                                 # ukf and lmpc: four slices of 8 (corner lists of 17 and 26)
 SEED = 2024
 
 SETS = dict(
@@ -49,6 +57,14 @@ SETS = dict(
                    nw=(0, 1, 127, 128, 129, 255, 256, 257, 1920, 1921, 2176), H=(0, 1, 2, 3, 7), short_u=(True, False)),
     simulate=dict(shape=((1, 1, 1), (2, 3, 3), (12, 35, 8), (12, 36, 9), (13, 36, 6), (12, 83, 8), (13, 84, 8), (12, 8, 0), (5, 8, 2), (9, 4, 6)),
                   nb=(1, 2, 127, 128, 129, 255, 256, 257, 300), T=(0, 1, 2, 3, 7, 50)),
+    ukf=dict(model=(0, 1), integ=("euler", "rk4"), lag_mode=(0, 1), lag=(True, False), P=(1, 2, 3), nrec=("1", "P"), alpha=(0.5, 1.0),
+             B=(1, 3, 4, 5, 8, 9), T=(1, 2, 3, 12), measured=("std", "all", "none"), r_inf=(0, 1, 3), q_zero=(True, False),
+             wrap=(True, False)),
+    lmpc=dict(n=(12, 13), r=(6, 8), k=(0, 5, 70),
+              Nv=(6, 8, 64, 66, 88, 90, 96, 126, 128, 132, 136, 192, 198, 200, 256, 258, 264, 306, 312), hold=(1, 2, 3, 8, 9, 10, 11),
+              H=(1, 3, 7, 12, 15, 25, 31, 33, 34, 39, 43, 48, 51, 63, 64, 65, 101, 121, 127, 128, 129), nb=(1, 3, 4, 5, 8, 9),
+              iters=(0, 1, 2, 40), traj=(True, False), y=(True, False), shift=(True, False),
+              special=(None, "quat_flip", "angle_wrap", "warm")),
 )
 
 
@@ -492,17 +508,140 @@ def draw_simulate(rng):
     return _simulate(rng, shape, _pick(rng, s["nb"]), T)
 
 
+# ------------------------------------------------------------------------------------------ unscented Kalman filter
+UKF_ROWS = 200                                                      # P B T of a case at most: the reference is plain Python loops
+
+
+def ukf_instance(c):
+    """the instantiation of ukf_filter_kernel a case runs: (model, integ, lag_mode, TRACK)"""
+    return (c["model"], c["integ"], c["lag_mode"], c["lag"])
+
+
+def _ukf(rng, model, integ, lag_mode, lag, P, nrec, alpha, B, T, measured, r_inf, q_zero, wrap):
+    """lag: the thruster model starts from a lag (TRACK; without one the kernel takes its other form); nrec: noise records, one or one
+    per candidate; measured: "std" about 30 % of the entries dropped and one row dropped entirely (tests/ukf_cases.py), "all" every
+    entry of every row, "none" no entry at all; r_inf: components with r = +inf whose Y columns still carry numbers; q_zero: three
+    process variances exactly 0; wrap: the true yaw passes pi while Y reports it wrapped.  The recordings are simulated with the last
+    candidate's vehicle."""
+    assert P * B * T <= UKF_ROWS, (P, B, T)
+    return dict(family="ukf", model=model, integ=integ, lag_mode=lag_mode if (model == 0 and integ == "rk4") else 0, lag=bool(lag and model == 0),
+                P=P, nrec=_sym(nrec, P=P), nrec_as=nrec, alpha=alpha, B=B, T=T, measured=measured, r_inf=r_inf, q_zero=bool(q_zero),
+                wrap=bool(wrap), names=_vehicles(rng, model, P), seed=int(rng.integers(0, 1 << 30)))
+
+
+UKF_CORNERS = (
+    # model integ lag_mode lag  P  nrec alpha B  T  measured r_inf q_zero wrap     -- every instantiation with a full and a ragged block
+    (0, "euler", 0, True, 2, "1", 1.0, 4, 12, "std", 1, False, True),              # the yaw through pi, as thr_euler_wrap
+    (0, "euler", 0, True, 1, "1", 0.5, 5, 12, "all", 0, True, False),              # 12 updates in every row; a full block and a lone wave
+    (0, "euler", 0, False, 3, "P", 1.0, 8, 2, "std", 3, False, False),             # no start lag; a noise record per candidate at P = 3
+    (0, "euler", 0, False, 2, "1", 0.5, 1, 12, "none", 1, True, False),            # pure prediction, one recording
+    (0, "rk4", 0, True, 1, "1", 1.0, 8, 3, "std", 1, False, False),
+    (0, "rk4", 0, True, 3, "P", 0.5, 3, 12, "std", 0, True, True),
+    (0, "rk4", 0, False, 2, "P", 1.0, 4, 1, "all", 0, False, False),               # T = 1
+    (0, "rk4", 0, False, 1, "1", 0.5, 9, 12, "std", 1, False, False),              # three blocks, the last with one wave
+    (0, "rk4", 1, True, 2, "1", 1.0, 4, 12, "all", 3, False, False),
+    (0, "rk4", 1, True, 1, "1", 0.5, 3, 2, "std", 1, True, False),
+    (0, "rk4", 1, False, 1, "1", 1.0, 8, 12, "std", 0, False, True),
+    (0, "rk4", 1, False, 3, "1", 0.5, 5, 1, "none", 1, False, False),
+    (1, "euler", 0, False, 2, "P", 1.0, 8, 3, "all", 0, True, False),
+    (1, "euler", 0, False, 1, "1", 0.5, 9, 2, "std", 3, False, True),
+    (1, "rk4", 0, False, 3, "1", 1.0, 4, 12, "std", 1, False, False),
+    (1, "rk4", 0, False, 2, "P", 0.5, 1, 1, "none", 0, False, False),
+    (1, "rk4", 0, False, 3, "P", 1.0, 5, 12, "all", 0, True, False),               # 180 filter rows of 12 updates each
+)
+
+
+def draw_ukf(rng):
+    s = SETS["ukf"]
+    while True:
+        P, B, T = _pick(rng, s["P"]), _pick(rng, s["B"]), _pick(rng, s["T"])
+        if P * B * T <= UKF_ROWS:                                     # a draw beyond the row budget is drawn again
+            break
+    return _ukf(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["lag_mode"]), _pick(rng, s["lag"]), P, _pick(rng, s["nrec"]),
+                _pick(rng, s["alpha"]), B, T, _pick(rng, s["measured"]), _pick(rng, s["r_inf"]), _pick(rng, s["q_zero"]), _pick(rng, s["wrap"]))
+
+
+# ------------------------------------------------------------------------------------------ Koopman linear MPC: the batched QP
+LMPC_H_MAX = 129                                                    # H + 1 = 130: one step into the third trip of the epilogue
+LMPC_H_EDGES = (63, 64, 65, 127, 128, 129)                          # H + 1 on both sides of 64 and 128
+LMPC_REF_TOTAL, LMPC_ROW0 = 4, 2                                    # tests/koopman_lmpc_ref.py: REF_TOTAL, ROW0
+LMPC_TOL, LMPC_LDS_NV = 1e-12, 95                                   # the tolerance of a "warm" case; W is staged in LDS up to this Nv
+
+
+def lmpc_rows(c):
+    """(rows per lane Q of qp_solve, W staged in LDS) of csrc/koopman_qp.hip: koopman_qp_solve_kernel"""
+    lds = c["Nv"] <= LMPC_LDS_NV
+    nq = (c["Nv"] + 63) // 64
+    return (nq if lds else 5 if nq > 4 else max(nq, 2)), lds
+
+
+def _lmpc(rng, n, r, k, Nv, hold, H, nb, iters, traj, y, shift, special):
+    """Nv = M r picks the knots, H lies in (M - 1) hold + 1 .. M hold; traj: a reference trajectory (else a set-point); y: the dual
+    variable given; special: references on the far hemisphere (n = 13) / a turn away (n = 12), or "warm": the residual stop of
+    tests/koopman_lmpc_ref.py's `tol` case (limits out of reach, rho = lambda_min / 10 000, every other problem started 10 000
+    times nearer to its minimiser, tol = 1e-12)"""
+    assert Nv % r == 0 and (H + hold - 1) // hold == Nv // r and 1 <= H <= LMPC_H_MAX, (Nv, r, hold, H)
+    assert special in (None, "warm") or (special == "quat_flip") == (n == 13), (special, n)
+    return dict(family="lmpc", n=n, r=r, k=k, Nv=Nv, M=Nv // r, hold=hold, H=H, nb=nb, iters=iters, tol=LMPC_TOL if special == "warm" else 0.0,
+                traj=bool(traj), y=bool(y), shift=bool(shift), special=special, seed=int(rng.integers(0, 1 << 30)))
+
+
+LMPC_CORNERS = (
+    # n   r  k   Nv   hold H    nb iters traj   y      shift  special
+    (13, 6, 5, 6, 3, 3, 1, 40, False, False, False, "quat_flip"),                  # one knot
+    (12, 8, 0, 8, 1, 1, 3, 2, True, True, False, None),                            # one knot, a linear model
+    (12, 8, 5, 8, 9, 7, 4, 0, True, True, True, None),                             # hold r = 72: a second trip of the u_apply loop; hold > H
+    (12, 8, 70, 64, 8, 64, 3, 1, False, False, False, None),                       # hold r = 64; H + 1 = 65; the last one-row size
+    (12, 6, 5, 66, 10, 101, 5, 40, True, True, True, "angle_wrap"),                # hold r = 60; two rows per lane, W in LDS, Nv % 8 = 2
+    (13, 6, 0, 66, 11, 121, 3, 2, False, True, False, "quat_flip"),                # hold r = 66
+    (12, 8, 5, 88, 3, 31, 8, 40, True, False, False, None),                        # two full blocks
+    (12, 6, 5, 90, 1, 15, 5, 40, False, False, True, None),                        # the last size with W in LDS
+    (12, 8, 5, 96, 1, 12, 5, 40, True, False, False, None),                        # W from global memory
+    (13, 6, 70, 96, 2, 31, 9, 1, True, True, True, None),                          # three blocks, the last with one wave
+    (13, 6, 5, 126, 3, 63, 4, 40, True, True, False, "quat_flip"),                 # H + 1 = 64: one full trip; the scalar tail (Nv % 8 = 6) from global memory
+    (12, 8, 0, 128, 8, 127, 3, 2, False, True, True, None),                        # H + 1 = 128; the last two-row size
+    (12, 6, 5, 132, 3, 64, 5, 40, True, True, True, "angle_wrap"),                 # three rows per lane, H + 1 = 65, a short last knot, Nv % 8 = 4
+    (12, 8, 70, 136, 8, 129, 3, 40, False, False, False, None),                    # H + 1 = 130: a third trip
+    (12, 8, 5, 192, 2, 48, 4, 1, True, True, False, None),                         # the last three-row size
+    (13, 6, 5, 198, 2, 65, 1, 40, True, False, True, None),                        # four rows per lane, H + 1 = 66, Nv % 8 = 6
+    (12, 8, 0, 200, 1, 25, 8, 2, False, True, False, None),
+    (12, 8, 5, 256, 2, 64, 3, 40, True, True, True, None),                         # the last four-row size, H + 1 = 65
+    (12, 6, 5, 258, 3, 128, 3, 40, False, True, False, None),                      # five rows per lane, H + 1 = 129, a short last knot, Nv % 8 = 2
+    (12, 8, 5, 264, 1, 33, 5, 0, True, True, True, None),
+    (13, 6, 5, 306, 1, 51, 4, 40, True, False, True, "quat_flip"),
+    (12, 8, 0, 312, 1, 39, 3, 40, False, False, False, None),                      # the largest problem
+    (12, 8, 5, 96, 3, 34, 5, 40, True, False, False, "warm"),                      # the residual stop at two rows per lane from global memory,
+    (12, 6, 5, 132, 2, 43, 5, 40, True, False, True, "warm"),                      # at three
+    (12, 8, 5, 264, 2, 65, 4, 40, True, False, False, "warm"),                     # and at five
+    (13, 6, 5, 258, 3, 127, 3, 2, True, False, True, "quat_flip"),                 # H + 1 = 128 at five rows per lane
+)
+
+
+def draw_lmpc(rng):
+    """never "warm": whether a residual stop can be compared exactly is a property of the seed, which the corner list has checked"""
+    s = SETS["lmpc"]
+    n, r = _pick(rng, s["n"]), _pick(rng, s["r"])
+    M = _pick(rng, [v for v in s["Nv"] if v % r == 0]) // r
+    hold = _pick(rng, [h for h in s["hold"] if (h <= 3 or h in ((8, 9) if r == 8 else (10, 11))) and (M - 1) * h + 1 <= LMPC_H_MAX])
+    lo, hi = (M - 1) * hold + 1, min(M * hold, LMPC_H_MAX)
+    H = _pick(rng, sorted({lo, hi} | {v for v in LMPC_H_EDGES if lo <= v <= hi}))
+    special = _pick(rng, (None, "quat_flip" if n == 13 else "angle_wrap"))
+    return _lmpc(rng, n, r, _pick(rng, s["k"]), M * r, hold, H, _pick(rng, s["nb"]), _pick(rng, s["iters"]), _pick(rng, s["traj"]),
+                 _pick(rng, s["y"]), _pick(rng, s["shift"]), special)
+
+
 # ------------------------------------------------------------------------------------------ the lists
 _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
              mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
              window_pop=(_window_pop, WINDOW_POP_CORNERS, draw_window_pop),
              lift=(_lift, LIFT_CORNERS, draw_lift), gram=(_gram, GRAM_CORNERS, draw_gram),
              pinv_apply=(_pinv_apply, PINV_APPLY_CORNERS, draw_pinv_apply), multistep=(_multistep, MULTISTEP_CORNERS, draw_multistep),
-             simulate=(_simulate, SIMULATE_CORNERS, draw_simulate))
+             simulate=(_simulate, SIMULATE_CORNERS, draw_simulate), ukf=(_ukf, UKF_CORNERS, draw_ukf), lmpc=(_lmpc, LMPC_CORNERS, draw_lmpc))
 FAMILIES = tuple(_MAKE)                                             # the order is part of the seeds: new families go last
 EDMDC_FAMILIES = ("lift", "gram", "pinv_apply", "multistep", "simulate")
 N_CORNERS = {f: len(_MAKE[f][1]) for f in FAMILIES}                 # 12 for the five older families
-N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES for f in FAMILIES}
+FILTER_FAMILIES = ("ukf", "lmpc")
+N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES_FILTER if f in FILTER_FAMILIES else N_CASES for f in FAMILIES}
 
 
 def corners(family, seed=SEED):
@@ -559,3 +698,11 @@ def multistep(seed=SEED):
 
 def simulate(seed=SEED):
     return cases("simulate", seed)
+
+
+def ukf(seed=SEED):
+    return cases("ukf", seed)
+
+
+def lmpc(seed=SEED):
+    return cases("lmpc", seed)

@@ -15,7 +15,9 @@ soft-min update is checked against a long-double soft-min of the kernel's OWN co
 errs by at most 513 x 2^-53 = 6e-14 of sum |terms|.  Every assertion message carries the case dict.
 
 The EDMDc families (lift, gram, pinv_apply, multistep, simulate) have their prepare / run / compare in tests/sweep_edmdc.py, with
-their own measures and bounds (a reference states its own gap condition as ref["gap_bound"]); PREPARE and sweep_one here cover them."""
+their own measures and bounds (a reference states its own gap condition as ref["gap_bound"]); PREPARE and sweep_one here cover them.
+So do the unscented Kalman filter (ukf) and the QP of the Koopman linear MPC (lmpc) in tests/sweep_ukf_lmpc.py, by the recipe above:
+a lane is a (candidate, recording) filter or a problem."""
 import numpy as np
 
 import feedback_ref as fr
@@ -23,6 +25,7 @@ import fossen_vehicles as fv
 import koopman_mppi_ref as kr
 import mppi_ref as mr
 import sweep_edmdc as se
+import sweep_ukf_lmpc as su
 from oracle import fossen_params as fp
 
 TOL_ROLL = 1e-10
@@ -397,7 +400,7 @@ def compare_window_pop(case, ref, got):
 
 
 PREPARE = dict(rollout_pop=prepare_rollout_pop, feedback=prepare_feedback, mppi=prepare_mppi, koopman_mppi=prepare_koopman_mppi,
-               window_pop=prepare_window_pop, **se.PREPARE)
+               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE)
 
 
 def sweep_one(eng, ctx, case, ref=None):
@@ -408,6 +411,8 @@ def sweep_one(eng, ctx, case, ref=None):
     out = well_posed(case, ref)
     if fam in se.PREPARE:
         e, e2 = se.sweep_one(eng, ctx, case, ref)
+    elif fam in su.PREPARE:
+        e, e2 = su.sweep_one(eng, ctx, case, ref)
     elif fam == "rollout_pop":
         e, e2 = compare_rollout_pop(case, ref, run_rollout_pop(eng, ctx, case, ref)), 0.0
     elif fam == "feedback":

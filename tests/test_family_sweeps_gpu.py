@@ -10,7 +10,14 @@ first cases of each list.  A failure message carries the case dict: sweep_run.sw
 The EDMDc families (lift, gram in its three entry forms, pinv_apply in both variants, the propagated and the linear multistep
 evaluator, simulate_lifted) run their 32 cases each in four slices of 8, by the measures and bounds of tests/sweep_edmdc.py: Gram and
 apply entries per entry against sum |terms| at 1e-12, x_hat per window and simulate rows per trajectory at 1e-10, the lift at 1e-13
-absolute and relative to the reference's own gap."""
+absolute and relative to the reference's own gap.
+
+The unscented Kalman filter (ukf) and the QP of the Koopman linear MPC (lmpc) run 32 cases each in four slices of 8, by
+tests/sweep_ukf_lmpc.py: a lane is a (candidate, recording) filter or a problem, every output at 1e-10, counts exact.  Their lists hold
+what the hand-picked shapes of tests/test_ukf_gpu.py and tests/test_koopman_lmpc_gpu.py never execute: the three thruster filters
+without a start lag, full and lone-wave blocks for every instantiation, T = 1, 12 updates per row and none at all; three and four rows
+per lane of the QP, the second and third trip of its epilogue and of its u_apply loop, the scalar tail of the blocked W loop with W
+from global memory, the shift and the residual stop beyond one row per lane."""
 import numpy as np
 import pytest
 
@@ -18,6 +25,7 @@ import mppi_ref as mr
 import sweep_cases as sc
 import sweep_edmdc as se
 import sweep_run as sr
+import sweep_ukf_lmpc as su
 
 pytestmark = pytest.mark.gpu
 
@@ -174,3 +182,120 @@ def test_simulate_repeats_and_a_trajectory_alone_is_the_batch_row(eng, ctx):
         for j in sorted({0, c["nb"] // 2, c["nb"] - 1} | {j for j in (127, 128, 255, 256) if j < c["nb"]}):
             alone = se.run_simulate(eng, ctx, c, ref, rows=slice(j, j + 1))
             assert alone.tobytes() == a[j:j + 1].tobytes(), ("trajectory alone", j, c)
+
+
+# ------------------------------------------------------------------------------------------ ukf: the exact identities
+UKF_KEYS = su.UKF_OUTS + ("lag",)
+
+
+def _ukf_same(a, b, what, ia=(), ib=()):
+    """a[k][ia] and b[k][ib] hold the same bits (NaN where NaN), for every output"""
+    for k in UKF_KEYS:
+        if a[k] is None or b[k] is None:
+            assert a[k] is None and b[k] is None, (k, what)
+        else:
+            assert np.array_equal(a[k][ia], b[k][ib], equal_nan=True), (k, what)
+
+
+def test_ukf_repeats_and_candidates_and_recordings_alone(eng, ctx):
+    """two calls give equal bytes; candidate j equals the P = 1 call; a recording run alone equals its row of the batch bit for bit:
+    B = 4 and 8 (every wave slot of full blocks), B = 5 (the lone wave of a ragged block), B = 1"""
+    cases = sc.cases("ukf")[:IDENTITY_CASES]
+    assert {c["B"] for c in cases} == {4, 5, 8, 1} and any(c["P"] == 3 and c["nrec"] == 3 for c in cases)
+    for c in cases:
+        ref = sr.PREPARE["ukf"](c)
+        a = su.run_ukf(eng, ctx, c, ref)
+        _ukf_same(a, su.run_ukf(eng, ctx, c, ref), ("repeat", c))
+        for j in range(c["P"]):
+            _ukf_same(su.run_ukf(eng, ctx, c, ref, cand=slice(j, j + 1)), a, ("candidate alone", j, c), (0,), (j,))
+        for b in range(c["B"]):
+            _ukf_same(su.run_ukf(eng, ctx, c, ref, rec=slice(b, b + 1)), a, ("recording alone", b, c), (slice(None), 0), (slice(None), b))
+
+
+def test_ukf_split_at_every_row_and_resumed(eng, ctx):
+    """T = 12 rows = T1 + (12 - T1) rows resumed from (xT, PT, lag_io), for every T1 = 1 .. 11: the unbroken bits in every row
+    output, xT, PT and lag_io; the update counts add up exactly and the log-likelihoods to rounding.  A thruster case with a start
+    lag and a wrench case (without a lag_io the thruster filter cannot be resumed: it restarts from a zero lag)."""
+    corners = sc.corners("ukf")
+    picked = [[c for c in corners if c["T"] == 12 and c["model"] == m and (c["lag"] or m == 1) and c["P"] > 1][0] for m in (0, 1)]
+    for c in picked:
+        ref = sr.PREPARE["ukf"](c)
+        a = su.run_ukf(eng, ctx, c, ref)
+        assert np.all(a["info"][..., 2] == -1), c
+        for T1 in range(1, c["T"]):
+            h = su.run_ukf(eng, ctx, c, ref, rows=slice(0, T1))
+            parts = [su.run_ukf(eng, ctx, c, ref, cand=slice(j, j + 1), rows=slice(T1, None), x0=h["xT"][j], P0=h["PT"][j],
+                                lag=None if h["lag"] is None else h["lag"][j:j + 1]) for j in range(c["P"])]       # x0 and P0 are shared: one by one
+            for k in ("xf", "pstd", "innov"):
+                both = np.concatenate([h[k], np.concatenate([p[k] for p in parts])], axis=2)
+                assert np.array_equal(both, a[k], equal_nan=True), (k, T1, c)
+            for k in ("xT", "PT") + (("lag",) if a["lag"] is not None else ()):
+                assert np.array_equal(np.concatenate([p[k] for p in parts]), a[k]), (k, T1, c)
+            info = np.concatenate([p["info"] for p in parts])
+            assert np.array_equal(h["info"][..., 1] + info[..., 1], a["info"][..., 1]), (T1, c)
+            assert np.max(np.abs(h["info"][..., 0] + info[..., 0] - a["info"][..., 0]) / np.maximum(1.0, np.abs(a["info"][..., 0]))) < 1e-12, (T1, c)
+
+
+def test_ukf_lag_io_is_rollout_pops(eng, ctx):
+    """lag_io out is rollout_pop's lag_io on the same commands, from the case's start lag and from a zero one: Euler, RK4 with the
+    lag per call and per step"""
+    import fossen_vehicles as fv
+    corners = [c for c in sc.corners("ukf") if c["lag"]]
+    picked = [[c for c in corners if (c["integ"], c["lag_mode"]) == v][0] for v in (("euler", 0), ("rk4", 0), ("rk4", 1))]
+    for c in picked:
+        ref = sr.PREPARE["ukf"](c)
+        for lag in (ref["lag"], np.zeros_like(ref["lag"])):
+            f = su.run_ukf(eng, ctx, c, ref, lag=lag)
+            pop = eng.rollout_pop(0, c["integ"], [fv.params(n) for n in c["names"]], np.zeros((c["B"], 12)), ref["U"], su.DT_UKF, lag=lag,
+                                  lag_mode=c["lag_mode"], store=False, ctx=ctx)
+            assert np.all(f["info"][..., 2] == -1) and np.array_equal(f["lag"], pop["lag"]), c
+
+
+# ------------------------------------------------------------------------------------------ lmpc: the exact identities
+LMPC_KEYS = ("U_nom", "y", "u_apply", "pred", "info")
+
+
+def _lmpc_same(a, b, keys=LMPC_KEYS, ia=slice(None), ib=slice(None)):
+    return all((a[k] is None and b[k] is None) or a[k][ia].tobytes() == b[k][ib].tobytes() for k in keys)
+
+
+def _lmpc_of_rows(nq, **want):
+    """the first corner with nq rows per lane (W from global memory from nq = 2 on) that holds `want`"""
+    return [c for c in sc.corners("lmpc") if sc.lmpc_rows(c)[0] == nq and all(c[k] == v for k, v in want.items())][0]
+
+
+def test_lmpc_repeats_and_a_problem_alone_is_the_batch_row(eng, ctx):
+    """two calls give equal bytes; a problem run alone equals its row of the batch in every wave slot: one case per rows-per-lane
+    count and W source, each with at least four problems"""
+    corners = sc.corners("lmpc")
+    picked = []
+    for rows in ((1, True), (2, True), (2, False), (3, False), (4, False), (5, False)):
+        fit = [c for c in corners if sc.lmpc_rows(c) == rows and c["nb"] >= 4]
+        picked.append(([c for c in fit if c["iters"] == 40] or fit)[0])
+    for c in corners[:IDENTITY_CASES] + picked:
+        ref = sr.PREPARE["lmpc"](c)
+        a = su.run_lmpc(eng, ctx, c, ref)
+        assert _lmpc_same(a, su.run_lmpc(eng, ctx, c, ref)), ("repeat", c)
+        for b in range(c["nb"]):
+            assert _lmpc_same(su.run_lmpc(eng, ctx, c, ref, sel=slice(b, b + 1)), a, ib=slice(b, b + 1)), ("problem alone", b, c)
+
+
+@pytest.mark.parametrize("nq", [3, 4, 5])
+def test_lmpc_resume_and_shift_beyond_two_rows_per_lane(eng, ctx, nq):
+    """iters = a, then iters = b on the returned (U_nom, y), is one call with iters = a + b; shift = 1 moves z and y one knot forward
+    with the last knot repeated and changes nothing else (tests/test_koopman_lmpc_gpu.py: test_resume, test_shift, which run one
+    and two rows per lane)"""
+    c = _lmpc_of_rows(nq, iters=40, tol=0.0)
+    ref = sr.PREPARE["lmpc"](c)
+    y0 = np.zeros_like(ref["U"])
+    for a, b in ((1, 1), (17, 23)):
+        first = su.run_lmpc(eng, ctx, c, ref, y=y0, iters=a, shift=False)
+        second = su.run_lmpc(eng, ctx, c, ref, U_nom=first["U_nom"], y=first["y"], iters=b, shift=False)
+        whole = su.run_lmpc(eng, ctx, c, ref, y=y0, iters=a + b, shift=False)
+        assert _lmpc_same(second, whole, ("U_nom", "y", "u_apply", "pred")), (a, b, c)
+        assert np.array_equal(second["info"][:, [0, 2, 3, 5]], whole["info"][:, [0, 2, 3, 5]]), (a, b, c)
+        assert np.all(second["info"][:, 4] == b) and np.all(whole["info"][:, 4] == a + b), (a, b, c)
+    plain, moved = su.run_lmpc(eng, ctx, c, ref, y=y0, shift=False), su.run_lmpc(eng, ctx, c, ref, y=y0, shift=True)
+    for key in ("U_nom", "y"):
+        assert np.array_equal(moved[key], np.concatenate([plain[key][:, 1:], plain[key][:, -1:]], axis=1)), (key, c)
+    assert _lmpc_same(plain, moved, ("u_apply", "pred", "info")), c

@@ -1,10 +1,11 @@
-"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the ten families' value sets occurs in
+"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the twelve families' value sets occurs in
 the hand-written corner list, by name, so that a list cannot shrink silently; (b) for every case the reference alone meets the
 conditions of tests/sweep_run.py (float64 against long double below a tenth of the bound on the compared lanes, at most 2 % of the
 lanes left out, never all), so that tests/test_family_sweeps_gpu.py can fail only because of a kernel; (c) the lists are a function
 of the seed alone and their hashes are pinned.  The vehicles come from tests/fossen_vehicles.py, which needs the built library.
 The EDMDc families' reference is oracle/edmdc_numpy.py restated with a dtype (tests/sweep_edmdc.py): (d) its float64 form is the
-oracle's bit for bit."""
+oracle's bit for bit.  The filter (ukf) and QP (lmpc) families take their references from tests/ukf_ref.py and
+tests/koopman_lmpc_ref.py through tests/sweep_ukf_lmpc.py; with at most 27 lanes a case the 2 % cap means that no lane is left out."""
 import numpy as np
 import pytest
 
@@ -12,8 +13,9 @@ import sweep_cases as sc
 
 SLICES = 4
 PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52",
-              lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921")
-CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12)
+              lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921",
+              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88")
+CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12, ukf=17, lmpc=26)
 
 
 def _value(c, key):
@@ -38,7 +40,7 @@ def _seen(family, key):
 @pytest.mark.parametrize("family", sc.FAMILIES)
 def test_every_value_is_in_the_corner_list(family):
     assert len(sc.corners(family)) == CORNERS[family] == sc.N_CORNERS[family], (family, len(sc.corners(family)))
-    assert len(sc.cases(family)) == (sc.N_CASES_EDMDC if family in sc.EDMDC_FAMILIES else sc.N_CASES)
+    assert len(sc.cases(family)) == (32 if family in sc.EDMDC_FAMILIES + sc.FILTER_FAMILIES else sc.N_CASES) == sc.N_CASES_OF[family]
     for key, values in sc.SETS[family].items():
         missing = set(values) - _seen(family, key)
         assert not missing, (family, key, "not in the corner list", missing)
@@ -46,6 +48,8 @@ def test_every_value_is_in_the_corner_list(family):
         for key, values in sc.SETS[family].items():
             if family == "window_pop" and key in ("nbags", "nwin"):      # a bag list: up to five bags of up to H + 65 rows each
                 assert (len(c["lens"]) in sc.SETS[family]["nbags"] and c["nwin"] <= 5 * 65) if c["bags"] else c["nwin"] in sc.SETS[family]["nwin"], c
+            elif family == "lmpc" and key == "H":                      # a draw's H: anywhere in the last knot, up to the third epilogue trip
+                assert (c["M"] - 1) * c["hold"] < c["H"] <= min(c["M"] * c["hold"], sc.LMPC_H_MAX), c
             elif not (family == "mppi" and key == "nparams"):
                 assert _value(c, key) in values, (family, key, c)
 
@@ -76,6 +80,37 @@ def test_corner_pairs():
     assert any(c["bags"] and 0 in c["lens"] for c in w) and any(c["bags"] and c["H"] in c["lens"] for c in w), "bags without a window"
     assert any(c["bags"] and c["lens"][0] == c["H"] + 64 and c["nwin"] > 64 for c in w), "a join at a chunk edge"
     assert any(c["bags"] for c in w) and any(not c["bags"] for c in w)
+
+
+def test_filter_and_qp_corner_pairs():
+    """the edges the ukf and lmpc corner lists must contain, by name"""
+    u = sc.corners("ukf")
+    inst = {(0, "euler", 0, True), (0, "euler", 0, False), (0, "rk4", 0, True), (0, "rk4", 0, False), (0, "rk4", 1, True), (0, "rk4", 1, False),
+            (1, "euler", 0, False), (1, "rk4", 0, False)}
+    assert {sc.ukf_instance(c) for c in u} == inst, "the eight instantiations of ukf_filter_kernel"
+    for i in inst:                                                   # every instantiation with a full and with a ragged last block
+        assert any(sc.ukf_instance(c) == i and c["B"] % 4 == 0 for c in u) and any(sc.ukf_instance(c) == i and c["B"] % 4 for c in u), i
+    for model in (0, 1):
+        assert _has("ukf", model=model, measured="none") and _has("ukf", model=model, measured="all", r_inf=0, T=12), model
+    assert _has("ukf", P=3, nrec=3) and _has("ukf", B=9) and _has("ukf", B=1, T=12) and _has("ukf", wrap=True, T=12)
+    assert all(c["P"] * c["B"] * c["T"] <= sc.UKF_ROWS and c["nrec"] in (1, c["P"]) for c in sc.cases("ukf"))
+    assert all(not c["lag"] and c["lag_mode"] == 0 for c in sc.cases("ukf") if c["model"] == 1)
+    q = sc.corners("lmpc")
+    rows = {sc.lmpc_rows(c) for c in q}
+    assert rows == {(1, True), (2, True), (2, False), (3, False), (4, False), (5, False)}, "every rows-per-lane count with both W sources where both exist"
+    for c in sc.cases("lmpc"):
+        assert c["M"] * c["r"] == c["Nv"] <= 312 and c["M"] == (c["H"] + c["hold"] - 1) // c["hold"] and 1 <= c["H"] <= sc.LMPC_H_MAX, c
+        assert (c["special"] == "warm") == (c["tol"] > 0) and (c["special"] != "quat_flip" or c["n"] == 13) and (c["special"] != "angle_wrap" or c["n"] == 12), c
+    assert {c["H"] + 1 for c in q} >= {64, 65, 66, 128, 129, 130}, "both sides of the epilogue's second and third trip"
+    assert any(c["H"] + 1 > 64 and c["Nv"] > 128 and c["H"] % c["hold"] for c in q), "a second trip with a short last knot at three rows per lane"
+    for nq in (3, 4, 5):
+        assert any(sc.lmpc_rows(c)[0] == nq and c["H"] + 1 > 64 for c in q), nq
+        assert any(sc.lmpc_rows(c)[0] == nq and c["shift"] and c["iters"] == 40 for c in q), ("the shift", nq)
+        assert any(sc.lmpc_rows(c)[0] == nq and c["Nv"] % 8 for c in q), ("the scalar tail of the blocked loop", nq)
+    assert any(sc.lmpc_rows(c) == (2, False) and c["Nv"] % 8 for c in q), "the scalar tail with W from global memory at two rows per lane"
+    assert {c["hold"] * c["r"] for c in q} >= {60, 64, 66, 72}, "hold r on both sides of 64"
+    assert {sc.lmpc_rows(c) for c in q if c["special"] == "warm"} == {(2, False), (3, False), (5, False)}
+    assert any(c["hold"] > c["H"] for c in q) and any(c["M"] == 1 and c["shift"] for c in q)
 
 
 def _chunk_edges(c):

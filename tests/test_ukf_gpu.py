@@ -11,13 +11,17 @@ checks it without a GPU).
 Shapes, the smallest that can still go wrong (tests/ukf_cases.py): P = 2 candidates; T = 12 rows; B = 3 recordings, which leaves
 the fourth wave of the one block idle (the kernel packs four recordings, one per wave, into a block), and B = 5 in the ragged case:
 a full block and a block with one live wave; about 30 % NaNs in Y, row 4 without any measurement, component 7 with r = +inf while its
-Y column carries numbers, a NaN upper triangle in P0, a start lag for the thruster model; alpha in {0.5, 1}."""
+Y column carries numbers, a NaN upper triangle in P0, a start lag for the thruster model; alpha in {0.5, 1}.  The other shapes (no start lag, full
+blocks, P = 1 and 3, T = 1 ..) run in the sweep of tests/test_family_sweeps_gpu.py; section 5 here takes the three failure
+conditions of the header on corner cases of that sweep (tests/sweep_cases.py: UKF_CORNERS), in every wave slot."""
 import ctypes
 
 import numpy as np
 import pytest
 
 import fossen_vehicles as fv
+import sweep_cases as sc
+import sweep_ukf_lmpc as su
 import ukf_cases as uc
 import ukf_ref as ur
 
@@ -196,6 +200,85 @@ def test_indefinite_P0_fails_alone(eng, ctx, name):
         for b in (0, 2):
             for k in OUTS + (("lag",) if got["lag"] is not None else ()):
                 assert np.array_equal(got[k][j, b], a[k][j, b], equal_nan=True), (k, j, b)
+
+
+
+def _sweep_case(**want):
+    """the first corner of the sweep's ukf list that holds `want`, with its inputs"""
+    c = [c for c in sc.corners("ukf") if all(c[k] == v for k, v in want.items())][0]
+    return c, su.ukf_inputs(c)
+
+
+def _failure(eng, ctx, c, i, clean, b, t_fail, row_kept, **kw):
+    """Filter b of the call with the inputs kw fails at row t_fail; ukf_ref says so too.  Against ukf_ref: info (l = -inf, the updates
+    counted up to the failure, the failed row, the smallest pivot), the NaN pattern of xf / pstd / innov with row t_fail kept or not
+    as the header states and the kept rows to TOL_ROLL, xT and PT all NaN.  lag_io of the failed filter is untouched, and every
+    other filter of the call keeps the bits of the clean call."""
+    got = su.run_ukf(eng, ctx, c, i, **kw)
+    a = dict(x0=i["x0"], P0=i["P0"], U=i["U"], Y=i["Y"])
+    a.update(kw)
+    with np.errstate(all="ignore"):
+        o = ur.filter(c["model"], su.INTEG[c["integ"]], c["lag_mode"], [fv.vehicle(n) for n in c["names"]], i["cfgs"], a["x0"][b:b + 1], a["P0"][b:b + 1],
+                      a["U"][b:b + 1], a["Y"][b:b + 1], DT, lag=None if i["lag"] is None else i["lag"][:, b:b + 1])
+    assert np.all(o["info"][:, 0, 2] == t_fail) and np.all(o["info"][:, 0, 0] == -np.inf), ("the reference must fail there", o["info"])
+    first_nan = t_fail + 1 if row_kept else t_fail
+    for j in range(c["P"]):
+        assert got["info"][j, b, 0] == -np.inf and np.array_equal(got["info"][j, b, 1:3], o["info"][j, 0, 1:3]), (j, b, got["info"][j, b], o["info"][j, 0])
+        assert uc.err(got["info"][j, b, 3], o["info"][j, 0, 3]) < TOL_ROLL, (j, b, got["info"][j, b], o["info"][j, 0])
+        assert np.isnan(got["xT"][j, b]).all() and np.isnan(got["PT"][j, b]).all(), (j, b)
+        for k in ("xf", "pstd", "innov"):
+            assert np.isnan(got[k][j, b, first_nan:]).all() and np.isnan(o[k][j, 0, first_nan:]).all(), (k, j, b)
+            if k != "innov" and first_nan:
+                assert np.isfinite(got[k][j, b, :first_nan]).all(), (k, j, b)
+            e = uc.err(got[k][j, b], o[k][j, 0])                    # inf where the NaN patterns differ
+            assert e < TOL_ROLL, (k, j, b, e)
+        if c["lag"]:
+            assert np.array_equal(got["lag"][j, b], i["lag"][j, b]), ("lag_io of a failed filter", j, b)
+        else:
+            assert got["lag"] is None
+        for other in range(c["B"]):
+            if other != b:
+                for k in OUTS + (("lag",) if c["lag"] else ()):
+                    assert np.array_equal(got[k][j, other], clean[k][j, other], equal_nan=True), (k, j, other, "with a failure in", b)
+
+
+@pytest.mark.parametrize("P,model", [(1, 0), (3, 1)])
+def test_bad_pivot_in_every_wave_slot(eng, ctx, P, model):
+    """the indefinite P0 of test_indefinite_P0_fails_alone, at P = 1 and P = 3 and B = 5, in each recording in turn: the four wave
+    slots of the full block and the lone wave of the ragged last block.  Row 0 of every recording carries no measurement here, so
+    that the indefinite matrix reaches the Cholesky factorisation whatever the noise (an update could meet s <= 0 first); the row's
+    update is complete, so row 0 is kept."""
+    c, i = _sweep_case(P=P, model=model, B=5, T=12, measured="all")
+    Y = i["Y"].copy()
+    Y[:, 0] = np.nan
+    clean = su.run_ukf(eng, ctx, c, i, Y=Y)
+    assert np.all(clean["info"][..., 2] == -1)
+    for b in range(c["B"]):
+        P0 = i["P0"].copy()
+        P0[b, 1, 0] = 2.0 * P0[b, 0, 0]                             # (the upper triangle is NaN: never read)
+        _failure(eng, ctx, c, i, clean, b, 0, True, P0=P0, Y=Y)
+
+
+@pytest.mark.parametrize("want", [dict(model=0, lag=True, T=12, measured="std", P=2), dict(model=0, lag=False, T=12, measured="std", B=9),
+                                  dict(model=1, T=12, measured="std", P=3)])
+def test_stage_one_failure_and_a_non_finite_prediction(eng, ctx, want):
+    """(a) s = P[i][i] + r[i] <= 0 at row 0: P0[i][i] = -2 r[i] on the last measured component of the row, so that the earlier
+    updates of the row are applied and counted; the row is not kept: rows 0 .. are NaN.  (b) an infinite command at row t > 0 (the
+    header does not validate U): the predicted mean is not finite, row t is kept, rows t + 1 .. are NaN.  Both in wave slot 1 of the
+    first block and in the last recording; a thruster filter with and without a start lag and a wrench filter."""
+    c, i = _sweep_case(**want)
+    clean = su.run_ukf(eng, ctx, c, i)
+    assert np.all(clean["info"][..., 2] == -1)
+    r = (i["cfgs"] if isinstance(i["cfgs"], ur.Cfg) else i["cfgs"][0]).r
+    for b in (1, c["B"] - 1):
+        comp = [k for k in range(12) if not np.isnan(i["Y"][b, 0, k]) and np.isfinite(r[k])][-1]
+        P0 = i["P0"].copy()
+        P0[b, comp, comp] = -2.0 * r[comp]
+        _failure(eng, ctx, c, i, clean, b, 0, False, P0=P0)
+        for t in (3, c["T"] - 1):
+            U = i["U"].copy()
+            U[b, t, 0] = np.inf
+            _failure(eng, ctx, c, i, clean, b, t, True, U=U)
 
 
 # ------------------------------------------------------------------------------------------ 6. the host contract
