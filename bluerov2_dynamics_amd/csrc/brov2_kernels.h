@@ -330,6 +330,10 @@ size_t kmeans_mstep_scratch_doubles(int k);
 hipError_t launch_kmeans_mstep(hipStream_t st, const KmMstepArgs& a, int phases);
 hipError_t launch_kmeans_reloc_dist(hipStream_t st, int64_t N, int n, const double* X, int64_t xstride, const double* mean, const double* Cold,
                                     const int* labels, const int* perm, double* dist_row, int* lab_row);
+// the inertia of the returned labels and centres by differences: partial [kmeans_inertia_blocks(N)], added by the host in block order
+int kmeans_inertia_blocks(int64_t N);
+hipError_t launch_kmeans_inertia(hipStream_t st, int64_t N, int n, int k, const double* X, int64_t xstride, const double* mean, const double* C,
+                                 const int* labels, double* partial);
 
 
 // width of the label field in the sort keys of the Lloyd loop's sample order (sortperm.hip); kmeans.hip checks its own limit against it

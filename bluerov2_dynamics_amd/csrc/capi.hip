@@ -3367,7 +3367,7 @@ int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d
                        (nbr ? Arena::al(k * kp_ * 8) : 0) +
                        (sorting ? 9 * Arena::al((size_t)N * 4) + Arena::al(sort_tmp + 256) : 0) +
                        (bnd ? 5 * Arena::al((size_t)N * 4) + Arena::al(lwords * 4) + Arena::al(rwords * 8) + 4 * Arena::al((size_t)k * 16 + 64) + 1024 : 0) +
-                       Arena::al(kmeans_mstep_scratch_doubles(k) * 8) + 8192);
+                       Arena::al(kmeans_mstep_scratch_doubles(k) * 8) + Arena::al((size_t)kmeans_inertia_blocks(N) * 8) + 8192);
     if (rc) return rc;
     unsigned long long* partial = a.take<unsigned long long>(pw_max);
     long long* red = a.take<long long>(rwords);
@@ -3383,6 +3383,7 @@ int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d
     unsigned long long* rng = a.take<unsigned long long>(16);
     double* dmean = a.take<double>(16);
     double* ms_scratch = a.take<double>(kmeans_mstep_scratch_doubles(k));      // the fused M-step's per-centre shifts / flags and its arrival ticket
+    double* ipart = a.take<double>(kmeans_inertia_blocks(N));                  // block partials of the returned inertia
     int *Ls[2] = {nullptr, nullptr}, *Ps[2] = {nullptr, nullptr};
     float* d2 = nullptr;
     float *d2s[2] = {nullptr, nullptr}, *ubs[2] = {nullptr, nullptr}, *lbs[2] = {nullptr, nullptr};      // per position: two copies each, swapped by a re-sort
@@ -3610,14 +3611,18 @@ int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d
     }
     HIPCK(c, hipMemcpyAsync(d_C, Cb[cc], (size_t)k * n * 8, hipMemcpyDeviceToDevice, c->stream));
     if (Pc) HIPCK(c, launch_kmeans_unpermute(c->stream, N, Pc, Lc, d_labels));      // labels back in the caller's order
-    if (!strict) {   // labels / inertia consistent with the final centres: the E-step already queued
-        std::vector<double> hb(e_nb);
-        HIPCK(c, d2h_copy(c, hb.data(), binert, e_nb * 8));
+    {
+        // The inertia of what is returned -- the labels of the last E-step (already queued when the loop ended on the shift or on
+        // max_iter; the unchanged ones under strict convergence) against the final centres -- summed by DIFFERENCES in one pass of its
+        // own (kmeans.hip: kmeans_inertia_kernel).  The E-steps' own sums (binert, hs[1]) are expanded forms: statistics of the loop only.
+        (void)strict;
+        const int nbi = kmeans_inertia_blocks(N);
+        std::vector<double> hb(nbi);
+        HIPCK(c, launch_kmeans_inertia(c->stream, N, n, k, d_X, xstride, mp, d_C, d_labels, ipart));
+        HIPCK(c, d2h_copy(c, hb.data(), ipart, (size_t)nbi * 8));
         HIPCK(c, hipStreamSynchronize(c->stream));
         in = 0.0;
         for (double v : hb) in += v;
-    } else {
-        HIPCK(c, hipStreamSynchronize(c->stream));
     }
     if (inertia) *inertia = in;
     if (n_iter) *n_iter = it;

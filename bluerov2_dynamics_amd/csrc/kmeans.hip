@@ -3445,6 +3445,53 @@ hipError_t launch_kmeans_average(hipStream_t st, int n, int k, const long long* 
     hipLaunchKernelGGL(kmeans_average_kernel, dim3(1), dim3(1024), 0, st, n, k, red, fix, Cold, Cnew, c2, stats, prm, mode, shiftc, nlist);
     return hipGetLastError();
 }
+// ---- the inertia a call returns: sum_i |x_i - mean - c_label(i)|^2 over the RETURNED labels and centres, by differences ----------------
+// The E-step kernels form a sample's squared distance as |x|^2 - 2 (x.c - |c|^2 / 2): good for the loop (its sums are statistics and
+// sort keys), but its absolute error of ~1e-17 |x|^2 per sample is no relative accuracy where the inertia is tiny against sum |x|^2 --
+// k = N returned 8.4e-15 for an inertia of 0, N = 65 / k = 63 missed 1e-10.  One pass per CALL (not per iteration) over the rows in the
+// caller's order: the difference first, as scikit-learn's `_inertia_dense` does; rows dealt grid-stride, a fixed butterfly per wave, the
+// four waves in index order, one partial per block, added by the host in block order: the value depends on (N, n, labels, centres) only.
+constexpr int KM_INERTIA_THREADS = 256;
+__global__ void __launch_bounds__(KM_INERTIA_THREADS) kmeans_inertia_kernel(int64_t N, int n, int k, const double* __restrict__ X, int64_t xstride,
+                                                                            const double* __restrict__ mean, const double* __restrict__ C,
+                                                                            const int* __restrict__ labels, double* __restrict__ partial) {
+    __shared__ double red[KM_INERTIA_THREADS / 64];
+    double m[KM_NMAX];
+#pragma unroll
+    for (int j = 0; j < KM_NMAX; ++j) m[j] = (mean && j < n) ? mean[j] : 0.0;
+    double acc = 0.0;
+    const int64_t step = (int64_t)gridDim.x * KM_INERTIA_THREADS;
+    for (int64_t i = (int64_t)blockIdx.x * KM_INERTIA_THREADS + threadIdx.x; i < N; i += step) {
+        const int lab = labels[i];
+        if ((unsigned)lab >= (unsigned)k) continue;      // (every returned label is one; a guard for the centre read all the same)
+        const double* x = X + i * xstride;
+        const double* c = C + (int64_t)lab * n;
+        double d2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < KM_NMAX; ++j)
+            if (j < n) { const double d = (x[j] - m[j]) - c[j]; d2 = fma(d, d, d2); }
+        acc += d2;
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = 0.0;
+        for (int w = 0; w < KM_INERTIA_THREADS / 64; ++w) v += red[w];
+        partial[blockIdx.x] = v;
+    }
+}
+int kmeans_inertia_blocks(int64_t N) {
+    const int64_t want = (N + KM_INERTIA_THREADS - 1) / KM_INERTIA_THREADS;
+    return (int)(want < 1 ? 1 : (want > 1024 ? 1024 : want));
+}
+hipError_t launch_kmeans_inertia(hipStream_t st, int64_t N, int n, int k, const double* X, int64_t xstride, const double* mean, const double* C,
+                                 const int* labels, double* partial) {
+    if (N < 1 || n < 1 || n > KM_NMAX || k < 1 || xstride < n) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kmeans_inertia_kernel, dim3((unsigned)kmeans_inertia_blocks(N)), dim3(KM_INERTIA_THREADS), 0, st, N, n, k, X, xstride, mean, C,
+                       labels, partial);
+    return hipGetLastError();
+}
 hipError_t launch_kmeans_reloc_dist(hipStream_t st, int64_t N, int n, const double* X, int64_t xstride, const double* mean, const double* Cold,
                                     const int* labels, const int* perm, double* dist_row, int* lab_row) {
     hipLaunchKernelGGL(kmeans_reloc_dist_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, N, n, X, xstride, mean, Cold, labels, perm,

@@ -285,17 +285,11 @@ def kmeans_lloyd_sharded(X_local, C0, mean=None, max_iter=300, tol_abs=0.0, grou
     if lloyd_fn is not None:
         ar = (lambda buf, op: allreduce_words_(buf, op, group)) if sharded else None
         return lloyd_fn(X_local, C0, mean, max_iter, tol_abs, ar)
-    import ctypes
     from . import engine
-    from ._lib import _hptr, as_f64
     ctx = ctx or engine.default_context(X_local.device.index)
     ctx.use_torch_stream()
-    N, n = X_local.shape
-    k = C0.shape[0]
+    N = X_local.shape[0]
     C = C0.to(device=X_local.device, dtype=torch.float64).contiguous().clone()
-    labels = torch.empty(N, dtype=torch.int32, device=X_local.device)
-    inertia, n_iter = ctypes.c_double(0.0), ctypes.c_int(0)
-    m = None if mean is None else as_f64(mean).reshape(n)
 
     def cb(ptr, count, op):
         allreduce_words_(torch.as_tensor(_DeviceWords(ptr, count), device=X_local.device), op, group)
@@ -306,15 +300,12 @@ def kmeans_lloyd_sharded(X_local, C0, mean=None, max_iter=300, tol_abs=0.0, grou
         ctx.set_kmeans_shard(rank, world, row0, Ng)
         ctx.set_kmeans_allreduce(cb)
     try:
-        torch.cuda.current_stream(X_local.device).synchronize()
-        ctx.check(ctx.lib.edmdc_kmeans_lloyd_dev(ctx.h, N, n, k, X_local.data_ptr(), X_local.stride(0), _hptr(m), C.data_ptr(), int(max_iter),
-                                                 float(tol_abs), labels.data_ptr(), ctypes.byref(inertia), ctypes.byref(n_iter)),
-                  "edmdc_kmeans_lloyd_dev (sharded)")
+        out = engine.kmeans_lloyd_dev(X_local, C, max_iter=max_iter, tol_abs=tol_abs, mean=mean, ctx=ctx, inplace=True)
     finally:
         if sharded:
             ctx.set_kmeans_allreduce(None)
             ctx.set_kmeans_shard()
-    return C, labels, inertia.value, n_iter.value
+    return out
 
 
 def column_stats_sharded(X_local, group=None):

@@ -1315,6 +1315,39 @@ def kmeans_lloyd(X, C_init, max_iter=300, tol_abs=0.0, mean=None, ctx=None):
     return C, labels, inertia.value, n_iter.value
 
 
+def kmeans_lloyd_dev(X, C_init, max_iter=300, tol_abs=0.0, mean=None, ctx=None, inplace=False):
+    """kmeans_lloyd for a device-resident X ([N,n] DevArray or torch CUDA tensor whose rows are contiguous, any row stride >= n: a
+    column block of a wider table; edmdc_kmeans_lloyd_dev).  C_init [k,n]: a host array, or a contiguous device array of X's kind; it
+    is left as it is unless inplace=True, when it receives the final centres and is what comes back (the C ABI's C_io).  mean [n]:
+    host.  Returns (centres [k,n] device array of X's kind, in the frame of X - mean; labels [N] int32 device array; inertia; n_iter).
+    Waits for the device before the call (work queued on any stream may have produced X)."""
+    ctx = _ctx_of(X, ctx)
+    ns = arrays_of(X, ctx)
+    ns.bind()
+    N, n = X.shape
+    if isinstance(C_init, DevArray) or _is_torch(C_init):
+        assert isinstance(C_init, DevArray) == isinstance(X, DevArray), "a device C_init must be of X's kind (DevArray or torch tensor)"
+        assert C_init.dim() == 2 and C_init.shape[1] == n and C_init.is_contiguous(), "C_init must be a contiguous [k, n]"
+        if inplace:
+            C = C_init
+        elif isinstance(C_init, DevArray):
+            C = ns.empty(C_init.shape).copy_from_device(C_init)
+        else:
+            C = C_init.clone()
+    else:
+        C = ns.upload(as_f64(C_init))
+    assert C.dim() == 2 and C.shape[1] == n, "C_init must be [k, n]"
+    k = C.shape[0]
+    m = None if mean is None else as_f64(mean).reshape(n)
+    labels = ns.empty((N,), np.int32)
+    inertia = ctypes.c_double(0.0)
+    n_iter = ctypes.c_int(0)
+    ns.sync()
+    ctx.check(ctx.lib.edmdc_kmeans_lloyd_dev(ctx.h, N, n, k, _drows(X), X.stride(0), _hptr(m), _dptr(C), int(max_iter), float(tol_abs),
+                                             labels.data_ptr(), ctypes.byref(inertia), ctypes.byref(n_iter)), "edmdc_kmeans_lloyd_dev")
+    return C, labels, inertia.value, n_iter.value
+
+
 KMEANSPP_MAX_ROWS = 30_000_000      # edmdc_kmeanspp_dev's limit (include/brov2.h)
 
 
@@ -1421,17 +1454,12 @@ def kmeans_centers_dev(X, k, random_state=0, max_iter=300, tol=1e-4, init="hip",
         C = ns.upload(C0)
     else:
         raise ValueError("init must be 'hip' or 'sklearn'")
-    labels = ns.empty((N,), np.int32)
-    inertia = ctypes.c_double(0.0)
-    n_iter = ctypes.c_int(0)
-    ns.sync()
-    ctx.check(ctx.lib.edmdc_kmeans_lloyd_dev(ctx.h, N, n, k, _drows(X), X.stride(0), _hptr(mean_h), _dptr(C), int(max_iter), tol_abs,
-                                             labels.data_ptr(), ctypes.byref(inertia), ctypes.byref(n_iter)), "edmdc_kmeans_lloyd_dev")
+    C, _, inertia, n_iter = kmeans_lloyd_dev(X, C, max_iter=max_iter, tol_abs=tol_abs, mean=mean_h, ctx=ctx, inplace=True)
     if timings is not None and getattr(ctx, "timing", False):
         timings["lloyd_ms"] = ctx.last_kernel_ms()
     # back to the caller's frame: k x n values through the host (IEEE addition either way: the same bits as a device add)
     Cf = ns.upload(ns.download(C) + mean_h)
-    return Cf, inertia.value, n_iter.value
+    return Cf, inertia, n_iter
 
 
 def pinv_apply(X_list, U_list, C, gamma, P, ctx=None):

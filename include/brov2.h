@@ -687,7 +687,9 @@ BROV_API int edmdc_simulate(brov_ctx* ctx, int n, int r, int k, double gamma, co
  * in C_io.  X [N][n] (row stride x_stride doubles), mean [n] = column means to subtract (NULL = none; centres
  * are then in the centred frame), stop when no label changes, when the summed squared centre shift is
  * <= tol_abs, or after max_iter iterations.  labels [N] int32 (host version: optional), inertia = sum of
- * squared distances to the final centres, n_iter = iterations run.
+ * squared distances of the samples to the centres of the returned labels, summed by differences (x - mean - c) in one pass of its own
+ * after the loop: accurate relative to itself also where it is tiny against sum |x|^2 (0 when every sample is its own centre);
+ * n_iter = iterations run.
  * Empty clusters follow scikit-learn 1.7.2 (sklearn/cluster/_k_means_common.pyx): `_relocate_empty_clusters_dense` moves
  * each of them to one of the n_empty samples farthest from their own centre (that sample leaves its cluster's sum), unless
  * all those distances are zero; `_average_centers` then gives a cluster that is still empty the row of the biggest cluster

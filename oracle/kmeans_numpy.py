@@ -261,13 +261,15 @@ def from_limbs(buf, k, n):
     return tot, cnt, int(buf[-2])
 
 
-def lloyd_fixed_point(X, C0, max_iter=300, tol_abs=0.0, allreduce=None, far_rows=far_rows_introselect, shard=None):
+def lloyd_fixed_point(X, C0, max_iter=300, tol_abs=0.0, allreduce=None, far_rows=far_rows_introselect, shard=None, e_step=e_step):
     """The device loop (edmdc_kmeans_lloyd_dev) restated: X = this rank's centred rows, C0 the common initial centres.
     allreduce(int64 array, op) combines a buffer over the ranks in place (op 0: sum, op 1: max) -- None: one rank.
     shard = (global index of this rank's first row, rows over all ranks) for a sharded run.
     Returns (centres, labels, n_iter, relocations).  Empty clusters, sharded: the ranks' distances are put side by side in global row
     order (a sum in which every rank fills its own rows), every rank applies `far_rows` to that array, and the owner of each chosen row
-    sends its label and fixed-point coordinates -- as csrc/capi.hip: kmeans_relocate does."""
+    sends its label and fixed-point coordinates -- as csrc/capi.hip: kmeans_relocate does.
+    e_step(X, C) -> labels: the plain GEMM form above unless given (tests/sweep_kmeans.py passes one that certifies every label in
+    long double, so that the labels -- and with them the centres, bit for bit -- are the device's)."""
     X = np.ascontiguousarray(X, dtype=float)
     N, n = X.shape
     k = len(C0)

@@ -19,7 +19,11 @@ with a ragged one, B = 1 .. 9, T = 1 .. 12, one noise record or one per candidat
 with none, components with r = +inf, process variances of 0, the yaw through pi) and the QP of the Koopman linear MPC (lmpc: Nv on
 both sides of every rows-per-lane step of csrc/koopman_qp.hip and of its LDS / global switch, a non-zero Nv % 8 at every step, H + 1
 on both sides of the 64-lane trips of the epilogue, hold r on both sides of the 64-lane trip of the u_apply loop, short last knots,
-iters 0 .. 40 and a residual stop at two, three and five rows per lane)."""
+iters 0 .. 40 and a residual stop at two, three and five rows per lane).  The k-means families (colstats, kmeanspp, lloyd; the end of
+the file) walk csrc/colstats.hip, the seeding and Lloyd's loop of csrc/kmeans.hip: every operand form (host, device, strided rows, a
+column block of a wider table on and off a 16-byte boundary), data scales 1e-13 .. 1e13, far column means, a constant column, the
+block, chunk and row edges of the seeding, and for the loop every kernel its dispatch rules pick (csrc/capi.hip:
+edmdc_kmeans_lloyd_dev), every stopping rule and every empty-cluster rule."""
 import hashlib
 import json
 
@@ -30,6 +34,7 @@ WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/foss
 N_CASES = 48                                                        # per family: four slices of 12
 N_CASES_EDMDC = 32                                                  # per EDMDc family: four slices of 8 (corner lists of 12 to 24)
 N_CASES_FILTER = 32                                                 # ukf and lmpc: four slices of 8 (corner lists of 17 and 26)
+N_CASES_KMEANS = 32                                                 # colstats, kmeanspp, lloyd: four slices of 8
 SEED = 2024
 
 SETS = dict(
@@ -65,6 +70,17 @@ SETS = dict(
               H=(1, 3, 7, 12, 15, 25, 31, 33, 34, 39, 43, 48, 51, 63, 64, 65, 101, 121, 127, 128, 129), nb=(1, 3, 4, 5, 8, 9),
               iters=(0, 1, 2, 40), traj=(True, False), y=(True, False), shift=(True, False),
               special=(None, "quat_flip", "angle_wrap", "warm")),
+    colstats=dict(N=(1, 2, 63, 64, 65, 255, 256, 257, 1023, 1025, 262401), n=(1, 2, 3, 12, 13, 16),
+                  form=("host", "dev", "dev_stride", "block_odd", "block_even"), scale=(1e-4, 1.0, 50.0, 1e4), order=("walk", "shuffled", "blobs"),
+                  offset=(True, False), const_col=(True, False), null=("none", "mean", "var")),
+    kmeanspp=dict(N=(1, 15, 16, 17, 60, 4095, 4096, 4097, 8191, 8192, 8193, 12289, 70001), k=(1, 2, 3, 7, 8, 9, 20, 60, 64, 512),
+                  trials=("1", "sk", "16"), n=(1, 2, 5, 12, 13, 16), mean=(True, False),
+                  form=("host", "dev", "dev_stride", "block_odd", "block_even"), scale=(1e-4, 1.0, 1e4), order=("walk", "shuffled", "blobs"),
+                  offset=(True, False), const_col=(True, False), first=("0", "N-1"), ind=(True, False)),
+    lloyd=dict(N=(1, 63, 64, 65, 1023, 1024, 1025, 16385, 262143, 262144, 262145, 264193, 1048576), n=(1, 2, 5, 12, 13, 14, 15),
+               k=(1, 2, 63, 64, 65, 128, 256, 512, 513, 600, 1024, 1200), stop=("max_iter", "strict", "shift"),
+               init=("rows", "dup", "far2", "far3", "allzero"), form=("host", "dev", "dev_stride", "block_odd", "block_even"),
+               scale=(1e-13, 1e-4, 1.0, 50.0, 1e4, 1e13), order=("walk", "shuffled", "blobs"), offset=(True, False), const_col=(True, False)),
 )
 
 
@@ -630,24 +646,228 @@ def draw_lmpc(rng):
                  _pick(rng, s["y"]), _pick(rng, s["shift"]), special)
 
 
+
+# ------------------------------------------------------------------------------------------ k-means: column statistics
+# The data recipe of the three k-means families (tests/sweep_kmeans.py: data): a random walk cumsum(N(0, 0.05)) + 0.3 sin(i w_j); order:
+# the walk, shuffled rows (more than KM_GMAX = 8 label groups per wave of the Lloyd filter: full scan) or four blobs; times scale; offset:
+# column means 20 .. 100 scale from 0; const_col: one column constant.  form: "host" a host array (colstats, kmeanspp: a DevArray
+# uploaded from it), "dev" a contiguous torch tensor, "dev_stride" rows n + 1 doubles apart, "block_odd" / "block_even" columns
+# 3 .. / 4 .. of a 40-column tensor (the base 8 bytes off a 16-byte boundary / on one).
+KM_BLOCK_WIDTH, KM_BLOCK_COL = 40, {"block_odd": 3, "block_even": 4}
+CS_SATURATED = 1024 * 256                                           # csrc/colstats.hip: colstats_blocks stays at 1024 blocks of 256 rows beyond
+
+
+def _colstats(rng, N, n, form, scale, order, offset, const_col, null):
+    """null: the output pointer that is NULL ("none": both given), through the C ABI"""
+    return dict(family="colstats", N=N, n=n, form=form, scale=scale, order=order, offset=bool(offset), const_col=bool(const_col), null=null,
+                seed=int(rng.integers(0, 1 << 30)))
+
+
+COLSTATS_CORNERS = (
+    # N     n   form          scale order       offset const_col null
+    (1, 1, "host", 1.0, "walk", False, False, "none"),                         # one row: variance exactly 0
+    (2, 2, "dev", 1e-4, "walk", True, False, "none"),
+    (63, 3, "dev_stride", 50.0, "shuffled", False, True, "none"),
+    (64, 12, "dev_stride", 1.0, "walk", True, False, "mean"),                  # x_stride 13
+    (65, 13, "block_odd", 1e4, "blobs", False, False, "var"),
+    (255, 16, "block_even", 1.0, "walk", True, True, "none"),
+    (256, 12, "block_odd", 1e-4, "shuffled", True, False, "none"),             # one full block
+    (257, 13, "block_even", 50.0, "walk", False, False, "none"),               # two blocks
+    (1023, 2, "host", 1e4, "blobs", True, False, "none"),
+    (1025, 16, "dev", 1.0, "shuffled", False, True, "none"),                   # five blocks, the last with one row
+    # beyond 1024 blocks x 256 rows, a second trip of the first 257 lanes.  Blobs about 0: NumPy's own mean over axis 0 adds the rows one
+    # after the other, and on a walk of this length (column means of ~10) or far from 0 its error exceeds a tenth of the bound (0.22 .. 0.25)
+    (262401, 12, "block_even", 1.0, "blobs", False, False, "none"),
+    (262401, 3, "dev_stride", 50.0, "blobs", False, False, "var"),
+)
+
+
+def draw_colstats(rng):
+    s = SETS["colstats"]
+    N, order, offset = _pick(rng, s["N"]), _pick(rng, s["order"]), _pick(rng, s["offset"])
+    if N > CS_SATURATED:                                              # (see the corner list)
+        order, offset = "blobs", False
+    return _colstats(rng, N, _pick(rng, s["n"]), _pick(rng, s["form"]), _pick(rng, s["scale"]), order, offset, _pick(rng, s["const_col"]),
+                     _pick(rng, s["null"]))
+
+
+# ------------------------------------------------------------------------------------------ k-means: k-means++ seeding
+PP_CHUNK, PP_ROW, PP_SCREEN_FROM, PP_LMAX = 4096, 16, 8, 16             # csrc/kmeans.hip
+PP_WORK = 2.0e8                                                     # (k - 1) trials N n of a case at most: the reference is long double (1 .. 2 s
+                                                                    # at 1e8; the corner list spreads such cases over the four slices)
+
+
+def pp_trials(c):
+    return _sym(c["trials_as"].replace("sk", str(2 + int(np.log(c["k"])))))
+
+
+def _kmeanspp(rng, N, k, trials, n, mean, form, scale, order, offset, const_col, first, ind):
+    """trials: candidates per round: "1", scikit-learn's 2 + int(log k) ("sk") or PP_LMAX; mean: column means given (else NULL: the data
+    are taken as they are, and offset is off); first: first_index as a symbol of N; ind: indices_host given.  The uniforms are the case's
+    own (seeded), not a RandomState's: tests/sweep_kmeans.py feeds the same numbers to scikit-learn."""
+    assert 1 <= k <= N, (N, k)
+    c = dict(family="kmeanspp", N=N, k=k, trials_as=trials, n=n, mean=bool(mean), form=form, scale=scale, order=order,
+             offset=bool(offset and mean), const_col=bool(const_col and n > 1), first=_sym(first, N=N), first_as=first, ind=bool(ind),
+             seed=int(rng.integers(0, 1 << 30)))
+    c["trials"] = pp_trials(c)
+    assert (k - 1) * c["trials"] * N * n <= PP_WORK, c
+    return c
+
+
+KMEANSPP_CORNERS = (
+    # N     k    trials n  mean   form          scale order       offset const_col first  ind
+    (1, 1, "sk", 1, True, "host", 1.0, "walk", False, False, "0", True),
+    (15, 2, "1", 2, False, "dev", 1e-4, "walk", False, False, "N-1", True),            # below one PP_ROW
+    (16, 3, "16", 5, True, "dev_stride", 1e4, "shuffled", True, False, "0", True),     # one row of 16, PP_LMAX candidates
+    (17, 7, "sk", 12, True, "dev_stride", 1.0, "walk", False, False, "N-1", False),    # x_stride 13; no indices
+    # k = N: the last round has one row left.  One candidate per round: with more, two mutually nearest rows are drawn together in some
+    # round of every seed, and their potentials tie in exact arithmetic (tests/stress_parity.py: kmeanspp)
+    (60, 60, "1", 13, True, "block_odd", 1.0, "blobs", False, False, "0", True),
+    (4097, 512, "sk", 5, True, "dev", 1.0, "walk", False, False, "0", True),           # two chunks, the second with one row; 8 trials
+    (4096, 9, "16", 12, True, "block_odd", 1e4, "walk", True, True, "0", True),        # one full chunk; the first screened round
+    (4095, 8, "sk", 16, False, "block_even", 1e-4, "walk", False, False, "N-1", True), # the last round before the screening
+    (8191, 64, "sk", 12, True, "dev", 1.0, "walk", True, False, "0", False),
+    (8192, 9, "sk", 1, False, "host", 1.0, "blobs", False, False, "N-1", True),
+    (12289, 20, "16", 13, True, "block_even", 1e-4, "walk", False, True, "N-1", True), # four chunks, the last with one row
+    (8193, 20, "1", 13, True, "block_even", 1.0, "shuffled", False, False, "N-1", True),
+    (70001, 20, "sk", 12, True, "dev_stride", 1.0, "walk", False, False, "0", True),   # most rows screened out
+    (60, 2, "16", 2, True, "host", 1e4, "walk", True, False, "N-1", True),
+)
+
+
+def draw_kmeanspp(rng):
+    s = SETS["kmeanspp"]
+    while True:
+        N, n, trials = _pick(rng, s["N"]), _pick(rng, s["n"]), _pick(rng, s["trials"])
+        k = _pick(rng, [v for v in s["k"] if v <= N])
+        L = _sym(trials.replace("sk", str(2 + int(np.log(k)))))
+        if (k - 1) * L * N * n <= PP_WORK:                             # a draw beyond the work budget is drawn again
+            break
+    return _kmeanspp(rng, N, k, trials, n, _pick(rng, s["mean"]), _pick(rng, s["form"]), _pick(rng, s["scale"]), _pick(rng, s["order"]),
+                     _pick(rng, s["offset"]), _pick(rng, s["const_col"]), _pick(rng, s["first"]), _pick(rng, s["ind"]))
+
+
+# ------------------------------------------------------------------------------------------ k-means: Lloyd's loop
+KM_SORTED_FROM = 1 << 18                                            # csrc/capi.hip: the loop keeps a sorted sample order from here on
+KM_LDS_BYTES = 150 * 1024                                           # k (n + 1) 8 at most
+KM_ALLZERO = (12, 6)                                                # (N, k) of the integer-point set of init "allzero"
+
+
+def lloyd_paths(c):
+    """what csrc/capi.hip: edmdc_kmeans_lloyd_dev picks for a case at the default variant: (filter, sorting, packed-fp32 kernel,
+    screening inside the LDS / DPP kernel, distance bounds)"""
+    N, n, k = c["N"], c["n"], c["k"]
+    filt = k >= 64
+    lds = n <= 14 and k <= 512                                      # kmeans_lds_form: the kernel that reads through the permutation
+    pk_ok = n in (12, 13) and 64 <= k <= 1024
+    big = not lds and pk_ok
+    sorting = filt and (lds or big) and N >= KM_SORTED_FROM
+    pk = sorting and big
+    pk_lds = sorting and not pk and pk_ok and lds
+    return filt, sorting, pk, pk_lds, pk_lds
+
+
+def _lloyd(rng, N, n, k, stop, max_iter, init, form, scale, order, offset, const_col):
+    """stop: "max_iter" tol_abs = 0 and the loop runs max_iter iterations with labels still moving; "strict" tol_abs = 0 and the labels
+    stop moving before max_iter; "shift" tol_abs = 1e-4 mean(var) (scikit-learn's) and the centre shift falls below it before max_iter.
+    init: "rows" k distinct rows; "dup" rows with centres 1 and k - 1 copies of centre 0 (exact ties, empty clusters: a relocation);
+    "far2" / "far3" rows with two / three centres far from all data; "allzero" the integer-point set whose distances are all zero.
+    From 2^18 rows on the case runs with bounds_rate 1 and `expect` names what kmeans_loop_info must show."""
+    if init == "allzero":
+        N, k, n = KM_ALLZERO[0], KM_ALLZERO[1], max(n, 4)
+    assert 1 <= k <= N and k * (n + 1) * 8 <= KM_LDS_BYTES and n <= 15, (N, n, k)
+    c = dict(family="lloyd", N=N, n=n, k=k, stop=stop, max_iter=max_iter, init=init, form=form, scale=scale, order=order, offset=bool(offset),
+             const_col=bool(const_col and n > 1), seed=int(rng.integers(0, 1 << 30)))
+    _, sorting, _, _, bnd = lloyd_paths(c)
+    c["rate1"] = bool(sorting)
+    c["expect"] = (["resort"] if sorting else []) + (["list"] if bnd else [])
+    return c
+
+
+LLOYD_CORNERS = (
+    # N       n   k     stop        max_iter init     form          scale  order       offset const_col
+    (1, 1, 1, "max_iter", 1, "rows", "host", 1.0, "walk", False, False),
+    (63, 2, 2, "max_iter", 3, "rows", "dev", 1e-4, "walk", True, False),
+    (64, 5, 63, "max_iter", 1, "rows", "dev_stride", 50.0, "shuffled", False, False),          # the last k without the filter
+    (65, 12, 64, "max_iter", 1, "rows", "dev_stride", 1.0, "walk", False, True),               # the first with it; x_stride 13: scalar loads
+    (1023, 13, 65, "max_iter", 3, "rows", "block_odd", 1.0, "walk", True, False),              # two mask words
+    (16385, 13, 65, "shift", 60, "rows", "block_odd", 1.0, "walk", True, False),               # stops on the shift (below ~1e4 rows the labels settle first)
+    (1024, 14, 128, "max_iter", 3, "rows", "block_even", 1e4, "walk", False, False),           # vec loads with a stride other than n
+    (1025, 15, 256, "max_iter", 3, "rows", "block_odd", 1.0, "shuffled", False, False),        # n = 15: beyond the LDS / DPP kernel
+    (1024, 5, 2, "strict", 60, "rows", "dev", 1.0, "blobs", False, False),                     # to strict convergence
+    (12, 5, 1, "strict", 5, "allzero", "host", 1.0, "walk", False, False),                     # _average_centers copies the SUM
+    (1025, 12, 64, "max_iter", 6, "dup", "host", 1.0, "walk", False, False),                   # exact ties; a relocation
+    (16385, 12, 64, "shift", 60, "far2", "dev", 1.0, "walk", True, False),                     # two empties, the library's selection rule
+    (1025, 13, 65, "max_iter", 5, "far3", "block_even", 50.0, "walk", False, False),           # three
+    (16385, 12, 512, "max_iter", 3, "rows", "block_even", 1.0, "walk", True, False),           # one past KM_THREADS KM_EPOCH_PASSES; the last k of the table
+    (16385, 13, 513, "max_iter", 2, "rows", "dev", 50.0, "walk", False, False),                # the first beyond it
+    (16385, 12, 1024, "max_iter", 2, "rows", "dev", 1e-4, "shuffled", False, True),
+    (16385, 15, 1200, "max_iter", 2, "rows", "host", 1.0, "walk", False, False),               # k (n + 1) 8 = 150 KiB exactly
+    # every sample (or all but two) its own centre: an inertia of 0, or tiny against sum |x|^2 -- what the expanded form
+    # |x|^2 - 2 (x.c - |c|^2 / 2) of the E-step kernels cannot give to a relative bound (it returned 8.4e-15 and missed by 2.0e-10 here)
+    (63, 1, 63, "max_iter", 1, "rows", "dev_stride", 50.0, "shuffled", True, False),
+    (65, 1, 63, "max_iter", 1, "rows", "block_even", 50.0, "walk", True, False),
+    # from 2^18 rows on: the sorted order; max_iter is the smallest at which kmeans_loop_info shows what `expect` names, found on an MI355X
+    # with bounds_rate 1: the first re-sort falls into iteration 3 in all eight, the first list-form E-step into iteration 4
+    (262143, 12, 64, "max_iter", 3, "rows", "dev", 1.0, "walk", False, False),                 # the last size in the caller's order
+    (262144, 12, 64, "max_iter", 4, "rows", "dev", 1.0, "walk", False, False),                 # the first sorted one: screening, bounds
+    (262145, 13, 128, "max_iter", 4, "rows", "block_odd", 50.0, "shuffled", False, False),
+    (264193, 12, 256, "max_iter", 4, "rows", "block_even", 1.0, "walk", True, False),          # 2^18 + 2049: a bounds tile of one row
+    (262144, 5, 128, "max_iter", 3, "rows", "host", 1.0, "walk", False, False),                # sorted, no screening, no bounds
+    (262145, 13, 600, "max_iter", 3, "rows", "dev_stride", 1.0, "walk", False, False),         # the packed-fp32 kernel
+    (264193, 13, 512, "max_iter", 4, "rows", "dev", 1e-13, "walk", False, False),              # M^2 below 1e-24: screening off by prm[5]
+    (262144, 12, 512, "max_iter", 4, "rows", "dev", 1e13, "shuffled", False, False),           # M^2 above 1e24
+    (262145, 13, 513, "max_iter", 3, "rows", "block_even", 1.0, "walk", False, True),          # the packed-fp32 kernel at its first k
+    (1048576, 2, 2, "max_iter", 2, "rows", "dev", 1.0, "walk", False, False),                  # member sums beyond 2^64: the high word of km_to_double
+)
+
+LLOYD_DRAW_N = tuple(v for v in SETS["lloyd"]["N"] if v < KM_SORTED_FROM - 1)      # draws stay below the sorted loop: its cases are hand-tuned
+
+
+def draw_lloyd(rng):
+    s = SETS["lloyd"]
+    N, n = _pick(rng, LLOYD_DRAW_N), _pick(rng, s["n"])
+    k = _pick(rng, [v for v in s["k"] if v <= N and v * (n + 1) * 8 <= KM_LDS_BYTES])
+    init = _pick(rng, [v for v in ("rows", "rows", "dup", "far2", "far3") if v == "rows" or (k >= 8 and 1000 <= N <= 1025)])
+    stop = "shift" if (63 <= k <= 128 and N == 16385 and init == "rows" and rng.integers(0, 2)) else "max_iter"
+    max_iter = 60 if stop == "shift" else 1 if (k * 2 > N or k <= 2) else int(_pick(rng, (1, 2, 3, 5)))      # few or single-row clusters settle at once
+    return _lloyd(rng, N, n, k, stop, max_iter, init, _pick(rng, s["form"]), _pick(rng, [v for v in s["scale"] if 1e-12 < v < 1e12]),
+                  _pick(rng, ("walk", "shuffled")), _pick(rng, s["offset"]), _pick(rng, s["const_col"]))
+
+
 # ------------------------------------------------------------------------------------------ the lists
 _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
              mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
              window_pop=(_window_pop, WINDOW_POP_CORNERS, draw_window_pop),
              lift=(_lift, LIFT_CORNERS, draw_lift), gram=(_gram, GRAM_CORNERS, draw_gram),
              pinv_apply=(_pinv_apply, PINV_APPLY_CORNERS, draw_pinv_apply), multistep=(_multistep, MULTISTEP_CORNERS, draw_multistep),
-             simulate=(_simulate, SIMULATE_CORNERS, draw_simulate), ukf=(_ukf, UKF_CORNERS, draw_ukf), lmpc=(_lmpc, LMPC_CORNERS, draw_lmpc))
+             simulate=(_simulate, SIMULATE_CORNERS, draw_simulate), ukf=(_ukf, UKF_CORNERS, draw_ukf), lmpc=(_lmpc, LMPC_CORNERS, draw_lmpc),
+             colstats=(_colstats, COLSTATS_CORNERS, draw_colstats), kmeanspp=(_kmeanspp, KMEANSPP_CORNERS, draw_kmeanspp),
+             lloyd=(_lloyd, LLOYD_CORNERS, draw_lloyd))
 FAMILIES = tuple(_MAKE)                                             # the order is part of the seeds: new families go last
 EDMDC_FAMILIES = ("lift", "gram", "pinv_apply", "multistep", "simulate")
 N_CORNERS = {f: len(_MAKE[f][1]) for f in FAMILIES}                 # 12 for the five older families
 FILTER_FAMILIES = ("ukf", "lmpc")
-N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES_FILTER if f in FILTER_FAMILIES else N_CASES for f in FAMILIES}
+KMEANS_FAMILIES = ("colstats", "kmeanspp", "lloyd")
+N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES_FILTER if f in FILTER_FAMILIES else N_CASES_KMEANS if f in KMEANS_FAMILIES
+              else N_CASES for f in FAMILIES}
+# a case whose reference is not decided (tests/sweep_kmeans.py) gets another data seed here: (family, index in the list) -> seed
+KM_RESEED = {("colstats", 10): 6}        # NumPy's own axis-0 mean at N = 262 401, n = 12: 0.13 .. 0.25 of the bound on six seeds of eight, 0.065 on this one
+
+
+def _reseeded(family, seed, out):
+    """KM_RESEED applied to the first len(out) cases of the list at the pinned SEED (another seed gives another list altogether)"""
+    if seed == SEED:
+        for (f, i), data_seed in KM_RESEED.items():
+            if f == family and i < len(out):
+                out[i] = dict(out[i], seed=data_seed)
+    return out
 
 
 def corners(family, seed=SEED):
     make, rows, _ = _MAKE[family]
     rng = np.random.default_rng([seed, FAMILIES.index(family), 0])
-    return [make(rng, *row) for row in rows]
+    return _reseeded(family, seed, [make(rng, *row) for row in rows])
 
 
 def cases(family, seed=SEED, n=None):
@@ -657,7 +877,7 @@ def cases(family, seed=SEED, n=None):
     rng = np.random.default_rng([seed, FAMILIES.index(family), 1])
     while len(out) < n:
         out.append(_MAKE[family][2](rng))
-    return out
+    return _reseeded(family, seed, out)
 
 
 def rollout_pop(seed=SEED):
@@ -706,3 +926,15 @@ def ukf(seed=SEED):
 
 def lmpc(seed=SEED):
     return cases("lmpc", seed)
+
+
+def colstats(seed=SEED):
+    return cases("colstats", seed)
+
+
+def kmeanspp(seed=SEED):
+    return cases("kmeanspp", seed)
+
+
+def lloyd(seed=SEED):
+    return cases("lloyd", seed)

@@ -17,7 +17,9 @@ errs by at most 513 x 2^-53 = 6e-14 of sum |terms|.  Every assertion message car
 The EDMDc families (lift, gram, pinv_apply, multistep, simulate) have their prepare / run / compare in tests/sweep_edmdc.py, with
 their own measures and bounds (a reference states its own gap condition as ref["gap_bound"]); PREPARE and sweep_one here cover them.
 So do the unscented Kalman filter (ukf) and the QP of the Koopman linear MPC (lmpc) in tests/sweep_ukf_lmpc.py, by the recipe above:
-a lane is a (candidate, recording) filter or a problem."""
+a lane is a (candidate, recording) filter or a problem.  The k-means families (colstats, kmeanspp, lloyd) are in tests/sweep_kmeans.py:
+their references are exact (indices, labels and centres bit for bit), a reference asserts in prepare that every decision it takes
+is certified, no lane is left out, and the fourth figure of sweep_one is the smallest decision gap instead of a reference gap."""
 import numpy as np
 
 import feedback_ref as fr
@@ -25,6 +27,7 @@ import fossen_vehicles as fv
 import koopman_mppi_ref as kr
 import mppi_ref as mr
 import sweep_edmdc as se
+import sweep_kmeans as sk
 import sweep_ukf_lmpc as su
 from oracle import fossen_params as fp
 
@@ -400,7 +403,7 @@ def compare_window_pop(case, ref, got):
 
 
 PREPARE = dict(rollout_pop=prepare_rollout_pop, feedback=prepare_feedback, mppi=prepare_mppi, koopman_mppi=prepare_koopman_mppi,
-               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE)
+               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE, **sk.PREPARE)
 
 
 def sweep_one(eng, ctx, case, ref=None):
@@ -413,6 +416,9 @@ def sweep_one(eng, ctx, case, ref=None):
         e, e2 = se.sweep_one(eng, ctx, case, ref)
     elif fam in su.PREPARE:
         e, e2 = su.sweep_one(eng, ctx, case, ref)
+    elif fam in sk.PREPARE:
+        e, e2 = sk.sweep_one(eng, ctx, case, ref)
+        return e, e2, out, ref["min_gap"]
     elif fam == "rollout_pop":
         e, e2 = compare_rollout_pop(case, ref, run_rollout_pop(eng, ctx, case, ref)), 0.0
     elif fam == "feedback":

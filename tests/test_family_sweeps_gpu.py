@@ -17,13 +17,23 @@ tests/sweep_ukf_lmpc.py: a lane is a (candidate, recording) filter or a problem,
 what the hand-picked shapes of tests/test_ukf_gpu.py and tests/test_koopman_lmpc_gpu.py never execute: the three thruster filters
 without a start lag, full and lone-wave blocks for every instantiation, T = 1, 12 updates per row and none at all; three and four rows
 per lane of the QP, the second and third trip of its epilogue and of its u_apply loop, the scalar tail of the blocked W loop with W
-from global memory, the shift and the residual stop beyond one row per lane."""
+from global memory, the shift and the residual stop beyond one row per lane.
+
+The k-means families (colstats, kmeanspp, lloyd) run 32 cases each in four slices of 8, by tests/sweep_kmeans.py, against exact
+references: column statistics per column against long double (1e-13 of mean |x|, 1e-12 of the variance); the seeding's indices equal
+to a long-double restatement of scikit-learn's `_kmeans_plusplus` whose every round is decided, and to scikit-learn itself, the
+centres X[idx] - mean bit for bit; Lloyd's n_iter, labels and centres (bit for bit) equal to the fixed-point restatement of
+oracle/kmeans_numpy.py with a certified E-step, the inertia at 1e-10 against long double, the relocation count, the same bytes from
+every public variant, both bounds rates and every operand form (host arrays, device rows with strides n, n + 1 and 40, on and off a
+16-byte boundary), and kmeans_loop_info showing that the path a case is tagged for ran.  For these families the fourth figure of
+sweep_one is the smallest decision gap of the reference, not a reference gap."""
 import numpy as np
 import pytest
 
 import mppi_ref as mr
 import sweep_cases as sc
 import sweep_edmdc as se
+import sweep_kmeans as sk
 import sweep_run as sr
 import sweep_ukf_lmpc as su
 
@@ -52,10 +62,14 @@ def ctx():
 def test_sweep(eng, ctx, family, part):
     cases = sc.cases(family)[part::SLICES]
     worst = second = gap = 0.0
-    left = 0
+    left, least = 0, np.inf
     for c in cases:
         e, e2, out, g = sr.sweep_one(eng, ctx, c)
-        worst, second, gap, left = max(worst, e), max(second, e2), max(gap, g), left + out
+        worst, second, gap, left, least = max(worst, e), max(second, e2), max(gap, g), left + out, min(least, g)
+    if family in sc.KMEANS_FAMILIES:
+        print(f"{family} slice {part}: {len(cases)} cases, first figure {worst:.2e}, second {second:.2e} (tests/sweep_kmeans.py: sweep_one), smallest "
+              f"decision gap {least:.2e}" + (" of R^2" if family == "lloyd" else " of its threshold"))
+        return
     if family in sc.EDMDC_FAMILIES:
         print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e}, second figure (tests/sweep_edmdc.py: sweep_one) "
               f"{second:.2e}, worst reference gap {gap:.2e}, lanes left out {left}")
@@ -299,3 +313,53 @@ def test_lmpc_resume_and_shift_beyond_two_rows_per_lane(eng, ctx, nq):
     for key in ("U_nom", "y"):
         assert np.array_equal(moved[key], np.concatenate([plain[key][:, 1:], plain[key][:, -1:]], axis=1)), (key, c)
     assert _lmpc_same(plain, moved, ("u_apply", "pred", "info")), c
+
+
+# ------------------------------------------------------------------------------------------ k-means: the exact identities
+@pytest.fixture(scope="module", autouse=True)
+def _kmeans_contexts():
+    yield
+    sk.close_contexts()
+
+
+def _lloyd_same(a, b):
+    return a["n_iter"] == b["n_iter"] and a["C"].tobytes() == b["C"].tobytes() and a["labels"].tobytes() == b["labels"].tobytes()
+
+
+def test_lloyd_repeats_and_resumes(eng, ctx):
+    """two identical calls give identical bytes; max_iter = a + b equals a run of a followed by a run of b from the returned centres
+    (centres, labels and the total n_iter: the loop carries no state besides the centres), on cases that do not stop early"""
+    cases = sc.cases("lloyd")
+    picked = cases[:IDENTITY_CASES] + [c for c in cases[IDENTITY_CASES:] if c["stop"] == "max_iter" and c["max_iter"] >= 3 and c["init"] == "rows"][:IDENTITY_CASES]
+    resumed = 0
+    for c in picked:
+        ref = sr.PREPARE["lloyd"](c)
+        lc = sk.lloyd_ctx(ctx)
+        whole = sk.lloyd_once(eng, lc, c, ref, c["form"])
+        assert _lloyd_same(whole, sk.lloyd_once(eng, lc, c, ref, c["form"])), ("repeat", c)
+        if c["stop"] == "max_iter" and c["max_iter"] >= 2 and not ref["nreloc"]:
+            for a in range(1, c["max_iter"]):
+                first = sk.lloyd_once(eng, lc, c, ref, c["form"], max_iter=a)
+                second = sk.lloyd_once(eng, lc, c, ref, c["form"], max_iter=c["max_iter"] - a, C0=first["C"])
+                assert first["n_iter"] == a and first["n_iter"] + second["n_iter"] == whole["n_iter"], (a, c)
+                assert second["C"].tobytes() == whole["C"].tobytes() and second["labels"].tobytes() == whole["labels"].tobytes(), ("resumed after", a, c)
+                resumed += 1
+    assert resumed >= 4
+
+
+def test_kmeans_centers_dev_on_a_strided_tensor_is_the_contiguous_call(eng, ctx):
+    """kmeans_centers_dev (column statistics, seeding, Lloyd) on rows n + 1 and 40 doubles apart, on and off a 16-byte boundary,
+    equals the same call on the contiguous copy: centres bit for bit, inertia, n_iter"""
+    done = 0
+    for c in sc.cases("lloyd"):
+        if c["init"] != "rows" or not (64 <= c["N"] <= 16385) or c["k"] > 128 or done == IDENTITY_CASES:
+            continue
+        X = sk.lloyd_inputs(c)[0]
+        want = None
+        for form in ("dev", "dev_stride", "block_odd", "block_even"):
+            C, inertia, n_iter = eng.kmeans_centers_dev(sk.operand(eng, ctx, X, form), c["k"], max_iter=8, ctx=ctx)
+            got = (C.cpu().numpy().tobytes(), inertia, n_iter)
+            want = want or got
+            assert got == want, (form, n_iter, want[2], c)
+        done += 1
+    assert done == IDENTITY_CASES

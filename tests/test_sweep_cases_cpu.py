@@ -1,11 +1,15 @@
-"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the twelve families' value sets occurs in
+"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the fifteen families' value sets occurs in
 the hand-written corner list, by name, so that a list cannot shrink silently; (b) for every case the reference alone meets the
 conditions of tests/sweep_run.py (float64 against long double below a tenth of the bound on the compared lanes, at most 2 % of the
 lanes left out, never all), so that tests/test_family_sweeps_gpu.py can fail only because of a kernel; (c) the lists are a function
 of the seed alone and their hashes are pinned.  The vehicles come from tests/fossen_vehicles.py, which needs the built library.
 The EDMDc families' reference is oracle/edmdc_numpy.py restated with a dtype (tests/sweep_edmdc.py): (d) its float64 form is the
 oracle's bit for bit.  The filter (ukf) and QP (lmpc) families take their references from tests/ukf_ref.py and
-tests/koopman_lmpc_ref.py through tests/sweep_ukf_lmpc.py; with at most 27 lanes a case the 2 % cap means that no lane is left out."""
+tests/koopman_lmpc_ref.py through tests/sweep_ukf_lmpc.py; with at most 27 lanes a case the 2 % cap means that no lane is left out.
+The k-means families (colstats, kmeanspp, lloyd; tests/sweep_kmeans.py) have exact references: (e) preparing one asserts that NumPy's
+own float64 statistics stay within a tenth of the bounds, that no round of the long-double k-means++ is undecided, and that no sample
+of any iteration of the certified Lloyd reference is undecided -- here for every case below 2^18 rows and for two of the larger ones
+(tests/test_family_sweeps_gpu.py prepares the others where it runs them)."""
 import numpy as np
 import pytest
 
@@ -14,8 +18,10 @@ import sweep_cases as sc
 SLICES = 4
 PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52",
               lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921",
-              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88")
-CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12, ukf=17, lmpc=26)
+              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88", colstats="36c523c381e38c6e", kmeanspp="ee864b94e8c1c124", lloyd="fedd81db4999f98f")
+CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12, ukf=17, lmpc=26,
+               colstats=12, kmeanspp=14, lloyd=29)
+LLOYD_LARGE_ON_CPU = 2                    # cases from 2^18 rows on whose reference is prepared here too: the first with bounds, the first without
 
 
 def _value(c, key):
@@ -40,7 +46,7 @@ def _seen(family, key):
 @pytest.mark.parametrize("family", sc.FAMILIES)
 def test_every_value_is_in_the_corner_list(family):
     assert len(sc.corners(family)) == CORNERS[family] == sc.N_CORNERS[family], (family, len(sc.corners(family)))
-    assert len(sc.cases(family)) == (32 if family in sc.EDMDC_FAMILIES + sc.FILTER_FAMILIES else sc.N_CASES) == sc.N_CASES_OF[family]
+    assert len(sc.cases(family)) == (32 if family in sc.EDMDC_FAMILIES + sc.FILTER_FAMILIES + sc.KMEANS_FAMILIES else sc.N_CASES) == sc.N_CASES_OF[family]
     for key, values in sc.SETS[family].items():
         missing = set(values) - _seen(family, key)
         assert not missing, (family, key, "not in the corner list", missing)
@@ -50,6 +56,8 @@ def test_every_value_is_in_the_corner_list(family):
                 assert (len(c["lens"]) in sc.SETS[family]["nbags"] and c["nwin"] <= 5 * 65) if c["bags"] else c["nwin"] in sc.SETS[family]["nwin"], c
             elif family == "lmpc" and key == "H":                      # a draw's H: anywhere in the last knot, up to the third epilogue trip
                 assert (c["M"] - 1) * c["hold"] < c["H"] <= min(c["M"] * c["hold"], sc.LMPC_H_MAX), c
+            elif family == "lloyd" and c["init"] == "allzero" and key in ("N", "k"):      # the integer-point set has its own size
+                assert (c["N"], c["k"]) == sc.KM_ALLZERO, c
             elif not (family == "mppi" and key == "nparams"):
                 assert _value(c, key) in values, (family, key, c)
 
@@ -182,12 +190,65 @@ def test_edmdc_corner_pairs():
     assert any(c["r"] == 0 and c["nb"] > 256 for c in s) and any(c["r"] > 0 and c["nb"] > 256 and c["T"] == 50 for c in s) and _has("simulate", T=0)
 
 
+def test_kmeans_corner_pairs():
+    """the edges the colstats, kmeanspp and lloyd corner lists must contain, by name"""
+    cs = sc.corners("colstats")
+    assert sum(c["N"] > sc.CS_SATURATED for c in cs) >= 1 and _has("colstats", N=256) and _has("colstats", N=257) and _has("colstats", N=1, n=1)
+    assert {c["null"] for c in cs} == {"none", "mean", "var"} and _has("colstats", form="dev_stride", n=12), "x_stride 13"
+    for form in ("block_odd", "block_even"):
+        assert any(c["form"] == form and c["n"] % 2 == 0 for c in cs) and any(c["form"] == form and c["n"] % 2 for c in cs), form
+    assert any(c["const_col"] and c["offset"] for c in cs) and any(c["offset"] and c["scale"] == 1e-4 for c in cs) and _has("colstats", scale=1e4)
+    pp = sc.corners("kmeanspp")
+    assert _has("kmeanspp", N=60, k=60) and _has("kmeanspp", N=1, k=1) and any(c["N"] > 60000 and c["k"] > sc.PP_SCREEN_FROM for c in pp)
+    assert {c["N"] - sc.PP_CHUNK for c in pp} >= {-1, 0, 1} and {c["N"] - 2 * sc.PP_CHUNK for c in pp} >= {-1, 0, 1} and {c["N"] - sc.PP_ROW for c in pp} >= {-1, 0, 1}
+    assert {c["k"] for c in pp} >= {sc.PP_SCREEN_FROM, sc.PP_SCREEN_FROM + 1} and {c["trials"] for c in pp} >= {1, sc.PP_LMAX}
+    assert any(c["trials_as"] == "sk" and c["trials"] == 8 for c in pp), "k = 512: eight trials"
+    assert any(not c["mean"] for c in pp) and any(not c["ind"] for c in pp) and {c["first_as"] for c in pp} == {"0", "N-1"}
+    assert all(c["trials"] == sc.pp_trials(c) and 1 <= c["k"] <= c["N"] and 0 <= c["first"] < c["N"] and (c["mean"] or not c["offset"])
+               and (c["k"] - 1) * c["trials"] * c["N"] * c["n"] <= sc.PP_WORK for c in sc.cases("kmeanspp"))
+    ll = sc.corners("lloyd")
+    large = [c for c in ll if c["N"] >= sc.KM_SORTED_FROM and c["k"] >= 64]
+    assert len(large) >= 8 and all(c["rate1"] and "resort" in c["expect"] for c in large) and all(not c["expect"] and not c["rate1"] for c in ll if c not in large)
+    paths = {(c["n"], sc.lloyd_paths(c)[2:]) for c in large}      # (n, (packed-fp32 kernel, screening, bounds))
+    assert paths >= {(12, (False, True, True)), (13, (False, True, True)), (5, (False, False, False)), (13, (True, False, False))}, paths
+    assert any(c["k"] == 600 and sc.lloyd_paths(c)[2] for c in large) and any(c["k"] == 513 and sc.lloyd_paths(c)[2] for c in large)
+    assert all(("list" in c["expect"]) == sc.lloyd_paths(c)[4] for c in sc.cases("lloyd"))
+    assert {c["scale"] for c in large if "list" in c["expect"]} >= {1e-13, 1e13}, "M^2 outside 1e-24 .. 1e24 in the screened loop"
+    assert {c["N"] for c in large} >= {1 << 18, (1 << 18) + 1, (1 << 18) + 2049} and _has("lloyd", N=(1 << 18) - 1)
+    assert {c["stop"] for c in ll} == {"max_iter", "strict", "shift"} and _has("lloyd", stop="strict", order="blobs")
+    assert {c["init"] for c in ll} == {"rows", "dup", "far2", "far3", "allzero"}
+    assert _has("lloyd", k=63) and _has("lloyd", k=64) and _has("lloyd", k=65) and _has("lloyd", k=512) and _has("lloyd", k=513)
+    assert any(c["n"] == 15 and c["k"] * 16 * 8 == sc.KM_LDS_BYTES for c in ll), "the LDS limit met from below at n = 15"
+    assert any(c["k"] == c["N"] > 1 and c["offset"] for c in ll) and _has("lloyd", N=65, k=63, n=1, offset=True), "an inertia of 0, and one tiny against sum |x|^2"
+    assert sc.corners("colstats") == sc.cases("colstats")[:len(sc.corners("colstats"))], "a reseeded corner is the same case in both lists"
+    assert _has("lloyd", form="dev_stride", n=12) and any(c["form"] == "block_even" and c["n"] % 2 == 0 for c in ll) and any(c["form"] == "block_odd" for c in ll)
+    assert any(c["const_col"] for c in ll) and any(c["offset"] for c in ll)
+    for c in sc.cases("lloyd"):
+        assert 1 <= c["k"] <= c["N"] and c["k"] * (c["n"] + 1) * 8 <= sc.KM_LDS_BYTES and c["n"] <= 15, c
+    import sweep_kmeans as sk
+    from oracle import kmeans_numpy as kn
+    wide = [c for c in ll if c["N"] == 1 << 20][0]                   # a member sum beyond 2^64: the high word of kmeans.hip: km_to_double
+    ref = sk.prepare_lloyd(wide)
+    Xc = ref["X"] - ref["mean"]
+    tot = kn._int_sums(np.rint(Xc * kn.fix_scales(np.abs(Xc).max(axis=0))[0]).astype(np.int64), ref["labels"], wide["k"])
+    assert max(abs(v) for row in tot for v in row) > 1 << 64, wide
+    for f in sc.KMEANS_FAMILIES:                                     # the slices share the expensive cases evenly
+        for part in range(SLICES):
+            heavy = [c for c in sc.cases(f)[part::SLICES] if c["N"] >= sc.KM_SORTED_FROM]
+            assert len(heavy) <= 3, (f, part, len(heavy))
+
+
 # ------------------------------------------------------------------------------------------ (b) well-posedness
 @pytest.mark.parametrize("part", range(SLICES))
 @pytest.mark.parametrize("family", sc.FAMILIES)
 def test_reference_alone_meets_the_conditions(family, part):
     import sweep_run as sr
     cases = sc.cases(family)[part::SLICES]
+    if family == "lloyd":                                            # (e): the large references belong to the GPU test, but for two of them
+        large = [c for c in sc.cases(family) if c["rate1"]]
+        here = [[c for c in large if ("list" in c["expect"]) == want][0] for want in (True, False)]
+        assert len(here) == LLOYD_LARGE_ON_CPU
+        cases = [c for c in cases if not c["rate1"] or c in here]
     lanes = left = 0
     gap = 0.0
     for c in cases:
