@@ -61,9 +61,24 @@ struct UkfArgs {
     double dt;
     const double *x0, *P0, *U, *Y;
     double *lag, *xf, *pstd, *innov, *xT, *PT, *info;
+    // the tape variant (tape != nullptr) alone reads these: tape [P][B][T][UKF_TAPE], nrows [P][B], and Bs, the number of recordings
+    // that the per-candidate outputs and lag are laid out for (>= B: the B recordings of this launch are a chunk of Bs, and the
+    // input and output pointers already point at the chunk's first recording)
+    double *tape, *nrows;
+    int64_t Bs;
 };
-int ukf_waves_per_block();      // recordings per block of the filter kernel
+constexpr int UKF_TAPE = 312;   // doubles of one tape record: Pf [78] | xp [12] | Pp [78] | C [12][12]  (include/brov2.h)
+int ukf_waves_per_block();      // recordings per block of the filter kernel and of the backward kernel
 hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a);
+// Backward (Rauch-Tung-Striebel) pass over a tape (ukf.hip; include/brov2.h: brov_ukf_rts_dev holds the law).  tape [P][B][T][UKF_TAPE]
+// and nrows [P][B] are a chunk's own; xf, the terminal pair and every output are laid out for Bs recordings per candidate and point
+// at the chunk's first recording.  xsT / PsT both nullptr or both set; every output may be nullptr.
+struct UkfRtsArgs {
+    int64_t B, T, Bs;
+    const double *xf, *tape, *nrows, *xsT, *PsT;
+    double *xs, *pstd, *Ps, *Ps0, *sinfo;
+};
+hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a);
 // One MPPI update for B problems (mppi.hip; include/brov2.h: brov_mppi_step holds the law).  MppiRec is struct brov_mppi byte for
 // byte; rec is ONE device record.  fp holds one parameter set (per_problem = 0) or B.  x [B][nx], lag [B][24] or nullptr (zero), ref
 // [B][ref_total][nx], eps [B][K][M][nu] or nullptr (the seeded stream), U_nom [B][M][nu] in / out, M = ceil(H / hold).  cost [B][K]

@@ -35,6 +35,10 @@ struct brov_ctx {
     // grow-only scratch arena (device)
     char* scratch = nullptr;
     size_t scratch_cap = 0;
+    // the smoother's tape (brov_ukf_smooth): a chunk of recordings at a time, with the chunk's nrows behind it; kept between calls unless
+    // the next one needs more or less than half of it
+    char* ukf_tape = nullptr;
+    size_t ukf_tape_cap = 0;
     // derived-parameter cache (per dt)
     bool dp_valid = false;
     double dp_dt = 0.0;
@@ -182,7 +186,7 @@ struct Arena {
     size_t off = 0, limit = ~(size_t)0;     // limit: what lay() reserved
     bool bind = true, fits = true, listed = true;
     struct Copy { void* dev; void* host; size_t bytes; bool up, down; };
-    static constexpr int MAX_COPIES = 12;    // staged buffers of one call (edmdc_mppi_step has eleven)
+    static constexpr int MAX_COPIES = 16;    // staged buffers of one call (brov_ukf_smooth has sixteen)
     Copy copies[MAX_COPIES];
     int ncopies = 0;
     explicit Arena(brov_ctx* ctx, bool staged_ = false) : c(ctx), staged(staged_) {}
@@ -586,6 +590,7 @@ void brov_destroy(brov_ctx* c) {
     (void)hipStreamSynchronize(c->stream);
     pool_release(c);
     if (c->scratch) (void)hipFree(c->scratch);
+    if (c->ukf_tape) (void)hipFree(c->ukf_tape);
     for (int m = 0; m < 3; ++m) if (c->d_tasks[m]) (void)hipFree(c->d_tasks[m]);
     if (c->d_fp) (void)hipFree(c->d_fp);
     if (c->d_fp_di) (void)hipFree(c->d_fp_di);
@@ -1670,22 +1675,44 @@ int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64
 static_assert(sizeof(brov_ukf) == 27 * 8 && sizeof(UkfRec) == 28 * 8, "brov_ukf: 27 doubles; UkfRec: the variances and three derived weights");
 // Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
 // and of the derived records, one launch.  host: the arrays are the caller's host memory.
-static int ukf_filter(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
-                      const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
-                      const double* Y, double* lag_io, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
+//
+// One body serves the filter, the tape filter and the smoother.  tape / nrows: the caller's device buffers (brov_ukf_filter_tape_dev),
+// both or neither.  sm: the smoother's outputs (brov_ukf_smooth[_dev]); then the tape is the ctx's own buffer of at most tape_bytes,
+// filled and read back a chunk of recordings at a time: one filter launch and one backward launch per chunk, the chunk's pointers
+// moved to its first recording and the outputs laid out for all B (UkfArgs::Bs).  A problem never looks at another, so the chunking
+// changes no bit.
+struct UkfSmoothOut { double *xs, *pstd_s, *Ps, *Ps0, *sinfo; };
+static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int integ, int lag_mode, int64_t P, const brov_params* params,
+                      int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
+                      const double* Y, double* lag_io, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
+                      double* tape = nullptr, double* nrows = nullptr, const UkfSmoothOut* sm = nullptr, int64_t tape_bytes = 0) {
     bool empty;
-    int rc = pop_call_ok(c, "brov_ukf_filter", model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
+    int rc = pop_call_ok(c, who_, model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
     if (rc) return rc;
+    const std::string fn = who_;
+    if ((tape == nullptr) != (nrows == nullptr)) return fail(c, BROV_ERR_ARG, fn + ": d_tape and d_nrows go together (both or neither)");
+    if (sm && tape_bytes < 0) return fail(c, BROV_ERR_ARG, fn + ": tape_bytes must be >= 0 (0: the default of 2 GiB)");
     if (model != BROV_THRUSTER_EULER && model != BROV_WRENCH_EULER)
-        return fail(c, BROV_ERR_ARG, "brov_ukf_filter: the 12-state Euler models only (BROV_THRUSTER_EULER, BROV_WRENCH_EULER)");
+        return fail(c, BROV_ERR_ARG, fn + ": the 12-state Euler models only (BROV_THRUSTER_EULER, BROV_WRENCH_EULER)");
     if (empty) return BROV_OK;
-    if (T < 1) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: T must be >= 1");
-    if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: NULL input");
-    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, "brov_ukf_filter: nrec must be 1 or P");
+    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
+    if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
+    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    int64_t chunk = B;                           // recordings per launch
+    if (sm) {
+        const int W = ukf_waves_per_block();
+        const double per_rec = (double)P * (double)T * UKF_TAPE * 8.0;           // tape bytes of one recording
+        const double budget = tape_bytes ? (double)tape_bytes : 2147483648.0;
+        if (budget < per_rec * W)
+            return fail(c, BROV_ERR_ARG, fn + ": tape_bytes is smaller than one block of recordings (P * " + std::to_string(W) + " * T * " +
+                                             std::to_string(UKF_TAPE * 8) + " bytes)");
+        const double fit = std::floor(budget / per_rec);
+        if (fit < (double)B) chunk = (int64_t)fit / W * W;
+    }
     std::vector<UkfRec> rec((size_t)nrec);
     for (int64_t k = 0; k < nrec; ++k) {
         const brov_ukf& u = ukf[k];
-        const std::string who = "brov_ukf_filter: ukf[" + std::to_string(k) + "]: ";
+        const std::string who = fn + ": ukf[" + std::to_string(k) + "]: ";
         if (!std::isfinite(u.alpha) || !(u.alpha > 0.0)) return fail(c, BROV_ERR_ARG, who + "alpha must be finite and > 0");
         const double n = 12.0, lambda = u.alpha * u.alpha * (n + u.kappa) - n, nl = n + lambda;
         if (!(nl > 0.0) || !std::isfinite(nl) || !std::isfinite(u.beta))
@@ -1712,16 +1739,29 @@ static int ukf_filter(brov_ctx* c, bool host, int model, int integ, int lag_mode
     UkfArgs args{};
     args.rec_per_candidate = nrec > 1;
     args.B = B; args.T = T; args.dt = dt;
+    args.Bs = B;
+    args.tape = tape;
+    args.nrows = nrows;
+    UkfRtsArgs back{};
+    back.B = B; back.T = T; back.Bs = B;
     FastParams* d_fp;
     UkfRec* d_rec;
     Arena a(c, host);
-    rc = a.lay("brov_ukf_filter", [&] {
+    rc = a.lay(who_, [&] {
         args.x0 = a.in(x0, nin * 12);
         args.P0 = a.in(P0, nin * 144);
         args.U = a.in(U, nin * T * nu);
         args.Y = a.in(Y, nin * T * 12);
         args.lag = lag ? a.inout(lag_io, nout * 24) : nullptr;
         args.xf = xf ? a.out(xf, nout * T * 12) : nullptr;
+        if (sm) {
+            if (!xf) args.xf = a.take<double>(nout * T * 12);        // the backward pass reads xf: scratch when the caller has none
+            back.xs = sm->xs ? a.out(sm->xs, nout * T * 12) : nullptr;
+            back.pstd = sm->pstd_s ? a.out(sm->pstd_s, nout * T * 12) : nullptr;
+            back.Ps = sm->Ps ? a.out(sm->Ps, nout * T * 144) : nullptr;
+            back.Ps0 = sm->Ps0 ? a.out(sm->Ps0, nout * 144) : nullptr;
+            back.sinfo = sm->sinfo ? a.out(sm->sinfo, nout * 2) : nullptr;
+        }
         args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
         args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
         args.xT = xT ? a.out(xT, nout * 12) : nullptr;
@@ -1731,6 +1771,21 @@ static int ukf_filter(brov_ctx* c, bool host, int model, int integ, int lag_mode
         d_rec = a.take<UkfRec>(nrec);
     });
     if (rc) return rc;
+    if (sm) {
+        // The ctx's tape: `chunk` recordings, then their nrows.  Nothing can refuse the call any more.  The buffer is kept for the next
+        // call unless that one needs more, or less than half of it: a ctx does not sit on a large tape after one large call.
+        const size_t tape_part = Arena::al((size_t)P * chunk * T * UKF_TAPE * 8), need = tape_part + Arena::al((size_t)P * chunk * 8);
+        if (need > c->ukf_tape_cap || need < c->ukf_tape_cap / 2) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            if (c->ukf_tape) (void)hipFree(c->ukf_tape);
+            c->ukf_tape = nullptr;
+            c->ukf_tape_cap = 0;
+            HIPCK(c, hipMalloc((void**)&c->ukf_tape, need));
+            c->ukf_tape_cap = need;
+        }
+        args.tape = reinterpret_cast<double*>(c->ukf_tape);
+        args.nrows = reinterpret_cast<double*>(c->ukf_tape + tape_part);
+    }
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
     HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
     HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
@@ -1738,23 +1793,87 @@ static int ukf_filter(brov_ctx* c, bool host, int model, int integ, int lag_mode
     args.rec = d_rec;
     {
         CallTimer t(c);
-        HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, args));
+        if (!sm) HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, args));
+        for (int64_t b0 = 0; sm && b0 < B; b0 += chunk) {
+            auto at = [b0](auto* p, int64_t per) { return p ? p + b0 * per : p; };
+            UkfArgs f = args;
+            f.B = std::min(chunk, B - b0);
+            f.x0 = at(args.x0, 12); f.P0 = at(args.P0, 144); f.U = at(args.U, T * nu); f.Y = at(args.Y, T * 12);
+            f.lag = at(args.lag, 24); f.xf = at(args.xf, T * 12); f.pstd = at(args.pstd, T * 12); f.innov = at(args.innov, T * 12);
+            f.xT = at(args.xT, 12); f.PT = at(args.PT, 144); f.info = at(args.info, 4);
+            HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, f));
+            UkfRtsArgs r = back;
+            r.B = f.B;
+            r.xf = f.xf; r.tape = f.tape; r.nrows = f.nrows;
+            r.xs = at(back.xs, T * 12); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
+            r.sinfo = at(back.sinfo, 2);
+            HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
+        }
     }
     return a.finish();
+}
+
+// The backward pass alone, over a tape that brov_ukf_filter_tape_dev wrote (or that the caller edited: it is a plain array)
+int brov_ukf_rts_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                     const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo) {
+    if (!c) return BROV_ERR_ARG;
+    if (P < 0 || B < 0 || T < 0) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: negative size");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: P must be <= 65535");
+    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: B must be <= 2^31");
+    if (P == 0 || B == 0) return BROV_OK;
+    if (T < 1) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: T must be >= 1");
+    if (!d_xf || !d_tape || !d_nrows) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: NULL input");
+    if ((d_xs_T == nullptr) != (d_Ps_T == nullptr))
+        return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: the terminal pair d_xs_T, d_Ps_T goes together (both or neither)");
+    DeviceGuard g(c);
+    UkfRtsArgs r{};
+    r.B = B; r.T = T; r.Bs = B;
+    r.xf = d_xf; r.tape = d_tape; r.nrows = d_nrows; r.xsT = d_xs_T; r.PsT = d_Ps_T;
+    r.xs = d_xs; r.pstd = d_pstd_s; r.Ps = d_Ps; r.Ps0 = d_Ps0; r.sinfo = d_sinfo;
+    CallTimer t(c);
+    HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
+    return BROV_OK;
+}
+
+int brov_ukf_filter_tape_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
+                             const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U,
+                             const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
+                             double* d_info, double* d_tape, double* d_nrows) {
+    return ukf_filter(c, false, "brov_ukf_filter_tape_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
+                      d_xf, d_pstd, d_innov, d_xT, d_PT, d_info, d_tape, d_nrows);
+}
+
+int brov_ukf_smooth_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
+                        int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U, const double* d_Y,
+                        double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT, double* d_info,
+                        double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo, int64_t tape_bytes) {
+    const UkfSmoothOut sm{d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo};
+    return ukf_filter(c, false, "brov_ukf_smooth_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf,
+                      d_pstd, d_innov, d_xT, d_PT, d_info, nullptr, nullptr, &sm, tape_bytes);
+}
+
+int brov_ukf_smooth(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
+                    int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
+                    double* xf, double* pstd, double* innov, double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps,
+                    double* Ps0, double* sinfo, int64_t tape_bytes) {
+    const UkfSmoothOut sm{xs, pstd_s, Ps, Ps0, sinfo};
+    return ukf_filter(c, true, "brov_ukf_smooth", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT,
+                      PT, info, nullptr, nullptr, &sm, tape_bytes);
 }
 
 int brov_ukf_filter_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
                         const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U,
                         const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
                         double* d_info) {
-    return ukf_filter(c, false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf, d_pstd, d_innov,
+    // (its refusals have always named brov_ukf_filter)
+    return ukf_filter(c, false, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf, d_pstd, d_innov,
                       d_xT, d_PT, d_info);
 }
 
 int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
                     int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
                     double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
-    return ukf_filter(c, true, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
+    return ukf_filter(c, true, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
 }
 
 // ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------

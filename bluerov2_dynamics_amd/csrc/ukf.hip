@@ -1,5 +1,6 @@
 // ukf.hip -- unscented Kalman filter on the Fossen model: candidate j filters B noisy recordings of T rows under params[j]
-// (include/brov2.h: brov_ukf_filter, which is the specification of the law).
+// (include/brov2.h: brov_ukf_filter, which is the specification of the law), and the unscented Rauch-Tung-Striebel smoother over it:
+// the filter's tape variant and the backward kernel ukf_rts_kernel (further down; brov_ukf_filter_tape_dev, brov_ukf_rts_dev).
 //
 // One wave per (candidate, recording): candidate = blockIdx.y with the vehicle constants through as_constant(fp + blockIdx.y) as in
 // rollout_feedback_kernel, UKF_WAVES recordings per block, the time loop inside the kernel.  The wave's (x, P), the Cholesky factor,
@@ -64,7 +65,9 @@ __device__ __forceinline__ void ukf_entry(int e, int& a, int& b) {
     b = e - a * (a + 1) / 2;
 }
 
-template <int MODEL, int INTEG, int LAGMODE, bool TRACK>
+// TAPE: step t also records what the backward pass (ukf_rts_kernel below) needs for the transition t -> t + 1.  Every tape store sits
+// behind `if constexpr (TAPE)`; the TAPE = false instantiations are the code they were before the tape existed.
+template <int MODEL, int INTEG, int LAGMODE, bool TRACK, bool TAPE>
 __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArgs a) {
     constexpr int NU = Dims<MODEL>::NU;
     static_assert(Dims<MODEL>::NX == 12, "the filter's state is the 12-state Euler model");
@@ -77,7 +80,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
     const int64_t b = (int64_t)blockIdx.x * UKF_WAVES + wave;
     if (b >= B) return;                                       // a whole wave: no workgroup barrier follows
     UkfLds& S = lds[wave];
-    const int64_t row = (int64_t)blockIdx.y * B + b;          // recording b of candidate blockIdx.y in the outputs
+    int64_t row = (int64_t)blockIdx.y * B + b;                // recording b of candidate blockIdx.y in the outputs
+    double* tp = nullptr;                                     // this problem's tape records
+    if constexpr (TAPE) {
+        tp = a.tape + row * T * UKF_TAPE;
+        row = (int64_t)blockIdx.y * a.Bs + b;                 // the outputs of a chunk lie among those of Bs recordings
+    }
     const CFP p = as_constant(a.fp + blockIdx.y);
     const CUK f = as_constant_uk(a.rec + (a.rec_per_candidate ? blockIdx.y : 0));
     HotConsts h;
@@ -150,6 +158,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
             ukf_wave_sync();                                           // P written
         }
         if (bad) { failed = t; nan_from = t; break; }
+        if constexpr (TAPE) {                                          // Pf_t: the entries this lane holds, 8-byte stores side by side
+            tp[t * UKF_TAPE + lane] = p0;
+            if (two) tp[t * UKF_TAPE + 64 + lane] = p1;
+        }
         if (lane < 12) {
             if (xfp) xfp[t * 12] = S.x[lane];
             if (psp) psp[t * 12] = sqrt(S.P[lane][lane]);
@@ -210,6 +222,9 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         const bool allfinite = __ballot(!finite) == 0;
         ukf_wave_sync();                                               // m, x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
+        if constexpr (TAPE) {
+            if (lane < 12) tp[t * UKF_TAPE + 78 + lane] = S.x[lane];  // xp_{t+1}
+        }
         {
             const double wc0 = f->wc0;
             const double ma = S.m[a0], mb = S.m[b0];
@@ -231,6 +246,23 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
                 S.P[b1][a1] = p1;
             }
         }
+        if constexpr (TAPE) {
+            tp[t * UKF_TAPE + 90 + lane] = p0;                         // Pp_{t+1}
+            if (two) tp[t * UKF_TAPE + 154 + lane] = p1;
+            // C_{t+1}[ca][cb] = sum_j L[ca][j] (c W_i (d_{j+1} - d_{j+13})[cb]): L and D are still in the image
+            const double g = cw * wi;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int e = lane + 64 * k;
+                if (e < 144) {
+                    const int ca = e / 12, cb = e % 12;
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) acc = fma(S.L[ca][j], g * (S.D[j + 1][cb] - S.D[j + 13][cb]), acc);
+                    tp[t * UKF_TAPE + 168 + e] = acc;
+                }
+            }
+        }
         ukf_wave_sync();                                               // P written
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
@@ -241,6 +273,13 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
             if (psp) psp[s * 12] = NaN;
             if (inp) inp[s * 12] = NaN;
         }
+    }
+    if constexpr (TAPE) {
+        // of a transition that did not complete xp, Pp and C are NaN; Pf_t stays when the update of row t was complete
+        if (!ok) {
+            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE + 78 : failed * UKF_TAPE) + lane; i < T * UKF_TAPE; i += 64) tp[i] = NaN;
+        }
+        if (lane == 0) a.nrows[(int64_t)blockIdx.y * B + b] = (double)nan_from;
     }
     if (a.xT && lane < 12) a.xT[row * 12 + lane] = ok ? S.x[lane] : NaN;
     if (a.PT) {
@@ -256,29 +295,253 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
 }
 
 // ---------------------------------------------------------------------------------------
+// Backward (Rauch-Tung-Striebel) pass over the tape (include/brov2.h: brov_ukf_rts_dev holds the law).  The filter's decomposition:
+// one wave per (candidate, recording), UKF_WAVES per block, the time loop -- downwards -- inside, the wave's image in LDS with the
+// stride-13 rows, ukf_wave_sync between phases and no workgroup barrier at all, so a ragged block or a problem without rows leaves.
+// A transition t -> t + 1 (tape record t, row xf_t) takes
+//   deposit   the record, fetched one transition ahead into 5 registers per lane (lane l holds doubles l, l + 64, ..: coalesced
+//             loads, and Pf's entries land on the lanes that own them), goes to the image; the fetch of record t - 1 and of
+//             xf_{t-1} is issued right after, so that its latency lies behind the work below;
+//   Cholesky  of Pp, the filter's: one lane per row, the same pivot rule;
+//   gain      lane a solves row a of G L L^T = C: forward through L, backward through L^T, L read wave-uniformly from the image;
+//   M, dx     M = Ps_{t+1} - Pp by the lanes that own the entries (Ps stays in their registers over the pass), dx = xs_{t+1} - xp;
+//   xs, G M   lane a: xs_t[a] = xf_t[a] + G[a][:] dx; the 144 entries of G M, one per lane and turn;
+//   Ps        Ps_t[a][b] = Pf_t[a][b] + (G M)[a][:] G[b][:] by the owner of (a, b), written to both triangles of the image.
+// Per row and problem 2.5 KB of tape come in (what the tape filter wrote), and 1.3 KB go out when Ps is asked for.
+struct UkfRtsLds {
+    double rec[UKF_TAPE];               // the tape record of the transition
+    double L[12][UKF_LD];               // Cholesky factor of Pp
+    double G[12][UKF_LD];               // the smoother gain
+    double M[12][UKF_LD];               // Ps_{t+1} - Pp_{t+1}, both triangles
+    double GM[12][UKF_LD];
+    double P[12][UKF_LD];               // Ps of the row last finished, both triangles
+    double dx[12];
+};
+
+__global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArgs a) {
+    __shared__ UkfRtsLds lds[UKF_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t B = a.B, T = a.T;
+    const int64_t b = (int64_t)blockIdx.x * UKF_WAVES + wave;
+    if (b >= B) return;                                       // a whole wave: there is no workgroup barrier
+    UkfRtsLds& S = lds[wave];
+    const int64_t loc = (int64_t)blockIdx.y * B + b;          // in the tape and nrows
+    const int64_t row = (int64_t)blockIdx.y * a.Bs + b;       // in xf, the terminal pair and the outputs
+    const double NaN = __builtin_nan(""), INF = __builtin_inf();
+    int a0, b0, a1, b1;
+    ukf_entry(lane, a0, b0);
+    const bool two = lane + 64 < 78;
+    ukf_entry(two ? lane + 64 : lane, a1, b1);
+    const int lr = lane < 12 ? lane : 11;
+    const double nd = ukf_uniform(a.nrows[loc]);
+    const int64_t n = nd >= 1.0 ? (nd < (double)T ? (int64_t)nd : T) : 0;
+    const double* tp = a.tape + loc * T * UKF_TAPE;
+    const double* xfp = a.xf + row * T * 12 + lr;
+    double* xsp = a.xs ? a.xs + row * T * 12 : nullptr;
+    double* psp = a.pstd ? a.pstd + row * T * 12 : nullptr;
+    double* Psp = a.Ps ? a.Ps + row * T * 144 : nullptr;
+    // row s of the outputs: NaN, or (xsv, the image's P)
+    auto put_nan = [&](int64_t s) {
+        if (lane < 12) {
+            if (xsp) xsp[s * 12 + lane] = NaN;
+            if (psp) psp[s * 12 + lane] = NaN;
+        }
+        if (Psp) {
+            for (int e = lane; e < 144; e += 64) Psp[s * 144 + e] = NaN;
+        }
+    };
+    for (int64_t s = n; s < T; ++s) put_nan(s);
+    if (n == 0) {
+        if (a.Ps0) {
+            for (int e = lane; e < 144; e += 64) a.Ps0[row * 144 + e] = NaN;
+        }
+        if (a.sinfo && lane == 0) {
+            const double v[2] = {NaN, NaN};
+            store_row<2>(a.sinfo + row * 2, v);
+        }
+        return;
+    }
+    // ---- start: the terminal pair of a later span, or the filter's last row ------------------------------------------------------
+    const bool terminal = a.xsT != nullptr && n == T;
+    double xsv, ps0, ps1;
+    if (terminal) {
+        xsv = a.xsT[row * 12 + lr];
+        ps0 = a.PsT[row * 144 + a0 * 12 + b0];
+        ps1 = a.PsT[row * 144 + a1 * 12 + b1];
+    } else {
+        xsv = xfp[(n - 1) * 12];
+        ps0 = tp[(n - 1) * UKF_TAPE + lane];
+        ps1 = tp[(n - 1) * UKF_TAPE + (two ? lane + 64 : lane)];
+    }
+    auto image_P = [&] {
+        S.P[a0][b0] = ps0;
+        S.P[b0][a0] = ps0;
+        if (two) { S.P[a1][b1] = ps1; S.P[b1][a1] = ps1; }
+        ukf_wave_sync();
+    };
+    auto put_row = [&](int64_t s) {
+        if (lane < 12) {
+            if (xsp) xsp[s * 12 + lane] = xsv;
+            if (psp) psp[s * 12 + lane] = sqrt(S.P[lane][lane]);
+        }
+        if (Psp) {
+            for (int e = lane; e < 144; e += 64) Psp[s * 144 + e] = S.P[e / 12][e % 12];
+        }
+    };
+    image_P();
+    if (!terminal) put_row(n - 1);
+    // ---- the transitions, last first ---------------------------------------------------------------------------------------------
+    double r[5], xfv;
+    auto fetch = [&](int64_t t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = tp[t * UKF_TAPE + 64 * k + lane];
+        r[4] = lane < UKF_TAPE - 256 ? tp[t * UKF_TAPE + 256 + lane] : 0.0;
+        xfv = xfp[t * 12];
+    };
+    int64_t t = terminal ? n - 1 : n - 2, failed = -1;
+    double minpiv = INF;
+    if (t >= 0) fetch(t);
+    for (; t >= 0; --t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S.rec[64 * k + lane] = r[k];
+        if (lane < UKF_TAPE - 256) S.rec[256 + lane] = r[4];
+        const double pf0 = r[0], pf1 = r[1], xft = xfv;       // Pf's entries lie on their owners
+        if (t > 0) fetch(t - 1);
+        ukf_wave_sync();                                      // rec written
+        // Cholesky of Pp, as in the filter
+        double Lr[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[90 + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            double s = Lr[j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
+            const double piv = ukf_lane(s, j);
+            double d = 1.0;
+            if (!bad) {
+                if (!(piv > 0.0) || piv == INF) bad = true;
+                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
+            }
+            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
+            if (lane < 12) S.L[lane][j] = Lr[j];
+            ukf_wave_sync();                                  // column j of L written
+        }
+        if (bad) { failed = t; break; }
+        // row lr of G: w L^T = C[lr][:], then g L = w
+        double g[12];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) {
+            double s = S.rec[168 + lr * 12 + j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) s = fma(-S.L[j][k], g[k], s);
+            g[j] = s / S.L[j][j];
+        }
+#pragma unroll
+        for (int j = 11; j >= 0; --j) {
+            double s = g[j];
+#pragma unroll
+            for (int k = j + 1; k < 12; ++k) s = fma(-S.L[k][j], g[k], s);
+            g[j] = s / S.L[j][j];
+        }
+        if (lane < 12) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) S.G[lane][k] = g[k];
+            S.dx[lane] = xsv - S.rec[78 + lane];              // not wrapped: xs, xp and xf live on the filter's continuous branch
+        }
+        {
+            const double m0 = ps0 - S.rec[90 + lane];
+            S.M[a0][b0] = m0;
+            S.M[b0][a0] = m0;
+            if (two) {
+                const double m1 = ps1 - S.rec[154 + lane];
+                S.M[a1][b1] = m1;
+                S.M[b1][a1] = m1;
+            }
+        }
+        ukf_wave_sync();                                      // G, dx, M written
+        {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) acc = fma(g[k], S.dx[k], acc);
+            xsv = xft + acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int e = lane + 64 * k;
+            if (e < 144) {
+                const int ga = e / 12, gb = e % 12;
+                double acc = 0.0;
+#pragma unroll
+                for (int c = 0; c < 12; ++c) acc = fma(S.G[ga][c], S.M[c][gb], acc);
+                S.GM[ga][gb] = acc;
+            }
+        }
+        ukf_wave_sync();                                      // GM written
+        {
+            double acc = 0.0;
+#pragma unroll
+            for (int c = 0; c < 12; ++c) acc = fma(S.GM[a0][c], S.G[b0][c], acc);
+            ps0 = pf0 + acc;
+            if (two) {
+                double acc1 = 0.0;
+#pragma unroll
+                for (int c = 0; c < 12; ++c) acc1 = fma(S.GM[a1][c], S.G[b1][c], acc1);
+                ps1 = pf1 + acc1;
+            }
+        }
+        image_P();
+        put_row(t);
+    }
+    // ---- outputs -------------------------------------------------------------------------------------------------------------
+    const bool ok = failed < 0;
+    for (int64_t s = failed; s >= 0; --s) put_nan(s);
+    if (a.Ps0) {
+        for (int e = lane; e < 144; e += 64) a.Ps0[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
+    }
+    if (a.sinfo && lane == 0) {
+        const double v[2] = {(double)failed, minpiv};
+        store_row<2>(a.sinfo + row * 2, v);
+    }
+}
+
+hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a) {
+    if (a.B <= 0 || P <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
+    hipLaunchKernelGGL(ukf_rts_kernel, grid, dim3(64 * UKF_WAVES), 0, st, a);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 // launch: grid (blocks of UKF_WAVES recordings, P)
 // ---------------------------------------------------------------------------------------
 int ukf_waves_per_block() { return UKF_WAVES; }
 
-template <int MODEL, int INTEG, int LAGMODE>
+template <int MODEL, int INTEG, int LAGMODE, bool TAPE>
 static hipError_t launch_ukf_t(hipStream_t st, int P, const UkfArgs& a) {
     const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
     if constexpr (MODEL == MODEL_THRUSTER_EULER) {
         if (a.lag) {
-            hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, true>), grid, dim3(64 * UKF_WAVES), 0, st, a);
+            hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, true, TAPE>), grid, dim3(64 * UKF_WAVES), 0, st, a);
             return hipGetLastError();
         }
     }
-    hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, false>), grid, dim3(64 * UKF_WAVES), 0, st, a);
+    hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, false, TAPE>), grid, dim3(64 * UKF_WAVES), 0, st, a);
     return hipGetLastError();
+}
+template <int MODEL, bool TAPE>
+static hipError_t launch_ukf_i(hipStream_t st, int integ, int lag_mode, int P, const UkfArgs& a) {
+    if (integ == INTEG_EULER) return launch_ukf_t<MODEL, INTEG_EULER, 0, TAPE>(st, P, a);
+    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
+        if (lag_mode == 1) return launch_ukf_t<MODEL, INTEG_RK4, 1, TAPE>(st, P, a);
+    }
+    return launch_ukf_t<MODEL, INTEG_RK4, 0, TAPE>(st, P, a);
 }
 template <int MODEL>
 static hipError_t launch_ukf_m(hipStream_t st, int integ, int lag_mode, int P, const UkfArgs& a) {
-    if (integ == INTEG_EULER) return launch_ukf_t<MODEL, INTEG_EULER, 0>(st, P, a);
-    if constexpr (MODEL == MODEL_THRUSTER_EULER) {
-        if (lag_mode == 1) return launch_ukf_t<MODEL, INTEG_RK4, 1>(st, P, a);
-    }
-    return launch_ukf_t<MODEL, INTEG_RK4, 0>(st, P, a);
+    if (a.tape) return launch_ukf_i<MODEL, true>(st, integ, lag_mode, P, a);
+    return launch_ukf_i<MODEL, false>(st, integ, lag_mode, P, a);
 }
 hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a0) {
     if (a0.B <= 0 || P <= 0) return hipSuccess;

@@ -595,25 +595,17 @@ def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=No
 
 
 UKF_OUTPUTS = ("xf", "pstd", "innov", "xT", "PT", "info")
+UKF_SMOOTH_OUTPUTS = ("xs", "pstd_s", "Ps", "Ps0", "sinfo")
+UKF_TAPE = 312          # doubles of a tape record (include/brov2.h: brov_ukf_filter_tape_dev)
 
 
-def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL, want=UKF_OUTPUTS, ctx=None):
-    """Unscented Kalman filter on the Fossen model for P vehicles x B recordings in one launch (include/brov2.h:
-    brov_ukf_filter_dev holds the law): candidate j filters the noisy state rows Y under params_list[j].
-
-    params_list: sequence of P _lib.BrovParams.  cfg: one _lib.BrovUkf (one noise model for every candidate) or a sequence of P
-    (fossen/estimate.py: ukf builds them).  Shared by the candidates: x0 [B,12], P0 [B,12,12] (lower triangle read), U [B,T,nu],
-    Y [B,T,12] with NaN where a component was not measured.  lag [P,B,8,3] (thruster model) is the start lag; None starts from
-    zero and returns None.  want: the outputs to compute, any of UKF_OUTPUTS.  Host and device arrays as in rollout_pop.
-    Returns dict(xf, pstd, innov [P,B,T,12], xT [P,B,12], PT [P,B,12,12], info [P,B,4] = log-likelihood, scalar updates applied,
-    first failed step (-1: none), smallest Cholesky pivot; lag | None), with None for what was not wanted.  Models THRUSTER_EULER
-    and WRENCH_EULER.  The ctx's own parameters are left alone."""
+def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx):
+    """the argument handling that ukf_filter and ukf_smooth share: (ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io) with
+    the arrays on the device"""
     P = len(params_list)
     pa = (_lib.BrovParams * max(P, 1))(*params_list)
     cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
     ca = (_lib.BrovUkf * max(len(cfgs), 1))(*cfgs)
-    want = tuple(want)
-    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
     nu = NU.get(model, 8)
     host = isinstance(x0, (np.ndarray, list, tuple))
     if host:
@@ -639,11 +631,93 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
             lag_io = arr.upload(lag.reshape(P, B, 8, 3))
     elif track:          # in / out in the ABI: work on a copy
         lag_io = (lag.clone() if _is_torch(lag) else arr.upload(lag.numpy())).reshape(P, B, 8, 3)
-    shapes = dict(xf=(P, B, T, 12), pstd=(P, B, T, 12), innov=(P, B, T, 12), xT=(P, B, 12), PT=(P, B, 12, 12), info=(P, B, 4))
+    return ctx, arr, host, P, B, T, pa, len(cfgs), ca, x0, P0, U, Y, lag_io
+
+
+def _ukf_shapes(P, B, T):
+    return dict(xf=(P, B, T, 12), pstd=(P, B, T, 12), innov=(P, B, T, 12), xT=(P, B, 12), PT=(P, B, 12, 12), info=(P, B, 4),
+                xs=(P, B, T, 12), pstd_s=(P, B, T, 12), Ps=(P, B, T, 12, 12), Ps0=(P, B, 12, 12), sinfo=(P, B, 2))
+
+
+def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL, want=UKF_OUTPUTS, ctx=None, tape=False):
+    """Unscented Kalman filter on the Fossen model for P vehicles x B recordings in one launch (include/brov2.h:
+    brov_ukf_filter_dev holds the law): candidate j filters the noisy state rows Y under params_list[j].
+
+    params_list: sequence of P _lib.BrovParams.  cfg: one _lib.BrovUkf (one noise model for every candidate) or a sequence of P
+    (fossen/estimate.py: ukf builds them).  Shared by the candidates: x0 [B,12], P0 [B,12,12] (lower triangle read), U [B,T,nu],
+    Y [B,T,12] with NaN where a component was not measured.  lag [P,B,8,3] (thruster model) is the start lag; None starts from
+    zero and returns None.  want: the outputs to compute, any of UKF_OUTPUTS.  Host and device arrays as in rollout_pop.
+    Returns dict(xf, pstd, innov [P,B,T,12], xT [P,B,12], PT [P,B,12,12], info [P,B,4] = log-likelihood, scalar updates applied,
+    first failed step (-1: none), smallest Cholesky pivot; lag | None), with None for what was not wanted.  Models THRUSTER_EULER
+    and WRENCH_EULER.  The ctx's own parameters are left alone.
+    tape=True (brov_ukf_filter_tape_dev): the dict also holds tape [P,B,T,UKF_TAPE], what ukf_rts needs for every transition, and
+    nrows [P,B], the number of rows whose update completed; every other output carries the same bits."""
+    want = tuple(want)
+    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
+    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx)
+    shapes = _ukf_shapes(P, B, T)
     out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
-    ctx.check(ctx.lib.brov_ukf_filter_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, len(cfgs), ca, B, T, float(dt), _dptr(x0),
-                                          _dptr(P0), _dptr(U), _dptr(Y), _dptr(lag_io), *(_dptr(out[k]) for k in UKF_OUTPUTS)),
-              "brov_ukf_filter_dev")
+    head = (ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
+            _dptr(lag_io), *(_dptr(out[k]) for k in UKF_OUTPUTS))
+    if tape:
+        out["tape"], out["nrows"] = arr.empty((P, B, T, UKF_TAPE)), arr.empty((P, B))
+        ctx.check(ctx.lib.brov_ukf_filter_tape_dev(*head, _dptr(out["tape"]), _dptr(out["nrows"])), "brov_ukf_filter_tape_dev")
+    else:
+        ctx.check(ctx.lib.brov_ukf_filter_dev(*head), "brov_ukf_filter_dev")
+    out["lag"] = lag_io
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None):
+    """Backward (Rauch-Tung-Striebel) pass over the tape of ukf_filter(..., tape=True) (include/brov2.h: brov_ukf_rts_dev holds
+    the law).  xf [P,B,T,12], tape [P,B,T,UKF_TAPE] and nrows [P,B] as that call returned them (the tape is a documented plain
+    array).  terminal: (xs_T [P,B,12], Ps_T [P,B,12,12]), the smoothed estimate of row T from a later span, or None.  want: any of
+    UKF_SMOOTH_OUTPUTS.  Host arrays or device arrays (all of one kind).  Returns dict(xs, pstd_s [P,B,T,12], Ps [P,B,T,12,12],
+    Ps0 [P,B,12,12], sinfo [P,B,2] = first failed transition (-1: none), smallest pivot), with None for what was not wanted."""
+    want = tuple(want)
+    assert all(w in UKF_SMOOTH_OUTPUTS for w in want), f"want must be among {UKF_SMOOTH_OUTPUTS}"
+    host = isinstance(xf, (np.ndarray, list, tuple))
+    ins = [xf, tape, nrows] + (list(terminal) if terminal is not None else [])
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        ins = [as_f64(v) for v in ins]
+    else:
+        ctx = _ctx_of(xf, ctx)
+        arr = arrays_of(xf, ctx)
+    arr.bind()
+    P, B, T = (int(s) for s in ins[0].shape[:3])
+    want_shape = [(P, B, T, 12), (P, B, T, UKF_TAPE), (P, B), (P, B, 12), (P, B, 12, 12)]
+    for v, shape in zip(ins, want_shape):
+        assert tuple(int(s) for s in v.shape) == shape, f"shape {tuple(v.shape)} != {shape}"
+    if host:
+        ins = [arr.upload(v) for v in ins]
+    ins += [None] * (5 - len(ins))
+    shapes = _ukf_shapes(P, B, T)
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_SMOOTH_OUTPUTS}
+    ctx.check(ctx.lib.brov_ukf_rts_dev(ctx.h, P, B, T, *(_dptr(v) for v in ins), *(_dptr(out[k]) for k in UKF_SMOOTH_OUTPUTS)),
+              "brov_ukf_rts_dev")
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def ukf_smooth(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL,
+               want=UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS, tape_bytes=0, ctx=None):
+    """Filter and smooth in one call (brov_ukf_smooth_dev): the arguments and outputs of ukf_filter plus the outputs of ukf_rts.  The
+    tape stays inside the library, in a buffer of the ctx of at most tape_bytes (0: 2 GiB): the recordings go through in chunks,
+    one filter launch and one backward launch each, which changes no bit."""
+    want = tuple(want)
+    keys = UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS
+    assert all(w in keys for w in want), f"want must be among {keys}"
+    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx)
+    shapes = _ukf_shapes(P, B, T)
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
+    ctx.check(ctx.lib.brov_ukf_smooth_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0),
+                                          _dptr(U), _dptr(Y), _dptr(lag_io), *(_dptr(out[k]) for k in keys), int(tape_bytes)),
+              "brov_ukf_smooth_dev")
     out["lag"] = lag_io
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}

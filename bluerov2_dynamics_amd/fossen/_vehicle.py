@@ -206,15 +206,9 @@ class VehicleBase:
         out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
         return tuple(v[0] for v in out) if single else out
 
-    def filter_states(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler"):
-        """Unscented Kalman filter over noisy recordings of the state (engine.ukf_filter; fossen/estimate.py: ukf builds `cfg`;
-        include/brov2.h: brov_ukf_filter holds the law).  Y [T,12] or [B,T,12]: the measured state rows, NaN where a component was
-        not measured; U [T,nu] or [B,T,nu] the commands.  x0 / P0 default to estimate.default_start: the first fully measured row
-        and diag(4 r), with estimate.P0_STAND_IN where r is infinite.  params: a _lib.BrovParams to filter under instead of this
-        vehicle's own.  Returns dict(x [.,T,12] the filtered means, std [.,T,12], innov [.,T,12] the normalised innovations (NaN
-        where nothing was measured), xT, PT, loglik, n_updates, failed_step (-1: none), min_pivot), without the leading B when Y
-        was one recording.  Thruster and Euler-wrench vehicles; starts from zero thruster lag; this object's own lag state is
-        neither read nor changed, and its parameters reach the kernel as arguments."""
+    def _ukf_inputs(self, Y, U, cfg, x0, P0, params):
+        """What filter_states and smooth_states make of their arguments: (single, Y [B,T,12], U [B,T,nu], x0 [B,12], P0 [B,12,12],
+        the parameters to filter under), with estimate.default_start where x0 / P0 are None."""
         from . import estimate, identify
         Y, U = np.asarray(Y, float), np.asarray(U, float)
         single = Y.ndim == 2
@@ -224,10 +218,38 @@ class VehicleBase:
             dx0, dP0 = estimate.default_start(Y, cfg)
         x0 = dx0 if x0 is None else np.asarray(x0, float).reshape(Y.shape[0], 12)
         P0 = dP0 if P0 is None else np.asarray(P0, float).reshape(Y.shape[0], 12, 12)
-        p = identify.params_of(self) if params is None else params
+        return single, Y, U, x0, P0, identify.params_of(self) if params is None else params
+
+    @staticmethod
+    def _filter_dict(r):
+        """the filter's part of the dicts of filter_states and smooth_states, from engine.ukf_filter's / ukf_smooth's outputs at P = 1"""
+        return dict(x=r["xf"][0], std=r["pstd"][0], innov=r["innov"][0], xT=r["xT"][0], PT=r["PT"][0], loglik=r["info"][0, :, 0],
+                    n_updates=r["info"][0, :, 1].astype(np.int64), failed_step=r["info"][0, :, 2].astype(np.int64), min_pivot=r["info"][0, :, 3])
+
+    def filter_states(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler"):
+        """Unscented Kalman filter over noisy recordings of the state (engine.ukf_filter; fossen/estimate.py: ukf builds `cfg`;
+        include/brov2.h: brov_ukf_filter holds the law).  Y [T,12] or [B,T,12]: the measured state rows, NaN where a component was
+        not measured; U [T,nu] or [B,T,nu] the commands.  x0 / P0 default to estimate.default_start: the first fully measured row
+        and diag(4 r), with estimate.P0_STAND_IN where r is infinite.  params: a _lib.BrovParams to filter under instead of this
+        vehicle's own.  Returns dict(x [.,T,12] the filtered means, std [.,T,12], innov [.,T,12] the normalised innovations (NaN
+        where nothing was measured), xT, PT, loglik, n_updates, failed_step (-1: none), min_pivot), without the leading B when Y
+        was one recording.  Thruster and Euler-wrench vehicles; starts from zero thruster lag; this object's own lag state is
+        neither read nor changed, and its parameters reach the kernel as arguments."""
+        single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
         r = engine.ukf_filter(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, ctx=self._ctx)
-        out = dict(x=r["xf"][0], std=r["pstd"][0], innov=r["innov"][0], xT=r["xT"][0], PT=r["PT"][0], loglik=r["info"][0, :, 0],
-                   n_updates=r["info"][0, :, 1].astype(np.int64), failed_step=r["info"][0, :, 2].astype(np.int64), min_pivot=r["info"][0, :, 3])
+        out = self._filter_dict(r)
+        return {k: v[0] for k, v in out.items()} if single else out
+
+    def smooth_states(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler", tape_bytes=0):
+        """Unscented Rauch-Tung-Striebel smoother over complete recordings (engine.ukf_smooth; include/brov2.h: brov_ukf_smooth
+        holds the law): the estimate of every row from ALL rows, where filter_states uses the rows up to it.  Arguments and
+        defaults as filter_states.  Returns the dict of filter_states plus xs [.,T,12] the smoothed means, std_s [.,T,12], Ps
+        [.,T,12,12] the smoothed covariances, Ps0 [.,12,12] and failed_transition (-1: none, also where the filter completed no
+        row and there was nothing to smooth), without the leading B when Y was one recording.  tape_bytes bounds the library's tape buffer (0: 2 GiB)."""
+        single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
+        r = engine.ukf_smooth(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, tape_bytes=tape_bytes, ctx=self._ctx)
+        out = dict(self._filter_dict(r), xs=r["xs"][0], std_s=r["pstd_s"][0], Ps=r["Ps"][0], Ps0=r["Ps0"][0],
+                   failed_transition=np.nan_to_num(r["sinfo"][0, :, 0], nan=-1.0).astype(np.int64))
         return {k: v[0] for k, v in out.items()} if single else out
 
     def log_likelihood_population(self, params_list, Y, U, dt, cfg, x0=None, P0=None, integrator="euler"):

@@ -8,7 +8,10 @@ the raw against the filtered RMSE (second half of the recording) and the mean sq
 the noise model fits.  Then the innovation log-likelihood ranks candidates: the true vehicle and --draws vehicles drawn around it
 with identify.sample_parameters (rov.log_likelihood_population: every candidate filters the recording in ONE launch).
 
-    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small]
+With --smooth, rov.smooth_states (the unscented Rauch-Tung-Striebel smoother, brov_ukf_smooth) runs instead of the filter alone and
+the smoothed RMSE is printed beside the filtered one: the recording is complete, so every row may be estimated from all rows.
+
+    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth]
 """
 import argparse
 import os
@@ -35,9 +38,10 @@ def drawn_vehicles(base, n, seed, rel_std):
     return identify.sample_parameters(fit, n, seed=seed)
 
 
-def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True):
+def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True, smooth=False):
     """Returns dict(X [T+1,12] the truth, Y [T,12] the noisy rows, x, std, innov [T,12] of the filter, rmse_raw, rmse_filtered, nis,
-    loglik [draws + 1] with the true vehicle at index 0, order: the candidates from best to worst)"""
+    loglik [draws + 1] with the true vehicle at index 0, order: the candidates from best to worst); with smooth also xs, std_s
+    [T,12] of the smoother, rmse_smoothed and rmse_unmeasured_filtered / _smoothed (the never-measured roll rate)"""
     rov = BlueROV2(dt=dt)
     true = identify.copy_params(identify.params_of(rov))
     for i, v in enumerate((0.15, -0.1, 0.03)):
@@ -57,12 +61,18 @@ def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="r
     cfg = estimate.ukf(q=1e-6, r=r)
     start = x0 + rng.normal(size=12) * SIGMA
     P0 = np.diag(np.where(np.isfinite(r), 4.0 * SIGMA ** 2, estimate.P0_STAND_IN))
-    f = rov.filter_states(Y, U, dt, cfg, x0=start, P0=P0, params=true, integrator=integrator)
+    estimator = rov.smooth_states if smooth else rov.filter_states
+    f = estimator(Y, U, dt, cfg, x0=start, P0=P0, params=true, integrator=integrator)
     half = slice(T // 2, T)
     seen = ~np.isnan(Y[half])
     rmse_raw = float(np.sqrt(np.mean((Y[half] - X[:T][half])[seen] ** 2)))
     rmse_f = float(np.sqrt(np.mean((f["x"][half] - X[:T][half])[seen] ** 2)))
     nis = float(np.nanmean(f["innov"] ** 2))
+    extra = {}
+    if smooth:
+        miss = lambda x: float(np.sqrt(np.mean((x[half, UNMEASURED] - X[:T][half, UNMEASURED]) ** 2)))
+        extra = dict(xs=f["xs"], std_s=f["std_s"], rmse_smoothed=float(np.sqrt(np.mean((f["xs"][half] - X[:T][half])[seen] ** 2))),
+                     rmse_unmeasured_filtered=miss(f["x"]), rmse_unmeasured_smoothed=miss(f["xs"]))
     cands = [true] + drawn_vehicles(true, int(draws), seed + 1, rel_std)
     ll = rov.log_likelihood_population(cands, Y, U, dt, cfg, x0=start, P0=P0, integrator=integrator)[:, 0]
     order = np.argsort(-ll)
@@ -72,12 +82,16 @@ def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="r
         print(f"RMSE over the second half, measured entries: raw {rmse_raw:.4f}, filtered {rmse_f:.4f}")
         print(f"error of the never-measured roll rate: {np.sqrt(np.mean((f['x'][half, UNMEASURED] - X[:T][half, UNMEASURED]) ** 2)):.4f} rad/s "
               f"(its own scale: {np.std(X[:, UNMEASURED]):.4f})")
+        if smooth:
+            print(f"smoothed (every row from all rows): RMSE {extra['rmse_smoothed']:.4f} against {rmse_f:.4f} filtered; "
+                  f"roll rate {extra['rmse_unmeasured_smoothed']:.4f} against {extra['rmse_unmeasured_filtered']:.4f} rad/s")
         print(f"mean squared normalised innovation {nis:.2f} (1 when the noise model fits)")
         print(f"log-likelihood of {len(cands)} candidates (0 = the true vehicle, the others drawn with {rel_std:.0%} on {len(SPREAD)} terms):")
         for k in order[:5]:
             print(f"    candidate {k:3d}   {ll[k]:12.1f}")
         print(f"    ...   worst   {ll[order[-1]]:12.1f}")
-    return dict(X=X, Y=Y, x=f["x"], std=f["std"], innov=f["innov"], rmse_raw=rmse_raw, rmse_filtered=rmse_f, nis=nis, loglik=ll, order=order)
+    return dict(X=X, Y=Y, x=f["x"], std=f["std"], innov=f["innov"], rmse_raw=rmse_raw, rmse_filtered=rmse_f, nis=nis, loglik=ll, order=order,
+                **extra)
 
 
 def main(argv=None):
@@ -88,10 +102,11 @@ def main(argv=None):
     ap.add_argument("--euler", action="store_true")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--small", action="store_true", help="3 s and 7 draws: runs in seconds")
+    ap.add_argument("--smooth", action="store_true", help="also smooth the recording (rov.smooth_states) and print the smoothed RMSE")
     a = ap.parse_args(argv)
     if a.small:
         a.seconds, a.draws = 3.0, 7
-    return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed)
+    return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth)
 
 
 if __name__ == "__main__":

@@ -396,6 +396,76 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
                         const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
                         double* d_innov, double* d_xT, double* d_PT, double* d_info);
 
+/* ---- state estimation after the fact: the unscented Rauch-Tung-Striebel smoother over the filter ------------------------------
+ * The filter estimates row t from rows 0 .. t.  For a recording that is complete the smoothed estimate E[x_t | all rows] is the
+ * better one: smaller errors, honest error bars in the first rows, better values of a component that is never measured.  It is a
+ * backward pass over what the forward pass leaves on a tape.
+ *
+ * Forward pass with a tape (brov_ukf_filter_tape_dev).  The filter is the law above, unchanged, bit for bit in every output and in
+ * lag_io.  Step t (update with row t, then predict with U[t]) also records what the backward pass needs for the transition
+ * t -> t + 1: tape [P][B][T][312], a record of 312 doubles for both models, triangles packed row by row (entry e = a (a + 1) / 2 + b
+ * holds [a][b], b <= a):
+ *       0 ..  77   Pf_t, the covariance after the update of row t, lower triangle
+ *      78 ..  89   xp_{t+1}, the predicted mean (the x that stage 2 leaves)
+ *      90 .. 167   Pp_{t+1}, the predicted covariance including diag(q), lower triangle
+ *     168 .. 311   C_{t+1} [12][12] row-major, C[a][b] = cov(x_t[a], x_{t+1}[b])
+ * In the notation of stage 2, C_{t+1} = sum_{i>=1} W_i (chi_i - x)(d_i - m)^T; chi_i - x = +- c L[:, i-1] and the m terms cancel, so
+ *     C[a][b] = sum_{j=0..11} L[a][j] ((c W_i) (d_{j+1}[b] - d_{j+13}[b])),  summed in index order.
+ * nrows [P][B], stored as doubles like info, is the number of rows whose update completed: T for a filter that did not fail, t for
+ * a failure in stage 1 of row t, t + 1 for a failure in stage 2 of row t.  Of a transition that did not complete, xp, Pp and C are
+ * NaN, and so are whole records of rows whose update did not complete; Pf_t is there whenever the update of row t was complete.
+ * d_tape and d_nrows go together; with both NULL the call is brov_ukf_filter_dev.
+ *
+ * Backward pass (brov_ukf_rts_dev), per (candidate, recording), with n = nrows (clamped to 0 .. T).  n = 0: every output of the
+ * problem is NaN, sinfo included.  Otherwise it starts from (xs, Ps)_{n-1} = (xf, Pf)_{n-1}; if n = T and a terminal pair
+ * (xs_T [P][B][12], Ps_T [P][B][12][12], lower triangle read) is given -- the smoothed estimate of row T from a later span -- it
+ * starts from that pair and takes the transition T-1 -> T first.  Then for t = n-2 .. 0 (with a terminal pair from t = T-1):
+ *     Pp_{t+1} = Lp Lp^T, the Cholesky factorisation and the pivot rule of the filter's stage 2;
+ *     G = C_{t+1} Pp_{t+1}^-1 by two triangular solves per row of C (w Lp^T = C[a][:] forwards, G[a][:] Lp = w backwards), no
+ *         explicit inverse;
+ *     xs_t = xf_t + G (xs_{t+1} - xp_{t+1}).  This difference is NOT wrapped: xf, xp and xs live on the filter's continuous
+ *         attitude branch (stage 2 never wraps the mean), so a yaw that has turned through pi needs nothing here;
+ *     Ps_t = Pf_t + G (Ps_{t+1} - Pp_{t+1}) G^T, one expression for both triangles: Ps is bit-symmetric.
+ * Outputs, per candidate, each may be NULL: xs, pstd_s [P][B][T][12] (pstd_s = sqrt of the diagonal of Ps); Ps [P][B][T][12][12],
+ * full; Ps0 [P][B][12][12] = Ps of row 0, which with xs[0] is the terminal pair for an earlier span; sinfo [P][B][2] = the first
+ * failed transition (-1: none), the smallest pivot Lp[j][j] of any factorisation (+inf when there was none).  Rows >= n are NaN.
+ * Row n-1 (T-1 without a terminal pair) carries the bits of the filter: xs = xf, pstd_s = pstd.
+ * Failure of transition t is a pivot argument <= 0 or not finite: xs, pstd_s and Ps of rows <= t are NaN, rows > t stay valid, Ps0
+ * is NaN, no other problem is touched, and the call returns BROV_OK.
+ * Splitting in time: filter span 1, then span 2 from (xT, PT, lag_io); smooth span 2; smooth span 1 with span 2's (xs[0], Ps0) as
+ * its terminal pair: the bits of the unbroken call in xs, pstd_s and Ps.
+ * Refused with BROV_ERR_ARG: negative sizes, P > 65535, T < 1, a NULL d_xf, d_tape or d_nrows, one terminal pointer without the
+ * other.  P = 0 or B = 0: BROV_OK, nothing touched.
+ *
+ * brov_ukf_smooth[_dev] is both passes: the inputs of brov_ukf_filter, the filter's outputs and the smoother's.  The tape lives in a
+ * buffer the ctx owns, and the tape itself never exceeds tape_bytes (0: the default of 2 GiB): the recordings are processed in
+ * chunks, one filter launch and one backward launch per chunk, and a chunk is a whole number of blocks of 4 recordings.  Chunking
+ * changes no bit.  The buffer holds the chunk's tape, its nrows (8 bytes per problem) and up to 512 bytes of alignment, so it is
+ * that much larger than the tape.  It is allocated once every refusal below has passed, and the ctx keeps it for the next call: a
+ * call that needs more, or less than half of what is held, frees it and allocates its own size, so that one call with a large
+ * tape_bytes does not bind that memory for the life of the ctx.  brov_destroy frees it.
+ * Refused on the host, before anything is copied, allocated or launched, with a text that names the function called: everything
+ * brov_ukf_filter refuses, a negative tape_bytes, and a tape_bytes smaller than one block of recordings (P * 4 * T * 2496 bytes).
+ * Deterministic (no atomics, fixed summation orders): two calls give the same bits.
+ * Still missing: the lag-one smoothed cross-covariance (for EM), a quaternion model, full Q and R. */
+BROV_API int brov_ukf_filter_tape_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                             int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                             const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
+                             double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_tape, double* d_nrows);
+BROV_API int brov_ukf_rts_dev(brov_ctx* ctx, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                     const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0,
+                     double* d_sinfo);
+BROV_API int brov_ukf_smooth(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                    int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0,
+                    const double* P0, const double* U, const double* Y, double* lag_io, double* xf, double* pstd, double* innov,
+                    double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps, double* Ps0, double* sinfo,
+                    int64_t tape_bytes);
+BROV_API int brov_ukf_smooth_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                        int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                        const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
+                        double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
+                        double* d_Ps0, double* d_sinfo, int64_t tape_bytes);
+
 /* ---- model-predictive control: one sampling-based (MPPI) update, sampled, rolled out and scored on the device ---------------------
  * brov_mppi_step performs one MPPI update for B independent problems (B vehicles, or B draws of a fit).  Problem b has a state
  * x [nx], for the thruster model optionally a start lag [8][3] (read only; NULL = zero), a reference, and a nominal knot sequence
