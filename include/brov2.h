@@ -416,7 +416,8 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
  * NaN, and so are whole records of rows whose update did not complete; Pf_t is there whenever the update of row t was complete.
  * d_tape and d_nrows go together; with both NULL the call is brov_ukf_filter_dev.
  *
- * Backward pass (brov_ukf_rts_dev), per (candidate, recording), with n = nrows (clamped to 0 .. T).  n = 0: every output of the
+ * Backward pass (brov_ukf_rts_dev), per (candidate, recording), with n = nrows (clamped to 0 .. T, so -inf counts as 0 and +inf as
+ * T; then the fraction is dropped; NaN counts as 0).  n = 0: every output of the
  * problem is NaN, sinfo included.  Otherwise it starts from (xs, Ps)_{n-1} = (xf, Pf)_{n-1}; if n = T and a terminal pair
  * (xs_T [P][B][12], Ps_T [P][B][12][12], lower triangle read) is given -- the smoothed estimate of row T from a later span -- it
  * starts from that pair and takes the transition T-1 -> T first.  Then for t = n-2 .. 0 (with a terminal pair from t = T-1):

@@ -442,7 +442,7 @@ def family_sweep(name):
     fd_normal_eq) and the EDMDc families of tests/sweep_edmdc.py (lift, gram, pinv_apply, multistep -- here `multistep_sweep`, next to
     the older `multistep` above --, simulate; their second figure is sweep_edmdc.sweep_one's), the unscented Kalman filter (ukf) and the QP of the
     Koopman linear MPC (lmpc; tests/sweep_ukf_lmpc.py), the k-means families (colstats, kmeanspp -- here `kmeanspp_sweep`, next to the older
-    `kmeanspp` above --, lloyd; tests/sweep_kmeans.py: a draw with an undecided round or sample counts as ill-posed): random cases from the generators of tests/sweep_cases.py against the references and bounds of tests/sweep_run.py,
+    `kmeanspp` above --, lloyd; tests/sweep_kmeans.py: a draw with an undecided round or sample counts as ill-posed), the unscented RTS smoother (smooth; tests/sweep_smooth.py): random cases from the generators of tests/sweep_cases.py against the references and bounds of tests/sweep_run.py,
     which tests/test_family_sweeps_gpu.py runs on a fixed list.  A case whose reference is not well-posed (more than 2 % of its lanes
     off the float64 / long double condition) is skipped and counted."""
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -477,7 +477,7 @@ if __name__ == "__main__":
     import functools
     fams = dict(copies=copies, linear_multistep=linear_multistep, applies=applies, lloyds=lloyds, lloyds_list=lloyds_list, rollouts=rollouts, windows=windows, grams=grams, multistep=multistep, kmeanspp=kmeanspp, pinc=pinc,
                 **{f: functools.partial(family_sweep, f) for f in ("rollout_pop", "feedback", "mppi", "koopman_mppi", "window_pop", "lift", "gram", "pinv_apply", "multistep_sweep", "simulate", "ukf", "lmpc",
-                                                                          "colstats", "kmeanspp_sweep", "lloyd")})
+                                                                          "colstats", "kmeanspp_sweep", "lloyd", "smooth")})
     for name in (sys.argv[3].split(",") if len(sys.argv) > 3 else list(fams)):
         fams[name]()
     print("stress parity: ok")

@@ -23,7 +23,10 @@ iters 0 .. 40 and a residual stop at two, three and five rows per lane).  The k-
 the file) walk csrc/colstats.hip, the seeding and Lloyd's loop of csrc/kmeans.hip: every operand form (host, device, strided rows, a
 column block of a wider table on and off a 16-byte boundary), data scales 1e-13 .. 1e13, far column means, a constant column, the
 block, chunk and row edges of the seeding, and for the loop every kernel its dispatch rules pick (csrc/capi.hip:
-edmdc_kmeans_lloyd_dev), every stopping rule and every empty-cluster rule."""
+edmdc_kmeans_lloyd_dev), every stopping rule and every empty-cluster rule.  The last family is the unscented RTS smoother (smooth: the
+eight TAPE = true instantiations of ukf_filter_kernel, each with a full and a ragged block, ukf_rts_kernel and the chunked
+brov_ukf_smooth; the shapes of ukf plus B = 13, T = 1, 2, 3 with and without a terminal pair, a tape budget with room for 4, 8 or 5
+recordings -- chunks 4 + 4 + 1, 8 + 5, 4 + 4 + 4 + 1, 5 rounded down to 4, nrec = P = 3 in chunks -- and strict subsets of the outputs)."""
 import hashlib
 import json
 
@@ -33,7 +36,7 @@ NAMES = ("V0", "V1", "V2", "V3", "V4", "V5", "V6", "V7", "V8")      # tests/foss
 WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/fossen_vehicles.py: WRENCH_NAMES
 N_CASES = 48                                                        # per family: four slices of 12
 N_CASES_EDMDC = 32                                                  # per EDMDc family: four slices of 8 (corner lists of 12 to 24)
-N_CASES_FILTER = 32                                                 # ukf and lmpc: four slices of 8 (corner lists of 17 and 26)
+N_CASES_FILTER = 32                                                 # ukf, lmpc and smooth: four slices of 8 (corner lists of 17, 26 and 20)
 N_CASES_KMEANS = 32                                                 # colstats, kmeanspp, lloyd: four slices of 8
 SEED = 2024
 
@@ -81,6 +84,9 @@ SETS = dict(
                k=(1, 2, 63, 64, 65, 128, 256, 512, 513, 600, 1024, 1200), stop=("max_iter", "strict", "shift"),
                init=("rows", "dup", "far2", "far3", "allzero"), form=("host", "dev", "dev_stride", "block_odd", "block_even"),
                scale=(1e-13, 1e-4, 1.0, 50.0, 1e4, 1e13), order=("walk", "shuffled", "blobs"), offset=(True, False), const_col=(True, False)),
+    smooth=dict(model=(0, 1), integ=("euler", "rk4"), lag_mode=(0, 1), lag=(True, False), P=(1, 2, 3), nrec=("1", "P"), alpha=(0.5, 1.0),
+                B=(1, 3, 4, 5, 8, 9, 13), T=(1, 2, 3, 12), measured=("std", "all", "none"), r_inf=(0, 1, 3), q_zero=(True, False),
+                wrap=(True, False), chunk=("whole", 4, 8, 5), terminal=(True, False), want=("all", "xs+sinfo", "Ps0", "pstd_s+Ps")),
 )
 
 
@@ -835,6 +841,72 @@ def draw_lloyd(rng):
                   _pick(rng, ("walk", "shuffled")), _pick(rng, s["offset"]), _pick(rng, s["const_col"]))
 
 
+# ------------------------------------------------------------------------------------------ unscented RTS smoother
+SMOOTH_OUTS = ("xs", "pstd_s", "Ps", "Ps0", "sinfo")                # bluerov2_dynamics_amd/engine.py: UKF_SMOOTH_OUTPUTS
+SMOOTH_WANT = {"all": SMOOTH_OUTS, "xs+sinfo": ("xs", "sinfo"), "Ps0": ("Ps0",), "pstd_s+Ps": ("pstd_s", "Ps")}
+SMOOTH_RECORD = 312 * 8                                             # bytes of a tape record: 2496
+SMOOTH_T_DRAW = (1, 2, 2, 3, 3, 12, 12, 12)                         # the weights of a draw's T: one in eight is a single row
+
+
+def smooth_tape_bytes(c):
+    """the tape_bytes a case passes: room for `chunk` recordings ("whole": for all B, and never below the one block of UKF_WAVES = 4
+    recordings that the host demands)"""
+    return c["P"] * (max(c["B"], 4) if c["chunk"] == "whole" else c["chunk"]) * c["T"] * SMOOTH_RECORD
+
+
+def smooth_chunks(c):
+    """the recordings per launch pair of brov_ukf_smooth under smooth_tape_bytes(c), by the rule of csrc/capi.hip: ukf_filter -- what
+    fits, rounded down to whole blocks of 4, unless all B fit"""
+    fit = smooth_tape_bytes(c) // (c["P"] * c["T"] * SMOOTH_RECORD)
+    step = c["B"] if fit >= c["B"] else fit // 4 * 4
+    return [min(step, c["B"] - b0) for b0 in range(0, c["B"], step)]
+
+
+def _smooth(rng, model, integ, lag_mode, lag, P, nrec, alpha, B, T, measured, r_inf, q_zero, wrap, chunk, terminal, want):
+    """the fields of _ukf (tests/sweep_ukf_lmpc.py: ukf_inputs reads no other), then chunk: the recordings the tape budget of the
+    chunked call has room for ("whole": all); terminal: the two-call path passes a terminal pair (tests/sweep_smooth.py:
+    terminal_pair); want: the smoother outputs asked for, by the names of SMOOTH_WANT"""
+    c = _ukf(rng, model, integ, lag_mode, lag, P, nrec, alpha, B, T, measured, r_inf, q_zero, wrap)
+    c.update(family="smooth", chunk=chunk, terminal=bool(terminal), want=list(SMOOTH_WANT[want]), want_as=want)
+    return c
+
+
+SMOOTH_CORNERS = (
+    # model integ lag_mode lag  P  nrec alpha B  T  measured r_inf q_zero wrap chunk terminal want  -- every tape instantiation with a full and a ragged block
+    (0, "euler", 0, True, 2, "1", 1.0, 4, 12, "std", 1, False, True, "whole", True, "all"),           # the yaw through pi into a terminal pair
+    (0, "euler", 0, True, 1, "1", 0.5, 5, 12, "all", 0, True, False, 4, False, "all"),                # chunks 4 + 1; 12 updates a row; q = 0 on three components
+    (0, "euler", 0, False, 3, "P", 1.0, 8, 3, "std", 3, False, False, 4, True, "xs+sinfo"),           # no start lag; nrec = P = 3 in chunks 4 + 4; T = 3 with a pair
+    (0, "euler", 0, False, 2, "1", 0.5, 1, 12, "none", 1, True, False, "whole", False, "all"),        # B = 1, pure prediction
+    (0, "rk4", 0, True, 2, "1", 1.0, 8, 12, "std", 1, False, False, 5, False, "all"),                 # room for 5, rounded down to 4: chunks 4 + 4
+    (0, "rk4", 0, True, 3, "P", 0.5, 3, 2, "std", 0, True, False, "whole", False, "Ps0"),             # T = 2 without a pair: one transition, no prefetch
+    (0, "rk4", 0, False, 2, "P", 1.0, 4, 1, "all", 0, False, False, "whole", True, "all"),            # T = 1 with a pair: one transition from the pair
+    (0, "rk4", 0, False, 1, "1", 0.5, 13, 12, "std", 1, False, False, 4, False, "all"),               # chunks 4 + 4 + 4 + 1
+    (0, "rk4", 1, True, 2, "1", 1.0, 4, 12, "all", 3, False, False, "whole", False, "pstd_s+Ps"),
+    (0, "rk4", 1, True, 1, "1", 0.5, 3, 2, "std", 1, True, False, 4, True, "all"),                    # T = 2 with a pair
+    (0, "rk4", 1, False, 1, "1", 1.0, 8, 12, "std", 0, False, True, 8, True, "all"),
+    (0, "rk4", 1, False, 3, "1", 0.5, 5, 1, "none", 1, False, False, 4, False, "all"),                # T = 1 without a pair: the loop and the fetch never run
+    (1, "euler", 0, False, 2, "P", 1.0, 8, 3, "all", 0, True, False, 5, False, "all"),                # T = 3 without a pair; room for 5 at B = 8
+    (1, "euler", 0, False, 1, "1", 0.5, 9, 12, "std", 3, False, True, 4, True, "all"),                # chunks 4 + 4 + 1
+    (1, "rk4", 0, False, 3, "1", 1.0, 4, 12, "std", 1, False, False, "whole", False, "all"),
+    (1, "rk4", 0, False, 2, "P", 0.5, 1, 1, "none", 0, False, False, "whole", True, "all"),           # B = 1, T = 1, a pair
+    (1, "rk4", 0, False, 3, "P", 1.0, 9, 3, "std", 0, False, False, 4, False, "all"),                 # nrec = P = 3 in chunks 4 + 4 + 1
+    (1, "rk4", 0, False, 1, "1", 1.0, 13, 12, "all", 0, True, False, 8, False, "all"),                # chunks 8 + 5: a ragged second chunk
+    (0, "rk4", 0, False, 2, "1", 1.0, 8, 12, "std", 1, False, False, 8, False, "all"),                # two full blocks without a start lag, 12 rows
+    (1, "euler", 0, False, 2, "1", 0.5, 8, 12, "std", 1, False, False, "whole", True, "xs+sinfo"),    # two full blocks of the wrench model, 12 rows
+)
+
+
+def draw_smooth(rng):
+    s = SETS["smooth"]
+    while True:
+        P, B, T = _pick(rng, s["P"]), _pick(rng, s["B"]), _pick(rng, SMOOTH_T_DRAW)
+        if P * B * T <= UKF_ROWS:                                     # a draw beyond the row budget is drawn again
+            break
+    return _smooth(rng, _pick(rng, s["model"]), _pick(rng, s["integ"]), _pick(rng, s["lag_mode"]), _pick(rng, s["lag"]), P, _pick(rng, s["nrec"]),
+                   _pick(rng, s["alpha"]), B, T, _pick(rng, s["measured"]), _pick(rng, s["r_inf"]), _pick(rng, s["q_zero"]), _pick(rng, s["wrap"]),
+                   _pick(rng, s["chunk"]), _pick(rng, s["terminal"]), _pick(rng, s["want"]))
+
+
 # ------------------------------------------------------------------------------------------ the lists
 _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
              mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
@@ -843,11 +915,11 @@ _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), 
              pinv_apply=(_pinv_apply, PINV_APPLY_CORNERS, draw_pinv_apply), multistep=(_multistep, MULTISTEP_CORNERS, draw_multistep),
              simulate=(_simulate, SIMULATE_CORNERS, draw_simulate), ukf=(_ukf, UKF_CORNERS, draw_ukf), lmpc=(_lmpc, LMPC_CORNERS, draw_lmpc),
              colstats=(_colstats, COLSTATS_CORNERS, draw_colstats), kmeanspp=(_kmeanspp, KMEANSPP_CORNERS, draw_kmeanspp),
-             lloyd=(_lloyd, LLOYD_CORNERS, draw_lloyd))
+             lloyd=(_lloyd, LLOYD_CORNERS, draw_lloyd), smooth=(_smooth, SMOOTH_CORNERS, draw_smooth))
 FAMILIES = tuple(_MAKE)                                             # the order is part of the seeds: new families go last
 EDMDC_FAMILIES = ("lift", "gram", "pinv_apply", "multistep", "simulate")
 N_CORNERS = {f: len(_MAKE[f][1]) for f in FAMILIES}                 # 12 for the five older families
-FILTER_FAMILIES = ("ukf", "lmpc")
+FILTER_FAMILIES = ("ukf", "lmpc", "smooth")
 KMEANS_FAMILIES = ("colstats", "kmeanspp", "lloyd")
 N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES_FILTER if f in FILTER_FAMILIES else N_CASES_KMEANS if f in KMEANS_FAMILIES
               else N_CASES for f in FAMILIES}
@@ -938,3 +1010,7 @@ def kmeanspp(seed=SEED):
 
 def lloyd(seed=SEED):
     return cases("lloyd", seed)
+
+
+def smooth(seed=SEED):
+    return cases("smooth", seed)

@@ -19,7 +19,9 @@ their own measures and bounds (a reference states its own gap condition as ref["
 So do the unscented Kalman filter (ukf) and the QP of the Koopman linear MPC (lmpc) in tests/sweep_ukf_lmpc.py, by the recipe above:
 a lane is a (candidate, recording) filter or a problem.  The k-means families (colstats, kmeanspp, lloyd) are in tests/sweep_kmeans.py:
 their references are exact (indices, labels and centres bit for bit), a reference asserts in prepare that every decision it takes
-is certified, no lane is left out, and the fourth figure of sweep_one is the smallest decision gap instead of a reference gap."""
+is certified, no lane is left out, and the fourth figure of sweep_one is the smallest decision gap instead of a reference gap.  The
+unscented RTS smoother (smooth) is in tests/sweep_smooth.py, by the recipe above with the covariance measures of
+tests/ukf_smooth_cases.py: a lane is a (candidate, recording) problem, every case runs as two calls, as one call and chunked."""
 import numpy as np
 
 import feedback_ref as fr
@@ -28,6 +30,7 @@ import koopman_mppi_ref as kr
 import mppi_ref as mr
 import sweep_edmdc as se
 import sweep_kmeans as sk
+import sweep_smooth as ss
 import sweep_ukf_lmpc as su
 from oracle import fossen_params as fp
 
@@ -403,7 +406,7 @@ def compare_window_pop(case, ref, got):
 
 
 PREPARE = dict(rollout_pop=prepare_rollout_pop, feedback=prepare_feedback, mppi=prepare_mppi, koopman_mppi=prepare_koopman_mppi,
-               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE, **sk.PREPARE)
+               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE, **sk.PREPARE, **ss.PREPARE)
 
 
 def sweep_one(eng, ctx, case, ref=None):
@@ -416,6 +419,8 @@ def sweep_one(eng, ctx, case, ref=None):
         e, e2 = se.sweep_one(eng, ctx, case, ref)
     elif fam in su.PREPARE:
         e, e2 = su.sweep_one(eng, ctx, case, ref)
+    elif fam in ss.PREPARE:
+        e, e2 = ss.sweep_one(eng, ctx, case, ref)
     elif fam in sk.PREPARE:
         e, e2 = sk.sweep_one(eng, ctx, case, ref)
         return e, e2, out, ref["min_gap"]

@@ -26,7 +26,19 @@ centres X[idx] - mean bit for bit; Lloyd's n_iter, labels and centres (bit for b
 oracle/kmeans_numpy.py with a certified E-step, the inertia at 1e-10 against long double, the relocation count, the same bytes from
 every public variant, both bounds rates and every operand form (host arrays, device rows with strides n, n + 1 and 40, on and off a
 16-byte boundary), and kmeans_loop_info showing that the path a case is tagged for ran.  For these families the fourth figure of
-sweep_one is the smallest decision gap of the reference, not a reference gap."""
+sweep_one is the smallest decision gap of the reference, not a reference gap.
+
+The unscented RTS smoother (smooth) runs 32 cases in four slices of 8, by tests/sweep_smooth.py: a lane is a (candidate, recording)
+problem; every case runs as tape filter plus backward pass (with the case's terminal pair), as one brov_ukf_smooth call and as a
+chunked one; xs and pstd_s in the mixed error, Ps, Ps0 and the tape's Pf and Pp as |dP_ij| / sqrt(P_ii P_jj), the tape's C as
+|dC_ab| / sqrt(Pf_aa Pp_bb), all at 1e-10 with the reference's own gap below a tenth of it; counts, nrows and the bit identities
+between the three runs exact.  Over the eight problems of tests/test_ukf_smooth_gpu.py (P = 2, T = 12, B = 3 or 5, every thruster
+case with a start lag, chunks 4 + 1 only) the list adds the three tape filters without a start lag, T = 1, 2 and 3 with and without a
+terminal pair, P = 1 and 3, B = 1, 4, 8, 9 and 13, a noise record per candidate in chunks, rows with 12 updates and recordings with
+none, r = +inf on 0 and 3 components, q = 0, middle chunks and a ragged second chunk, a budget rounded down to whole blocks, and strict
+subsets of the outputs.  The identities after it: repeats and problems alone, a split at every row, failures in the second and third
+chunk, a terminal pair given to a short prefix, an nrows edited by the caller (include/brov2.h: the clamp) and the life of the ctx's
+tape buffer."""
 import numpy as np
 import pytest
 
@@ -35,7 +47,9 @@ import sweep_cases as sc
 import sweep_edmdc as se
 import sweep_kmeans as sk
 import sweep_run as sr
+import sweep_smooth as ss
 import sweep_ukf_lmpc as su
+import ukf_cases as uc
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +83,10 @@ def test_sweep(eng, ctx, family, part):
     if family in sc.KMEANS_FAMILIES:
         print(f"{family} slice {part}: {len(cases)} cases, first figure {worst:.2e}, second {second:.2e} (tests/sweep_kmeans.py: sweep_one), smallest "
               f"decision gap {least:.2e}" + (" of R^2" if family == "lloyd" else " of its threshold"))
+        return
+    if family == "smooth":
+        print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e} (bound {ss.TOL:.0e}; two calls and one call, smoother, tape "
+              f"and filter outputs), worst reference gap {gap:.2e}, lanes left out {left}")
         return
     if family in sc.EDMDC_FAMILIES:
         print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e}, second figure (tests/sweep_edmdc.py: sweep_one) "
@@ -263,6 +281,210 @@ def test_ukf_lag_io_is_rollout_pops(eng, ctx):
             pop = eng.rollout_pop(0, c["integ"], [fv.params(n) for n in c["names"]], np.zeros((c["B"], 12)), ref["U"], su.DT_UKF, lag=lag,
                                   lag_mode=c["lag_mode"], store=False, ctx=ctx)
             assert np.all(f["info"][..., 2] == -1) and np.array_equal(f["lag"], pop["lag"]), c
+
+
+# ------------------------------------------------------------------------------------------ smooth: the exact identities
+SM_ALL = ss.F_OUTS + ss.S_OUTS + ("lag",)
+SM_TAPE = SM_ALL + ss.TAPE_KEYS
+
+
+def _smooth_corner(**want):
+    """the first corner of the smooth list that holds `want` (a callable value is a predicate on the field)"""
+    return [c for c in sc.corners("smooth") if all(v(c[k]) if callable(v) else c[k] == v for k, v in want.items())][0]
+
+
+@pytest.mark.parametrize("model", [0, 1])
+def test_smooth_repeats_and_problems_alone(eng, ctx, model):
+    """a thruster case without a start lag (TRACK = false) and a wrench case, 12 rows, run on their first B = 4, 8, 5 and 1 recordings:
+    two calls give equal bytes; candidate j alone and recording b alone carry the bits they have in the batch, in every filter and
+    smoother output and in the tape; the one-call smoother says the same"""
+    c = _smooth_corner(model=model, lag=False, B=8, T=12, P=lambda v: v > 1)
+    ins = su.ukf_inputs(c)
+    for B in (4, 8, 5, 1):
+        rec = slice(0, B)
+        a = ss.two_step(eng, ctx, c, ins, rec=rec)
+        assert np.all(a["nrows"] == c["T"]) and np.all(a["sinfo"][..., 0] == -1), (B, c)
+        ss.same(ss.two_step(eng, ctx, c, ins, rec=rec), a, SM_TAPE, ("repeat", B, c))
+        one = ss.smooth(eng, ctx, c, ins, rec=rec)
+        ss.same(one, a, SM_ALL, ("one call", B, c))
+        ss.same(ss.smooth(eng, ctx, c, ins, rec=rec), one, SM_ALL, ("one call, repeated", B, c))
+        for j in range(c["P"]):
+            ss.same(ss.two_step(eng, ctx, c, ins, cand=slice(j, j + 1), rec=rec), a, SM_TAPE, ("candidate alone", j, B, c), (0,), (j,))
+        for b in range(B):
+            ss.same(ss.two_step(eng, ctx, c, ins, rec=slice(b, b + 1)), a, SM_TAPE, ("recording alone", b, B, c), (slice(None), 0), (slice(None), b))
+            ss.same(ss.smooth(eng, ctx, c, ins, rec=slice(b, b + 1)), a, SM_ALL, ("recording alone, one call", b, B, c), (slice(None), 0), (slice(None), b))
+
+
+@pytest.mark.parametrize("model", [0, 1])
+def test_smooth_split_at_every_row(eng, ctx, model):
+    """T = 12 rows = T1 + (12 - T1), for every T1 = 1 .. 11: filter rows 0 .. T1 - 1 with a tape, smooth rows T1 .. 11 from (xT, PT,
+    lag_io), then the backward pass over the first span with the second's (xs[0], Ps0) as its terminal pair: the bits of the unbroken
+    call in xs, pstd_s, Ps and Ps0.  A thruster case with a start lag and a wrench case, more than one candidate each."""
+    c = _smooth_corner(model=model, lag=model == 0, T=12, P=lambda v: v > 1, measured="std")
+    ins = su.ukf_inputs(c)
+    whole = ss.smooth(eng, ctx, c, ins)
+    assert np.all(whole["info"][..., 2] == -1) and np.all(whole["sinfo"][..., 0] == -1), c
+    for T1 in range(1, c["T"]):
+        for j in range(c["P"]):                                      # x0 and P0 are shared by the candidates: resume one by one
+            cj = slice(j, j + 1)
+            first = ss.call(eng.ukf_filter, ctx, c, ins, cand=cj, rows=slice(0, T1), extra=dict(tape=True))
+            second = ss.smooth(eng, ctx, c, ins, cand=cj, rows=slice(T1, None), x0=first["xT"][0], P0=first["PT"][0], lag=first["lag"])
+            back = eng.ukf_rts(first["xf"], first["tape"], first["nrows"], terminal=(second["xs"][:, :, 0], second["Ps0"]), ctx=ctx)
+            for k in ss.ROWS:
+                assert np.array_equal(np.concatenate([back[k], second[k]], axis=2), whole[k][cj]), (k, T1, j, c)
+            assert np.array_equal(back["Ps0"], whole["Ps0"][cj]), (T1, j, c)
+
+
+def _nan_like(got, want):
+    return np.array_equal(np.isnan(got), np.isnan(want))
+
+
+def test_smooth_chunking_with_failures(eng, ctx):
+    """P = 3 candidates with a noise record each, B = 9 recordings, a tape budget of 4: chunks 4 + 4 + 1.  The corner of the list with
+    12 rows instead of its 3 (the row budget of the references does not bind here: the reference runs on the failing recording
+    alone).  The three conditions under which a filter stops, by the mechanisms of tests/test_ukf_smooth_gpu.py:
+    test_valid_prefix_in_every_wave_slot -- an indefinite P0 under a row 0 without measurements (n = 1), an infinite command at row 6
+    (n = 7), P0[i][i] = -2 r[i] on the last measured component of row 0 (n = 0; the largest r[i] of the candidates) -- in recording 5
+    (second chunk, wave slot 1, where the chunk-local index of the tape and of nrows is not the output row) and in recording 8 (the
+    lone recording of the third chunk): nrows, the NaN pattern of the rows and of the tape, info[2] and sinfo are the reference's; the
+    valid prefix is the problem cut to n rows, bit for bit; every other problem carries the bits of the clean call; the chunked
+    call equals the one-chunk call and the two calls."""
+    c3 = _smooth_corner(P=3, nrec=3, B=9, chunk=4, measured="std", terminal=False)
+    c = dict(c3, T=12)
+    assert sc.smooth_chunks(c) == [4, 4, 1]
+    ins = su.ukf_inputs(c)
+    P, B, T = c["P"], c["B"], c["T"]
+    Y0 = ins["Y"].copy()
+    Y0[:, 0] = np.nan
+    clean = ss.two_step(eng, ctx, c, ins)
+    clean_y0 = ss.two_step(eng, ctx, c, ins, Y=Y0)
+    assert np.all(clean["nrows"] == T) and np.all(clean_y0["nrows"] == T) and np.all(clean["sinfo"][..., 0] == -1), c
+    rmax = np.max([k.r for k in ins["cfgs"]], axis=0)
+    for b in (5, 8):
+        P0a = ins["P0"].copy()
+        P0a[b, 1, 0] = 2.0 * P0a[b, 0, 0]                            # (the upper triangle is NaN: never read)
+        U = ins["U"].copy()
+        U[b, 6, 0] = np.inf
+        comp = [k for k in range(12) if not np.isnan(ins["Y"][b, 0, k]) and np.isfinite(rmax[k])][-1]
+        P0c = ins["P0"].copy()
+        P0c[b, comp, comp] = -2.0 * rmax[comp]
+        for n, stage, base, kw in ((1, 2, clean_y0, dict(P0=P0a, Y=Y0)), (7, 2, clean, dict(U=U)), (0, 1, clean, dict(P0=P0c))):
+            what = (b, n, c)
+            got = ss.two_step(eng, ctx, c, ins, **kw)
+            with np.errstate(all="ignore"):
+                o = ss.ref_smooth(c, dict(ins, **kw), rec=slice(b, b + 1))
+            assert np.all(o["nrows"] == n) and np.all(o["info"][..., 2] == (n if stage == 1 else n - 1)), ("the reference stops there too", what)
+            assert np.array_equal(got["nrows"][:, b], o["nrows"][:, 0]) and np.array_equal(got["info"][:, b, 2], o["info"][:, 0, 2]), what
+            for k in ss.ROWS + ("tape", "xf", "pstd", "Ps0"):
+                assert _nan_like(got[k][:, b], o[k][:, 0]), (k, what)
+            assert np.array_equal(got["sinfo"][:, b, 0], o["sinfo"][:, 0, 0], equal_nan=True), what
+            assert uc.err(got["sinfo"][:, b, 1], o["sinfo"][:, 0, 1]) < ss.TOL, what
+            for k in ss.ROWS:
+                assert np.isnan(got[k][:, b, n:]).all() and np.isfinite(got[k][:, b, :n]).all(), (k, what)
+            if n:
+                cut = ss.smooth(eng, ctx, c, ins, rows=slice(0, n), **{k: (v[:, :n] if k in ("U", "Y") else v) for k, v in kw.items()})
+                for k in ss.ROWS:
+                    assert np.array_equal(got[k][:, b, :n], cut[k][:, b]), (k, "the valid prefix", what)
+                assert np.array_equal(got["Ps0"][:, b], cut["Ps0"][:, b]) and np.array_equal(got["sinfo"][:, b], cut["sinfo"][:, b]), what
+            for other in range(B):
+                if other != b:
+                    ss.same(got, base, SM_TAPE, ("another problem, with a failure in", other, what), (slice(None), other), (slice(None), other))
+            one = ss.smooth(eng, ctx, c, ins, **kw)
+            ss.same(one, got, SM_ALL, ("one chunk against two calls", what))
+            ss.same(ss.smooth(eng, ctx, c, ins, tape_bytes=sc.smooth_tape_bytes(c), **kw), one, SM_ALL, ("chunks 4 + 4 + 1 against one chunk", what))
+
+
+def test_smooth_terminal_pair_and_a_short_prefix(eng, ctx):
+    """a terminal pair (sweep_smooth.terminal_pair, from the filter's own xT and PT where they are finite) in a call in which one
+    problem stopped early: that problem is the call without a pair, bit for bit (the law ignores the pair when n < T); the problems
+    with n = T move by more than 1e3 TOL.  The upper triangle of Ps_T is NaN."""
+    c = _smooth_corner(B=4, T=12, P=lambda v: v > 1, measured="std")
+    ins = su.ukf_inputs(c)
+    b, n = 2, 7
+    U = ins["U"].copy()
+    U[b, n - 1, 0] = np.inf
+    f = ss.call(eng.ukf_filter, ctx, c, ins, extra=dict(tape=True), U=U)
+    want_n = np.full((c["P"], c["B"]), float(c["T"]))
+    want_n[:, b] = n
+    assert np.array_equal(f["nrows"], want_n), (f["nrows"], c)
+    clean = ss.call(eng.ukf_filter, ctx, c, ins)
+    pair = ss.terminal_pair(c, dict(xT=np.where(np.isnan(f["xT"]), clean["xT"], f["xT"]), PT=np.where(np.isnan(f["PT"]), clean["PT"], f["PT"])))
+    assert np.isnan(pair[1][..., 0, 1]).all() and np.isfinite(pair[0]).all()
+    without = eng.ukf_rts(f["xf"], f["tape"], f["nrows"], ctx=ctx)
+    with_pair = eng.ukf_rts(f["xf"], f["tape"], f["nrows"], terminal=pair, ctx=ctx)
+    ss.same(with_pair, without, ss.S_OUTS, ("a pair given to a short prefix", c), (slice(None), b), (slice(None), b))
+    assert np.isfinite(with_pair["xs"][:, b, :n]).all() and np.isnan(with_pair["xs"][:, b, n:]).all(), c
+    for other in range(c["B"]):
+        if other != b:
+            assert np.all(with_pair["sinfo"][:, other, 0] == -1) and np.isfinite(with_pair["Ps"][:, other]).all(), (other, c)
+            for j in range(c["P"]):
+                moved = uc.err(with_pair["xs"][j, other], without["xs"][j, other])
+                assert moved > 1e3 * ss.TOL, ("the pair must move a complete problem", moved, j, other, c)
+    optional = eng.ukf_rts(f["xf"], f["tape"], f["nrows"], terminal=pair, want=(), ctx=ctx)      # a pair with every optional output NULL
+    assert all(v is None for v in optional.values())
+    ss.same(eng.ukf_rts(f["xf"], f["tape"], f["nrows"], terminal=pair, want=("sinfo",), ctx=ctx), with_pair, ("sinfo",), ("sinfo alone", c))
+
+
+def test_smooth_nrows_edited_by_the_caller(eng, ctx):
+    """include/brov2.h: the tape and nrows are plain arrays, n = nrows clamped to 0 .. T, the fraction dropped, NaN as 0.  On a clean
+    T = 12 tape of B = 4, nrows of one problem in turn (every wave slot) is NaN, -inf, -1, 0, 0.5: every output NaN, sinfo included;
+    1: row 0 with the filter's bits, sinfo = (-1, +inf); 6.7: the problem cut to 6 rows; 12, 17, +inf: the clean bits.  The other
+    three problems never change."""
+    c = _smooth_corner(B=4, T=12, P=lambda v: v > 1, measured="std")
+    ins = su.ukf_inputs(c)
+    T = c["T"]
+    clean = ss.two_step(eng, ctx, c, ins)
+    assert np.all(clean["nrows"] == T), c
+    Pf = ss.us.tape_fields(clean["tape"])["Pf"]
+    cut6 = ss.smooth(eng, ctx, c, ins, rows=slice(0, 6))
+    for i, v in enumerate((np.nan, -np.inf, -1.0, 0.0, 0.5, 1.0, 6.7, 12.0, 17.0, np.inf)):
+        b = i % c["B"]
+        nrows = clean["nrows"].copy()
+        nrows[:, b] = v
+        got = eng.ukf_rts(clean["xf"], clean["tape"], nrows, ctx=ctx)
+        what = (v, b, c)
+        n = 0 if not v >= 1 else int(min(v, T))
+        for k in ss.ROWS:
+            assert np.isnan(got[k][:, b, n:]).all() and np.isfinite(got[k][:, b, :n]).all(), (k, what)
+        if n == 0:
+            assert np.isnan(got["Ps0"][:, b]).all() and np.isnan(got["sinfo"][:, b]).all(), what
+        elif n == 1:
+            assert np.array_equal(got["xs"][:, b, 0], clean["xf"][:, b, 0]) and np.array_equal(got["pstd_s"][:, b, 0], clean["pstd"][:, b, 0]), what
+            assert np.array_equal(got["Ps"][:, b, 0], Pf[:, b, 0]) and np.array_equal(got["Ps0"][:, b], Pf[:, b, 0]), what
+            assert np.all(got["sinfo"][:, b, 0] == -1) and np.all(got["sinfo"][:, b, 1] == np.inf), what
+        elif n == 6:
+            for k in ss.ROWS:
+                assert np.array_equal(got[k][:, b, :6], cut6[k][:, b]), (k, what)
+            assert np.array_equal(got["Ps0"][:, b], cut6["Ps0"][:, b]) and np.array_equal(got["sinfo"][:, b], cut6["sinfo"][:, b]), what
+        else:
+            ss.same(got, clean, ss.S_OUTS, ("the clean bits", what), (slice(None), b), (slice(None), b))
+        for other in range(c["B"]):
+            if other != b:
+                ss.same(got, clean, ss.S_OUTS, ("another problem", other, what), (slice(None), other), (slice(None), other))
+
+
+def test_smooth_tape_buffer_life():
+    """the ctx's tape buffer grows, shrinks below half and grows again between calls: every call gives the bits it gives on a fresh
+    ctx"""
+    from bluerov2_dynamics_amd import _lib, engine
+    large, small = _smooth_corner(B=13, T=12), _smooth_corner(B=1, T=1)
+    assert 2 * large["P"] * large["B"] * large["T"] > 8 * small["P"] * small["B"] * small["T"]
+    ins = {id(c): su.ukf_inputs(c) for c in (large, small)}
+    fresh = {}
+    for c in (large, small):
+        one = _lib.Context(0)
+        try:
+            fresh[id(c)] = ss.smooth(engine, one, c, ins[id(c)])
+        finally:
+            one.close()
+    kept = _lib.Context(0)
+    try:
+        for step, c in enumerate((large, small, large, small, large)):
+            ss.same(ss.smooth(engine, kept, c, ins[id(c)]), fresh[id(c)], SM_ALL, ("call", step, "on one ctx", c))
+            if step == 2:                                            # and a chunked call on the grown buffer, which needs less than half of it
+                ss.same(ss.smooth(engine, kept, c, ins[id(c)], tape_bytes=c["P"] * 4 * c["T"] * sc.SMOOTH_RECORD), fresh[id(c)], SM_ALL, ("chunked", c))
+    finally:
+        kept.close()
 
 
 # ------------------------------------------------------------------------------------------ lmpc: the exact identities

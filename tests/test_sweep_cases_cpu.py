@@ -1,4 +1,4 @@
-"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the fifteen families' value sets occurs in
+"""The case lists of tests/sweep_cases.py, without a GPU: (a) every value and corner pair of the sixteen families' value sets occurs in
 the hand-written corner list, by name, so that a list cannot shrink silently; (b) for every case the reference alone meets the
 conditions of tests/sweep_run.py (float64 against long double below a tenth of the bound on the compared lanes, at most 2 % of the
 lanes left out, never all), so that tests/test_family_sweeps_gpu.py can fail only because of a kernel; (c) the lists are a function
@@ -9,7 +9,11 @@ tests/koopman_lmpc_ref.py through tests/sweep_ukf_lmpc.py; with at most 27 lanes
 The k-means families (colstats, kmeanspp, lloyd; tests/sweep_kmeans.py) have exact references: (e) preparing one asserts that NumPy's
 own float64 statistics stay within a tenth of the bounds, that no round of the long-double k-means++ is undecided, and that no sample
 of any iteration of the certified Lloyd reference is undecided -- here for every case below 2^18 rows and for two of the larger ones
-(tests/test_family_sweeps_gpu.py prepares the others where it runs them)."""
+(tests/test_family_sweeps_gpu.py prepares the others where it runs them).
+The smoother family (smooth; tests/sweep_smooth.py) takes its reference from tests/ukf_smooth_ref.py with and without the case's
+terminal pair: a lane needs the gaps of tests/ukf_smooth_cases.py and of the filter below a tenth of 1e-10, wrap margins above 1e-6,
+forward and backward pivots above 1e-4 and every row and transition completed in both precisions; with at most 39 lanes a case the
+2 % cap again means that no lane is left out, and (f) the reference's clamp of an edited nrows is the header's."""
 import numpy as np
 import pytest
 
@@ -18,9 +22,9 @@ import sweep_cases as sc
 SLICES = 4
 PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52",
               lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921",
-              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88", colstats="36c523c381e38c6e", kmeanspp="ee864b94e8c1c124", lloyd="fedd81db4999f98f")
+              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88", colstats="36c523c381e38c6e", kmeanspp="ee864b94e8c1c124", lloyd="fedd81db4999f98f", smooth="805feafecaca48a9")
 CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12, ukf=17, lmpc=26,
-               colstats=12, kmeanspp=14, lloyd=29)
+               colstats=12, kmeanspp=14, lloyd=29, smooth=20)
 LLOYD_LARGE_ON_CPU = 2                    # cases from 2^18 rows on whose reference is prepared here too: the first with bounds, the first without
 
 
@@ -119,6 +123,55 @@ def test_filter_and_qp_corner_pairs():
     assert {c["hold"] * c["r"] for c in q} >= {60, 64, 66, 72}, "hold r on both sides of 64"
     assert {sc.lmpc_rows(c) for c in q if c["special"] == "warm"} == {(2, False), (3, False), (5, False)}
     assert any(c["hold"] > c["H"] for c in q) and any(c["M"] == 1 and c["shift"] for c in q)
+
+
+def test_smoother_corner_pairs():
+    """the edges the smooth corner list must contain, by name"""
+    s = sc.corners("smooth")
+    inst = {(0, "euler", 0, True), (0, "euler", 0, False), (0, "rk4", 0, True), (0, "rk4", 0, False), (0, "rk4", 1, True), (0, "rk4", 1, False),
+            (1, "euler", 0, False), (1, "rk4", 0, False)}
+    assert {sc.ukf_instance(c) for c in s} == inst, "the eight tape instantiations of ukf_filter_kernel"
+    for i in inst:                                                   # every instantiation with a full and with a ragged last block
+        assert any(sc.ukf_instance(c) == i and c["B"] % 4 == 0 for c in s) and any(sc.ukf_instance(c) == i and c["B"] % 4 for c in s), i
+    for T in (1, 2, 3):
+        assert _has("smooth", T=T, terminal=True) and _has("smooth", T=T, terminal=False), T
+    assert any(c["P"] == 3 and c["nrec"] == 3 and len(sc.smooth_chunks(c)) > 1 for c in s), "a noise record per candidate at P = 3, chunked"
+    chunks = [(c["B"], c["chunk"], sc.smooth_chunks(c)) for c in s]
+    assert (9, 4, [4, 4, 1]) in chunks and (13, 8, [8, 5]) in chunks and (13, 4, [4, 4, 4, 1]) in chunks, chunks
+    assert any(c["chunk"] == 5 and c["B"] >= 8 and sc.smooth_chunks(c)[0] == 4 for c in s), "room for 5 recordings is rounded down to 4"
+    assert any(c["P"] == 3 and c["nrec"] == 3 and c["B"] == 9 and sc.smooth_chunks(c) == [4, 4, 1] and c["measured"] == "std" and not c["terminal"]
+               for c in s), "the corner of test_smooth_chunking_with_failures"
+    for model in (0, 1):
+        assert _has("smooth", model=model, measured="none") and _has("smooth", model=model, measured="all"), model
+        assert any(c["model"] == model and c["B"] == 8 and c["T"] == 12 and not c["lag"] for c in s), ("two full blocks of 12 rows", model)
+    assert _has("smooth", q_zero=True) and _has("smooth", r_inf=0) and _has("smooth", r_inf=3) and _has("smooth", wrap=True, T=12, terminal=True)
+    assert _has("smooth", B=1) and _has("smooth", B=4, T=12) and any(c["lag"] and c["T"] == 12 and c["P"] > 1 for c in s)
+    assert {c["want_as"] for c in s} == set(sc.SMOOTH_WANT) and all(c["want"] == list(sc.SMOOTH_WANT[c["want_as"]]) for c in sc.cases("smooth"))
+    allc = sc.cases("smooth")
+    assert all(c["P"] * c["B"] * c["T"] <= sc.UKF_ROWS and c["nrec"] in (1, c["P"]) and sum(sc.smooth_chunks(c)) == c["B"] for c in allc)
+    assert all(not c["lag"] and c["lag_mode"] == 0 for c in allc if c["model"] == 1)
+    assert all(sc.smooth_tape_bytes(c) >= c["P"] * 4 * c["T"] * sc.SMOOTH_RECORD for c in allc), "never below the one block the host demands"
+    assert 3 * sum(c["T"] >= 2 for c in allc) >= 2 * len(allc), "at least two thirds of the cases have a transition"
+
+
+def test_reference_clamps_an_edited_nrows_as_the_header_says():
+    """(f) include/brov2.h: n = nrows clamped to 0 .. T, the fraction dropped, NaN as 0 -- and every n the filter itself writes as before"""
+    import sweep_smooth as ss
+    import ukf_smooth_ref as usr
+    c = [c for c in sc.corners("smooth") if c["B"] == 1 and c["T"] == 12][0]
+    o = ss.ref_smooth(c, ss.su.ukf_inputs(c), cand=slice(0, 1))
+    xf, tape = o["xf"][0, 0], o["tape"][0, 0]
+    rows = lambda n: int(np.isfinite(usr.rts_one(xf, tape, n, np.float64)["xs"][:, 0]).sum())
+    for n, want in ((np.nan, 0), (-np.inf, 0), (-1, 0), (0, 0), (0.5, 0), (1, 1), (6.7, 6), (12, 12), (17, 12), (np.inf, 12), (np.float64(7.0), 7),
+                    (np.longdouble(5), 5)):
+        assert rows(n) == want, (n, rows(n), want)
+    r = usr.rts_one(xf, tape, 0.5, np.float64)
+    assert np.isnan(r["sinfo"]).all() and np.isnan(r["Ps0"]).all()
+    r = usr.rts_one(xf, tape, 1, np.float64)
+    assert np.array_equal(r["sinfo"], [-1.0, np.inf]) and np.array_equal(r["xs"][0], xf[0])
+    for k in ("xs", "Ps", "sinfo"):
+        assert np.array_equal(usr.rts_one(xf, tape, np.inf, np.float64)[k], o[k][0, 0]) and np.array_equal(usr.rts_one(xf, tape, 6.7, np.float64)[k],
+                                                                                                             usr.rts_one(xf, tape, 6, np.float64)[k], equal_nan=True), k
 
 
 def _chunk_edges(c):

@@ -119,7 +119,8 @@ def rts_one(xf, tape, n, dtype, terminal=None):
     Ps = np.full((T, N, N), np.nan, dtype=dtype)
     Pf = np.stack([unpack(tape[t, PF], dtype) for t in range(T)])
     nan2 = np.full((N, N), np.nan, dtype=dtype)
-    n = int(min(max(n, 0), T)) if np.isfinite(n) else 0
+    n = float(n)
+    n = 0 if np.isnan(n) else int(min(max(n, 0.0), float(T)))       # the clamp of the header: the fraction dropped, NaN counts as 0, +inf as T
     if n == 0:
         return dict(xs=xs, pstd_s=xs.copy(), Ps=Ps, Ps0=nan2, sinfo=np.full(2, np.nan, dtype=dtype), Pf=Pf, rts_pivot_min=np.inf)
     if terminal is not None and n == T:
