@@ -73,11 +73,18 @@ hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode,
 // Backward (Rauch-Tung-Striebel) pass over a tape (ukf.hip; include/brov2.h: brov_ukf_rts_dev holds the law).  tape [P][B][T][UKF_TAPE]
 // and nrows [P][B] are a chunk's own; xf, the terminal pair and every output are laid out for Bs recordings per candidate and point
 // at the chunk's first recording.  xsT / PsT both nullptr or both set; every output may be nullptr.
+// em != nullptr selects the EM instantiation, which alone reads the fields behind sinfo: em [P][Bs][UKF_EM] (laid out like the other
+// outputs), Y [B][T][12] at the chunk's first recording (shared by the candidates), and the filter's records rec (one, or P).
 struct UkfRtsArgs {
     int64_t B, T, Bs;
     const double *xf, *tape, *nrows, *xsT, *PsT;
     double *xs, *pstd, *Ps, *Ps0, *sinfo;
+    double* em;
+    const double* Y;
+    const UkfRec* rec;
+    int rec_per_candidate, pad;
 };
+constexpr int UKF_EM = 37;      // doubles of one em record: Sq [12] | Sr [12] | nr [12] | nq  (include/brov2.h)
 hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a);
 // One MPPI update for B problems (mppi.hip; include/brov2.h: brov_mppi_step holds the law).  MppiRec is struct brov_mppi byte for
 // byte; rec is ONE device record.  fp holds one parameter set (per_problem = 0) or B.  x [B][nx], lag [B][24] or nullptr (zero), ref

@@ -186,7 +186,7 @@ struct Arena {
     size_t off = 0, limit = ~(size_t)0;     // limit: what lay() reserved
     bool bind = true, fits = true, listed = true;
     struct Copy { void* dev; void* host; size_t bytes; bool up, down; };
-    static constexpr int MAX_COPIES = 16;    // staged buffers of one call (brov_ukf_smooth has sixteen)
+    static constexpr int MAX_COPIES = 20;    // staged buffers of one call (brov_ukf_smooth_em has seventeen)
     Copy copies[MAX_COPIES];
     int ncopies = 0;
     explicit Arena(brov_ctx* ctx, bool staged_ = false) : c(ctx), staged(staged_) {}
@@ -1680,8 +1680,8 @@ static_assert(sizeof(brov_ukf) == 27 * 8 && sizeof(UkfRec) == 28 * 8, "brov_ukf:
 // both or neither.  sm: the smoother's outputs (brov_ukf_smooth[_dev]); then the tape is the ctx's own buffer of at most tape_bytes,
 // filled and read back a chunk of recordings at a time: one filter launch and one backward launch per chunk, the chunk's pointers
 // moved to its first recording and the outputs laid out for all B (UkfArgs::Bs).  A problem never looks at another, so the chunking
-// changes no bit.
-struct UkfSmoothOut { double *xs, *pstd_s, *Ps, *Ps0, *sinfo; };
+// changes no bit.  em_call: the caller is brov_ukf_smooth_em[_dev], whose backward launches are the EM instantiation and write em.
+struct UkfSmoothOut { double *xs, *pstd_s, *Ps, *Ps0, *sinfo; bool em_call = false; double* em = nullptr; };
 static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int integ, int lag_mode, int64_t P, const brov_params* params,
                       int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
                       const double* Y, double* lag_io, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
@@ -1697,8 +1697,9 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     if (empty) return BROV_OK;
     if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
     if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
+    if (sm && sm->em_call && !sm->em) return fail(c, BROV_ERR_ARG, fn + ": NULL em");
     if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
-    int64_t chunk = B;                           // recordings per launch
+    int64_t chunk = B;                          // recordings per launch
     if (sm) {
         const int W = ukf_waves_per_block();
         const double per_rec = (double)P * (double)T * UKF_TAPE * 8.0;           // tape bytes of one recording
@@ -1761,6 +1762,7 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
             back.Ps = sm->Ps ? a.out(sm->Ps, nout * T * 144) : nullptr;
             back.Ps0 = sm->Ps0 ? a.out(sm->Ps0, nout * 144) : nullptr;
             back.sinfo = sm->sinfo ? a.out(sm->sinfo, nout * 2) : nullptr;
+            back.em = sm->em_call ? a.out(sm->em, nout * UKF_EM) : nullptr;
         }
         args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
         args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
@@ -1791,6 +1793,8 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
     args.fp = d_fp;
     args.rec = d_rec;
+    back.rec = d_rec;
+    back.rec_per_candidate = args.rec_per_candidate;
     {
         CallTimer t(c);
         if (!sm) HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, args));
@@ -1807,6 +1811,8 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
             r.xf = f.xf; r.tape = f.tape; r.nrows = f.nrows;
             r.xs = at(back.xs, T * 12); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
             r.sinfo = at(back.sinfo, 2);
+            r.em = at(back.em, UKF_EM);
+            r.Y = f.Y;
             HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
         }
     }
@@ -1833,6 +1839,68 @@ int brov_ukf_rts_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double*
     CallTimer t(c);
     HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
     return BROV_OK;
+}
+
+// The backward pass with the sufficient statistics of the EM fit of q and r.  Of the filter's records it needs q and r alone.
+int brov_ukf_rts_em_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                        const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo,
+                        int64_t nrec, const brov_ukf* ukf, const double* d_Y, double* d_em) {
+    if (!c) return BROV_ERR_ARG;
+    const std::string fn = "brov_ukf_rts_em_dev";
+    if (P < 0 || B < 0 || T < 0) return fail(c, BROV_ERR_ARG, fn + ": negative size");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, fn + ": P must be <= 65535");
+    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, fn + ": B must be <= 2^31");
+    if (P == 0 || B == 0) return BROV_OK;
+    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
+    if (!d_xf || !d_tape || !d_nrows || !ukf || !d_Y || !d_em) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
+    if ((d_xs_T == nullptr) != (d_Ps_T == nullptr))
+        return fail(c, BROV_ERR_ARG, fn + ": the terminal pair d_xs_T, d_Ps_T goes together (both or neither)");
+    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    std::vector<UkfRec> rec((size_t)nrec);
+    for (int64_t k = 0; k < nrec; ++k) {
+        const std::string who = fn + ": ukf[" + std::to_string(k) + "]: ";
+        rec[k] = UkfRec{};
+        for (int i = 0; i < 12; ++i) {
+            if (!(ukf[k].q[i] >= 0.0) || std::isinf(ukf[k].q[i])) return fail(c, BROV_ERR_ARG, who + "q must be finite and >= 0");
+            if (!(ukf[k].r[i] >= 0.0)) return fail(c, BROV_ERR_ARG, who + "r must be >= 0 (+inf: never measured)");
+            rec[k].q[i] = ukf[k].q[i];
+            rec[k].r[i] = ukf[k].r[i];
+        }
+    }
+    DeviceGuard g(c);
+    UkfRec* d_rec;
+    Arena a(c);
+    int rc = a.lay("brov_ukf_rts_em_dev", [&] { d_rec = a.take<UkfRec>(nrec); });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // rec is a local
+    UkfRtsArgs r{};
+    r.B = B; r.T = T; r.Bs = B;
+    r.xf = d_xf; r.tape = d_tape; r.nrows = d_nrows; r.xsT = d_xs_T; r.PsT = d_Ps_T;
+    r.xs = d_xs; r.pstd = d_pstd_s; r.Ps = d_Ps; r.Ps0 = d_Ps0; r.sinfo = d_sinfo;
+    r.em = d_em; r.Y = d_Y; r.rec = d_rec; r.rec_per_candidate = nrec > 1;
+    CallTimer t(c);
+    HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
+    return BROV_OK;
+}
+
+int brov_ukf_smooth_em_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,
+                           const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U,
+                           const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
+                           double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo, int64_t tape_bytes,
+                           double* d_em) {
+    const UkfSmoothOut sm{d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo, true, d_em};
+    return ukf_filter(c, false, "brov_ukf_smooth_em_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
+                      d_xf, d_pstd, d_innov, d_xT, d_PT, d_info, nullptr, nullptr, &sm, tape_bytes);
+}
+
+int brov_ukf_smooth_em(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
+                       int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
+                       double* xf, double* pstd, double* innov, double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps,
+                       double* Ps0, double* sinfo, int64_t tape_bytes, double* em) {
+    const UkfSmoothOut sm{xs, pstd_s, Ps, Ps0, sinfo, true, em};
+    return ukf_filter(c, true, "brov_ukf_smooth_em", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov,
+                      xT, PT, info, nullptr, nullptr, &sm, tape_bytes);
 }
 
 int brov_ukf_filter_tape_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec,

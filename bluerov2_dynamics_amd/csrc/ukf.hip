@@ -48,6 +48,9 @@ __device__ __forceinline__ void ukf_wave_sync() {
     __builtin_amdgcn_wave_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
+// keeps the image reads of the EM term (ukf_em_term) from mixing with those of the phases around it, which would cost more registers
+// than a lane has
+__device__ __forceinline__ void ukf_fence() { asm volatile("" ::: "memory"); }
 // the value of lane l (a constant) / of the first lane, as a wave-uniform scalar
 __device__ __forceinline__ double ukf_lane(double v, int l) {
     return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
@@ -308,6 +311,13 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
 //   xs, G M   lane a: xs_t[a] = xf_t[a] + G[a][:] dx; the 144 entries of G M, one per lane and turn;
 //   Ps        Ps_t[a][b] = Pf_t[a][b] + (G M)[a][:] G[b][:] by the owner of (a, b), written to both triangles of the image.
 // Per row and problem 2.5 KB of tape come in (what the tape filter wrote), and 1.3 KB go out when Ps is asked for.
+//
+// EM: the pass also sums the sufficient statistics of the EM fit of q and r (include/brov2.h: brov_ukf_rts_em_dev holds the law) in
+// registers of lanes 0..11, lane i owning component i: at the end of a transition, where the fewest values are live (after the gain
+// the same code does not fit a lane's registers), lane i adds (Y[t][i] - xs_t[i])^2 + Ps_t[i][i] for the row just finished, solves
+// Lp Lp^T u = e_i by the gain's two substitutions through the L image and adds q_i + q_i^2 (u^T M u + (u . dx)^2) with the M and dx
+// of the image, which stay until the next deposit.  No LDS and no barrier of its own.  Every EM statement sits behind `if constexpr (EM)`;
+// the EM = false instantiation is the code it was before (DESIGN.md section 4 has the comparison of the two listings).
 struct UkfRtsLds {
     double rec[UKF_TAPE];               // the tape record of the transition
     double L[12][UKF_LD];               // Cholesky factor of Pp
@@ -318,6 +328,42 @@ struct UkfRtsLds {
     double dx[12];
 };
 
+// EM: the process term of one transition for component i (include/brov2.h: brov_ukf_rts_em_dev), q_i + q_i^2 (u^T M u + (u . dx)^2) with
+// u = Pp^-1 e_i: w from L w = e_i, then L^T u = w, the substitutions of a gain row, through the L, M and dx that the transition left
+// in the image (they stay until the next transition's deposit).  Every sum in index order.
+template <typename Lds>
+__device__ __forceinline__ double ukf_em_term(const Lds& S, int i, double qi) {
+    asm volatile("" : "+v"(i));                               // (keeps the twelve selects of e_i out of the loop-invariant registers)
+    double u[12];
+    ukf_fence();
+#pragma unroll
+    for (int j = 0; j < 12; ++j) {
+        double s = i == j ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < j; ++k) s = fma(-S.L[j][k], u[k], s);
+        u[j] = s / S.L[j][j];
+    }
+#pragma unroll
+    for (int j = 11; j >= 0; --j) {
+        double s = u[j];
+#pragma unroll
+        for (int k = j + 1; k < 12; ++k) s = fma(-S.L[k][j], u[k], s);
+        u[j] = s / S.L[j][j];
+    }
+    double umu = 0.0, udx = 0.0;
+#pragma unroll
+    for (int c = 0; c < 12; ++c) {
+        double mu = 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; ++k) mu = fma(S.M[c][k], u[k], mu);
+        umu = fma(u[c], mu, umu);
+        udx = fma(u[c], S.dx[c], udx);
+    }
+    ukf_fence();
+    return qi + qi * qi * (umu + udx * udx);
+}
+
+template <bool EM>
 __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArgs a) {
     __shared__ UkfRtsLds lds[UKF_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -351,7 +397,28 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         }
     };
     for (int64_t s = n; s < T; ++s) put_nan(s);
+    // EM: the statistics of component lr, the noise model of this candidate, the rows of this recording
+    double sq = 0.0, sr = 0.0, nr = 0.0, nq = 0.0, qi = 0.0, ri = 0.0;
+    const double* yp = nullptr;
+    if constexpr (EM) {
+        const UkfRec* f = a.rec + (a.rec_per_candidate ? blockIdx.y : 0);
+        qi = f->q[lr];
+        ri = f->r[lr];
+        yp = a.Y + b * T * 12 + lr;
+    }
+    auto put_em = [&](bool ok) {
+        if constexpr (EM) {
+            double* e = a.em + row * UKF_EM;
+            if (lane < 12) {
+                e[lane] = ok ? sq : NaN;
+                e[12 + lane] = ok ? sr : NaN;
+                e[24 + lane] = ok ? nr : NaN;
+            }
+            if (lane == 0) e[36] = ok ? nq : NaN;
+        }
+    };
     if (n == 0) {
+        put_em(false);
         if (a.Ps0) {
             for (int e = lane; e < 144; e += 64) a.Ps0[row * 144 + e] = NaN;
         }
@@ -388,15 +455,30 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
             for (int e = lane; e < 144; e += 64) Psp[s * 144 + e] = S.P[e / 12][e % 12];
         }
     };
+    // EM: the measurement term of a row whose (xsv, the image's P) is final; y = Y[s][lr]
+    auto em_row = [&](double y) {
+        if constexpr (EM) {
+            if (y == y && ri != INF) {
+                double v = y - xsv;
+                if (lr >= 3 && lr < 6) v = ukf_wrap(v);
+                sr += v * v + S.P[lr][lr];
+                nr += 1.0;
+            }
+        }
+    };
     image_P();
-    if (!terminal) put_row(n - 1);
+    if (!terminal) {
+        put_row(n - 1);
+        if constexpr (EM) em_row(yp[(n - 1) * 12]);
+    }
     // ---- the transitions, last first ---------------------------------------------------------------------------------------------
-    double r[5], xfv;
+    double r[5], xfv, yv = 0.0;
     auto fetch = [&](int64_t t) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) r[k] = tp[t * UKF_TAPE + 64 * k + lane];
         r[4] = lane < UKF_TAPE - 256 ? tp[t * UKF_TAPE + 256 + lane] : 0.0;
         xfv = xfp[t * 12];
+        if constexpr (EM) yv = yp[t * 12];
     };
     int64_t t = terminal ? n - 1 : n - 2, failed = -1;
     double minpiv = INF;
@@ -406,6 +488,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         for (int k = 0; k < 4; ++k) S.rec[64 * k + lane] = r[k];
         if (lane < UKF_TAPE - 256) S.rec[256 + lane] = r[4];
         const double pf0 = r[0], pf1 = r[1], xft = xfv;       // Pf's entries lie on their owners
+        const double yt = yv;
         if (t > 0) fetch(t - 1);
         ukf_wave_sync();                                      // rec written
         // Cholesky of Pp, as in the filter
@@ -493,6 +576,11 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         }
         image_P();
         put_row(t);
+        if constexpr (EM) {
+            em_row(yt);
+            sq += ukf_em_term(S, lr, qi);
+            nq += 1.0;
+        }
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
     const bool ok = failed < 0;
@@ -504,12 +592,14 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         const double v[2] = {(double)failed, minpiv};
         store_row<2>(a.sinfo + row * 2, v);
     }
+    put_em(ok);
 }
 
 hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a) {
     if (a.B <= 0 || P <= 0) return hipSuccess;
     const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
-    hipLaunchKernelGGL(ukf_rts_kernel, grid, dim3(64 * UKF_WAVES), 0, st, a);
+    if (a.em) hipLaunchKernelGGL(ukf_rts_kernel<true>, grid, dim3(64 * UKF_WAVES), 0, st, a);
+    else hipLaunchKernelGGL(ukf_rts_kernel<false>, grid, dim3(64 * UKF_WAVES), 0, st, a);
     return hipGetLastError();
 }
 

@@ -597,6 +597,7 @@ def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=No
 UKF_OUTPUTS = ("xf", "pstd", "innov", "xT", "PT", "info")
 UKF_SMOOTH_OUTPUTS = ("xs", "pstd_s", "Ps", "Ps0", "sinfo")
 UKF_TAPE = 312          # doubles of a tape record (include/brov2.h: brov_ukf_filter_tape_dev)
+UKF_EM = 37             # doubles of an em record: Sq [12] | Sr [12] | nr [12] | nq (include/brov2.h: brov_ukf_rts_em_dev)
 
 
 def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx):
@@ -636,7 +637,7 @@ def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx):
 
 def _ukf_shapes(P, B, T):
     return dict(xf=(P, B, T, 12), pstd=(P, B, T, 12), innov=(P, B, T, 12), xT=(P, B, 12), PT=(P, B, 12, 12), info=(P, B, 4),
-                xs=(P, B, T, 12), pstd_s=(P, B, T, 12), Ps=(P, B, T, 12, 12), Ps0=(P, B, 12, 12), sinfo=(P, B, 2))
+                xs=(P, B, T, 12), pstd_s=(P, B, T, 12), Ps=(P, B, T, 12, 12), Ps0=(P, B, 12, 12), sinfo=(P, B, 2), em=(P, B, UKF_EM))
 
 
 def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL, want=UKF_OUTPUTS, ctx=None, tape=False):
@@ -670,16 +671,23 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     return out
 
 
-def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None):
+def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _em=None):
     """Backward (Rauch-Tung-Striebel) pass over the tape of ukf_filter(..., tape=True) (include/brov2.h: brov_ukf_rts_dev holds
     the law).  xf [P,B,T,12], tape [P,B,T,UKF_TAPE] and nrows [P,B] as that call returned them (the tape is a documented plain
     array).  terminal: (xs_T [P,B,12], Ps_T [P,B,12,12]), the smoothed estimate of row T from a later span, or None.  want: any of
     UKF_SMOOTH_OUTPUTS.  Host arrays or device arrays (all of one kind).  Returns dict(xs, pstd_s [P,B,T,12], Ps [P,B,T,12,12],
-    Ps0 [P,B,12,12], sinfo [P,B,2] = first failed transition (-1: none), smallest pivot), with None for what was not wanted."""
+    Ps0 [P,B,12,12], sinfo [P,B,2] = first failed transition (-1: none), smallest pivot), with None for what was not wanted.
+    (_em = (cfg, Y): the call of ukf_rts_em.)"""
     want = tuple(want)
-    assert all(w in UKF_SMOOTH_OUTPUTS for w in want), f"want must be among {UKF_SMOOTH_OUTPUTS}"
+    keys = UKF_SMOOTH_OUTPUTS + (("em",) if _em else ())
+    assert all(w in keys for w in want), f"want must be among {keys}"
     host = isinstance(xf, (np.ndarray, list, tuple))
     ins = [xf, tape, nrows] + (list(terminal) if terminal is not None else [])
+    Y = None
+    if _em:
+        cfgs = [_em[0]] if isinstance(_em[0], _lib.BrovUkf) else list(_em[0])
+        ca = (_lib.BrovUkf * max(len(cfgs), 1))(*cfgs)
+        Y = as_f64(_em[1]) if host else _em[1]
     if host:
         ctx = ctx or default_context()
         arr = _NativeArrays(ctx)
@@ -692,32 +700,51 @@ def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None):
     want_shape = [(P, B, T, 12), (P, B, T, UKF_TAPE), (P, B), (P, B, 12), (P, B, 12, 12)]
     for v, shape in zip(ins, want_shape):
         assert tuple(int(s) for s in v.shape) == shape, f"shape {tuple(v.shape)} != {shape}"
+    if Y is not None:
+        assert tuple(int(s) for s in Y.shape) == (B, T, 12), f"Y shape {tuple(Y.shape)} != {(B, T, 12)}"
     if host:
         ins = [arr.upload(v) for v in ins]
+        Y = None if Y is None else arr.upload(Y)
     ins += [None] * (5 - len(ins))
     shapes = _ukf_shapes(P, B, T)
-    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_SMOOTH_OUTPUTS}
-    ctx.check(ctx.lib.brov_ukf_rts_dev(ctx.h, P, B, T, *(_dptr(v) for v in ins), *(_dptr(out[k]) for k in UKF_SMOOTH_OUTPUTS)),
-              "brov_ukf_rts_dev")
+    out = {k: (arr.empty(shapes[k]) if k in want or k == "em" else None) for k in keys}
+    head = (ctx.h, P, B, T, *(_dptr(v) for v in ins), *(_dptr(out[k]) for k in UKF_SMOOTH_OUTPUTS))
+    if _em:
+        ctx.check(ctx.lib.brov_ukf_rts_em_dev(*head, len(cfgs), ca, _dptr(Y), _dptr(out["em"])), "brov_ukf_rts_em_dev")
+    else:
+        ctx.check(ctx.lib.brov_ukf_rts_dev(*head), "brov_ukf_rts_dev")
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out
+
+
+def ukf_rts_em(xf, tape, nrows, cfg, Y, terminal=None, want=UKF_SMOOTH_OUTPUTS + ("em",), ctx=None):
+    """ukf_rts with the sufficient statistics of the EM fit of q and r (include/brov2.h: brov_ukf_rts_em_dev holds the law): cfg, one
+    _lib.BrovUkf or P, and Y [B,T,12] are those of the filter call that wrote the tape.  Returns the dict of ukf_rts, bit for bit,
+    and em [P,B,UKF_EM] = Sq [12] | Sr [12] | nr [12] | nq, which is always computed (fossen/estimate.py: em_update is the M-step)."""
+    return ukf_rts(xf, tape, nrows, terminal=terminal, want=want, ctx=ctx, _em=(cfg, Y))
 
 
 def ukf_smooth(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL,
                want=UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS, tape_bytes=0, ctx=None):
     """Filter and smooth in one call (brov_ukf_smooth_dev): the arguments and outputs of ukf_filter plus the outputs of ukf_rts.  The
     tape stays inside the library, in a buffer of the ctx of at most tape_bytes (0: 2 GiB): the recordings go through in chunks,
-    one filter launch and one backward launch each, which changes no bit."""
+    one filter launch and one backward launch each, which changes no bit.
+    want may also hold "em" (brov_ukf_smooth_em_dev): em [P,B,UKF_EM], the sufficient statistics of the EM fit of q and r as in
+    ukf_rts_em; every other output keeps its bits.  want=("info", "sinfo", "em") is one EM iteration and stores no rows."""
     want = tuple(want)
     keys = UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS
-    assert all(w in keys for w in want), f"want must be among {keys}"
+    assert all(w in keys + ("em",) for w in want), f"want must be among {keys + ('em',)}"
     ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx)
     shapes = _ukf_shapes(P, B, T)
     out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
-    ctx.check(ctx.lib.brov_ukf_smooth_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0),
-                                          _dptr(U), _dptr(Y), _dptr(lag_io), *(_dptr(out[k]) for k in keys), int(tape_bytes)),
-              "brov_ukf_smooth_dev")
+    head = (ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
+            _dptr(lag_io), *(_dptr(out[k]) for k in keys), int(tape_bytes))
+    if "em" in want:
+        out["em"] = arr.empty(shapes["em"])
+        ctx.check(ctx.lib.brov_ukf_smooth_em_dev(*head, _dptr(out["em"])), "brov_ukf_smooth_em_dev")
+    else:
+        ctx.check(ctx.lib.brov_ukf_smooth_dev(*head), "brov_ukf_smooth_dev")
     out["lag"] = lag_io
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}

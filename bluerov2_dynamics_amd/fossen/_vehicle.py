@@ -268,6 +268,28 @@ class VehicleBase:
         r = engine.ukf_filter(self.MODEL, integrator, list(params_list), cfg, x0, P0, U, Y, dt, want=("info",), ctx=self._ctx)
         return r["info"][:, :, 0]
 
+    def fit_noise(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler", iters=20, tol=1e-4, **kw):
+        """Fit the filter's q and r to recordings by expectation-maximisation from the guess `cfg` (fossen/estimate.py: fit_noise; an
+        iteration is one engine.ukf_smooth that stores no rows).  Y, U, x0, P0, params and their defaults as smooth_states; x0 and
+        P0 come from the START record and are not re-estimated.  kw: fit_q, fit_r (bool or bool[12]), q_floor, r_floor,
+        tape_bytes.  Returns dict(cfg: the fitted record, for filter_states / smooth_states, q, r [12], loglik [its + 1] the
+        log-likelihood summed over the recordings after each update, q_hist, r_hist [its + 1, 12], n_excluded, converged)."""
+        from . import estimate
+        _, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
+        f = estimate.fit_noise(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, iters=iters, tol=tol, ctx=self._ctx, **kw)
+        return dict(cfg=f["cfg"][0], q=f["q"][0], r=f["r"][0], loglik=f["loglik"][:, 0], q_hist=f["q_hist"][:, 0], r_hist=f["r_hist"][:, 0],
+                    n_excluded=f["n_excluded"], converged=f["converged"])
+
+    def fit_noise_population(self, params_list, Y, U, dt, cfg, x0=None, P0=None, integrator="euler", iters=20, tol=1e-4, **kw):
+        """fit_noise for each of P vehicles (params_list) in the same launches: one noise model per candidate, so that
+        log_likelihood_population need not score every candidate under one guessed noise model.  cfg: the start, one record or P.
+        Returns the dict of estimate.fit_noise (cfg: P records, q, r [P,12], loglik [its + 1, P], ..) plus loglik_fitted [P] =
+        loglik[-1], the log-likelihood of each candidate under its own fitted noise, summed over the recordings."""
+        from . import estimate
+        _, Y, U, x0, P0, _ = self._ukf_inputs(Y, U, cfg if isinstance(cfg, _lib.BrovUkf) else cfg[0], x0, P0, None)
+        f = estimate.fit_noise(self.MODEL, integrator, list(params_list), cfg, x0, P0, U, Y, dt, iters=iters, tol=tol, ctx=self._ctx, **kw)
+        return dict(f, loglik_fitted=f["loglik"][-1])
+
     def simulate_mppi(self, x0, ref, dt, cfg, T, K, H, plant_params=None, integrator="euler", seed=0, planner=None):
         """Receding-horizon control of B plants by the sampling-based model-predictive update (engine.mppi_step; fossen/control.py:
         mppi builds `cfg`), planned with THIS vehicle's parameters.  The loop is device-resident: the state, the thruster lag and

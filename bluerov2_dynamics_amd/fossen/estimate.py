@@ -1,9 +1,10 @@
 """State estimation on the Fossen model: the record of the unscented Kalman filter (engine.ukf_filter, VehicleBase.filter_states,
-VehicleBase.log_likelihood_population).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
+VehicleBase.log_likelihood_population), and the EM fit of its q and r (em_update, fit_noise; VehicleBase.fit_noise).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
 scalar Kalman updates with the measured components of the state (a NaN = not measured), then an unscented prediction through the
 vehicle's own step with 2 n + 1 = 25 sigma points.
 
-Nothing here runs on the device; the struct goes to the kernel through engine.ukf_filter."""
+Nothing here runs on the device: the struct goes to the kernel through engine.ukf_filter, and fit_noise sums nothing itself (the
+statistics of an EM iteration come from engine.ukf_smooth)."""
 import numpy as np
 
 from .. import _lib
@@ -57,3 +58,91 @@ def default_start(Y, cfg):
         x0[b] = np.where(need, Y[b, full[0]], 0.0)
     d = np.where(need, 4.0 * np.where(need, r, 0.0), P0_STAND_IN)
     return x0, np.repeat(np.diag(d)[None], Y.shape[0], axis=0)
+
+
+# ---- fitting q and r by expectation-maximisation (include/brov2.h: brov_ukf_rts_em_dev holds the law of the statistics) -------------
+def _records(cfgs, P):
+    out = [cfgs] * P if isinstance(cfgs, _lib.BrovUkf) else list(cfgs)
+    if len(out) == 1 and P > 1:
+        out = out * P
+    if len(out) != P:
+        raise ValueError(f"{len(out)} records for {P} candidates: one or P")
+    return out
+
+
+def em_update(em, info, sinfo, cfgs, fit_q=True, fit_r=True, q_floor=0.0, r_floor=0.0):
+    """The M-step of the EM fit of q and r, on the host.  em [P,B,37] = Sq [12] | Sr [12] | nr [12] | nq, info [P,B,4] and sinfo
+    [P,B,2] are those of engine.ukf_smooth(..., want=("info", "sinfo", "em")); cfgs is the record (or the P records) that call ran
+    under.  Per candidate, pooled over its recordings whose filter (info[2] = -1) and backward pass (sinfo[0] = -1) both completed:
+        q_i <- max(sum Sq_i / sum nq, q_floor),     r_i <- max(sum Sr_i / sum nr_i, r_floor) where sum nr_i > 0,
+    otherwise r_i stays, so +inf stays +inf.  fit_q / fit_r: a bool or bool[12], the components to update.  q_i = 0 stays 0 (the
+    statistic is 0 there: EM cannot leave a zero).  x0 and P0 are not re-estimated.  Returns (the P new records, the number of
+    (candidate, recording) problems left out); ValueError when every recording of a candidate failed."""
+    em, info, sinfo = np.asarray(em, float), np.asarray(info, float), np.asarray(sinfo, float)
+    P = em.shape[0]
+    cfgs = _records(cfgs, P)
+    fq, fr = np.broadcast_to(np.asarray(fit_q, bool), (12,)), np.broadcast_to(np.asarray(fit_r, bool), (12,))
+    out, left = [], 0
+    for j in range(P):
+        ok = (info[j, :, 2] == -1) & (sinfo[j, :, 0] == -1)
+        left += int((~ok).sum())
+        if not ok.any():
+            raise ValueError(f"every recording of candidate {j} failed: no statistics to fit its noise model from")
+        e = em[j][ok]
+        q, r = np.array(list(cfgs[j].q)), np.array(list(cfgs[j].r))
+        nq, nr = e[:, 36].sum(), e[:, 24:36].sum(axis=0)
+        if nq > 0:
+            q = np.where(fq, np.maximum(e[:, :12].sum(axis=0) / nq, q_floor), q)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            r = np.where(fr & (nr > 0), np.maximum(e[:, 12:24].sum(axis=0) / nr, r_floor), r)
+        out.append(ukf(q, r, cfgs[j].alpha, cfgs[j].beta, cfgs[j].kappa))
+    return out, left
+
+
+def fit_noise(model, integrator, params_list, cfg, x0, P0, U, Y, dt, iters=20, tol=1e-4, fit_q=True, fit_r=True, q_floor=0.0, r_floor=0.0,
+              lag=None, lag_mode=0, tape_bytes=0, ctx=None):
+    """EM fit of the filter's q and r to recordings, one noise model per candidate of params_list, all candidates in the same
+    launches.  cfg: the start, one record or P; x0 [B,12], P0 [B,12,12], U [B,T,nu], Y [B,T,12] as engine.ukf_smooth takes them
+    (host arrays; they are uploaded once).  An iteration is one engine.ukf_smooth(want=("info", "sinfo", "em")), which stores no
+    rows, and em_update on the host.  The loop stops after `iters` updates, or before an update when the rise of the summed
+    log-likelihood over the last update is below tol times its magnitude; an update that lowered it (the E-step is approximate, so
+    EM's monotonicity is not guaranteed) is taken back.  ValueError when every recording of a candidate failed.
+    Returns dict(cfg: the P fitted records, q, r [P,12], loglik [its + 1, P] the log-likelihood of each candidate summed over its
+    completed recordings, row k under the noise model after k updates, q_hist, r_hist [its + 1, P, 12], n_excluded: the
+    (candidate, recording) problems left out of the last update, converged)."""
+    from .. import engine
+    P = len(params_list)
+    cfgs = _records(cfg, P)
+    ctx = ctx or engine.default_context()
+    D = engine.DevArray.from_host
+    dev = [D(ctx, np.asarray(v, float)) for v in (x0, P0, U, Y)]
+    lag_d = None if lag is None else D(ctx, np.asarray(lag, float))
+    hist = lambda: (np.array([list(c.q) for c in cfgs]), np.array([list(c.r) for c in cfgs]))
+
+    def loglik(info, sinfo=None):
+        ok = info[:, :, 2] == -1
+        if sinfo is not None:
+            ok &= sinfo[:, :, 0] == -1
+        return np.where(ok, info[:, :, 0], 0.0).sum(axis=1)
+    ll, qh, rh, left, converged = [], [], [], 0, False
+    for it in range(int(iters) + 1):
+        q, r = hist()
+        qh.append(q)
+        rh.append(r)
+        if it == iters:
+            o = engine.ukf_filter(model, integrator, list(params_list), cfgs, *dev, dt, lag=lag_d, lag_mode=lag_mode, want=("info",), ctx=ctx)
+            ll.append(loglik(o["info"].numpy()))
+            break
+        o = engine.ukf_smooth(model, integrator, list(params_list), cfgs, *dev, dt, lag=lag_d, lag_mode=lag_mode, want=("info", "sinfo", "em"),
+                              tape_bytes=tape_bytes, ctx=ctx)
+        info, sinfo = o["info"].numpy(), o["sinfo"].numpy()
+        ll.append(loglik(info, sinfo))
+        if it >= 1 and ll[-1].sum() - ll[-2].sum() < tol * abs(ll[-2].sum()):
+            converged = True
+            if ll[-1].sum() < ll[-2].sum():      # the E-step is approximate: an update may lose likelihood; then the one before stands
+                cfgs = before
+                del ll[-1], qh[-1], rh[-1]
+            break
+        before = cfgs
+        cfgs, left = em_update(o["em"].numpy(), info, sinfo, cfgs, fit_q, fit_r, q_floor, r_floor)
+    return dict(cfg=cfgs, q=qh[-1], r=rh[-1], loglik=np.array(ll), q_hist=np.array(qh), r_hist=np.array(rh), n_excluded=left, converged=converged)

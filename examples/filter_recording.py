@@ -11,7 +11,14 @@ with identify.sample_parameters (rov.log_likelihood_population: every candidate 
 With --smooth, rov.smooth_states (the unscented Rauch-Tung-Striebel smoother, brov_ukf_smooth) runs instead of the filter alone and
 the smoothed RMSE is printed beside the filtered one: the recording is complete, so every row may be estimated from all rows.
 
-    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth]
+With --fit-noise the noise model is not given but fitted: rov.fit_noise runs expectation-maximisation on q and r (brov_ukf_smooth_em,
+one smoother call per iteration that stores no rows) from a deliberately wrong guess, q x 100 and sigma x 3, and the script prints
+the log-likelihood per iteration, the fitted against the true sigma, and the filtered and smoothed RMSE under the guess and under
+the fit.  EM finds r within a few updates and moves q slowly (some 75 updates until the log-likelihood rises by less than 1e-4 of
+itself here); stopped after 10 or 20, r has already shrunk to the truth while q is still far too large, and the RMSE is then worse
+than under the guess, so the loop runs to its tolerance.
+
+    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth] [--fit-noise]
 """
 import argparse
 import os
@@ -38,7 +45,38 @@ def drawn_vehicles(base, n, seed, rel_std):
     return identify.sample_parameters(fit, n, seed=seed)
 
 
-def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True, smooth=False):
+def fit_noise_demo(rov, true, X, Y, U, dt, start, P0, integrator, iters, verbose):
+    """EM from (q x 100, sigma x 3): dict(sigma_start, sigma_fit [12], q_fit, loglik_fit [its + 1], fit_converged,
+    rmse_filtered_before / _after, rmse_smoothed_before / _after (second half, measured entries))"""
+    T = Y.shape[0]
+    r = (3.0 * SIGMA) ** 2
+    r[UNMEASURED] = np.inf
+    guess = estimate.ukf(q=1e-4, r=r)
+    half = slice(T // 2, T)
+    seen = ~np.isnan(Y[half])
+    rmse = lambda x: float(np.sqrt(np.mean((x[half] - X[:T][half])[seen] ** 2)))
+    before = rov.smooth_states(Y, U, dt, guess, x0=start, P0=P0, params=true, integrator=integrator)
+    fit = rov.fit_noise(Y, U, dt, guess, x0=start, P0=P0, params=true, integrator=integrator, iters=iters)
+    after = rov.smooth_states(Y, U, dt, fit["cfg"], x0=start, P0=P0, params=true, integrator=integrator)
+    out = dict(sigma_start=3.0 * SIGMA, sigma_fit=np.sqrt(fit["r"]), q_fit=fit["q"], loglik_fit=fit["loglik"], fit_converged=fit["converged"],
+               rmse_filtered_before=rmse(before["x"]), rmse_filtered_after=rmse(after["x"]),
+               rmse_smoothed_before=rmse(before["xs"]), rmse_smoothed_after=rmse(after["xs"]))
+    if verbose:
+        print(f"EM fit of q and r from q x 100 and sigma x 3, {len(fit['loglik']) - 1} updates" + (" (converged)" if fit["converged"] else ""))
+        for k, l in enumerate(fit["loglik"]):
+            if k < 5 or k % 10 == 0 or k == len(fit["loglik"]) - 1:
+                print(f"    after {k:3d} updates   log-likelihood {l:12.1f}")
+        print("    component   sigma true    start   fitted")
+        for i in range(12):
+            if i != UNMEASURED:
+                print(f"    {i:9d}   {SIGMA[i]:10.4f} {3 * SIGMA[i]:8.4f} {out['sigma_fit'][i]:8.4f}")
+        print(f"    RMSE filtered {out['rmse_filtered_before']:.4f} -> {out['rmse_filtered_after']:.4f}, "
+              f"smoothed {out['rmse_smoothed_before']:.4f} -> {out['rmse_smoothed_after']:.4f}")
+    return out
+
+
+def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True, smooth=False, fit_noise=False,
+        fit_iters=100):
     """Returns dict(X [T+1,12] the truth, Y [T,12] the noisy rows, x, std, innov [T,12] of the filter, rmse_raw, rmse_filtered, nis,
     loglik [draws + 1] with the true vehicle at index 0, order: the candidates from best to worst); with smooth also xs, std_s
     [T,12] of the smoother, rmse_smoothed and rmse_unmeasured_filtered / _smoothed (the never-measured roll rate)"""
@@ -73,6 +111,8 @@ def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="r
         miss = lambda x: float(np.sqrt(np.mean((x[half, UNMEASURED] - X[:T][half, UNMEASURED]) ** 2)))
         extra = dict(xs=f["xs"], std_s=f["std_s"], rmse_smoothed=float(np.sqrt(np.mean((f["xs"][half] - X[:T][half])[seen] ** 2))),
                      rmse_unmeasured_filtered=miss(f["x"]), rmse_unmeasured_smoothed=miss(f["xs"]))
+    if fit_noise:
+        extra.update(fit_noise_demo(rov, true, X, Y, U, dt, start, P0, integrator, fit_iters, verbose))
     cands = [true] + drawn_vehicles(true, int(draws), seed + 1, rel_std)
     ll = rov.log_likelihood_population(cands, Y, U, dt, cfg, x0=start, P0=P0, integrator=integrator)[:, 0]
     order = np.argsort(-ll)
@@ -103,10 +143,12 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--small", action="store_true", help="3 s and 7 draws: runs in seconds")
     ap.add_argument("--smooth", action="store_true", help="also smooth the recording (rov.smooth_states) and print the smoothed RMSE")
+    ap.add_argument("--fit-noise", action="store_true", help="fit q and r by EM from a wrong guess (rov.fit_noise) and print what it gains")
     a = ap.parse_args(argv)
     if a.small:
         a.seconds, a.draws = 3.0, 7
-    return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth)
+    return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth,
+               fit_noise=a.fit_noise)
 
 
 if __name__ == "__main__":

@@ -448,7 +448,40 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
  * Refused on the host, before anything is copied, allocated or launched, with a text that names the function called: everything
  * brov_ukf_filter refuses, a negative tape_bytes, and a tape_bytes smaller than one block of recordings (P * 4 * T * 2496 bytes).
  * Deterministic (no atomics, fixed summation orders): two calls give the same bits.
- * Still missing: the lag-one smoothed cross-covariance (for EM), a quaternion model, full Q and R. */
+ * Still missing: a quaternion model, full Q and R.
+ *
+ * ---- fitting q and r: the sufficient statistics of expectation-maximisation (EM) ------------------------------------------------
+ * Every call above takes a record whose q[12] and r[12] are guesses.  brov_ukf_rts_em_dev and brov_ukf_smooth_em[_dev] are the
+ * backward pass and the smooth calls, unchanged bit for bit in every output they share with them, which also sum what one EM
+ * iteration needs.  Model: x_{t+1} = f(x_t, u_t) + w, w ~ N(0, Q), Q = diag(q); Y_t[i] = x_t[i] + v, v ~ N(0, r[i]).  The
+ * filter predicts Pp = (sigma-point covariance) + Q.  Taking the sigma-point covariance as independent of w, conditioning on all
+ * rows Y gives for the transition t -> t + 1
+ *     E[w w^T | Y] = Q + Q Pp^-1 (Ps_{t+1} - Pp_{t+1} + d d^T) Pp^-1 Q,   d = xs_{t+1} - xp_{t+1},
+ * in which everything is local to the transition.  For a linear model this IS the Shumway-Stoffer expression with the lag-one
+ * smoothed covariance Ps_{t+1} G_t^T substituted, so no lag-one covariance has to be formed or stored (tests/test_ukf_em_cpu.py
+ * checks the identity on a linear-Gaussian model to 1e-12).  Q is diagonal, so only the diagonal is needed.
+ * Per (candidate, recording), with n = nrows and the walk of brov_ukf_rts_dev (terminal pair included), in the order of the
+ * backward pass, last row first, with M = Ps_{t+1} - Pp_{t+1} and d as that pass has them:
+ *     Sq[i]  the sum over every completed transition t of  q_i + q_i^2 (u^T M u + (u . d)^2),  where u solves Lp Lp^T u = e_i by
+ *            the forward and the backward substitution of a gain row; the inner sums run in index order;
+ *     nq     the number of transitions summed: n - 1, or n with a terminal pair;
+ *     Sr[i]  the sum of  v^2 + Ps_t[i][i],  v = Y[t][i] - xs_t[i] (for i in {3, 4, 5} wrapped by the filter's rule), over the rows
+ *            t < n where Y[t][i] is not NaN and r_i is finite; row n-1 without a terminal pair uses (xf, Pf)_{n-1}, as the
+ *            smoother's outputs do;
+ *     nr[i]  the number of terms of Sr[i].
+ * Output em [P][B][37] = Sq[12] | Sr[12] | nr[12] | nq, the counts stored as doubles like info.  q_i = 0 gives Sq[i] = 0.0
+ * exactly: EM cannot leave a zero, so a component fixed at q_i = 0 stays there.  n = 0, or a failed backward transition: 37 NaN
+ * for that problem alone.  Y [B][T][12] is indexed by the recording and shared by the candidates; q and r come from the record of
+ * candidate j (nrec = 1 or P).  Spans split in time add: the em of span 2 (no terminal pair) plus the em of span 1 (with span 2's
+ * pair) equals that of the unbroken call up to rounding.  Deterministic: per-lane accumulators, no atomics.
+ * The M-step is the host's (fossen/estimate.py: em_update), per candidate, pooled over its recordings whose filter and backward
+ * pass both completed:  q_i <- max(sum Sq_i / sum nq, q_floor);  r_i <- max(sum Sr_i / sum nr_i, r_floor) where sum nr_i > 0,
+ * otherwise r_i stays (+inf stays +inf).  x0 and P0 are not re-estimated.
+ * brov_ukf_rts_em_dev: the arguments of brov_ukf_rts_dev, then nrec, ukf [nrec] (host), d_Y and d_em.  brov_ukf_smooth_em[_dev]:
+ * the arguments of brov_ukf_smooth[_dev], then em; they run through the same chunks.  Every per-row output may be NULL: an EM
+ * iteration asks for info, sinfo and em and then stores no rows.
+ * Refused with BROV_ERR_ARG and a text naming the function, before any copy or launch: everything the plain calls refuse; a NULL
+ * d_Y, ukf or em; nrec not in {1, P}; a negative, NaN or infinite q; a negative or NaN r.  P = 0 or B = 0: BROV_OK. */
 BROV_API int brov_ukf_filter_tape_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
                              int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
                              const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
@@ -466,6 +499,19 @@ BROV_API int brov_ukf_smooth_dev(brov_ctx* ctx, int model, int integrator, int l
                         const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
                         double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
                         double* d_Ps0, double* d_sinfo, int64_t tape_bytes);
+BROV_API int brov_ukf_rts_em_dev(brov_ctx* ctx, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                        const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0,
+                        double* d_sinfo, int64_t nrec, const brov_ukf* ukf /* [nrec], host */, const double* d_Y, double* d_em);
+BROV_API int brov_ukf_smooth_em(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                       int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0,
+                       const double* P0, const double* U, const double* Y, double* lag_io, double* xf, double* pstd, double* innov,
+                       double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps, double* Ps0, double* sinfo,
+                       int64_t tape_bytes, double* em);
+BROV_API int brov_ukf_smooth_em_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                           int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                           const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
+                           double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
+                           double* d_Ps0, double* d_sinfo, int64_t tape_bytes, double* d_em);
 
 /* ---- model-predictive control: one sampling-based (MPPI) update, sampled, rolled out and scored on the device ---------------------
  * brov_mppi_step performs one MPPI update for B independent problems (B vehicles, or B draws of a fit).  Problem b has a state
