@@ -171,9 +171,7 @@ struct CallTimer {
 
 // Bump allocator over the ctx scratch arena; grows (after a stream sync) when too small.
 //
-// The EDMDc and k-means code sizes a call by hand: reserve(total), then take<T>(count).
-//
-// The Fossen and PINc entry points declare their buffers once, in a layout function that lay() runs twice: a measuring pass in which
+// An entry point declares its buffers once, in a layout function that lay() runs twice: a measuring pass in which
 // take only adds up offsets, then -- the arena grown to exactly that total -- a binding pass that hands the pointers out, so a take
 // cannot leave what was reserved.  A buffer with a host side is declared with in / out / inout.  In a host form (`staged`) it is arena
 // memory and a recorded copy: lay() ends with the uploads, finish() makes the downloads and the one stream synchronisation of the
@@ -183,7 +181,7 @@ struct CallTimer {
 struct Arena {
     brov_ctx* c;
     const bool staged;
-    size_t off = 0, limit = ~(size_t)0;     // limit: what lay() reserved
+    size_t off = 0, limit = 0;              // limit: what lay() reserved
     bool bind = true, fits = true, listed = true;
     struct Copy { void* dev; void* host; size_t bytes; bool up, down; };
     static constexpr int MAX_COPIES = 20;    // staged buffers of one call (brov_ukf_smooth_em has seventeen)
@@ -191,7 +189,6 @@ struct Arena {
     int ncopies = 0;
     explicit Arena(brov_ctx* ctx, bool staged_ = false) : c(ctx), staged(staged_) {}
     static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
-    int reserve(size_t total) { return grow(al(total) + 4096); }
     int grow(size_t total) {
         if (total <= c->scratch_cap) return BROV_OK;
         (void)hipStreamSynchronize(c->stream);
@@ -246,15 +243,26 @@ struct Arena {
     }
 };
 
-// The lifted-row cache (edmdc_lift_cache) is keyed by the DEVICE addresses of X / U / C.  The host entry points edmdc_gram and
-// edmdc_pinv_apply stage their arrays in allocations of their own and free them on return: a cache armed with those addresses
-// would be found valid by the next host call of the same shape -- hipMalloc hands the same addresses out again -- and that call
-// would read the lifted rows of the PREVIOUS data.  Only a direct _dev call (whose buffers the caller owns and promises to leave
-// alone) may leave the cache armed: the host wrappers disarm it on entry and on every way out.
+// device memory that lives as long as a scope of kmeans_relocate (the one place that allocates beside a bound arena)
+template <typename T> struct RelocBlock {
+    T* p = nullptr;
+    RelocBlock() = default;
+    RelocBlock(const RelocBlock&) = delete;
+    RelocBlock& operator=(const RelocBlock&) = delete;
+    ~RelocBlock() { (void)hipFree(p); }
+    hipError_t alloc(size_t count) { return hipMalloc((void**)&p, count * sizeof(T)); }
+};
+
+// The lifted-row cache (edmdc_lift_cache) is keyed by the DEVICE addresses of X / U / C.  The host forms of edmdc_gram and
+// edmdc_pinv_apply stage their arrays in the ctx arena: a cache armed with those addresses would be found valid by the next host
+// call of the same shape -- the arena hands the same addresses out again -- and that call would read the lifted rows of the
+// PREVIOUS data.  Only a direct _dev call (whose buffers the caller owns and promises to leave alone) may leave the cache armed:
+// a host form disarms it on entry and on every way out.
 struct LiftCacheDisarm {
     brov_ctx* c;
-    explicit LiftCacheDisarm(brov_ctx* ctx) : c(ctx) { c->lift_cache_valid = false; }
-    ~LiftCacheDisarm() { c->lift_cache_valid = false; }
+    const bool host;
+    LiftCacheDisarm(brov_ctx* ctx, bool host_) : c(ctx), host(host_) { if (host) c->lift_cache_valid = false; }
+    ~LiftCacheDisarm() { if (host) c->lift_cache_valid = false; }
 };
 
 // ... and the same holds for buffers that come from brov_malloc (the Python host paths stage their lists there): freeing or
@@ -2574,21 +2582,20 @@ int edmdc_lift(brov_ctx* c, int64_t N, int n, int k, double gamma, const double*
     if (N < 0 || (N && (!X || !Z)) || !C) return fail(c, BROV_ERR_ARG, "edmdc_lift: bad argument");
     if (N == 0) return BROV_OK;
     DeviceGuard g(c);
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * n * 8) + Arena::al((size_t)k * n * 8) + Arena::al((size_t)N * (n + k) * 8));
+    const double *dX, *dC;
+    double* dZ;
+    Arena a(c, /*staged=*/true);
+    rc = a.lay("edmdc_lift", [&] {
+        dX = a.in(X, N * n);
+        dC = a.in(C, (size_t)k * n);
+        dZ = a.out(Z, (size_t)N * (n + k));
+    });
     if (rc) return rc;
-    double* dX = a.take<double>(N * n);
-    double* dC = a.take<double>((size_t)k * n);
-    double* dZ = a.take<double>((size_t)N * (n + k));
-    HIPCK(c, h2d_copy(c, dX, X, N * n * 8));
-    HIPCK(c, h2d_copy(c, dC, C, (size_t)k * n * 8));
     {
         CallTimer t(c);
         HIPCK(c, launch_lift_ref(c->stream, N, n, k, gamma, dX, dC, dZ));
     }
-    HIPCK(c, d2h_copy(c, Z, dZ, (size_t)N * (n + k) * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 static int ensure_tasks(brov_ctx* c, const EdmdcShape& s, int mode) {
@@ -2632,20 +2639,31 @@ static int ensure_partial(brov_ctx* c, size_t pdoubles) {
 // list fit_multi takes (edmdc_gram_ragged_dev).  Either way a lifted chunk is `chunk` consecutive rows and a pair never crosses a bag.
 struct BagLayout {
     int64_t nbags = 0, L = 0, xs = 0, us = 0;
-    int64_t total_rows = 0;
+    int64_t total_rows = 0, u_rows = 0;         // rows of X and of U that the layout spans (what a host form stages)
     const int64_t* offsets_host = nullptr;      // ragged: [nbags + 1], validated by bag_layout_ragged
     uint64_t hash = 0;                          // ragged: fingerprint of the offsets (part of the lift-cache key)
     bool ragged() const { return offsets_host != nullptr; }
-    size_t scratch_bytes() const { return ragged() ? Arena::al((size_t)(nbags + 1) * 8) + Arena::al((size_t)total_rows + 16) : 0; }
 };
 
-static void bag_layout_uniform(int64_t nbags, int64_t L, int64_t xs, int64_t us, BagLayout* bl) {
+// The argument checks of the Gram and apply entry points, per layout kind.  `ptrs`: the call's other pointers are all there.
+static int bag_layout_uniform(brov_ctx* c, const char* who, int n, int r, int k, bool ptrs, int64_t nbags, int64_t L, int64_t xs, int64_t us,
+                              const double* X, const double* U, BagLayout* bl) {
+    int rc = edmdc_shape_ok(c, n, r, k);
+    if (rc) return rc;
+    if (nbags < 0 || L < 0 || !ptrs || (nbags && L && (!X || (r && !U))) || (nbags > 1 && (xs < L + 1 || us < L)))
+        return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument");
     if (nbags <= 1) { xs = L + 1; us = L; }
     bl->nbags = nbags; bl->L = L; bl->xs = xs; bl->us = us;
     bl->total_rows = nbags > 0 ? (nbags - 1) * xs + L + 1 : 0;
+    bl->u_rows = nbags > 0 ? (nbags - 1) * us + L : 0;
+    return BROV_OK;
 }
 
-static int bag_layout_ragged(brov_ctx* c, int64_t nbags, const int64_t* off, BagLayout* bl, const char* who) {
+static int bag_layout_ragged(brov_ctx* c, const char* who, int n, int r, int k, bool ptrs, int64_t nbags, const int64_t* off,
+                             const double* X, const double* U, BagLayout* bl) {
+    int rc = edmdc_shape_ok(c, n, r, k);
+    if (rc) return rc;
+    if (!ptrs) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument");
     if (nbags < 0 || !off) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad bag list");
     if (off[0] != 0) return fail(c, BROV_ERR_ARG, std::string(who) + ": bag_offsets[0] must be 0");
     uint64_t h = 1469598103934665603ull;
@@ -2657,30 +2675,39 @@ static int bag_layout_ragged(brov_ctx* c, int64_t nbags, const int64_t* off, Bag
     bl->xs = (int64_t)1 << 62;                  // one "bag" longer than any data: every row below total_rows is a state row,
     bl->L = bl->xs - 1;                         // the pair flags say where the real bags end
     bl->us = 0;
-    bl->total_rows = off[nbags];
+    bl->total_rows = bl->u_rows = off[nbags];
     bl->offsets_host = off;
     bl->hash = h | 1;
+    if (bl->total_rows > 1 && (!X || (r && !U))) return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument");
     return BROV_OK;
 }
 
-// the pair flags of a ragged bag list in the call's arena (nullptr for a uniform layout)
-static int bag_pairflags(brov_ctx* c, Arena& a, const BagLayout& bl, const unsigned char** out) {
-    *out = nullptr;
-    if (!bl.ragged()) return BROV_OK;
-    int64_t* d_off = a.take<int64_t>((size_t)bl.nbags + 1);
-    unsigned char* pf = a.take<unsigned char>((size_t)bl.total_rows + 16);
-    HIPCK(c, h2d_copy(c, d_off, bl.offsets_host, (size_t)(bl.nbags + 1) * 8));
-    HIPCK(c, launch_bag_pairflags(c->stream, bl.nbags, d_off, bl.total_rows, pf));
-    HIPCK(c, hipStreamSynchronize(c->stream));  // the offsets are the caller's (host) array: it may go away when the call returns
-    *out = pf;
-    return BROV_OK;
-}
+// the pair flags of a ragged bag list (pf stays nullptr for a uniform layout): take() in the call's layout, fill() after it
+struct PairFlags {
+    int64_t* d_off = nullptr;
+    unsigned char* pf = nullptr;
+    void take(Arena& a, const BagLayout& bl) {
+        if (!bl.ragged()) return;
+        d_off = a.take<int64_t>((size_t)bl.nbags + 1);
+        pf = a.take<unsigned char>((size_t)bl.total_rows + 16);
+    }
+    int fill(brov_ctx* c, const BagLayout& bl) const {
+        if (!bl.ragged()) return BROV_OK;
+        HIPCK(c, h2d_copy(c, d_off, bl.offsets_host, (size_t)(bl.nbags + 1) * 8));
+        HIPCK(c, launch_bag_pairflags(c->stream, bl.nbags, d_off, bl.total_rows, pf));
+        HIPCK(c, hipStreamSynchronize(c->stream));  // the offsets are the caller's (host) array: it may go away when the call returns
+        return BROV_OK;
+    }
+};
 
-static int gram_core(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, const BagLayout& bl,
-                     const double* d_X, const double* d_U, int accumulate, double* d_GtG, double* d_GtY) {
-    const int mode = d_GtY ? 0 : 2;                     // no G^T Y wanted (fit()'s Gram pass): the staircase over the G tiles alone
+// host: the arrays are the caller's host memory, staged in the ctx arena for the call (`who` names the form)
+static int gram(brov_ctx* c, bool host, const char* who, int n, int r, int k, double gamma, const double* C, const BagLayout& bl,
+                const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
+    const int mode = GtY ? 0 : 2;                       // no G^T Y wanted (fit()'s Gram pass): the staircase over the G tiles alone
     DeviceGuard g(c);
+    LiftCacheDisarm disarm(c, host);
     const EdmdcShape s = edmdc_shape(n, r, k);
+    const size_t d = (size_t)n + k, p = d + r;
     int rc = ensure_tasks(c, s, mode);
     if (rc) return rc;
     const int64_t L = bl.L, xs = bl.xs, us = bl.us;
@@ -2693,14 +2720,28 @@ static int gram_core(brov_ctx* c, int n, int r, int k, double gamma, const doubl
     int64_t chunk = c->chunk_rows;
     if (chunk > (total_pairs_rows + 3) / 4 * 4) chunk = (total_pairs_rows + 3) / 4 * 4;
     if (chunk < 4) chunk = 4;
-    Arena a(c);
-    rc = a.reserve(Arena::al((size_t)(chunk + 8) * s.width * 8) + Arena::al((chunk + 8) * 8) + bl.scratch_bytes());
+    const double *d_X, *d_U, *d_C;
+    double *d_GtG, *d_GtY, *dZ, *dw;
+    PairFlags flags;
+    Arena a(c, host);
+    rc = a.lay(who, [&] {
+        d_X = a.in(X, (size_t)bl.total_rows * n);
+        d_U = a.in(U, (size_t)bl.u_rows * r);
+        d_C = a.in(C, (size_t)k * n);
+        d_GtG = accumulate ? a.inout(GtG, p * p) : a.out(GtG, p * p);
+        d_GtY = accumulate ? a.inout(GtY, p * d) : a.out(GtY, p * d);
+        dZ = a.take<double>((size_t)(chunk + 8) * s.width);
+        dw = a.take<double>(chunk + 8);
+        flags.take(a, bl);
+    });
     if (rc) return rc;
-    double* dZ = a.take<double>((size_t)(chunk + 8) * s.width);
-    double* dw = a.take<double>(chunk + 8);
-    const unsigned char* pf = nullptr;
-    rc = bag_pairflags(c, a, bl, &pf);
+    if (host && !accumulate) {
+        HIPCK(c, hipMemsetAsync(d_GtG, 0, p * p * 8, c->stream));
+        HIPCK(c, hipMemsetAsync(d_GtY, 0, p * d * 8, c->stream));
+    }
+    rc = flags.fill(c, bl);
     if (rc) return rc;
+    const unsigned char* pf = flags.pf;
     // lifted-row cache (edmdc_lift_cache): when every chunk of this call fits, lift straight into the cache slots
     c->lift_cache_valid = false;
     const int64_t nchunks = total_pairs_rows > 0 ? (total_pairs_rows + chunk - 1) / chunk : 0;
@@ -2725,31 +2766,36 @@ static int gram_core(brov_ctx* c, int n, int r, int k, double gamma, const doubl
         c->lift_key = {d_X, d_U, d_C, n, r, k, gamma, bl.nbags, L, xs, us, chunk, bl.hash};
         c->lift_cache_valid = true;
     }
-    HIPCK(c, launch_gram_finish_tasks(c->stream, s, c->ntasks[mode], c->d_tasks[mode], c->d_partial, accumulate, d_GtG, d_GtY));
-    return BROV_OK;
+    HIPCK(c, launch_gram_finish_tasks(c->stream, s, c->ntasks[mode], c->d_tasks[mode], c->d_partial, accumulate, d_GtG, mode == 0 ? d_GtY : nullptr));
+    return a.finish();
 }
 
 int edmdc_gram_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, int64_t nbags, int64_t L,
                    int64_t xs, int64_t us, const double* d_X, const double* d_U, int accumulate, double* d_GtG, double* d_GtY) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (nbags < 0 || L < 0 || !d_C || !d_GtG || (nbags && L && (!d_X || (r && !d_U))) || (nbags > 1 && (xs < L + 1 || us < L)))
-        return fail(c, BROV_ERR_ARG, "edmdc_gram_dev: bad argument");
     BagLayout bl;
-    bag_layout_uniform(nbags, L, xs, us, &bl);
-    return gram_core(c, n, r, k, gamma, d_C, bl, d_X, d_U, accumulate, d_GtG, d_GtY);
+    int rc = bag_layout_uniform(c, "edmdc_gram_dev", n, r, k, d_C && d_GtG, nbags, L, xs, us, d_X, d_U, &bl);
+    return rc ? rc : gram(c, false, "edmdc_gram_dev", n, r, k, gamma, d_C, bl, d_X, d_U, accumulate, d_GtG, d_GtY);
 }
 
 int edmdc_gram_ragged_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, int64_t nbags, const int64_t* bag_offsets,
                           const double* d_X, const double* d_U, int accumulate, double* d_GtG, double* d_GtY) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (!d_C || !d_GtG) return fail(c, BROV_ERR_ARG, "edmdc_gram_ragged_dev: bad argument");
     BagLayout bl;
-    rc = bag_layout_ragged(c, nbags, bag_offsets, &bl, "edmdc_gram_ragged_dev");
-    if (rc) return rc;
-    if (bl.total_rows > 1 && (!d_X || (r && !d_U))) return fail(c, BROV_ERR_ARG, "edmdc_gram_ragged_dev: bad argument");
-    return gram_core(c, n, r, k, gamma, d_C, bl, d_X, d_U, accumulate, d_GtG, d_GtY);
+    int rc = bag_layout_ragged(c, "edmdc_gram_ragged_dev", n, r, k, d_C && d_GtG, nbags, bag_offsets, d_X, d_U, &bl);
+    return rc ? rc : gram(c, false, "edmdc_gram_ragged_dev", n, r, k, gamma, d_C, bl, d_X, d_U, accumulate, d_GtG, d_GtY);
+}
+
+int edmdc_gram(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, int64_t L, int64_t xs, int64_t us,
+               const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
+    BagLayout bl;
+    int rc = bag_layout_uniform(c, "edmdc_gram", n, r, k, C && GtG && GtY, nbags, L, xs, us, X, U, &bl);
+    return rc ? rc : gram(c, true, "edmdc_gram", n, r, k, gamma, C, bl, X, U, accumulate, GtG, GtY);
+}
+
+int edmdc_gram_ragged(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, const int64_t* bag_offsets,
+                      const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
+    BagLayout bl;
+    int rc = bag_layout_ragged(c, "edmdc_gram_ragged", n, r, k, C && GtG && GtY, nbags, bag_offsets, X, U, &bl);
+    return rc ? rc : gram(c, true, "edmdc_gram_ragged", n, r, k, gamma, C, bl, X, U, accumulate, GtG, GtY);
 }
 
 int edmdc_gram_decomposition(int n, int r, int k, int* ntasks, int* nslabs) {
@@ -2858,12 +2904,14 @@ int edmdc_set_apply_variant(brov_ctx* c, int variant) {
 }
 
 // ---- fit()'s own association: M = (P G^T) Y  (Koopman/koopmanEDMDc.py:97) ------------------------------------------
-static int apply_core(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, const BagLayout& bl,
-                      const double* d_X, const double* d_U, const double* P_host, double* d_M) {
-    int rc = BROV_OK;
+// host: X, U, C and M are the caller's host memory, staged in the ctx arena for the call; P is a host array in both forms
+static int apply(brov_ctx* c, bool host, const char* who, int n, int r, int k, double gamma, const double* C, const BagLayout& bl,
+                 const double* X, const double* U, const double* P_host, double* M) {
     DeviceGuard g(c);
+    LiftCacheDisarm disarm(c, host);
     const EdmdcShape s = edmdc_shape(n, r, k);
-    rc = ensure_tasks(c, s, 1);
+    const size_t d = (size_t)n + k;
+    int rc = ensure_tasks(c, s, 1);
     if (rc) return rc;
     const int64_t nbags = bl.nbags, L = bl.L, xs = bl.xs, us = bl.us;
     const int64_t total_rows = bl.total_rows;
@@ -2876,16 +2924,26 @@ static int apply_core(brov_ctx* c, int n, int r, int k, double gamma, const doub
     if (chunk > (total_pairs_rows + 3) / 4 * 4) chunk = (total_pairs_rows + 3) / 4 * 4;
     if (chunk < 4) chunk = 4;
     const int W = s.width;
-    Arena a(c);
-    rc = a.reserve(2 * Arena::al((size_t)(chunk + 8) * W * 8) + Arena::al((chunk + 8) * 8) + Arena::al((size_t)(W + 8) * W * 8) + bl.scratch_bytes());
+    const double *d_X, *d_U, *d_C;
+    double *d_M, *dZ, *dWr, *dw, *dPt;
+    PairFlags flags;
+    Arena a(c, host);
+    rc = a.lay(who, [&] {
+        d_X = a.in(X, (size_t)bl.total_rows * n);
+        d_U = a.in(U, (size_t)bl.u_rows * r);
+        d_C = a.in(C, (size_t)k * n);
+        d_M = a.out(M, (d + r) * d);
+        dZ = a.take<double>((size_t)(chunk + 8) * W);
+        dWr = a.take<double>((size_t)(chunk + 8) * W);
+        dw = a.take<double>(chunk + 8);
+        dPt = a.take<double>((size_t)(W + 8) * W);      // 8 rows of padding: wrows_kernel prefetches two K-steps past the last feature
+        flags.take(a, bl);
+    });
     if (rc) return rc;
-    double* dZ = a.take<double>((size_t)(chunk + 8) * W);
-    double* dWr = a.take<double>((size_t)(chunk + 8) * W);
-    double* dw = a.take<double>(chunk + 8);
-    double* dPt = a.take<double>((size_t)(W + 8) * W);      // 8 rows of padding: wrows_kernel prefetches two K-steps past the last feature
-    const unsigned char* pf = nullptr;
-    rc = bag_pairflags(c, a, bl, &pf);
+    if (host) HIPCK(c, hipMemsetAsync(d_M, 0, (d + r) * d * 8, c->stream));
+    rc = flags.fill(c, bl);
     if (rc) return rc;
+    const unsigned char* pf = flags.pf;
     {   // PdT[f][j] = P[ref(j)][ref(f)]: P^T permuted to the device feature order, zero for padding features
         std::vector<double> h((size_t)(W + 8) * W, 0.0);
         const int p = s.p;
@@ -2921,135 +2979,35 @@ static int apply_core(brov_ctx* c, int n, int r, int k, double gamma, const doub
         first = 0;
     }
     HIPCK(c, launch_gram_finish_tasks(c->stream, s, c->ntasks[1], c->d_tasks[1], c->d_partial, 0, nullptr, d_M));
-    return BROV_OK;
+    return a.finish();
 }
 
 int edmdc_pinv_apply_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, int64_t nbags, int64_t L,
                          int64_t xs, int64_t us, const double* d_X, const double* d_U, const double* P_host, double* d_M) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (nbags < 0 || L < 0 || !d_C || !P_host || !d_M || (nbags && L && (!d_X || (r && !d_U))) || (nbags > 1 && (xs < L + 1 || us < L)))
-        return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply_dev: bad argument");
     BagLayout bl;
-    bag_layout_uniform(nbags, L, xs, us, &bl);
-    return apply_core(c, n, r, k, gamma, d_C, bl, d_X, d_U, P_host, d_M);
+    int rc = bag_layout_uniform(c, "edmdc_pinv_apply_dev", n, r, k, d_C && P_host && d_M, nbags, L, xs, us, d_X, d_U, &bl);
+    return rc ? rc : apply(c, false, "edmdc_pinv_apply_dev", n, r, k, gamma, d_C, bl, d_X, d_U, P_host, d_M);
 }
 
 int edmdc_pinv_apply_ragged_dev(brov_ctx* c, int n, int r, int k, double gamma, const double* d_C, int64_t nbags, const int64_t* bag_offsets,
                                 const double* d_X, const double* d_U, const double* P_host, double* d_M) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (!d_C || !P_host || !d_M) return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply_ragged_dev: bad argument");
     BagLayout bl;
-    rc = bag_layout_ragged(c, nbags, bag_offsets, &bl, "edmdc_pinv_apply_ragged_dev");
-    if (rc) return rc;
-    if (bl.total_rows > 1 && (!d_X || (r && !d_U))) return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply_ragged_dev: bad argument");
-    return apply_core(c, n, r, k, gamma, d_C, bl, d_X, d_U, P_host, d_M);
-}
-
-// host forms: the arrays are staged in device allocations of their own for the duration of the call
-static int apply_host(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const BagLayout& bl, int64_t urows,
-                      const double* X, const double* U, const double* P, double* M) {
-    DeviceGuard g(c);
-    LiftCacheDisarm disarm(c);
-    const int64_t xrows = bl.total_rows;
-    const int d = n + k, p = d + r;
-    double *dX = nullptr, *dU = nullptr, *dC = nullptr, *dM = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dX); (void)hipFree(dU); (void)hipFree(dC); (void)hipFree(dM); };
-#define HIPCK_CLEAN(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(c, e__, #call); } } while (0)
-    HIPCK_CLEAN(hipMalloc((void**)&dX, (size_t)(xrows > 0 ? xrows : 1) * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dU, (size_t)(urows > 0 ? urows : 1) * (r > 0 ? r : 1) * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dC, (size_t)k * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dM, (size_t)p * d * 8));
-    if (xrows) HIPCK_CLEAN(h2d_copy(c, dX, X, (size_t)xrows * n * 8));
-    if (urows && r) HIPCK_CLEAN(h2d_copy(c, dU, U, (size_t)urows * r * 8));
-    HIPCK_CLEAN(h2d_copy(c, dC, C, (size_t)k * n * 8));
-    HIPCK_CLEAN(hipMemsetAsync(dM, 0, (size_t)p * d * 8, c->stream));
-    int rc = apply_core(c, n, r, k, gamma, dC, bl, dX, dU, P, dM);
-    if (rc) { cleanup(); return rc; }
-    HIPCK_CLEAN(d2h_copy(c, M, dM, (size_t)p * d * 8));
-    HIPCK_CLEAN(hipStreamSynchronize(c->stream));
-    cleanup();
-    return BROV_OK;
+    int rc = bag_layout_ragged(c, "edmdc_pinv_apply_ragged_dev", n, r, k, d_C && P_host && d_M, nbags, bag_offsets, d_X, d_U, &bl);
+    return rc ? rc : apply(c, false, "edmdc_pinv_apply_ragged_dev", n, r, k, gamma, d_C, bl, d_X, d_U, P_host, d_M);
 }
 
 int edmdc_pinv_apply(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, int64_t L, int64_t xs, int64_t us,
                      const double* X, const double* U, const double* P, double* M) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (nbags < 0 || L < 0 || !C || !P || !M || (nbags && L && (!X || (r && !U))) || (nbags > 1 && (xs < L + 1 || us < L)))
-        return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply: bad argument");
     BagLayout bl;
-    bag_layout_uniform(nbags, L, xs, us, &bl);
-    return apply_host(c, n, r, k, gamma, C, bl, nbags > 0 ? (nbags - 1) * bl.us + L : 0, X, U, P, M);
+    int rc = bag_layout_uniform(c, "edmdc_pinv_apply", n, r, k, C && P && M, nbags, L, xs, us, X, U, &bl);
+    return rc ? rc : apply(c, true, "edmdc_pinv_apply", n, r, k, gamma, C, bl, X, U, P, M);
 }
 
 int edmdc_pinv_apply_ragged(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, const int64_t* bag_offsets,
                             const double* X, const double* U, const double* P, double* M) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (!C || !P || !M) return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply_ragged: bad argument");
     BagLayout bl;
-    rc = bag_layout_ragged(c, nbags, bag_offsets, &bl, "edmdc_pinv_apply_ragged");
-    if (rc) return rc;
-    if (bl.total_rows > 1 && (!X || (r && !U))) return fail(c, BROV_ERR_ARG, "edmdc_pinv_apply_ragged: bad argument");
-    return apply_host(c, n, r, k, gamma, C, bl, bl.total_rows, X, U, P, M);
-}
-
-static int gram_host(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const BagLayout& bl, int64_t urows,
-                     const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
-    DeviceGuard g(c);
-    LiftCacheDisarm disarm(c);
-    const int64_t xrows = bl.total_rows;
-    const int d = n + k, p = d + r;
-    // inputs live in plain device allocations (the arena is used by gram_core itself)
-    double *dX = nullptr, *dU = nullptr, *dC = nullptr, *dG = nullptr, *dY = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dX); (void)hipFree(dU); (void)hipFree(dC); (void)hipFree(dG); (void)hipFree(dY); };
-    HIPCK_CLEAN(hipMalloc((void**)&dX, (size_t)(xrows > 0 ? xrows : 1) * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dU, (size_t)(urows > 0 ? urows : 1) * (r > 0 ? r : 1) * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dC, (size_t)k * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dG, (size_t)p * p * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dY, (size_t)p * d * 8));
-    if (xrows) HIPCK_CLEAN(h2d_copy(c, dX, X, (size_t)xrows * n * 8));
-    if (urows && r) HIPCK_CLEAN(h2d_copy(c, dU, U, (size_t)urows * r * 8));
-    HIPCK_CLEAN(h2d_copy(c, dC, C, (size_t)k * n * 8));
-    if (accumulate) {
-        HIPCK_CLEAN(h2d_copy(c, dG, GtG, (size_t)p * p * 8));
-        HIPCK_CLEAN(h2d_copy(c, dY, GtY, (size_t)p * d * 8));
-    } else {
-        HIPCK_CLEAN(hipMemsetAsync(dG, 0, (size_t)p * p * 8, c->stream));
-        HIPCK_CLEAN(hipMemsetAsync(dY, 0, (size_t)p * d * 8, c->stream));
-    }
-    int rc = gram_core(c, n, r, k, gamma, dC, bl, dX, dU, accumulate, dG, dY);
-    if (rc) { cleanup(); return rc; }
-    HIPCK_CLEAN(d2h_copy(c, GtG, dG, (size_t)p * p * 8));
-    HIPCK_CLEAN(d2h_copy(c, GtY, dY, (size_t)p * d * 8));
-    HIPCK_CLEAN(hipStreamSynchronize(c->stream));
-    cleanup();
-    return BROV_OK;
-}
-
-int edmdc_gram(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, int64_t L, int64_t xs, int64_t us,
-               const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (nbags < 0 || L < 0 || !C || !GtG || !GtY || (nbags && L && (!X || (r && !U))) || (nbags > 1 && (xs < L + 1 || us < L)))
-        return fail(c, BROV_ERR_ARG, "edmdc_gram: bad argument");
-    BagLayout bl;
-    bag_layout_uniform(nbags, L, xs, us, &bl);
-    return gram_host(c, n, r, k, gamma, C, bl, nbags > 0 ? (nbags - 1) * bl.us + L : 0, X, U, accumulate, GtG, GtY);
-}
-
-int edmdc_gram_ragged(brov_ctx* c, int n, int r, int k, double gamma, const double* C, int64_t nbags, const int64_t* bag_offsets,
-                      const double* X, const double* U, int accumulate, double* GtG, double* GtY) {
-    int rc = edmdc_shape_ok(c, n, r, k);
-    if (rc) return rc;
-    if (!C || !GtG || !GtY) return fail(c, BROV_ERR_ARG, "edmdc_gram_ragged: bad argument");
-    BagLayout bl;
-    rc = bag_layout_ragged(c, nbags, bag_offsets, &bl, "edmdc_gram_ragged");
-    if (rc) return rc;
-    if (bl.total_rows > 1 && (!X || (r && !U))) return fail(c, BROV_ERR_ARG, "edmdc_gram_ragged: bad argument");
-    return gram_host(c, n, r, k, gamma, C, bl, bl.total_rows, X, U, accumulate, GtG, GtY);
+    int rc = bag_layout_ragged(c, "edmdc_pinv_apply_ragged", n, r, k, C && P && M, nbags, bag_offsets, X, U, &bl);
+    return rc ? rc : apply(c, true, "edmdc_pinv_apply_ragged", n, r, k, gamma, C, bl, X, U, P, M);
 }
 
 // ---- lifted propagation: evaluate / multistep_rmse / simulate ---------------------------------------
@@ -3076,21 +3034,22 @@ int edmdc_multistep_se(brov_ctx* c, int n, int r, int k, double gamma, const dou
     const PropShape s = prop_shape(n, r, k, nw);
     const int rpad = s.ppad - s.d;
     const int64_t NUt = s.nwp + H + 16;
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * n * 8) + Arena::al(N * (r ? r : 1) * 8) + Arena::al((size_t)k * n * 8) + Arena::al((size_t)s.ppad * s.dpad * 8) +
-                   2 * Arena::al((size_t)s.zrows * s.nwp * 8) + Arena::al((size_t)rpad * NUt * 8) + Arena::al(nw * 8) + Arena::al(nw * n * 8) + 4096);
+    const double *dX, *dC;
+    double *dU, *dABt, *dZ0, *dZ1, *dUt, *dse, *dxh, *dtot;
+    Arena a(c, /*staged=*/true);
+    rc = a.lay("edmdc_multistep_se", [&] {
+        dX = a.in(X, N * n);
+        dU = a.take<double>(N * (r ? r : 1));             // N rows, N - 1 of them the caller's (below)
+        dC = a.in(C, (size_t)k * n);
+        dABt = a.take<double>((size_t)s.ppad * s.dpad);
+        dZ0 = a.take<double>((size_t)s.zrows * s.nwp);
+        dZ1 = a.take<double>((size_t)s.zrows * s.nwp);
+        dUt = a.take<double>((size_t)rpad * NUt);
+        dse = a.take<double>(nw);
+        dxh = a.out(xhat_end, nw * n);
+        dtot = a.take<double>(8);
+    });
     if (rc) return rc;
-    double* dX = a.take<double>(N * n);
-    double* dU = a.take<double>(N * (r ? r : 1));
-    double* dC = a.take<double>((size_t)k * n);
-    double* dABt = a.take<double>((size_t)s.ppad * s.dpad);
-    double* dZ0 = a.take<double>((size_t)s.zrows * s.nwp);
-    double* dZ1 = a.take<double>((size_t)s.zrows * s.nwp);
-    double* dUt = a.take<double>((size_t)rpad * NUt);
-    double* dse = a.take<double>(nw);
-    double* dxh = a.take<double>(nw * n);
-    double* dtot = a.take<double>(8);
-    HIPCK(c, h2d_copy(c, dX, X, N * n * 8));
     // the windows read input rows 0 .. N-2 only (window k, step t uses U[k+t], k+t <= N-2): like the reference's
     // multistep_rmse / evaluate, accept a U with N-1 rows and never touch row N-1 of the caller's buffer
     const int64_t urows = N - 1;
@@ -3098,7 +3057,6 @@ int edmdc_multistep_se(brov_ctx* c, int n, int r, int k, double gamma, const dou
         HIPCK(c, hipMemsetAsync(dU + urows * r, 0, (size_t)r * 8, c->stream));
         if (urows > 0) HIPCK(c, h2d_copy(c, dU, U, urows * r * 8));
     }
-    HIPCK(c, h2d_copy(c, dC, C, (size_t)k * n * 8));
     rc = upload_ABt(c, s, A, B, dABt);
     if (rc) return rc;
     HIPCK(c, hipMemsetAsync(dUt, 0, (size_t)rpad * NUt * 8, c->stream));
@@ -3149,9 +3107,7 @@ int edmdc_multistep_se(brov_ctx* c, int n, int r, int k, double gamma, const dou
         HIPCK(c, launch_sum(c->stream, nw, dse, dtot));
     }
     HIPCK(c, d2h_copy(c, se_total, dtot, 8));
-    if (xhat_end) HIPCK(c, d2h_copy(c, xhat_end, dxh, nw * n * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 int edmdc_multistep_se_linear(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const double* RHt, const double* Gt,
@@ -3164,25 +3120,24 @@ int edmdc_multistep_se_linear(brov_ctx* c, int n, int r, int k, double gamma, co
     DeviceGuard g(c);
     const int d = n + k;
     const int64_t urows = N - 1;                       // like edmdc_multistep_se: rows 0 .. N-2 of U are read, a shorter-by-one U is accepted
-    Arena a(c);
-    rc = a.reserve(Arena::al(N * n * 8) + Arena::al(N * (r ? r : 1) * 8) + Arena::al((size_t)k * n * 8) + Arena::al((size_t)d * n * 8) +
-                   Arena::al((size_t)(H ? H : 1) * (r ? r : 1) * n * 8) + Arena::al(nw * 8) + Arena::al(nw * n * 8) + 4096);
+    const double *dX, *dC, *dR;
+    double *dU, *dG, *dse, *dxh, *dtot;
+    Arena a(c, /*staged=*/true);
+    rc = a.lay("edmdc_multistep_se_linear", [&] {
+        dX = a.in(X, N * n);
+        dU = a.take<double>(N * (r ? r : 1));
+        dC = a.in(C, (size_t)k * n);
+        dR = a.in(RHt, (size_t)d * n);
+        dG = a.take<double>((size_t)(H ? H : 1) * (r ? r : 1) * n);      // at least one element; the caller's H r n are copied below
+        dse = a.take<double>(nw);
+        dxh = a.out(xhat_end, nw * n);
+        dtot = a.take<double>(8);
+    });
     if (rc) return rc;
-    double* dX = a.take<double>(N * n);
-    double* dU = a.take<double>(N * (r ? r : 1));
-    double* dC = a.take<double>((size_t)k * n);
-    double* dR = a.take<double>((size_t)d * n);
-    double* dG = a.take<double>((size_t)(H ? H : 1) * (r ? r : 1) * n);
-    double* dse = a.take<double>(nw);
-    double* dxh = a.take<double>(nw * n);
-    double* dtot = a.take<double>(8);
-    HIPCK(c, h2d_copy(c, dX, X, N * n * 8));
     if (r) {
         HIPCK(c, hipMemsetAsync(dU + urows * r, 0, (size_t)r * 8, c->stream));
         if (urows > 0) HIPCK(c, h2d_copy(c, dU, U, urows * r * 8));
     }
-    HIPCK(c, h2d_copy(c, dC, C, (size_t)k * n * 8));
-    HIPCK(c, h2d_copy(c, dR, RHt, (size_t)d * n * 8));
     if (H && r) HIPCK(c, h2d_copy(c, dG, Gt, (size_t)H * r * n * 8));
     {
         CallTimer t(c);
@@ -3190,9 +3145,7 @@ int edmdc_multistep_se_linear(brov_ctx* c, int n, int r, int k, double gamma, co
         HIPCK(c, launch_sum(c->stream, nw, dse, dtot));
     }
     HIPCK(c, d2h_copy(c, se_total, dtot, 8));
-    if (xhat_end) HIPCK(c, d2h_copy(c, xhat_end, dxh, nw * n * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 int edmdc_simulate(brov_ctx* c, int n, int r, int k, double gamma, const double* C, const double* A, const double* B,
@@ -3205,22 +3158,21 @@ int edmdc_simulate(brov_ctx* c, int n, int r, int k, double gamma, const double*
     const PropShape s = prop_shape(n, r, k, nb);
     const int rpad = s.ppad - s.d;
     const int64_t ust_rows = (T > 0 ? T : 1) * (int64_t)rpad;   // [t][rpad][nbp]: step t uses rows t*r .. (reads up to rpad rows)
-    Arena a(c);
-    rc = a.reserve(Arena::al(nb * n * 8) + Arena::al((size_t)nb * T * (r ? r : 1) * 8 + 8) + Arena::al((size_t)k * n * 8) +
-                   Arena::al((size_t)s.ppad * s.dpad * 8) + 2 * Arena::al((size_t)s.zrows * s.nwp * 8) +
-                   Arena::al((size_t)(ust_rows + rpad) * s.nwp * 8) + Arena::al((size_t)nb * (T + 1) * n * 8) + 4096);
+    const double *dx0, *dC;
+    double *dUs, *dABt, *dZ0, *dZ1, *dUst, *dXp;
+    Arena a(c, /*staged=*/true);
+    rc = a.lay("edmdc_simulate", [&] {
+        dx0 = a.in(x0, nb * n);
+        dUs = a.take<double>((size_t)nb * T * (r ? r : 1) + 1);      // one element more than the caller's nb T r (copied below)
+        dC = a.in(C, (size_t)k * n);
+        dABt = a.take<double>((size_t)s.ppad * s.dpad);
+        dZ0 = a.take<double>((size_t)s.zrows * s.nwp);
+        dZ1 = a.take<double>((size_t)s.zrows * s.nwp);
+        dUst = a.take<double>((size_t)(ust_rows + rpad) * s.nwp);
+        dXp = a.out(X_pred, (size_t)nb * (T + 1) * n);
+    });
     if (rc) return rc;
-    double* dx0 = a.take<double>(nb * n);
-    double* dUs = a.take<double>((size_t)nb * T * (r ? r : 1) + 1);
-    double* dC = a.take<double>((size_t)k * n);
-    double* dABt = a.take<double>((size_t)s.ppad * s.dpad);
-    double* dZ0 = a.take<double>((size_t)s.zrows * s.nwp);
-    double* dZ1 = a.take<double>((size_t)s.zrows * s.nwp);
-    double* dUst = a.take<double>((size_t)(ust_rows + rpad) * s.nwp);
-    double* dXp = a.take<double>((size_t)nb * (T + 1) * n);
-    HIPCK(c, h2d_copy(c, dx0, x0, nb * n * 8));
     if (T && r) HIPCK(c, h2d_copy(c, dUs, U_seq, (size_t)nb * T * r * 8));
-    HIPCK(c, h2d_copy(c, dC, C, (size_t)k * n * 8));
     rc = upload_ABt(c, s, A, B, dABt);
     if (rc) return rc;
     HIPCK(c, hipMemsetAsync(dUst, 0, (size_t)(ust_rows + rpad) * s.nwp * 8, c->stream));
@@ -3239,9 +3191,7 @@ int edmdc_simulate(brov_ctx* c, int n, int r, int k, double gamma, const double*
             HIPCK(c, launch_extract_state(c->stream, s, T + 1, t + 1, zin, dXp));
         }
     }
-    HIPCK(c, d2h_copy(c, X_pred, dXp, (size_t)nb * (T + 1) * n * 8));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 // ---- k-means (Lloyd) --------------------------------------------------------------------------------------
@@ -3372,24 +3322,24 @@ static void far_select_default(const double* dist, int64_t N, int n_empty, int64
 static int kmeans_relocate(brov_ctx* c, int64_t N, int n, int k, const double* d_X, int64_t xstride, const double* mean_host, const double* mp,
                            const double* fix, const double* Cold, double* Cnew, double* c2, double* stats, double* prm, long long* red,
                            const int* Lc, const int* Pc) {
-    double* d_dist = nullptr;
-    int* d_lab = nullptr;
-    long long* d_words = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_dist); (void)hipFree(d_lab); (void)hipFree(d_words); };
-#define HIPCK_R(call) do { hipError_t e__ = (call); if (e__ != hipSuccess) { cleanup(); return hip_fail(c, e__, #call); } } while (0)
-    HIPCK_R(hipMalloc((void**)&d_dist, (size_t)N * 8));
-    HIPCK_R(hipMalloc((void**)&d_lab, (size_t)N * 4));
-    HIPCK_R(hipMalloc((void**)&d_words, 64 * 8));
-    HIPCK_R(launch_kmeans_reloc_dist(c->stream, N, n, d_X, xstride, mp, Cold, Lc, Pc, d_dist, d_lab));
+    // allocations of its own, freed on every way out: the loop's arena is bound while this runs, and the path is too rare to
+    // charge every Lloyd call 12 bytes per sample for it
+    RelocBlock<double> d_dist;
+    RelocBlock<int> d_lab;
+    RelocBlock<long long> d_words;
+    HIPCK(c, d_dist.alloc((size_t)N));
+    HIPCK(c, d_lab.alloc((size_t)N));
+    HIPCK(c, d_words.alloc(64));
+    HIPCK(c, launch_kmeans_reloc_dist(c->stream, N, n, d_X, xstride, mp, Cold, Lc, Pc, d_dist.p, d_lab.p));
     std::vector<double> dist((size_t)N);
     std::vector<int> lab((size_t)N);
     std::vector<long long> hred(kmeans_red_words(n, k));
     double hfix[32];
-    HIPCK_R(d2h_copy(c, dist.data(), d_dist, (size_t)N * 8));
-    HIPCK_R(d2h_copy(c, lab.data(), d_lab, (size_t)N * 4));
-    HIPCK_R(d2h_copy(c, hred.data(), red, hred.size() * 8));
-    HIPCK_R(d2h_copy(c, hfix, fix, sizeof hfix));
-    HIPCK_R(hipStreamSynchronize(c->stream));
+    HIPCK(c, d2h_copy(c, dist.data(), d_dist.p, (size_t)N * 8));
+    HIPCK(c, d2h_copy(c, lab.data(), d_lab.p, (size_t)N * 4));
+    HIPCK(c, d2h_copy(c, hred.data(), red, hred.size() * 8));
+    HIPCK(c, d2h_copy(c, hfix, fix, sizeof hfix));
+    HIPCK(c, hipStreamSynchronize(c->stream));
     const int np1 = n + 1;
     auto load = [&](int q, int j) { return ((__int128)hred[((size_t)q * np1 + j) * 2] << 42) + (__int128)hred[((size_t)q * np1 + j) * 2 + 1]; };
     auto store = [&](int q, int j, __int128 v) {
@@ -3399,12 +3349,12 @@ static int kmeans_relocate(brov_ctx* c, int64_t N, int n, int k, const double* d
     // words through the ranks (device buffer in, device buffer out: the callback's contract), synchronous: this path is rare
     auto exchange = [&](long long* w, int count, int op) -> int {
         if (!c->km_allreduce) return BROV_OK;
-        if (h2d_copy(c, d_words, w, (size_t)count * 8) != hipSuccess) return BROV_ERR_HIP;
-        if (c->km_allreduce(c->km_allreduce_user, d_words, count, op) != 0) return BROV_ERR_COMM;
-        if (d2h_copy(c, w, d_words, (size_t)count * 8) != hipSuccess) return BROV_ERR_HIP;
+        if (h2d_copy(c, d_words.p, w, (size_t)count * 8) != hipSuccess) return BROV_ERR_HIP;
+        if (c->km_allreduce(c->km_allreduce_user, d_words.p, count, op) != 0) return BROV_ERR_COMM;
+        if (d2h_copy(c, w, d_words.p, (size_t)count * 8) != hipSuccess) return BROV_ERR_HIP;
         return hipStreamSynchronize(c->stream) == hipSuccess ? BROV_OK : BROV_ERR_HIP;
     };
-#define EXCH(w, count, op) do { int rc__ = exchange((w), (count), (op)); if (rc__) { cleanup(); return fail(c, rc__, "edmdc_kmeans_lloyd: exchange of the relocation failed"); } } while (0)
+#define EXCH(w, count, op) do { int rc__ = exchange((w), (count), (op)); if (rc__) return fail(c, rc__, "edmdc_kmeans_lloyd: exchange of the relocation failed"); } while (0)
     // empty_clusters = np.where(weight_in_clusters == 0)[0], ascending
     std::vector<int> new_ids;
     for (int q = 0; q < k; ++q)
@@ -3439,17 +3389,17 @@ static int kmeans_relocate(brov_ctx* c, int64_t N, int n, int k, const double* d
     // `if np.max(distances) == 0: return` -- more clusters than distinct samples: nothing to relocate to
     if (n_empty > 0 && (dmax != 0.0 || any_nan)) {
         if (!c->km_allreduce) {
-            if (n_empty > N) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: more empty clusters than samples"); }
+            if (n_empty > N) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: more empty clusters than samples");
             std::vector<int64_t> far((size_t)n_empty);
             if (c->far_select) {
-                if (c->far_select(c->far_select_user, dist.data(), N, n_empty, far.data()) != 0) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback failed"); }
-                for (int64_t r : far) if (r < 0 || r >= N) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback returned a row out of range"); }
+                if (c->far_select(c->far_select_user, dist.data(), N, n_empty, far.data()) != 0) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback failed");
+                for (int64_t r : far) if (r < 0 || r >= N) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback returned a row out of range");
             } else {
                 far_select_default(dist.data(), N, n_empty, far.data());
             }
             for (int q = 0; q < n_empty; ++q) {
                 long long qv[16];
-                if (quantise_row(far[q], qv)) { cleanup(); return fail(c, BROV_ERR_HIP, "edmdc_kmeans_lloyd: reading a far row failed"); }
+                if (quantise_row(far[q], qv)) return fail(c, BROV_ERR_HIP, "edmdc_kmeans_lloyd: reading a far row failed");
                 apply(new_ids[q], lab[(size_t)far[q]], qv);
             }
         } else {
@@ -3459,24 +3409,23 @@ static int kmeans_relocate(brov_ctx* c, int64_t N, int n, int k, const double* d
             // rows: this path runs when a cluster runs empty, i.e. hardly ever) -- and every rank then applies the same rule to the same
             // array: the rows of the unsharded run, callback or library rule alike.
             const int64_t Ng = c->km_n_global > 0 ? (int64_t)c->km_n_global : N;
-            if (c->km_row_offset + N > Ng) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: edmdc_set_kmeans_shard does not cover this rank's rows"); }
-            if (n_empty > Ng) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: more empty clusters than samples"); }
+            if (c->km_row_offset + N > Ng) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: edmdc_set_kmeans_shard does not cover this rank's rows");
+            if (n_empty > Ng) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: more empty clusters than samples");
             std::vector<double> gdist((size_t)Ng, 0.0);
             {
-                long long* d_all = nullptr;
-                if (hipMalloc((void**)&d_all, (size_t)Ng * 8) != hipSuccess) { cleanup(); return fail(c, BROV_ERR_NOMEM, "edmdc_kmeans_lloyd: no memory for the gathered distances"); }
-                bool ok = hipMemsetAsync(d_all, 0, (size_t)Ng * 8, c->stream) == hipSuccess &&
-                          hipMemcpyAsync(d_all + c->km_row_offset, d_dist, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
-                const int arc = ok ? c->km_allreduce(c->km_allreduce_user, d_all, Ng, 0) : 1;
-                ok = ok && arc == 0 && d2h_copy(c, gdist.data(), d_all, (size_t)Ng * 8) == hipSuccess &&
+                RelocBlock<long long> d_all;
+                if (d_all.alloc((size_t)Ng) != hipSuccess) return fail(c, BROV_ERR_NOMEM, "edmdc_kmeans_lloyd: no memory for the gathered distances");
+                bool ok = hipMemsetAsync(d_all.p, 0, (size_t)Ng * 8, c->stream) == hipSuccess &&
+                          hipMemcpyAsync(d_all.p + c->km_row_offset, d_dist.p, (size_t)N * 8, hipMemcpyDeviceToDevice, c->stream) == hipSuccess;
+                const int arc = ok ? c->km_allreduce(c->km_allreduce_user, d_all.p, Ng, 0) : 1;
+                ok = ok && arc == 0 && d2h_copy(c, gdist.data(), d_all.p, (size_t)Ng * 8) == hipSuccess &&
                      hipStreamSynchronize(c->stream) == hipSuccess;
-                (void)hipFree(d_all);
-                if (!ok) { cleanup(); return fail(c, arc ? BROV_ERR_COMM : BROV_ERR_HIP, "edmdc_kmeans_lloyd: gathering the distances of the ranks failed"); }
+                if (!ok) return fail(c, arc ? BROV_ERR_COMM : BROV_ERR_HIP, "edmdc_kmeans_lloyd: gathering the distances of the ranks failed");
             }
             std::vector<int64_t> far((size_t)n_empty);
             if (c->far_select) {
-                if (c->far_select(c->far_select_user, gdist.data(), Ng, n_empty, far.data()) != 0) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback failed"); }
-                for (int64_t r : far) if (r < 0 || r >= Ng) { cleanup(); return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback returned a row out of range"); }
+                if (c->far_select(c->far_select_user, gdist.data(), Ng, n_empty, far.data()) != 0) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback failed");
+                for (int64_t r : far) if (r < 0 || r >= Ng) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: the far-sample callback returned a row out of range");
             } else {
                 far_select_default(gdist.data(), Ng, n_empty, far.data());
             }
@@ -3487,38 +3436,37 @@ static int kmeans_relocate(brov_ctx* c, int64_t N, int n, int k, const double* d
                 long long msg[18];
                 for (long long& v : msg) v = 0;
                 if (owner) {
-                    if (quantise_row(lrow, msg)) { cleanup(); return fail(c, BROV_ERR_HIP, "edmdc_kmeans_lloyd: reading a far row failed"); }
+                    if (quantise_row(lrow, msg)) return fail(c, BROV_ERR_HIP, "edmdc_kmeans_lloyd: reading a far row failed");
                     msg[16] = lab[(size_t)lrow];
                     msg[17] = 1;
                 }
                 EXCH(msg, 18, 0);
-                if (msg[17] != 1) { cleanup(); return fail(c, BROV_ERR_COMM, "edmdc_kmeans_lloyd: the ranks disagree about a relocated row"); }
+                if (msg[17] != 1) return fail(c, BROV_ERR_COMM, "edmdc_kmeans_lloyd: the ranks disagree about a relocated row");
                 apply(new_ids[q], (int)msg[16], msg);
             }
         }
-        HIPCK_R(h2d_copy(c, red, hred.data(), hred.size() * 8));
-        HIPCK_R(hipStreamSynchronize(c->stream));
+        HIPCK(c, h2d_copy(c, red, hred.data(), hred.size() * 8));
+        HIPCK(c, hipStreamSynchronize(c->stream));
         ++c->kmeans_relocations;
     }
-    HIPCK_R(launch_kmeans_average(c->stream, n, k, red, fix, Cold, Cnew, c2, stats, prm, 1));
-    HIPCK_R(hipStreamSynchronize(c->stream));
+    HIPCK(c, launch_kmeans_average(c->stream, n, k, red, fix, Cold, Cnew, c2, stats, prm, 1));
+    HIPCK(c, hipStreamSynchronize(c->stream));
 #undef EXCH
-#undef HIPCK_R
-    cleanup();
     return BROV_OK;
 }
 
-int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d_X, int64_t xstride, const double* mean_host,
-                           double* d_C, int max_iter, double tol_abs, int32_t* d_labels, double* inertia, int* n_iter) {
-    if (!c || N < 1 || n < 1 || n > 15 || k < 1 || !d_X || !d_C || !d_labels || max_iter < 1 || xstride < n || (size_t)k * (n + 1) * 8 > 150 * 1024)
-        return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd_dev: bad argument (need 1<=n<=15, k*(n+1)*8 <= 150 KiB of LDS)");
+// host: X, C and labels are the caller's host memory, staged in the ctx arena for the call (`who` names the form); there labels may
+// be NULL (arena scratch takes its place: the loop needs the array)
+static int kmeans_lloyd(brov_ctx* c, bool host, const char* who, int64_t N, int n, int k, const double* X, int64_t xstride, const double* mean_host,
+                        double* C_io, int max_iter, double tol_abs, int32_t* labels, double* inertia, int* n_iter) {
+    if (!c || N < 1 || n < 1 || n > 15 || k < 1 || !X || !C_io || (!host && !labels) || max_iter < 1 || xstride < n || (size_t)k * (n + 1) * 8 > 150 * 1024)
+        return fail(c, BROV_ERR_ARG, std::string(who) + ": bad argument (need 1<=n<=15, k*(n+1)*8 <= 150 KiB of LDS)");
     DeviceGuard g(c);
     const int variant = c->kmeans_variant & 3;
     const bool scalar_records = (c->kmeans_variant & KMV_SCALAR_RECORDS) != 0;     // the E-step kernel with scalar centre records (kmeans.hip)
     const int nb = kmeans_blocks(N, n, k, scalar_records);
     const int nparts = nb * kmeans_epochs(N, n, k, scalar_records);
     const size_t pwords = kmeans_partial_words(N, n, k, scalar_records), rwords = kmeans_red_words(n, k);
-    Arena a(c);
     const bool filter = variant != 1 && k >= 64;       // below one mask word there is nothing to skip
     // sample order (sortperm.hip): the filter decides per wave of 64 consecutive samples, so the loop keeps a permutation that orders the
     // samples by (label, distance to the centre), re-sorted when enough labels have moved; the LDS / DPP kernel reads its rows
@@ -3548,53 +3496,59 @@ int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d
     const size_t pwords_pk = (size_t)nparts_pk * k * (n + 1);
     const size_t pw_max = pwords > pwords_pk ? pwords : pwords_pk;
     const int nb_max = nb > nb_pk ? nb : nb_pk;
-    int rc = a.reserve(Arena::al(pw_max * 8) + Arena::al(rwords * 8) + Arena::al(nb_max * 8) + Arena::al(nb_max * 4) + Arena::al((size_t)k * 16 * 8) +
-                       ((pk || pk_lds) ? Arena::al(k * (kp_ / 2) * 32 * 4) : 0) + 256 +
-                       2 * Arena::al((size_t)k * n * 8) + Arena::al(filter ? (size_t)k * ((k + 255) & ~255) * 4 : 8) +
-                       (nbr ? Arena::al(k * kp_ * 8) : 0) +
-                       (sorting ? 9 * Arena::al((size_t)N * 4) + Arena::al(sort_tmp + 256) : 0) +
-                       (bnd ? 5 * Arena::al((size_t)N * 4) + Arena::al(lwords * 4) + Arena::al(rwords * 8) + 4 * Arena::al((size_t)k * 16 + 64) + 1024 : 0) +
-                       Arena::al(kmeans_mstep_scratch_doubles(k) * 8) + Arena::al((size_t)kmeans_inertia_blocks(N) * 8) + 8192);
-    if (rc) return rc;
-    unsigned long long* partial = a.take<unsigned long long>(pw_max);
-    long long* red = a.take<long long>(rwords);
-    double* binert = a.take<double>(nb_max);
-    float* Dc = a.take<float>(filter ? (size_t)k * ((k + 255) & ~255) : 1);
-    unsigned long long* Nk = nbr ? a.take<unsigned long long>(k * kp_) : nullptr;      // sorted rows of the centre distances (keys)
-    int* bchg = a.take<int>(nb_max);
-    float* Pf = (pk || pk_lds) ? a.take<float>(k * (kp_ / 2) * 32) : nullptr;         // float pair records of the sorted rows
-    double* c2 = a.take<double>((size_t)k * 16);       // packed centre table (kmeans.hip)
-    double* Cb[2] = {a.take<double>((size_t)k * n), a.take<double>((size_t)k * n)};     // centres of this / the next iteration
-    double* stats = a.take<double>(16);                // [0] squared shift, [1] inertia, [2] changed labels, [3] empty clusters; [4..11] = prm
-    double* fix = a.take<double>(32);                  // fixed-point scales of the member sums
-    unsigned long long* rng = a.take<unsigned long long>(16);
-    double* dmean = a.take<double>(16);
-    double* ms_scratch = a.take<double>(kmeans_mstep_scratch_doubles(k));      // the fused M-step's per-centre shifts / flags and its arrival ticket
-    double* ipart = a.take<double>(kmeans_inertia_blocks(N));                  // block partials of the returned inertia
+    const double* d_X;
+    double* d_C;
+    int32_t* d_labels;
+    unsigned long long *partial, *Nk = nullptr, *rng;      // Nk: sorted rows of the centre distances (keys)
+    long long *red, *tot = nullptr;
+    double *binert, *c2, *Cb[2], *stats, *fix, *dmean, *ms_scratch, *ipart;
+    float *Dc, *Pf = nullptr;                              // Pf: float pair records of the sorted rows
+    int* bchg;
     int *Ls[2] = {nullptr, nullptr}, *Ps[2] = {nullptr, nullptr};
     float* d2 = nullptr;
     float *d2s[2] = {nullptr, nullptr}, *ubs[2] = {nullptr, nullptr}, *lbs[2] = {nullptr, nullptr};      // per position: two copies each, swapped by a re-sort
-    long long* tot = nullptr;
     float *shiftc = nullptr, *mvd = nullptr, *rw2 = nullptr;
     int *blist = nullptr, *nlist = nullptr;
     unsigned *kin = nullptr, *kout = nullptr, *vin = nullptr, *vout = nullptr;
     void* stmp = nullptr;
-    if (sorting) {
-        for (int q = 0; q < 2; ++q) { Ls[q] = a.take<int>(N); Ps[q] = a.take<int>(N); }
-        d2 = a.take<float>(N);
-        kin = a.take<unsigned>(N); kout = a.take<unsigned>(N); vin = a.take<unsigned>(N); vout = a.take<unsigned>(N);
-        stmp = a.take<char>(sort_tmp + 256);
-    }
-    if (bnd) {
-        d2s[0] = d2; d2s[1] = a.take<float>(N);
-        for (int q = 0; q < 2; ++q) { ubs[q] = a.take<float>(N); lbs[q] = a.take<float>(N); }
-        blist = a.take<int>(lwords);
-        tot = a.take<long long>(rwords);
-        shiftc = a.take<float>((size_t)k + kmeans_bounds_tail());
-        mvd = a.take<float>((size_t)k * 4 + 4);
-        rw2 = a.take<float>((size_t)k + 4);
-        nlist = a.take<int>(64);
-    }
+    Arena a(c, host);
+    int rc = a.lay(who, [&] {
+        d_X = a.in(X, (size_t)N * n);                   // (a host form's rows are dense: xstride = n)
+        d_C = a.inout(C_io, (size_t)k * n);
+        d_labels = a.out(labels, N);
+        partial = a.take<unsigned long long>(pw_max);
+        red = a.take<long long>(rwords);
+        binert = a.take<double>(nb_max);
+        Dc = a.take<float>(filter ? (size_t)k * ((k + 255) & ~255) : 1);
+        if (nbr) Nk = a.take<unsigned long long>(k * kp_);
+        bchg = a.take<int>(nb_max);
+        if (pk || pk_lds) Pf = a.take<float>(k * (kp_ / 2) * 32);
+        c2 = a.take<double>((size_t)k * 16);            // packed centre table (kmeans.hip)
+        for (int q = 0; q < 2; ++q) Cb[q] = a.take<double>((size_t)k * n);      // centres of this / the next iteration
+        stats = a.take<double>(16);                     // [0] squared shift, [1] inertia, [2] changed labels, [3] empty clusters; [4..11] = prm
+        fix = a.take<double>(32);                       // fixed-point scales of the member sums
+        rng = a.take<unsigned long long>(16);
+        dmean = a.take<double>(16);
+        ms_scratch = a.take<double>(kmeans_mstep_scratch_doubles(k));      // the fused M-step's per-centre shifts / flags and its arrival ticket
+        ipart = a.take<double>(kmeans_inertia_blocks(N));                  // block partials of the returned inertia
+        if (sorting) {
+            for (int q = 0; q < 2; ++q) { Ls[q] = a.take<int>(N); Ps[q] = a.take<int>(N); }
+            d2 = a.take<float>(N);
+            kin = a.take<unsigned>(N); kout = a.take<unsigned>(N); vin = a.take<unsigned>(N); vout = a.take<unsigned>(N);
+            stmp = a.take<char>(sort_tmp + 256);
+        }
+        if (bnd) {
+            d2s[0] = d2; d2s[1] = a.take<float>(N);
+            for (int q = 0; q < 2; ++q) { ubs[q] = a.take<float>(N); lbs[q] = a.take<float>(N); }
+            blist = a.take<int>(lwords);
+            tot = a.take<long long>(rwords);
+            shiftc = a.take<float>((size_t)k + kmeans_bounds_tail());
+            mvd = a.take<float>((size_t)k * 4 + 4);
+            rw2 = a.take<float>((size_t)k + 4);
+            nlist = a.take<int>(64);
+        }
+    });
+    if (rc) return rc;
     if (mean_host) {
         HIPCK(c, h2d_copy(c, dmean, mean_host, n * 8));
         HIPCK(c, hipStreamSynchronize(c->stream));
@@ -3813,7 +3767,17 @@ int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d
     }
     if (inertia) *inertia = in;
     if (n_iter) *n_iter = it;
-    return BROV_OK;
+    return a.finish();
+}
+
+int edmdc_kmeans_lloyd_dev(brov_ctx* c, int64_t N, int n, int k, const double* d_X, int64_t xstride, const double* mean_host,
+                           double* d_C, int max_iter, double tol_abs, int32_t* d_labels, double* inertia, int* n_iter) {
+    return kmeans_lloyd(c, false, "edmdc_kmeans_lloyd_dev", N, n, k, d_X, xstride, mean_host, d_C, max_iter, tol_abs, d_labels, inertia, n_iter);
+}
+
+int edmdc_kmeans_lloyd(brov_ctx* c, int64_t N, int n, int k, const double* X, const double* mean, double* C_io, int max_iter,
+                       double tol_abs, int32_t* labels, double* inertia, int* n_iter) {
+    return kmeans_lloyd(c, true, "edmdc_kmeans_lloyd", N, n, k, X, n, mean, C_io, max_iter, tol_abs, labels, inertia, n_iter);
 }
 
 // ---- k-means++ seeding (scikit-learn's algorithm, scikit-learn's random numbers) ----------------------------
@@ -3827,25 +3791,32 @@ int edmdc_kmeanspp_dev(brov_ctx* c, int64_t N, int n, int k, const double* d_X, 
     DeviceGuard g(c);
     const size_t nsum = kmeanspp_sum_doubles(N);
     const size_t nu = (size_t)(k > 1 ? k : 1) * n_trials;        // one spare row: the last round's (unused) draw pointer stays in bounds
-    Arena a(c);
     // a float copy of the coordinates screens out the rows a round cannot affect (kmeans.hip, pp_round_kernel); + 8 in the k-means
     // variant: every row goes through the fp64 path
     const bool screening = (c->kmeans_variant & KMV_PP_UNSCREENED) == 0;
     const size_t nshard = kmeanspp_shard_doubles(sharded ? c->km_world : 1);
-    int rc = a.reserve(Arena::al((size_t)N * n * 8) + 2 * Arena::al((size_t)N * 8) + Arena::al(nsum * 8) + Arena::al(nu * 8) + Arena::al(nshard * 8) +
-                       Arena::al((size_t)k * 8) + Arena::al(kmeanspp_state_bytes()) + (screening ? Arena::al((size_t)N * n * 4) + Arena::al(kmeanspp_row_bytes(N, n)) : 0) + 8192);
+    static_assert(sizeof(long long) == sizeof(int64_t), "index width");
+    double *Xt, *xsq, *closest, *dsum, *du, *dmean, *dshard;
+    long long* dind;
+    char *state, *rowbuf = nullptr;                     // rowbuf: row level of the screening (kmeans.hip: PPRows)
+    float* Xf = nullptr;
+    Arena a(c, /*staged=*/true);                        // X and C are device arrays; the indices are the one host array of the layout
+    int rc = a.lay("edmdc_kmeanspp_dev", [&] {
+        Xt = a.take<double>((size_t)N * n);
+        xsq = a.take<double>(N);
+        closest = a.take<double>(N);
+        dsum = a.take<double>(nsum);
+        du = a.take<double>(nu);                        // (k - 1) n_trials of them are the caller's
+        dind = a.out(reinterpret_cast<long long*>(indices_host), k);
+        state = a.take<char>(kmeanspp_state_bytes());
+        dmean = a.take<double>(16);                     // n of them are the caller's
+        if (screening) {
+            Xf = a.take<float>((size_t)N * n);
+            rowbuf = a.take<char>(kmeanspp_row_bytes(N, n));
+        }
+        dshard = a.take<double>(nshard);
+    });
     if (rc) return rc;
-    double* Xt = a.take<double>((size_t)N * n);
-    double* xsq = a.take<double>(N);
-    double* closest = a.take<double>(N);
-    double* dsum = a.take<double>(nsum);
-    double* du = a.take<double>(nu);
-    long long* dind = a.take<long long>(k);
-    char* state = a.take<char>(kmeanspp_state_bytes());
-    double* dmean = a.take<double>(16);
-    float* Xf = screening ? a.take<float>((size_t)N * n) : nullptr;
-    char* rowbuf = screening ? a.take<char>(kmeanspp_row_bytes(N, n)) : nullptr;      // row level of the screening (kmeans.hip: PPRows)
-    double* dshard = a.take<double>(nshard);
     if (mean_host) HIPCK(c, h2d_copy(c, dmean, mean_host, n * 8));
     if (k > 1) HIPCK(c, h2d_copy(c, du, uniforms_host, (size_t)(k - 1) * n_trials * 8));
     HIPCK(c, hipStreamSynchronize(c->stream));          // the host buffers may be temporaries of the caller
@@ -3864,23 +3835,20 @@ int edmdc_kmeanspp_dev(brov_ctx* c, int64_t N, int n, int k, const double* d_X, 
                                      closest, dsum, state, d_C, dind, Xf, rowbuf));
         }
     }
-    if (indices_host) {
-        static_assert(sizeof(long long) == sizeof(int64_t), "index width");
-        HIPCK(c, d2h_copy(c, indices_host, dind, (size_t)k * 8));
-    }
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return BROV_OK;
+    return a.finish();
 }
 
 int edmdc_col_stats_dev(brov_ctx* c, int64_t N, int n, const double* d_X, int64_t xstride, double* mean_host, double* var_host) {
     if (!c || N < 1 || n < 1 || n > 16 || !d_X || xstride < n) return fail(c, BROV_ERR_ARG, "edmdc_col_stats_dev: bad argument (1 <= n <= 16, x_stride >= n)");
     DeviceGuard g(c);
     const int nb = colstats_blocks(N);
-    Arena a(c);
-    int rc = a.reserve((size_t)nb * 16 * 8 + 16 * 8 + 1024);
+    double *d_part, *d_mean;
+    Arena a(c);                                // (the host operands are totals the host forms from the block partials: nothing to stage)
+    int rc = a.lay("edmdc_col_stats_dev", [&] {
+        d_part = a.take<double>((size_t)nb * 16);
+        d_mean = a.take<double>(16);
+    });
     if (rc) return rc;
-    double* d_part = a.take<double>((size_t)nb * 16);
-    double* d_mean = a.take<double>(16);
     std::vector<double> part((size_t)nb * 16);
     double mean[16] = {0};
     auto total = [&](double* out) {            // the partial rows in block order
@@ -3902,27 +3870,6 @@ int edmdc_col_stats_dev(brov_ctx* c, int64_t N, int n, const double* d_X, int64_
         HIPCK(c, hipStreamSynchronize(c->stream));
         total(var_host);
     }
-    return BROV_OK;
-}
-
-int edmdc_kmeans_lloyd(brov_ctx* c, int64_t N, int n, int k, const double* X, const double* mean, double* C_io, int max_iter,
-                       double tol_abs, int32_t* labels, double* inertia, int* n_iter) {
-    if (!c || N < 1 || n < 1 || k < 1 || !X || !C_io) return fail(c, BROV_ERR_ARG, "edmdc_kmeans_lloyd: bad argument");
-    DeviceGuard g(c);
-    double *dX = nullptr, *dC = nullptr;
-    int32_t* dL = nullptr;
-    auto cleanup = [&]() { (void)hipFree(dX); (void)hipFree(dC); (void)hipFree(dL); };
-    HIPCK_CLEAN(hipMalloc((void**)&dX, (size_t)N * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dC, (size_t)k * n * 8));
-    HIPCK_CLEAN(hipMalloc((void**)&dL, (size_t)N * 4));
-    HIPCK_CLEAN(h2d_copy(c, dX, X, (size_t)N * n * 8));
-    HIPCK_CLEAN(h2d_copy(c, dC, C_io, (size_t)k * n * 8));
-    int rc = edmdc_kmeans_lloyd_dev(c, N, n, k, dX, n, mean, dC, max_iter, tol_abs, dL, inertia, n_iter);
-    if (rc) { cleanup(); return rc; }
-    HIPCK_CLEAN(d2h_copy(c, C_io, dC, (size_t)k * n * 8));
-    if (labels) HIPCK_CLEAN(d2h_copy(c, labels, dL, (size_t)N * 4));
-    HIPCK_CLEAN(hipStreamSynchronize(c->stream));
-    cleanup();
     return BROV_OK;
 }
 

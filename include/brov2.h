@@ -752,7 +752,9 @@ BROV_API int edmdc_lift(brov_ctx* ctx, int64_t N, int n, int k, double gamma, co
  *   d = n + k, p = d + r, feature order exactly the reference's ([x, rbf..., u]).
  * Data: nbags trajectories ("bags"); bag b holds states X[b*x_bag_stride + t], t = 0..L,
  * and inputs U[b*u_bag_stride + t], t = 0..L-1, i.e. L pairs per bag and no pair crosses
- * a bag.  fit(X,U) is nbags=1, L=N-1.  accumulate=1 adds to the GtG/GtY passed in. */
+ * a bag.  fit(X,U) is nbags=1, L=N-1.  accumulate=1 adds to the GtG/GtY passed in.
+ * The host forms of edmdc_gram*, edmdc_pinv_apply* and edmdc_kmeans_lloyd stage their arrays in the ctx's scratch arena like every
+ * other host form: it only grows, so a context keeps the device bytes of its largest host call until brov_destroy. */
 BROV_API int edmdc_gram(brov_ctx* ctx, int n, int r, int k, double gamma, const double* C,
                int64_t nbags, int64_t L, int64_t x_bag_stride, int64_t u_bag_stride,
                const double* X, const double* U, int accumulate, double* GtG, double* GtY);

@@ -344,7 +344,7 @@ def tiles(n, r, k):
 
 
 def chunk_rows(chunk, lens, xpad=0):
-    """the rows per lifted chunk that gram_core / apply_core use: the setting rounded up to 4, at most the rows that can start a pair"""
+    """the rows per lifted chunk that gram / apply (csrc/capi.hip) use: the setting rounded up to 4, at most the rows that can start a pair"""
     rows = sum(lens) + xpad * (len(lens) - 1)
     top = max((max(rows - 1, 0) + 3) // 4 * 4, 4)
     return min((chunk + 3) // 4 * 4, top) if chunk else top

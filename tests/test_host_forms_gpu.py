@@ -1,12 +1,14 @@
-"""The host entry points of the Fossen and PINc section of csrc/capi.hip (NumPy arrays staged by the library through the ctx arena)
-against their `_dev` forms on device arrays: both launch the same kernels on the same shapes, so every output is compared with
-tobytes().  The `_dev` forms are called through ctx.lib like the host forms, so that one argument list serves both.
+"""The host entry points of csrc/capi.hip (NumPy arrays staged by the library through the ctx arena) against their `_dev` forms on
+device arrays: both launch the same kernels on the same shapes, so every output is compared with tobytes().  The `_dev` forms are
+called through ctx.lib like the host forms, so that one argument list serves both.  The EDMDc and k-means entry points that exist
+in one form only are called alone in a fresh context and behind a much larger call (alone_and_behind).
 
 Every case runs in two fresh contexts (one per form) and makes its call twice in each: the first call grows the arena, the second
 reuses it, and both give the same bytes.  Output buffers start from a pattern, so what a call leaves unwritten is compared too.
 
 Shapes are the smallest that reach every staging branch: B = 3 trajectories, T = 5 steps at stride 2 (3 stored rows), P = 3
 vehicles of tests/fossen_vehicles.py, N = 70 rows at H = 5 (65 windows: two scan chunks of 64, the second with one window)."""
+import ctypes
 import os
 
 import numpy as np
@@ -32,10 +34,11 @@ W_RAGGED = 100
 
 
 class Buf:
-    """an array argument: staged by the library in the host form, a DevArray in the `_dev` form; out = compared afterwards"""
+    """an array argument: staged by the library in the host form, a DevArray in the `_dev` form; out = compared afterwards.
+    host = True: host memory in both forms (ptr: the ctypes type the binding declares a pointer to, where it is not void)"""
 
-    def __init__(self, name, a, out):
-        self.name, self.a, self.out = name, np.ascontiguousarray(a, dtype=np.float64), out
+    def __init__(self, name, a, out, dtype=np.float64, host=False, ptr=None):
+        self.name, self.a, self.out, self.host, self.ptr = name, np.ascontiguousarray(a, dtype=dtype), out, host, ptr
 
 
 def I(a):
@@ -53,25 +56,25 @@ def IO(name, a):
 def _call(ctx, name, args):
     """one call of ctx.lib.<name>; the outputs by name"""
     from bluerov2_dynamics_amd import engine
-    dev = name.endswith("_dev")
     ctx.use_null_stream()
     live, cargs = [], []
     for a in args:
         if isinstance(a, Buf):
-            h = engine.DevArray.from_host(ctx, a.a) if dev else a.a.copy()
-            live.append((a, h))
-            cargs.append(h.ptr if dev else h.ctypes.data)
+            dev = name.endswith("_dev") and not a.host
+            h = engine.DevArray.from_host(ctx, a.a, a.a.dtype) if dev else a.a.copy()
+            live.append((a, h, dev))
+            cargs.append(h.ptr if dev else h.ctypes.data_as(ctypes.POINTER(a.ptr)) if a.ptr else h.ctypes.data)
         else:
             cargs.append(a)
     rc = getattr(ctx.lib, name)(ctx.h, *cargs)
     assert rc == 0, (name, rc, ctx.lib.brov_last_error(ctx.h))
     ctx.sync()
-    return {a.name: (h.numpy() if dev else h) for a, h in live if a.out}
+    return {a.name: (h.numpy() if dev else h) for a, h, dev in live if a.out}
 
 
-def both(name, host_args, dev_args=None, setup=None, view=None):
+def both(name, host_args, dev_args=None, setup=None, view=None, after=None):
     """host form and `_dev` form, twice each in a fresh context: the outputs both forms have agree byte for byte (view[name]: the
-    part of that output which is compared).  Returns the host form's outputs."""
+    part of that output which is compared; after(ctx): called behind the two calls of a form).  Returns the host form's outputs."""
     from bluerov2_dynamics_amd import _lib
     res = []
     for nm, args in ((name, host_args), (name + "_dev", dev_args or host_args)):
@@ -80,6 +83,8 @@ def both(name, host_args, dev_args=None, setup=None, view=None):
             if setup:
                 setup(ctx)
             first, second = _call(ctx, nm, args), _call(ctx, nm, args)
+            if after:
+                after(ctx)
         finally:
             ctx.close()
         for k in first:
@@ -347,3 +352,198 @@ def test_thruster_stream():
     U, lag = controls(rng, THR, n), rng.uniform(-1, 1, 24)
     r = both("brov_thruster_stream", [n, I(U), DT, IO("lag", lag), O("tau", n, 6)], setup=own_vehicle)
     assert written(r["tau"]) and r["lag"].tobytes() != lag.tobytes()
+
+
+# ------------------------------------------------------------------------------------------ EDMDc and k-means
+# n = 12 states, r = 8 inputs, k = 20 centres (the feature tiles have padding columns), 64 rows per lifted chunk.  A fresh context's
+# arena is exactly what the call's layout declared: a take that the layout missed fails with BROV_ERR_NOMEM, a kernel that counted
+# on bytes behind the last take reads something else in the second call or in the other form.
+EN, ER, EK, GAMMA = 12, 8, 20, 1.0
+EP, ED = EN + EK + ER, EN + EK
+UNI = dict(nbags=3, L=37, xs=40, us=38)                                  # 3 bags of 37 pairs, gap rows between them: 117 pair rows = 64 + 53
+RAG = np.array([0, 40, 41, 41, 113], dtype=np.int64)                     # a one-row bag, an empty bag, a bag across the chunk edge: 64 + 48
+
+
+def chunk64(ctx):
+    ctx.check(ctx.lib.edmdc_set_chunk_rows(ctx.h, 64), "edmdc_set_chunk_rows")
+
+
+def H_(name, a, dtype=np.float64, ptr=None):
+    """a host array in both forms, compared afterwards"""
+    return Buf(name, a, True, dtype, host=True, ptr=ptr)
+
+
+def edmdc_data(layout):
+    rng = np.random.default_rng(21)
+    xrows, urows = ((UNI["nbags"] - 1) * UNI["xs"] + UNI["L"] + 1, (UNI["nbags"] - 1) * UNI["us"] + UNI["L"]) if layout == "uniform" else (int(RAG[-1]),) * 2
+    return np.cumsum(rng.normal(0, 0.05, (xrows, EN)), 0), rng.uniform(-1, 1, (urows, ER)), rng.normal(0, 0.4, (EK, EN)), rng
+
+
+def bag_args(layout):
+    return [UNI["nbags"], UNI["L"], UNI["xs"], UNI["us"]] if layout == "uniform" else [len(RAG) - 1, RAG.ctypes.data]
+
+
+@pytest.mark.parametrize("accumulate", [0, 1])
+@pytest.mark.parametrize("layout", ["uniform", "ragged"])
+def test_gram(layout, accumulate):
+    """accumulate = 1 adds to a non-zero G^T G / G^T Y; the ragged `_dev` form once more without G^T Y (the task table of G^T G alone)"""
+    X, U, C, rng = edmdc_data(layout)
+    G0, Y0 = rng.normal(size=(EP, EP)), rng.normal(size=(EP, ED))
+    name = "edmdc_gram" if layout == "uniform" else "edmdc_gram_ragged"
+    outs = [IO("GtG", G0), IO("GtY", Y0)] if accumulate else [O("GtG", EP, EP), O("GtY", EP, ED)]
+    head = [EN, ER, EK, GAMMA, I(C)] + bag_args(layout) + [I(X), I(U), accumulate]
+    r = both(name, head + outs, setup=chunk64)
+    assert written(r["GtG"]) and written(r["GtY"]) and (accumulate or np.array_equal(r["GtG"], r["GtG"].T))
+    assert not accumulate or (r["GtG"].tobytes() != G0.tobytes() and r["GtY"].tobytes() != Y0.tobytes())
+    if layout == "ragged":
+        from bluerov2_dynamics_amd import _lib
+        ctx = _lib.Context(0)
+        try:
+            chunk64(ctx)
+            alone = _call(ctx, name + "_dev", head + [outs[0], None])
+        finally:
+            ctx.close()
+        assert alone["GtG"].tobytes() == r["GtG"].tobytes()
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("layout", ["uniform", "ragged"])
+def test_pinv_apply(layout, variant):
+    """P is a host array in both forms"""
+    X, U, C, rng = edmdc_data(layout)
+    P = rng.normal(size=(EP, EP)) / np.sqrt(EP)
+
+    def setup(ctx):
+        chunk64(ctx)
+        ctx.set_apply_variant(variant)
+
+    name = "edmdc_pinv_apply" if layout == "uniform" else "edmdc_pinv_apply_ragged"
+    r = both(name, [EN, ER, EK, GAMMA, I(C)] + bag_args(layout) + [I(X), I(U), P.ctypes.data, O("M", EP, ED)], setup=setup)
+    assert written(r["M"])
+
+
+def lloyd_data(k, empty=False):
+    rng = np.random.default_rng(22)
+    X = np.cumsum(rng.normal(0, 0.05, (300, EN)), 0)
+    C0 = X[rng.choice(300, k, replace=False)].copy()
+    if empty:
+        C0[1] += 100.0                                    # tests/test_gpu_parity.py: test_lloyd_empty_clusters_follow_sklearn -- a far initial centre
+    return X, C0
+
+
+@pytest.mark.parametrize("k,mean,empty,host_labels", [(5, True, False, True), (5, False, False, False), (5, True, True, True), (64, True, False, True)])
+def test_kmeans_lloyd(k, mean, empty, host_labels):
+    """with and without a mean; labels = NULL in the host form (arena scratch takes their place); an initial centre far from all
+    samples leaves its cluster empty, so that kmeans_relocate and its own allocations run beside the bound arena; k = 64 takes the
+    candidate filter's buffers.  inertia and n_iter are host scalars in both forms."""
+    X, C0 = lloyd_data(k, empty)
+    m = X.mean(0) if mean else None
+    if mean:
+        C0 = C0 - m
+    mp, seen = None if m is None else m.ctypes.data, []
+    labels = Buf("labels", np.full(300, -7), True, np.int32)
+    tail = [H_("inertia", np.full(1, PAT), ptr=ctypes.c_double), H_("n_iter", np.full(1, -7), np.int32, ptr=ctypes.c_int)]
+    r = both("edmdc_kmeans_lloyd", [300, EN, k, I(X), mp, IO("C", C0), 20, 0.0, labels if host_labels else None] + tail,
+             [300, EN, k, I(X), EN, mp, IO("C", C0), 20, 0.0, labels] + tail, after=lambda ctx: seen.append(ctx.kmeans_relocations()))
+    assert r["C"].tobytes() != C0.tobytes() and r["inertia"][0] > 0 and 1 <= r["n_iter"][0] <= 20
+    assert not host_labels or np.all((r["labels"] >= 0) & (r["labels"] < k))
+    assert all(v >= 1 for v in seen) if empty else seen == [0, 0]
+
+
+def alone_and_behind(name, args, bigger, setup=None):
+    """twice alone in a fresh context, and once in a context whose arena a much larger call has grown: the same bytes all three times --
+    nothing depends on what lies behind the arena's last take.  Returns the outputs."""
+    from bluerov2_dynamics_amd import _lib
+    res = []
+    for first in (args, bigger):
+        ctx = _lib.Context(0)
+        try:
+            if setup:
+                setup(ctx)
+            res += [_call(ctx, name, first), _call(ctx, name, args)]
+        finally:
+            ctx.close()
+    a, b, _, c = res
+    for k in a:
+        assert a[k].tobytes() == b[k].tobytes() == c[k].tobytes(), (name, k)
+    return a
+
+
+def sweep_case(family, pick=None):
+    import sweep_cases as sc
+    return next(c for c in sc.cases(family) if pick is None or pick(c))
+
+
+def test_lift_alone():
+    c = sweep_case("lift")
+
+    def args(N, n, k):
+        rng = np.random.default_rng(23)
+        return [N, n, k, c["gamma"], I(rng.uniform(-0.5, 0.5, (N, n))), I(rng.uniform(-0.5, 0.5, (k, n))), O("Z", N, n + k)]
+
+    r = alone_and_behind("edmdc_lift", args(c["N"], c["n"], c["k"]), args(3000, 12, 300))
+    assert written(r["Z"])
+
+
+def multistep_args(c, N, want_xhat, linear):
+    import sweep_run as sr
+    from bluerov2_dynamics_amd import engine
+    rng = np.random.default_rng(24)
+    n, r, k, Hh = c["n"], c["r"], c["k"], c["H"]
+    C, gamma, A, B = sr.koopman_model(rng, n, r, k)
+    X, U = rng.uniform(-0.5, 0.5, (N, n)), rng.uniform(-1, 1, (max(N - 1, 1), r))       # the shape the header allows: N - 1 rows of U
+    model = [I(m) if m.size else None for m in engine.linear_coefficients(A, B, n, Hh)] if linear else [I(A), I(B)]
+    return [n, r, k, gamma, I(C)] + model + [N, Hh, I(X), I(U), O("se", 1), O("xhat", N - Hh, n) if want_xhat else None]
+
+
+@pytest.mark.parametrize("want_xhat", [True, False])
+@pytest.mark.parametrize("two_groups", [False, True])
+@pytest.mark.parametrize("name", ["edmdc_multistep_se", "edmdc_multistep_se_linear"])
+def test_multistep_alone(name, two_groups, want_xhat):
+    """the family's first case, and its first with H > 1 and 1921 windows or more (16 window blocks: two stream groups)"""
+    c = sweep_case("multistep", (lambda c: c["nw"] >= 1921 and c["H"] > 1) if two_groups else None)
+    linear = name.endswith("linear")
+    r = alone_and_behind(name, multistep_args(c, c["N"], want_xhat, linear), multistep_args(dict(c, H=max(c["H"], 2)), 6000, True, linear))
+    assert written(r["se"]) and (not want_xhat or written(r["xhat"]))
+
+
+def test_simulate_alone():
+    import sweep_run as sr
+    c = sweep_case("simulate")
+
+    def args(nb, T):
+        rng = np.random.default_rng(25)
+        C, gamma, A, B = sr.koopman_model(rng, c["n"], c["r"], c["k"])
+        return [c["n"], c["r"], c["k"], gamma, I(C), I(A), I(B), nb, T, I(rng.uniform(-0.5, 0.5, (nb, c["n"]))),
+                I(rng.uniform(-1, 1, (nb, T, c["r"]))) if T else None, O("Xp", nb, T + 1, c["n"])]
+
+    r = alone_and_behind("edmdc_simulate", args(c["nb"], c["T"]), args(700, 9))
+    assert written(r["Xp"])
+
+
+def test_col_stats_alone():
+    """X is a device array; mean and variance are host arrays"""
+    c = sweep_case("colstats")
+
+    def args(N, n):
+        X = np.random.default_rng(26).normal(size=(N, n))
+        return [N, n, I(X), n, H_("mean", np.full(n, PAT)), H_("var", np.full(n, PAT))]
+
+    r = alone_and_behind("edmdc_col_stats_dev", args(c["N"], c["n"]), args(70000, 12))
+    assert written(r["mean"]) and written(r["var"])
+
+
+def test_kmeanspp_alone():
+    """X and C are device arrays; the mean, the uniforms and the indices are host arrays"""
+    c = sweep_case("kmeanspp")
+    keep = []
+
+    def args(N, n, k, trials):
+        rng = np.random.default_rng(27)
+        X = rng.normal(size=(N, n))
+        keep.extend([X.mean(0), rng.uniform(0, 1, (max(k - 1, 1), trials))])
+        return [N, n, k, I(X), n, keep[-2].ctypes.data, c["first"], trials, keep[-1].ctypes.data if k > 1 else None, O("C", k, n),
+                H_("ind", np.full(k, -7), np.int64)]
+
+    r = alone_and_behind("edmdc_kmeanspp_dev", args(c["N"], c["n"], c["k"], c["trials"]), args(5000, 12, 16, 3))
+    assert written(r["C"]) and np.all((r["ind"] >= 0) & (r["ind"] < c["N"]))
