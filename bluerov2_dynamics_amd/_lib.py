@@ -205,6 +205,12 @@ SIGNATURES = {
                                           ctypes.POINTER(BrovUkf), i64, i64, ctypes.c_double] + [c_void_p] * 16 + [i64, c_void_p]),
     "brov_ukf_smooth_em_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
                                               ctypes.POINTER(BrovUkf), i64, i64, ctypes.c_double] + [c_void_p] * 16 + [i64, c_void_p]),
+    "brov_output_feedback": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                            ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovFeedback), i64, ctypes.POINTER(BrovUkf), i64,
+                                            i64, ctypes.c_double] + [c_void_p] * 7 + [i64] + [c_void_p] * 14),
+    "brov_output_feedback_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
+                                                ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovFeedback), i64, ctypes.POINTER(BrovUkf),
+                                                i64, i64, ctypes.c_double] + [c_void_p] * 7 + [i64] + [c_void_p] * 14),
     "brov_mppi_step":(ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, i64, ctypes.POINTER(BrovParams),
                                       ctypes.POINTER(BrovMppi), i64, i64, ctypes.c_double, ctypes.c_uint64, c_void_p, c_void_p, c_void_p,
                                       i64, i64, c_void_p, c_void_p, ctypes.c_int, c_void_p, c_void_p, c_void_p]),

@@ -86,6 +86,26 @@ struct UkfRtsArgs {
 };
 constexpr int UKF_EM = 37;      // doubles of one em record: Sq [12] | Sr [12] | nr [12] | nq  (include/brov2.h)
 hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a);
+// Output-feedback closed loop (ukf_feedback.hip; include/brov2.h: brov_output_feedback holds the law): candidate j runs B closed loops
+// of T steps, the filter of launch_ukf_filter under fp[j] inside the loop, the law of launch_rollout_feedback on its estimate, the
+// plant under plant[j] (plant_per_candidate) or plant[0].  rec and fb hold one record or P.  x0_true, x0_est [B][12], P0 [B][12][12],
+// V [B][T][12], W [B][T][12] or nullptr, u_ff [B][T][nu] or nullptr and ref [B][ref_rows][12] are shared by the candidates; everything
+// else is per candidate and may be nullptr: lag_est, lag_plant [P][B][24] (both or neither) and z [P][B][6] in / out, traj
+// [P][B][T+1][12], y_out, xf, pstd, innov [P][B][T][12], u_applied [P][B][T][nu], xT_true, xT [P][B][12], PT [P][B][144], metrics
+// [P][B][7], info [P][B][4].  One launch; T >= 1.
+struct UkfFbArgs {
+    const FastParams *fp, *plant;
+    const UkfRec* rec;
+    const FeedbackRec* fb;
+    int rec_per_candidate, fb_per_candidate, plant_per_candidate, pad;
+    int64_t B, T, ref_rows;
+    double dt;
+    const double *x0_true, *x0_est, *P0, *V, *W, *u_ff, *ref;
+    double *lag_est, *lag_plant, *z;
+    double *traj, *y_out, *u_applied, *xf, *pstd, *innov;
+    double *xT_true, *xT, *PT, *metrics, *info;
+};
+hipError_t launch_ukf_feedback(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfFbArgs& a);
 // One MPPI update for B problems (mppi.hip; include/brov2.h: brov_mppi_step holds the law).  MppiRec is struct brov_mppi byte for
 // byte; rec is ONE device record.  fp holds one parameter set (per_problem = 0) or B.  x [B][nx], lag [B][24] or nullptr (zero), ref
 // [B][ref_total][nx], eps [B][K][M][nu] or nullptr (the seeded stream), U_nom [B][M][nu] in / out, M = ceil(H / hold).  cost [B][K]

@@ -1596,6 +1596,22 @@ int brov_rollout_pop(brov_ctx* c, int model, int integ, int lag_mode, int64_t P,
 
 // ---- closed-loop rollouts (feedback.hip) --------------------------------------------------------------------------------------
 static_assert(sizeof(brov_feedback) == sizeof(FeedbackRec) && sizeof(brov_feedback) == 167 * 8, "FeedbackRec is brov_feedback byte for byte");
+// the rules of a feedback record, for brov_rollout_feedback and brov_output_feedback (`fn`)
+static int feedback_records_ok(brov_ctx* c, const std::string& fn, int64_t nfb, const brov_feedback* fb, int nu) {
+    for (int64_t k = 0; k < nfb; ++k) {
+        const brov_feedback& f = fb[k];
+        const std::string who = fn + ": fb[" + std::to_string(k) + "]: ";
+        const double* v = &f.K[0][0];
+        for (int i = 0; i < 166; ++i)
+            if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, who + "NaN in the record");
+        if (f.hold < 1) return fail(c, BROV_ERR_ARG, who + "hold must be >= 1");
+        for (int i = 0; i < nu; ++i)
+            if (f.u_min[i] > f.u_max[i]) return fail(c, BROV_ERR_ARG, who + "u_min must be <= u_max");
+        for (int i = 0; i < 6; ++i)
+            if (f.z_max[i] < 0.0) return fail(c, BROV_ERR_ARG, who + "z_max must be >= 0");
+    }
+    return BROV_OK;
+}
 // Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
 // and of the feedback records, one launch.  host: the arrays are the caller's host memory.
 static int rollout_feedback(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nfb,
@@ -1610,18 +1626,8 @@ static int rollout_feedback(brov_ctx* c, bool host, int model, int integ, int la
     if (ref_rows != 1 && ref_rows != T) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: ref_rows must be 1 or T");
     if (stride < 1) return fail(c, BROV_ERR_ARG, "brov_rollout_feedback: traj_stride must be >= 1");
     const int nx = NX(model), nu = NU(model);
-    for (int64_t k = 0; k < nfb; ++k) {
-        const brov_feedback& f = fb[k];
-        const std::string who = "brov_rollout_feedback: fb[" + std::to_string(k) + "]: ";
-        const double* v = &f.K[0][0];
-        for (int i = 0; i < 166; ++i)
-            if (std::isnan(v[i])) return fail(c, BROV_ERR_ARG, who + "NaN in the record");
-        if (f.hold < 1) return fail(c, BROV_ERR_ARG, who + "hold must be >= 1");
-        for (int i = 0; i < nu; ++i)
-            if (f.u_min[i] > f.u_max[i]) return fail(c, BROV_ERR_ARG, who + "u_min must be <= u_max");
-        for (int i = 0; i < 6; ++i)
-            if (f.z_max[i] < 0.0) return fail(c, BROV_ERR_ARG, who + "z_max must be >= 0");
-    }
+    rc = feedback_records_ok(c, "brov_rollout_feedback", nfb, fb, nu);
+    if (rc) return rc;
     std::vector<FastParams> fp;
     std::vector<double> phi;
     rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
@@ -1681,6 +1687,29 @@ int brov_rollout_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64
 
 // ---- state estimation: the unscented Kalman filter (ukf.hip) -----------------------------------------------------------------------
 static_assert(sizeof(brov_ukf) == 27 * 8 && sizeof(UkfRec) == 28 * 8, "brov_ukf: 27 doubles; UkfRec: the variances and three derived weights");
+// the rules of a filter record and what the kernels derive from it, for the brov_ukf_* calls and brov_output_feedback (`fn`)
+static int ukf_records(brov_ctx* c, const std::string& fn, int64_t nrec, const brov_ukf* ukf, std::vector<UkfRec>& rec) {
+    rec.assign((size_t)nrec, UkfRec{});
+    for (int64_t k = 0; k < nrec; ++k) {
+        const brov_ukf& u = ukf[k];
+        const std::string who = fn + ": ukf[" + std::to_string(k) + "]: ";
+        if (!std::isfinite(u.alpha) || !(u.alpha > 0.0)) return fail(c, BROV_ERR_ARG, who + "alpha must be finite and > 0");
+        const double n = 12.0, lambda = u.alpha * u.alpha * (n + u.kappa) - n, nl = n + lambda;
+        if (!(nl > 0.0) || !std::isfinite(nl) || !std::isfinite(u.beta))
+            return fail(c, BROV_ERR_ARG, who + "n + lambda must be finite and > 0 (and beta finite)");
+        for (int i = 0; i < 12; ++i) {
+            if (!(u.q[i] >= 0.0) || std::isinf(u.q[i])) return fail(c, BROV_ERR_ARG, who + "q must be finite and >= 0");
+            if (!(u.r[i] >= 0.0)) return fail(c, BROV_ERR_ARG, who + "r must be >= 0 (+inf: never measured)");
+            rec[k].q[i] = u.q[i];
+            rec[k].r[i] = u.r[i];
+        }
+        rec[k].c = std::sqrt(nl);
+        rec[k].wc0 = lambda / nl + 1.0 - u.alpha * u.alpha + u.beta;
+        rec[k].wi = 1.0 / (2.0 * nl);
+        rec[k].pad = 0.0;
+    }
+    return BROV_OK;
+}
 // Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
 // and of the derived records, one launch.  host: the arrays are the caller's host memory.
 //
@@ -1718,25 +1747,9 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
         const double fit = std::floor(budget / per_rec);
         if (fit < (double)B) chunk = (int64_t)fit / W * W;
     }
-    std::vector<UkfRec> rec((size_t)nrec);
-    for (int64_t k = 0; k < nrec; ++k) {
-        const brov_ukf& u = ukf[k];
-        const std::string who = fn + ": ukf[" + std::to_string(k) + "]: ";
-        if (!std::isfinite(u.alpha) || !(u.alpha > 0.0)) return fail(c, BROV_ERR_ARG, who + "alpha must be finite and > 0");
-        const double n = 12.0, lambda = u.alpha * u.alpha * (n + u.kappa) - n, nl = n + lambda;
-        if (!(nl > 0.0) || !std::isfinite(nl) || !std::isfinite(u.beta))
-            return fail(c, BROV_ERR_ARG, who + "n + lambda must be finite and > 0 (and beta finite)");
-        for (int i = 0; i < 12; ++i) {
-            if (!(u.q[i] >= 0.0) || std::isinf(u.q[i])) return fail(c, BROV_ERR_ARG, who + "q must be finite and >= 0");
-            if (!(u.r[i] >= 0.0)) return fail(c, BROV_ERR_ARG, who + "r must be >= 0 (+inf: never measured)");
-            rec[k].q[i] = u.q[i];
-            rec[k].r[i] = u.r[i];
-        }
-        rec[k].c = std::sqrt(nl);
-        rec[k].wc0 = lambda / nl + 1.0 - u.alpha * u.alpha + u.beta;
-        rec[k].wi = 1.0 / (2.0 * nl);
-        rec[k].pad = 0.0;
-    }
+    std::vector<UkfRec> rec;
+    rc = ukf_records(c, fn, nrec, ukf, rec);
+    if (rc) return rc;
     std::vector<FastParams> fp;
     std::vector<double> phi;
     rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
@@ -1950,6 +1963,121 @@ int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, 
                     int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
                     double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
     return ukf_filter(c, true, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
+}
+
+// ---- output-feedback closed loop: the filter inside the rollout (ukf_feedback.hip) ---------------------------------------------------
+// Everything the host can refuse comes first -- sizes, models and counts (nplant and the pair of lag banks among them), then the rules of
+// a feedback record, of a filter record, and the derivation of both vehicle lists -- and nothing has been copied or launched when one
+// fires.  Then one upload of the derived constants (filter models, plants) and of both kinds of record, one launch.
+static int output_feedback(brov_ctx* c, bool host, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nplant,
+                           const brov_params* plant, int64_t nfb, const brov_feedback* fb, int64_t nrec, const brov_ukf* ukf, int64_t B,
+                           int64_t T, double dt, const double* x0_true, const double* x0_est, const double* P0, const double* V,
+                           const double* W, const double* u_ff, const double* ref, int64_t ref_rows, double* lag_est_io,
+                           double* lag_plant_io, double* z_io, double* traj, double* y_out, double* u_applied, double* xf, double* pstd,
+                           double* innov, double* xT_true, double* xT, double* PT, double* metrics, double* info) {
+    const std::string fn = "brov_output_feedback";
+    bool empty;
+    int rc = pop_call_ok(c, "brov_output_feedback", model, integ, lag_mode, P, B, T, (int64_t)1 << 31, &empty);
+    if (rc) return rc;
+    if (model != BROV_THRUSTER_EULER && model != BROV_WRENCH_EULER)
+        return fail(c, BROV_ERR_ARG, fn + ": the 12-state Euler models only (BROV_THRUSTER_EULER, BROV_WRENCH_EULER)");
+    if (empty) return BROV_OK;
+    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
+    if (!params || !plant || !fb || !ukf || !x0_true || !x0_est || !P0 || !V || !ref) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
+    if (nplant != 1 && nplant != P) return fail(c, BROV_ERR_ARG, fn + ": nplant must be 1 or P");
+    if (nfb != 1 && nfb != P) return fail(c, BROV_ERR_ARG, fn + ": nfb must be 1 or P");
+    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    if (ref_rows != 1 && ref_rows != T) return fail(c, BROV_ERR_ARG, fn + ": ref_rows must be 1 or T");
+    if ((lag_est_io == nullptr) != (lag_plant_io == nullptr))
+        return fail(c, BROV_ERR_ARG, fn + ": lag_est_io and lag_plant_io go together (both or neither)");
+    const int nu = NU(model);
+    rc = feedback_records_ok(c, fn, nfb, fb, nu);
+    if (rc) return rc;
+    std::vector<UkfRec> rec;
+    rc = ukf_records(c, fn, nrec, ukf, rec);
+    if (rc) return rc;
+    std::vector<FastParams> fp, fpl;
+    std::vector<double> phi;
+    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    rc = derive_candidates(c, integ, (int)nplant, plant, 0, dt, false, fpl, phi);
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const bool lag = lag_est_io && model == BROV_THRUSTER_EULER;
+    const size_t nin = (size_t)B, nout = (size_t)P * B;
+    UkfFbArgs args{};
+    args.rec_per_candidate = nrec > 1;
+    args.fb_per_candidate = nfb > 1;
+    args.plant_per_candidate = nplant > 1;
+    args.B = B; args.T = T; args.ref_rows = ref_rows; args.dt = dt;
+    FastParams *d_fp, *d_fpl;
+    UkfRec* d_rec;
+    FeedbackRec* d_fb;
+    Arena a(c, host);
+    rc = a.lay("brov_output_feedback", [&] {
+        args.x0_true = a.in(x0_true, nin * 12);
+        args.x0_est = a.in(x0_est, nin * 12);
+        args.P0 = a.in(P0, nin * 144);
+        args.V = a.in(V, nin * T * 12);
+        args.W = W ? a.in(W, nin * T * 12) : nullptr;
+        args.u_ff = u_ff ? a.in(u_ff, nin * T * nu) : nullptr;
+        args.ref = a.in(ref, nin * ref_rows * 12);
+        args.lag_est = lag ? a.inout(lag_est_io, nout * 24) : nullptr;
+        args.lag_plant = lag ? a.inout(lag_plant_io, nout * 24) : nullptr;
+        args.z = z_io ? a.inout(z_io, nout * 6) : nullptr;
+        args.traj = traj ? a.out(traj, nout * (T + 1) * 12) : nullptr;
+        args.y_out = y_out ? a.out(y_out, nout * T * 12) : nullptr;
+        args.u_applied = u_applied ? a.out(u_applied, nout * T * nu) : nullptr;
+        args.xf = xf ? a.out(xf, nout * T * 12) : nullptr;
+        args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
+        args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
+        args.xT_true = xT_true ? a.out(xT_true, nout * 12) : nullptr;
+        args.xT = xT ? a.out(xT, nout * 12) : nullptr;
+        args.PT = PT ? a.out(PT, nout * 144) : nullptr;
+        args.metrics = metrics ? a.out(metrics, nout * 7) : nullptr;
+        args.info = info ? a.out(info, nout * 4) : nullptr;
+        d_fp = a.take<FastParams>(P);
+        d_fpl = a.take<FastParams>(nplant);
+        d_rec = a.take<UkfRec>(nrec);
+        d_fb = a.take<FeedbackRec>(nfb);
+    });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    HIPCK(c, h2d_copy(c, d_fpl, fpl.data(), (size_t)nplant * sizeof(FastParams)));
+    HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
+    HIPCK(c, h2d_copy(c, d_fb, fb, (size_t)nfb * sizeof(FeedbackRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp, fpl and rec are locals, fb the caller's
+    args.fp = d_fp;
+    args.plant = d_fpl;
+    args.rec = d_rec;
+    args.fb = d_fb;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_ukf_feedback(c->stream, model, integ, lag_mode, (int)P, args));
+    }
+    return a.finish();
+}
+
+int brov_output_feedback_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nplant,
+                             const brov_params* plant, int64_t nfb, const brov_feedback* fb, int64_t nrec, const brov_ukf* ukf, int64_t B,
+                             int64_t T, double dt, const double* d_x0_true, const double* d_x0_est, const double* d_P0, const double* d_V,
+                             const double* d_W, const double* d_u_ff, const double* d_ref, int64_t ref_rows, double* d_lag_est_io,
+                             double* d_lag_plant_io, double* d_z_io, double* d_traj, double* d_y_out, double* d_u_applied, double* d_xf,
+                             double* d_pstd, double* d_innov, double* d_xT_true, double* d_xT, double* d_PT, double* d_metrics,
+                             double* d_info) {
+    return output_feedback(c, false, model, integ, lag_mode, P, params, nplant, plant, nfb, fb, nrec, ukf, B, T, dt, d_x0_true, d_x0_est, d_P0,
+                           d_V, d_W, d_u_ff, d_ref, ref_rows, d_lag_est_io, d_lag_plant_io, d_z_io, d_traj, d_y_out, d_u_applied, d_xf, d_pstd,
+                           d_innov, d_xT_true, d_xT, d_PT, d_metrics, d_info);
+}
+
+int brov_output_feedback(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nplant,
+                         const brov_params* plant, int64_t nfb, const brov_feedback* fb, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
+                         double dt, const double* x0_true, const double* x0_est, const double* P0, const double* V, const double* W,
+                         const double* u_ff, const double* ref, int64_t ref_rows, double* lag_est_io, double* lag_plant_io, double* z_io,
+                         double* traj, double* y_out, double* u_applied, double* xf, double* pstd, double* innov, double* xT_true, double* xT,
+                         double* PT, double* metrics, double* info) {
+    return output_feedback(c, true, model, integ, lag_mode, P, params, nplant, plant, nfb, fb, nrec, ukf, B, T, dt, x0_true, x0_est, P0, V, W, u_ff,
+                           ref, ref_rows, lag_est_io, lag_plant_io, z_io, traj, y_out, u_applied, xf, pstd, innov, xT_true, xT, PT, metrics, info);
 }
 
 // ---- model-predictive control: one MPPI update (mppi.hip) ------------------------------------------------------------------------

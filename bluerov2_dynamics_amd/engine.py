@@ -671,6 +671,91 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     return out
 
 
+OUTPUT_FEEDBACK_OUTPUTS = ("traj", "y", "u", "xf", "pstd", "innov", "xT_true", "xT", "PT", "metrics", "info")
+
+
+def output_feedback(model, integrator, params_list, feedback, cfg, x0_true, x0_est, P0, V, ref, dt, plant_params=None, W=None, u_ff=None,
+                    lag=None, z=None, lag_mode=LAG_PER_CALL, want=OUTPUT_FEEDBACK_OUTPUTS, ctx=None):
+    """Output-feedback closed loops of a population in one launch: the unscented Kalman filter runs inside the rollout kernel and
+    the feedback law reads its estimate (include/brov2.h: brov_output_feedback_dev holds the law).
+
+    params_list: sequence of P _lib.BrovParams, the filter models.  plant_params: None (every candidate's plant is its own model), one
+    _lib.BrovParams (one true vehicle controlled through P model draws) or a sequence of P.  feedback: one _lib.BrovFeedback or P;
+    cfg: one _lib.BrovUkf or P.  Shared by the candidates: x0_true, x0_est [B,12], P0 [B,12,12], V [B,T,12] (the measurement noise;
+    NaN = not measured at this row; fossen/estimate.py: measurement_noise draws it), W [B,T,12] or None (process disturbance), u_ff
+    [B,T,nu] or None, ref [B,rows,12] with rows 1 or T.  lag: None or the pair (lag_est, lag_plant), each [P,B,8,3] (thruster model);
+    z [P,B,6] or None.  want: the outputs to compute, any of OUTPUT_FEEDBACK_OUTPUTS.  Host and device arrays as in rollout_pop.
+    Returns dict(traj [P,B,T+1,12], y, xf, pstd, innov [P,B,T,12], u [P,B,T,nu], xT_true, xT [P,B,12], PT [P,B,12,12], metrics
+    [P,B,7], info [P,B,4]; lag_est, lag_plant, z | None), with None for what was not wanted.  The shapes are checked before anything
+    touches the device.  The ctx's own parameters are left alone."""
+    want = tuple(want)
+    assert all(w in OUTPUT_FEEDBACK_OUTPUTS for w in want), f"want must be among {OUTPUT_FEEDBACK_OUTPUTS}"
+    assert model in (THRUSTER_EULER, WRENCH_EULER), "output_feedback: the 12-state Euler models only (THRUSTER_EULER, WRENCH_EULER)"
+    P = len(params_list)
+    plants = list(params_list) if plant_params is None else ([plant_params] if isinstance(plant_params, _lib.BrovParams) else list(plant_params))
+    assert len(plants) in (1, P), f"plant_params must be one _lib.BrovParams or {P} of them"
+    fbs = [feedback] if isinstance(feedback, _lib.BrovFeedback) else list(feedback)
+    assert len(fbs) in (1, P), f"feedback must be one _lib.BrovFeedback or {P} of them"
+    cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
+    assert len(cfgs) in (1, P), f"cfg must be one _lib.BrovUkf or {P} of them"
+    nu = NU.get(model, 8)
+    host = isinstance(x0_true, (np.ndarray, list, tuple))
+    lag_est, lag_plant = (None, None) if lag is None else lag
+    assert (lag_est is None) == (lag_plant is None), "lag must be None or the pair (lag_est, lag_plant)"
+    if host:
+        x0_true, x0_est, P0, V, ref = (as_f64(v) for v in (x0_true, x0_est, P0, V, ref))
+        W, u_ff, lag_est, lag_plant, z = (None if v is None else as_f64(v) for v in (W, u_ff, lag_est, lag_plant, z))
+    assert len(V.shape) == 3 and int(V.shape[2]) == 12, "V must be [B,T,12]"
+    B, T = int(V.shape[0]), int(V.shape[1])
+    assert T >= 1, "output_feedback: T must be >= 1"
+    assert len(ref.shape) == 3 and int(ref.shape[0]) == B and int(ref.shape[1]) in (1, T) and int(ref.shape[2]) == 12, \
+        f"ref shape {tuple(ref.shape)} != {(B, '1 or T', 12)}"
+    ref_rows = int(ref.shape[1])
+    for name, v, shape in (("x0_true", x0_true, (B, 12)), ("x0_est", x0_est, (B, 12)), ("P0", P0, (B, 12, 12)), ("W", W, (B, T, 12)),
+                           ("u_ff", u_ff, (B, T, nu))):
+        assert v is None or tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
+    track = model == THRUSTER_EULER and lag_est is not None
+    if track:
+        assert int(np.prod(lag_est.shape)) == P * B * 24 and int(np.prod(lag_plant.shape)) == P * B * 24, "lag_est and lag_plant must be [P,B,8,3]"
+    if z is not None:
+        assert int(np.prod(z.shape)) == P * B * 6, "z must be [P,B,6]"
+    # ---- the device from here on
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+    else:
+        ctx = _ctx_of(x0_true, ctx)
+        arr = arrays_of(x0_true, ctx)
+    arr.bind()
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    pl = (_lib.BrovParams * len(plants))(*plants)
+    fa = (_lib.BrovFeedback * len(fbs))(*fbs)
+    ca = (_lib.BrovUkf * len(cfgs))(*cfgs)
+
+    def in_out(v, shape):          # in / out in the ABI: work on a copy
+        if v is None:
+            return None
+        if host:
+            return arr.upload(v.reshape(shape))
+        return (v.clone() if _is_torch(v) else arr.upload(v.numpy())).reshape(shape)
+    if host:
+        x0_true, x0_est, P0, V, ref = (arr.upload(v) for v in (x0_true, x0_est, P0, V, ref))
+        W, u_ff = (None if v is None else arr.upload(v) for v in (W, u_ff))
+    le, lp = (in_out(lag_est, (P, B, 8, 3)), in_out(lag_plant, (P, B, 8, 3))) if track else (None, None)
+    z_io = in_out(z, (P, B, 6))
+    shapes = dict(traj=(P, B, T + 1, 12), y=(P, B, T, 12), u=(P, B, T, nu), xf=(P, B, T, 12), pstd=(P, B, T, 12), innov=(P, B, T, 12),
+                  xT_true=(P, B, 12), xT=(P, B, 12), PT=(P, B, 12, 12), metrics=(P, B, 7), info=(P, B, 4))
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in OUTPUT_FEEDBACK_OUTPUTS}
+    ctx.check(ctx.lib.brov_output_feedback_dev(ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, len(plants), pl, len(fbs), fa,
+                                               len(cfgs), ca, B, T, float(dt), _dptr(x0_true), _dptr(x0_est), _dptr(P0), _dptr(V), _dptr(W),
+                                               _dptr(u_ff), _dptr(ref), ref_rows, _dptr(le), _dptr(lp), _dptr(z_io),
+                                               *(_dptr(out[k]) for k in OUTPUT_FEEDBACK_OUTPUTS)), "brov_output_feedback_dev")
+    out.update(lag_est=le, lag_plant=lp, z=z_io)
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
 def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _em=None):
     """Backward (Rauch-Tung-Striebel) pass over the tape of ukf_filter(..., tape=True) (include/brov2.h: brov_ukf_rts_dev holds
     the law).  xf [P,B,T,12], tape [P,B,T,UKF_TAPE] and nrows [P,B] as that call returned them (the tape is a documented plain

@@ -206,6 +206,44 @@ class VehicleBase:
         out = (r["traj"][:, 0], r["u"][:, 0], r["metrics"][:, 0])
         return tuple(v[0] for v in out) if single else out
 
+    def simulate_output_feedback(self, x0, ref, dt, feedback, cfg, V, T=None, W=None, x0_est=None, P0=None, params_list=None, plant_params=None,
+                                 integrator="euler"):
+        """One closed loop through the ESTIMATE (engine.output_feedback; include/brov2.h: brov_output_feedback holds the law): the
+        unscented Kalman filter of filter_states runs inside the rollout kernel on y = x_true + V[t], and `feedback` reads its
+        filtered mean, never the true state.  x0 [12] the plant's start; ref [12] (a set-point) or [T,12]; V [T,12] the measurement
+        noise, NaN = not measured at this row (estimate.measurement_noise draws it); W [T,12] an optional process disturbance; T
+        defaults to the rows of V and must equal them.  x0_est defaults to x0, P0 to estimate.default_start's diag(4 r) with
+        estimate.P0_STAND_IN where r is infinite.  The filter models: this vehicle, or params_list (P _lib.BrovParams, e.g. the draws of
+        identify.sample_parameters), and then every result gains a leading P axis.  The plant: plant_params (one _lib.BrovParams),
+        default this vehicle -- so params_list alone asks how much model error the estimator-plus-controller pair tolerates on the
+        one true vehicle.  Returns dict(traj [T+1,12] the true states, y [T,12], u [T,nu], x [T,12] the filtered means, std, innov
+        [T,12], metrics [7], loglik, n_updates, failed_step, min_pivot).  Thruster and Euler-wrench vehicles; starts from zero
+        thruster lag and zero integral state; this object's own lag state is neither read nor changed."""
+        from . import estimate, identify
+        V = np.asarray(V, float)
+        if V.ndim != 2 or V.shape[1] != 12:
+            raise ValueError("V must be [T,12]")
+        if T is not None and int(T) != V.shape[0]:
+            raise ValueError(f"T = {T} but V has {V.shape[0]} rows")
+        ref = np.asarray(ref, float)
+        ref = ref[None] if ref.ndim == 1 else ref
+        x0 = np.asarray(x0, float).reshape(1, 12)
+        x0_est = x0 if x0_est is None else np.asarray(x0_est, float).reshape(1, 12)
+        if P0 is None:
+            r = np.array(list(cfg.r), dtype=float)
+            P0 = np.diag(np.where(np.isfinite(r), 4.0 * np.where(np.isfinite(r), r, 0.0), estimate.P0_STAND_IN))
+        P0 = np.asarray(P0, float).reshape(1, 12, 12)
+        single = params_list is None
+        me = identify.params_of(self)
+        ps = [me] if single else list(params_list)
+        r = engine.output_feedback(self.MODEL, integrator, ps, feedback, cfg, x0, x0_est, P0, V[None], ref[None], dt,
+                                   plant_params=me if plant_params is None else plant_params, W=None if W is None else np.asarray(W, float)[None],
+                                   ctx=self._ctx)
+        out = dict(traj=r["traj"][:, 0], y=r["y"][:, 0], u=r["u"][:, 0], x=r["xf"][:, 0], std=r["pstd"][:, 0], innov=r["innov"][:, 0],
+                   metrics=r["metrics"][:, 0], loglik=r["info"][:, 0, 0], n_updates=r["info"][:, 0, 1].astype(np.int64),
+                   failed_step=r["info"][:, 0, 2].astype(np.int64), min_pivot=r["info"][:, 0, 3])
+        return {k: v[0] for k, v in out.items()} if single else out
+
     def _ukf_inputs(self, Y, U, cfg, x0, P0, params):
         """What filter_states and smooth_states make of their arguments: (single, Y [B,T,12], U [B,T,nu], x0 [B,12], P0 [B,12,12],
         the parameters to filter under), with estimate.default_start where x0 / P0 are None."""

@@ -1,5 +1,6 @@
 """State estimation on the Fossen model: the record of the unscented Kalman filter (engine.ukf_filter, VehicleBase.filter_states,
-VehicleBase.log_likelihood_population), and the EM fit of its q and r (em_update, fit_noise; VehicleBase.fit_noise).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
+VehicleBase.log_likelihood_population), the EM fit of its q and r (em_update, fit_noise; VehicleBase.fit_noise), and the draw of the
+measurement noise that the output-feedback closed loop takes (measurement_noise).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
 scalar Kalman updates with the measured components of the state (a NaN = not measured), then an unscented prediction through the
 vehicle's own step with 2 n + 1 = 25 sigma points.
 
@@ -58,6 +59,28 @@ def default_start(Y, cfg):
         x0[b] = np.where(need, Y[b, full[0]], 0.0)
     d = np.where(need, 4.0 * np.where(need, r, 0.0), P0_STAND_IN)
     return x0, np.repeat(np.diag(d)[None], Y.shape[0], axis=0)
+
+
+def measurement_noise(cfg, shape, dropout=0.0, never=(), seed=0):
+    """The noise rows V [..., 12] of the output-feedback closed loop (engine.output_feedback, VehicleBase.simulate_output_feedback;
+    include/brov2.h: brov_output_feedback): component i is drawn from N(0, cfg.r[i]), seeded; every entry is then dropped (NaN =
+    "not measured at this row") with probability `dropout`.  The components in `never` and those with r = +inf are never measured:
+    their whole column is NaN.  shape: the leading dimensions, (T,) or (B, T).  Runs on the host: the kernel has no random
+    generator of its own.  The draw depends on (seed, shape) alone, not on dropout or never: two calls that differ in those keep the
+    same numbers where both measure."""
+    shape = (int(shape),) if np.isscalar(shape) else tuple(int(s) for s in shape)
+    dropout = float(dropout)
+    if not 0.0 <= dropout <= 1.0:
+        raise ValueError("dropout must lie in [0, 1]")
+    never = [int(i) for i in never]
+    if any(i < 0 or i >= 12 for i in never):
+        raise ValueError("never: components 0 .. 11")
+    r = np.array(list(cfg.r), dtype=float)
+    rng = np.random.default_rng(seed)
+    V = rng.standard_normal(shape + (12,)) * np.sqrt(np.where(np.isfinite(r), r, 0.0))
+    V[rng.random(shape + (12,)) < dropout] = np.nan
+    V[..., [i for i in range(12) if i in never or not np.isfinite(r[i])]] = np.nan
+    return V
 
 
 # ---- fitting q and r by expectation-maximisation (include/brov2.h: brov_ukf_rts_em_dev holds the law of the statistics) -------------

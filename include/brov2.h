@@ -513,6 +513,82 @@ BROV_API int brov_ukf_smooth_em_dev(brov_ctx* ctx, int model, int integrator, in
                            double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
                            double* d_Ps0, double* d_sinfo, int64_t tape_bytes, double* d_em);
 
+/* ---- output-feedback closed loop: the filter inside the rollout kernel ----------------------------------------------------------
+ * brov_rollout_feedback feeds the TRUE state back, and brov_ukf_filter runs over recordings whose commands are fixed.  A vehicle
+ * never sees its true state: brov_output_feedback closes the loop through the estimate.  Candidate j pairs a filter model
+ * params[j] with a plant plant[j] (nplant = P), or with the one plant plant[0] (nplant = 1: one true vehicle controlled through P
+ * model draws); both are HOST arrays as in brov_rollout_pop.  Every candidate runs B closed loops of T steps, in one launch whatever
+ * P, B and T are.  Models BROV_THRUSTER_EULER and BROV_WRENCH_EULER, both integrators, both lag modes, the range of P: those of
+ * brov_ukf_filter.  fb [nfb] and ukf [nrec] are the records of brov_rollout_feedback and brov_ukf_filter with their rules (nfb and
+ * nrec 1 or P).
+ *
+ * Inputs, shared by the candidates: x0_true [B][12], the plant's start; x0_est [B][12] and P0 [B][12][12] (lower triangle read),
+ * the filter's start, the estimate of row 0 BEFORE its measurement; V [B][T][12], the measurement noise, where a NaN means "this
+ * component is not measured at this row" (there is no random generator in the kernel: the caller draws V); W [B][T][12], an
+ * optional process disturbance (NULL = none); u_ff [B][T][nu] optional (NULL = 0); ref [B][ref_rows][12], ref_rows 1 (a set-point)
+ * or T.
+ *
+ * For t = 0 .. T-1, from (x_true, x, P, z) = (x0_true, x0_est, P0, z_io):
+ *   1. Measure.  y = x_true + V[t] component-wise; y_out[t] = y (NaN exactly where V[t] is NaN).
+ *   2. Update.  Stage 1 of brov_ukf_filter on (x, P) with the row y: the same order, wrap, skips and log-likelihood.  Outputs
+ *      xf[t], pstd[t], innov[t].
+ *   3. Command.  At a tick (t a multiple of hold, counted from the start of the call) the law of brov_rollout_feedback with the
+ *      tracking error e taken from the ESTIMATE, e = e(xf[t], ref[t]):
+ *          u = clip(u_ff[t] + K e + Ki z, u_min, u_max),   then   z <- clip(z + hold dt e[0:6], -z_max, z_max),
+ *      in that kernel's order of operations.  Between ticks the command is held.  u_applied[t] = u.
+ *   4. Plant.  x_true advances one step under u through the general step of brov_rollout_pop with the PLANT's parameters and the
+ *      plant's own lag bank; with W, x_true += W[t] afterwards.  traj[t+1] = x_true (traj[0] = x0_true).
+ *   5. Predict.  Stage 2 of brov_ukf_filter on (x, P) with the command u, under params[j], with the filter's own lag bank.
+ * So the estimator is brov_ukf_filter on the rows (u_applied, y_out) and the plant is brov_rollout_pop on u_applied, bit for bit.
+ *
+ * Metrics [7] per (candidate, run).  Entries 0 .. 3 are the four of brov_rollout_feedback, evaluated at every step on the TRUE state
+ * at the start of the step: sum dt |e[0:3]|^2 and sum dt |e[3:6]|^2 with e = e(x_true, ref[t]), sum dt |u|^2 of the applied command,
+ * and the number of steps at which a channel of the applied command equals its u_min or u_max.  Entries 4 .. 6 are the estimation
+ * error sum dt |xf[t] - x_true|^2 over the position (components 0 .. 2), the attitude (3 .. 5, each difference wrapped as in the
+ * filter) and the velocity (6 .. 11), x_true at the start of step t.  info [4] is brov_ukf_filter's.
+ *
+ * Outputs, per candidate, each may be NULL: traj [P][B][T+1][12]; y_out, xf, pstd, innov [P][B][T][12]; u_applied [P][B][T][nu];
+ * xT_true, xT [P][B][12]; PT [P][B][12][12]; metrics [P][B][7]; info [P][B][4].  In / out, per candidate: lag_est_io and
+ * lag_plant_io [P][B][8][3] (thruster model; both or neither; NULL = both start from zero lag, nothing returned) and z_io [P][B][6]
+ * (NULL = start from zero, nothing returned).
+ * Checkpoint: (xT_true, xT, PT, lag_est_io, lag_plant_io, z_io).  A call of T1 steps, T1 a multiple of hold, continued by a call
+ * from the checkpoint with the remaining rows of V, W, u_ff and ref gives the bits of the unbroken call in every per-row output
+ * (traj: the second call's row 0 repeats the first call's last) and in the checkpoint; the metrics and info[0] of the two spans
+ * add up to rounding, info[1] exactly.
+ *
+ * Failure is the filter's: a numerical condition of one (candidate, run), handled in the kernel, which stops that run alone; the
+ * call returns BROV_OK and no other run is touched.  What was complete before the failing stage is kept, the rest is NaN:
+ *   stage 1 of row t fails (s <= 0 or not finite):  kept  traj [0 .. t], y_out [0 .. t], xf, pstd, innov, u_applied [0 .. t-1];
+ *                                                   NaN   traj [t+1 ..], y_out [t+1 ..], xf, pstd, innov, u_applied [t ..];
+ *   stage 2 of row t fails (a pivot argument <= 0 or not finite, or a non-finite predicted mean; the command and the plant's
+ *   step of row t are complete):                    kept  traj [0 .. t+1], y_out, xf, pstd, innov, u_applied [0 .. t];
+ *                                                   NaN   traj [t+2 ..], y_out, xf, pstd, innov, u_applied [t+1 ..].
+ * In both cases xT_true, xT, PT and all seven metrics are NaN, info = (-inf, updates so far, t, smallest pivot so far), and
+ * lag_est_io, lag_plant_io and z_io are left as they came.
+ *
+ * Refused on the host with BROV_ERR_ARG and a brov_last_error text naming the rule, before anything is copied or launched: what
+ * brov_rollout_feedback refuses of a record and of ref_rows (hold < 1, nfb not in {1, P}, ref_rows not in {1, T}, u_min > u_max,
+ * a negative z_max, a NaN anywhere in fb), what brov_ukf_filter refuses (a model other than the two above, nrec not in {1, P}, the
+ * rules of alpha, lambda, q and r, T < 1, P > 65535, dt not finite and > 0, a singular mass matrix of a model or of a plant), and:
+ * nplant not in {1, P}; one of lag_est_io, lag_plant_io without the other; a NULL params, plant, fb, ukf, x0_true, x0_est, P0, V or
+ * ref.  B = 0 or P = 0: BROV_OK, nothing touched.  The ctx's own parameters are neither read nor written.
+ * Deterministic (no atomics, fixed summation orders, every run writes its own outputs): two calls give the same bits. */
+BROV_API int brov_output_feedback(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                         int64_t nplant, const brov_params* plant /* [nplant], host */, int64_t nfb, const brov_feedback* fb /* [nfb], host */,
+                         int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0_true,
+                         const double* x0_est, const double* P0, const double* V, const double* W, const double* u_ff, const double* ref,
+                         int64_t ref_rows, double* lag_est_io, double* lag_plant_io, double* z_io, double* traj, double* y_out,
+                         double* u_applied, double* xf, double* pstd, double* innov, double* xT_true, double* xT, double* PT,
+                         double* metrics, double* info);
+BROV_API int brov_output_feedback_dev(brov_ctx* ctx, int model, int integrator, int lag_mode, int64_t P, const brov_params* params /* [P], host */,
+                             int64_t nplant, const brov_params* plant /* [nplant], host */, int64_t nfb,
+                             const brov_feedback* fb /* [nfb], host */, int64_t nrec, const brov_ukf* ukf /* [nrec], host */, int64_t B,
+                             int64_t T, double dt, const double* d_x0_true, const double* d_x0_est, const double* d_P0, const double* d_V,
+                             const double* d_W, const double* d_u_ff, const double* d_ref, int64_t ref_rows, double* d_lag_est_io,
+                             double* d_lag_plant_io, double* d_z_io, double* d_traj, double* d_y_out, double* d_u_applied, double* d_xf,
+                             double* d_pstd, double* d_innov, double* d_xT_true, double* d_xT, double* d_PT, double* d_metrics,
+                             double* d_info);
+
 /* ---- model-predictive control: one sampling-based (MPPI) update, sampled, rolled out and scored on the device ---------------------
  * brov_mppi_step performs one MPPI update for B independent problems (B vehicles, or B draws of a fit).  Problem b has a state
  * x [nx], for the thruster model optionally a start lag [8][3] (read only; NULL = zero), a reference, and a nominal knot sequence
