@@ -70,6 +70,10 @@ struct UkfArgs {
 constexpr int UKF_TAPE = 312;   // doubles of one tape record: Pf [78] | xp [12] | Pp [78] | C [12][12]  (include/brov2.h)
 int ukf_waves_per_block();      // recordings per block of the filter kernel and of the backward kernel
 hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a);
+// The multiplicative filter on the quaternion model (ukf_quat.hip; include/brov2.h: brov_ukf_filter_quat holds the law).  UkfArgs with
+// x0 [B][13], Y [B][T][13], xf [P][B][T][13] and xT [P][B][13]; P0, pstd, innov, PT and the records stay in the 12-component error
+// state; lag, tape, nrows and Bs are not read.  One launch; T >= 1.
+hipError_t launch_ukf_filter_quat(hipStream_t st, int integ, int P, const UkfArgs& a);
 // Backward (Rauch-Tung-Striebel) pass over a tape (ukf.hip; include/brov2.h: brov_ukf_rts_dev holds the law).  tape [P][B][T][UKF_TAPE]
 // and nrows [P][B] are a chunk's own; xf, the terminal pair and every output are laid out for Bs recordings per candidate and point
 // at the chunk's first recording.  xsT / PsT both nullptr or both set; every output may be nullptr.

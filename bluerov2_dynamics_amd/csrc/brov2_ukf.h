@@ -1,6 +1,6 @@
 // brov2_ukf.h -- the wave's LDS image and the cross-lane helpers of the unscented Kalman filter kernels: shared by ukf.hip (the
-// filter, its tape variant and the backward pass) and ukf_feedback.hip (the filter inside the closed loop).  ukf.hip's head comment
-// describes the layout and the synchronisation they serve.
+// filter, its tape variant and the backward pass), ukf_feedback.hip (the filter inside the closed loop) and ukf_quat.hip (the filter
+// of the quaternion model).  ukf.hip's head comment describes the layout and the synchronisation they serve.
 #pragma once
 #include "brov2_device.h"
 #include "brov2_kernels.h"
@@ -16,6 +16,16 @@ struct UkfLds {
     double P[12][UKF_LD];               // covariance, both triangles
     double L[12][UKF_LD];               // its lower Cholesky factor
     double x[12], m[12], c0[12], k[12]; // mean, mean deviation, propagated point 0, gain column
+};
+
+// the image of the quaternion-model filter (ukf_quat.hip): D, P, L, m and k live in the 12-component error state, the mean and the
+// propagated point 0 in the 13-component state; d is the error-state correction that the updates of a row add up
+struct UkfQuatLds {
+    double D[UKF_NS][UKF_LD];
+    double P[12][UKF_LD];
+    double L[12][UKF_LD];
+    double x[13], c0[13];
+    double d[12], m[12], k[12];
 };
 
 typedef const UkfRec __attribute__((address_space(4)))* CUK;

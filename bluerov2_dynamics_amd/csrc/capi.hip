@@ -1965,6 +1965,75 @@ int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, 
     return ukf_filter(c, true, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
 }
 
+// ---- the multiplicative filter on the quaternion model (ukf_quat.hip) ------------------------------------------------------------------
+// brov_ukf_filter's order: everything the host can refuse first, with the same words; then one upload of FastParams[P] and of the
+// derived records, one launch.  The state arrays are 13 wide, everything in the error state 12.
+static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B,
+                           int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* xf, double* pstd,
+                           double* innov, double* xT, double* PT, double* info) {
+    const char* who_ = "brov_ukf_filter_quat";
+    bool empty;
+    int rc = pop_call_ok(c, who_, BROV_WRENCH_QUAT, integ, BROV_LAG_PER_CALL, P, B, T, (int64_t)1 << 31, &empty);
+    if (rc || empty) return rc;
+    const std::string fn = who_;
+    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
+    if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
+    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    std::vector<UkfRec> rec;
+    rc = ukf_records(c, fn, nrec, ukf, rec);
+    if (rc) return rc;
+    std::vector<FastParams> fp;
+    std::vector<double> phi;
+    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
+    if (rc) return rc;
+    DeviceGuard g(c);
+    const size_t nin = (size_t)B, nout = (size_t)P * B;
+    UkfArgs args{};
+    args.rec_per_candidate = nrec > 1;
+    args.B = B; args.T = T; args.dt = dt;
+    args.Bs = B;
+    FastParams* d_fp;
+    UkfRec* d_rec;
+    Arena a(c, host);
+    rc = a.lay(who_, [&] {
+        args.x0 = a.in(x0, nin * 13);
+        args.P0 = a.in(P0, nin * 144);
+        args.U = a.in(U, nin * T * 6);
+        args.Y = a.in(Y, nin * T * 13);
+        args.xf = xf ? a.out(xf, nout * T * 13) : nullptr;
+        args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
+        args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
+        args.xT = xT ? a.out(xT, nout * 13) : nullptr;
+        args.PT = PT ? a.out(PT, nout * 144) : nullptr;
+        args.info = info ? a.out(info, nout * 4) : nullptr;
+        d_fp = a.take<FastParams>(P);
+        d_rec = a.take<UkfRec>(nrec);
+    });
+    if (rc) return rc;
+    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
+    HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
+    HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
+    args.fp = d_fp;
+    args.rec = d_rec;
+    {
+        CallTimer t(c);
+        HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, args));
+    }
+    return a.finish();
+}
+
+int brov_ukf_filter_quat_dev(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
+                             double dt, const double* d_x0, const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd,
+                             double* d_innov, double* d_xT, double* d_PT, double* d_info) {
+    return ukf_filter_quat(c, false, integ, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_xf, d_pstd, d_innov, d_xT, d_PT, d_info);
+}
+
+int brov_ukf_filter_quat(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
+                         double dt, const double* x0, const double* P0, const double* U, const double* Y, double* xf, double* pstd, double* innov,
+                         double* xT, double* PT, double* info) {
+    return ukf_filter_quat(c, true, integ, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, xf, pstd, innov, xT, PT, info);
+}
+
 // ---- output-feedback closed loop: the filter inside the rollout (ukf_feedback.hip) ---------------------------------------------------
 // Everything the host can refuse comes first -- sizes, models and counts (nplant and the pair of lag banks among them), then the rules of
 // a feedback record, of a filter record, and the derivation of both vehicle lists -- and nothing has been copied or launched when one

@@ -602,7 +602,7 @@ hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode,
     switch (model) {
         case MODEL_THRUSTER_EULER: return launch_ukf_m<MODEL_THRUSTER_EULER>(st, integ, lag_mode, P, a);
         case MODEL_WRENCH_EULER: return launch_ukf_m<MODEL_WRENCH_EULER>(st, integ, lag_mode, P, a);
-        default: return hipErrorInvalidValue;     // a manifold mean for the quaternion model is another feature
+        default: return hipErrorInvalidValue;     // the quaternion model's mean lives on a manifold: ukf_quat.hip is its filter
     }
 }
 

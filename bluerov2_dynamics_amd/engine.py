@@ -671,6 +671,46 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     return out
 
 
+def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS, ctx=None):
+    """The multiplicative unscented Kalman filter on the quaternion model (WRENCH_QUAT) for P vehicles x B recordings in one launch
+    (include/brov2.h: brov_ukf_filter_quat_dev holds the law).  The state is 13 wide (p, q with w first, nu); the covariance, cfg.q
+    and cfg.r live in the 12-component error state (dp, twice the Gibbs vector of a body-frame rotation, dnu).
+
+    params_list, cfg and want as in ukf_filter.  Shared by the candidates: x0 [B,13], P0 [B,12,12] (lower triangle read), U [B,T,6],
+    Y [B,T,13] with NaN where a component was not measured (the attitude of a row counts as measured when none of its four numbers
+    is NaN; it need not be unit, nor on the hemisphere of the estimate).  Host and device arrays as in ukf_filter.
+    Returns dict(xf [P,B,T,13], pstd, innov [P,B,T,12], xT [P,B,13], PT [P,B,12,12], info [P,B,4]), with None for what was not
+    wanted.  The ctx's own parameters are left alone."""
+    want = tuple(want)
+    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
+    P = len(params_list)
+    pa = (_lib.BrovParams * max(P, 1))(*params_list)
+    cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
+    ca = (_lib.BrovUkf * max(len(cfgs), 1))(*cfgs)
+    host = isinstance(x0, (np.ndarray, list, tuple))
+    if host:
+        ctx = ctx or default_context()
+        arr = _NativeArrays(ctx)
+        x0, P0, U, Y = as_f64(x0), as_f64(P0), as_f64(U), as_f64(Y)
+    else:
+        ctx = _ctx_of(x0, ctx)
+        arr = arrays_of(x0, ctx)
+    arr.bind()
+    assert len(U.shape) == 3 and int(U.shape[2]) == 6, "U must be [B,T,6]"
+    B, T = int(U.shape[0]), int(U.shape[1])
+    for name, v, shape in (("x0", x0, (B, 13)), ("P0", P0, (B, 12, 12)), ("Y", Y, (B, T, 13))):
+        assert tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
+    if host:
+        x0, P0, U, Y = arr.upload(x0), arr.upload(P0), arr.upload(U), arr.upload(Y)
+    shapes = dict(_ukf_shapes(P, B, T), xf=(P, B, T, 13), xT=(P, B, 13))
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
+    ctx.check(ctx.lib.brov_ukf_filter_quat_dev(ctx.h, INTEGRATORS[integrator], P, pa, len(cfgs), ca, B, T, float(dt), _dptr(x0), _dptr(P0),
+                                               _dptr(U), _dptr(Y), *(_dptr(out[k]) for k in UKF_OUTPUTS)), "brov_ukf_filter_quat_dev")
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
 OUTPUT_FEEDBACK_OUTPUTS = ("traj", "y", "u", "xf", "pstd", "innov", "xT_true", "xT", "PT", "metrics", "info")
 
 

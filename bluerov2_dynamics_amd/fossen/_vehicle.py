@@ -217,9 +217,11 @@ class VehicleBase:
         identify.sample_parameters), and then every result gains a leading P axis.  The plant: plant_params (one _lib.BrovParams),
         default this vehicle -- so params_list alone asks how much model error the estimator-plus-controller pair tolerates on the
         one true vehicle.  Returns dict(traj [T+1,12] the true states, y [T,12], u [T,nu], x [T,12] the filtered means, std, innov
-        [T,12], metrics [7], loglik, n_updates, failed_step, min_pivot).  Thruster and Euler-wrench vehicles; starts from zero
-        thruster lag and zero integral state; this object's own lag state is neither read nor changed."""
+        [T,12], metrics [7], loglik, n_updates, failed_step, min_pivot).  Thruster and Euler-wrench vehicles (the quaternion vehicle
+        raises NotImplementedError: its filter, filter_states, does not run inside the loop); starts from zero thruster lag and zero
+        integral state; this object's own lag state is neither read nor changed."""
         from . import estimate, identify
+        self._euler_only("simulate_output_feedback")
         V = np.asarray(V, float)
         if V.ndim != 2 or V.shape[1] != 12:
             raise ValueError("V must be [T,12]")
@@ -245,18 +247,37 @@ class VehicleBase:
         return {k: v[0] for k, v in out.items()} if single else out
 
     def _ukf_inputs(self, Y, U, cfg, x0, P0, params):
-        """What filter_states and smooth_states make of their arguments: (single, Y [B,T,12], U [B,T,nu], x0 [B,12], P0 [B,12,12],
-        the parameters to filter under), with estimate.default_start where x0 / P0 are None."""
+        """What filter_states and smooth_states make of their arguments: (single, Y [B,T,nx], U [B,T,nu], x0 [B,nx], P0 [B,12,12],
+        the parameters to filter under), with estimate.default_start where x0 / P0 are None.  The quaternion vehicle: nx = 13,
+        estimate.default_start_quat, and the quaternion of a given x0 normalised."""
         from . import estimate, identify
         Y, U = np.asarray(Y, float), np.asarray(U, float)
         single = Y.ndim == 2
         if single:
             Y, U = Y[None], U[None]
+        quat = self.MODEL == engine.WRENCH_QUAT
+        nx = 13 if quat else 12
         if x0 is None or P0 is None:
-            dx0, dP0 = estimate.default_start(Y, cfg)
-        x0 = dx0 if x0 is None else np.asarray(x0, float).reshape(Y.shape[0], 12)
+            dx0, dP0 = (estimate.default_start_quat if quat else estimate.default_start)(Y, cfg)
+        if x0 is None:
+            x0 = dx0
+        else:
+            x0 = np.array(x0, float).reshape(Y.shape[0], nx)
+            if quat:
+                x0[:, 3:7] /= np.linalg.norm(x0[:, 3:7], axis=1, keepdims=True)
         P0 = dP0 if P0 is None else np.asarray(P0, float).reshape(Y.shape[0], 12, 12)
         return single, Y, U, x0, P0, identify.params_of(self) if params is None else params
+
+    def _ukf_filter(self, integrator, params_list, cfg, x0, P0, U, Y, dt, **kw):
+        """engine.ukf_filter, or engine.ukf_filter_quat on the quaternion vehicle"""
+        if self.MODEL == engine.WRENCH_QUAT:
+            return engine.ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, ctx=self._ctx, **kw)
+        return engine.ukf_filter(self.MODEL, integrator, params_list, cfg, x0, P0, U, Y, dt, ctx=self._ctx, **kw)
+
+    def _euler_only(self, what):
+        if self.MODEL == engine.WRENCH_QUAT:
+            raise NotImplementedError(f"{what}: thruster and Euler-wrench vehicles only; the quaternion vehicle has filter_states and "
+                                      "log_likelihood_population")
 
     @staticmethod
     def _filter_dict(r):
@@ -271,10 +292,14 @@ class VehicleBase:
         and diag(4 r), with estimate.P0_STAND_IN where r is infinite.  params: a _lib.BrovParams to filter under instead of this
         vehicle's own.  Returns dict(x [.,T,12] the filtered means, std [.,T,12], innov [.,T,12] the normalised innovations (NaN
         where nothing was measured), xT, PT, loglik, n_updates, failed_step (-1: none), min_pivot), without the leading B when Y
-        was one recording.  Thruster and Euler-wrench vehicles; starts from zero thruster lag; this object's own lag state is
-        neither read nor changed, and its parameters reach the kernel as arguments."""
+        was one recording.  Starts from zero thruster lag; this object's own lag state is neither read nor changed, and its
+        parameters reach the kernel as arguments.
+        The quaternion vehicle runs the multiplicative filter (engine.ukf_filter_quat; brov_ukf_filter_quat holds the law): Y is
+        [.,T,13], x and xT are 13 wide, std, innov, PT and cfg live in the 12-component error state (dp, g, dnu; estimate.quat_boxminus
+        gives g), the attitude of a row is measured when none of its four numbers is NaN, the default start is
+        estimate.default_start_quat, and the quaternion of a given x0 is normalised here."""
         single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
-        r = engine.ukf_filter(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, ctx=self._ctx)
+        r = self._ukf_filter(integrator, [p], cfg, x0, P0, U, Y, dt)
         out = self._filter_dict(r)
         return {k: v[0] for k, v in out.items()} if single else out
 
@@ -283,7 +308,9 @@ class VehicleBase:
         holds the law): the estimate of every row from ALL rows, where filter_states uses the rows up to it.  Arguments and
         defaults as filter_states.  Returns the dict of filter_states plus xs [.,T,12] the smoothed means, std_s [.,T,12], Ps
         [.,T,12,12] the smoothed covariances, Ps0 [.,12,12] and failed_transition (-1: none, also where the filter completed no
-        row and there was nothing to smooth), without the leading B when Y was one recording.  tape_bytes bounds the library's tape buffer (0: 2 GiB)."""
+        row and there was nothing to smooth), without the leading B when Y was one recording.  tape_bytes bounds the library's tape buffer (0: 2 GiB).
+        Thruster and Euler-wrench vehicles: the quaternion vehicle has no smoother and raises NotImplementedError."""
+        self._euler_only("smooth_states")
         single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
         r = engine.ukf_smooth(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, tape_bytes=tape_bytes, ctx=self._ctx)
         out = dict(self._filter_dict(r), xs=r["xs"][0], std_s=r["pstd_s"][0], Ps=r["Ps"][0], Ps0=r["Ps0"][0],
@@ -294,16 +321,10 @@ class VehicleBase:
         """Which of P vehicles explains noisy recordings best: the innovation log-likelihood of filter_states for every candidate
         of params_list (P _lib.BrovParams, e.g. identify.sample_parameters' draws) in one launch.  Y [B,T,12] (or [T,12]), U, cfg,
         x0, P0 as in filter_states.  Returns l [P,B]; -inf where a filter failed.  Unlike the window evaluator's endpoint error this
-        does not take the measured rows as truth: noise, dropouts and never-measured components are part of the model."""
-        from . import estimate
-        Y, U = np.asarray(Y, float), np.asarray(U, float)
-        if Y.ndim == 2:
-            Y, U = Y[None], U[None]
-        if x0 is None or P0 is None:
-            dx0, dP0 = estimate.default_start(Y, cfg)
-        x0 = dx0 if x0 is None else np.asarray(x0, float).reshape(Y.shape[0], 12)
-        P0 = dP0 if P0 is None else np.asarray(P0, float).reshape(Y.shape[0], 12, 12)
-        r = engine.ukf_filter(self.MODEL, integrator, list(params_list), cfg, x0, P0, U, Y, dt, want=("info",), ctx=self._ctx)
+        does not take the measured rows as truth: noise, dropouts and never-measured components are part of the model.
+        The quaternion vehicle: Y [B,T,13] and x0 [B,13], as in filter_states."""
+        _, Y, U, x0, P0, _ = self._ukf_inputs(Y, U, cfg, x0, P0, None)
+        r = self._ukf_filter(integrator, list(params_list), cfg, x0, P0, U, Y, dt, want=("info",))
         return r["info"][:, :, 0]
 
     def fit_noise(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler", iters=20, tol=1e-4, **kw):
@@ -311,8 +332,10 @@ class VehicleBase:
         iteration is one engine.ukf_smooth that stores no rows).  Y, U, x0, P0, params and their defaults as smooth_states; x0 and
         P0 come from the START record and are not re-estimated.  kw: fit_q, fit_r (bool or bool[12]), q_floor, r_floor,
         tape_bytes.  Returns dict(cfg: the fitted record, for filter_states / smooth_states, q, r [12], loglik [its + 1] the
-        log-likelihood summed over the recordings after each update, q_hist, r_hist [its + 1, 12], n_excluded, converged)."""
+        log-likelihood summed over the recordings after each update, q_hist, r_hist [its + 1, 12], n_excluded, converged).
+        Thruster and Euler-wrench vehicles: EM needs the smoother, so the quaternion vehicle raises NotImplementedError."""
         from . import estimate
+        self._euler_only("fit_noise")
         _, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
         f = estimate.fit_noise(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, iters=iters, tol=tol, ctx=self._ctx, **kw)
         return dict(cfg=f["cfg"][0], q=f["q"][0], r=f["r"][0], loglik=f["loglik"][:, 0], q_hist=f["q_hist"][:, 0], r_hist=f["r_hist"][:, 0],
@@ -322,8 +345,10 @@ class VehicleBase:
         """fit_noise for each of P vehicles (params_list) in the same launches: one noise model per candidate, so that
         log_likelihood_population need not score every candidate under one guessed noise model.  cfg: the start, one record or P.
         Returns the dict of estimate.fit_noise (cfg: P records, q, r [P,12], loglik [its + 1, P], ..) plus loglik_fitted [P] =
-        loglik[-1], the log-likelihood of each candidate under its own fitted noise, summed over the recordings."""
+        loglik[-1], the log-likelihood of each candidate under its own fitted noise, summed over the recordings.  Thruster and
+        Euler-wrench vehicles, as fit_noise."""
         from . import estimate
+        self._euler_only("fit_noise_population")
         _, Y, U, x0, P0, _ = self._ukf_inputs(Y, U, cfg if isinstance(cfg, _lib.BrovUkf) else cfg[0], x0, P0, None)
         f = estimate.fit_noise(self.MODEL, integrator, list(params_list), cfg, x0, P0, U, Y, dt, iters=iters, tol=tol, ctx=self._ctx, **kw)
         return dict(f, loglik_fitted=f["loglik"][-1])

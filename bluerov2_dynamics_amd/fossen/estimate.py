@@ -2,7 +2,8 @@
 VehicleBase.log_likelihood_population), the EM fit of its q and r (em_update, fit_noise; VehicleBase.fit_noise), and the draw of the
 measurement noise that the output-feedback closed loop takes (measurement_noise).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
 scalar Kalman updates with the measured components of the state (a NaN = not measured), then an unscented prediction through the
-vehicle's own step with 2 n + 1 = 25 sigma points.
+vehicle's own step with 2 n + 1 = 25 sigma points.  The quaternion vehicle has the multiplicative form of the same filter
+(engine.ukf_filter_quat; brov_ukf_filter_quat); quat_boxplus, quat_boxminus and default_start_quat are its chart and its default start.
 
 Nothing here runs on the device: the struct goes to the kernel through engine.ukf_filter, and fit_noise sums nothing itself (the
 statistics of an EM iteration come from engine.ukf_smooth)."""
@@ -17,7 +18,8 @@ P0_STAND_IN = 1.0       # default start variance of a component that is never me
 def ukf(q, r, alpha=1.0, beta=2.0, kappa=1.0, n=12):
     """struct brov_ukf (include/brov2.h: brov_ukf_filter) from the per-step process variances q and the measurement variances r
     (scalar or [n]; r = +inf: the component is never measured), and the sigma-point settings alpha, beta, kappa.  n is the state
-    size: 12, the Euler models.  ValueError where the library would refuse the record: n != 12, a NaN, a negative q or r, an infinite
+    size: 12, the Euler models -- and the quaternion model too, whose record lives in its 12-component error state (q[3..5] and
+    r[3..5] in the units of quat_boxminus, rad^2 at small angles).  ValueError where the library would refuse the record: n != 12, a NaN, a negative q or r, an infinite
     q, alpha not finite or <= 0, n + lambda <= 0 with lambda = alpha^2 (n + kappa) - n.  A small alpha costs digits (alpha = 1e-3:
     a centre weight of -1.2e7); alpha in [0.5, 1] is the tested range."""
     n = int(n)
@@ -57,6 +59,65 @@ def default_start(Y, cfg):
         if full.size == 0:
             raise ValueError(f"recording {b} has no row with every measured component present: give x0")
         x0[b] = np.where(need, Y[b, full[0]], 0.0)
+    d = np.where(need, 4.0 * np.where(need, r, 0.0), P0_STAND_IN)
+    return x0, np.repeat(np.diag(d)[None], Y.shape[0], axis=0)
+
+
+# ---- the quaternion model: the chart of the multiplicative filter (include/brov2.h: brov_ukf_filter_quat holds the law) ------------
+def _qmul(a, b):
+    """Hamilton product over leading dimensions, w first"""
+    aw, ax, ay, az = (a[..., i] for i in range(4))
+    bw, bx, by, bz = (b[..., i] for i in range(4))
+    return np.stack([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw], -1)
+
+
+def quat_boxplus(X, D):
+    """X [+] D of the quaternion model's filter: X [...,13] = (p, q with w first, nu), D [...,12] = (dp, g, dnu) with g twice the
+    Gibbs vector of a rotation in the body frame.  Returns (p + dp, q (x) dq(g), nu + dnu) with dq(g) = (1, g / 2) / sqrt(1 +
+    |g|^2 / 4).  No branch: negating q negates the result's quaternion; the norm of q is kept."""
+    X, D = np.asarray(X), np.asarray(D)
+    h = D[..., 3:6] / 2
+    dq = np.concatenate([np.ones_like(h[..., :1]), h], -1) / np.sqrt(1 + np.sum(h * h, -1, keepdims=True))
+    return np.concatenate([X[..., :3] + D[..., :3], _qmul(X[..., 3:7], dq), X[..., 7:] + D[..., 6:]], -1)
+
+
+def quat_boxminus(A, B):
+    """A [-] B, the inverse of quat_boxplus in its second argument: (p_a - p_b, 2 e_v / e_w, nu_a - nu_b) [...,12] with
+    e = conj(q_b) (x) q_a.  Invariant to the sign and the norm of either quaternion; not finite at exactly half a turn (e_w = 0).
+    The attitude part is 2 tan(angle / 2) along the axis: the angle in rad when it is small."""
+    A, B = np.asarray(A), np.asarray(B)
+    qb = B[..., 3:7] * np.array([1.0, -1.0, -1.0, -1.0], dtype=B.dtype)
+    e = _qmul(qb, A[..., 3:7])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        g = 2 * e[..., 1:] / e[..., :1]
+    return np.concatenate([A[..., :3] - B[..., :3], g, A[..., 7:] - B[..., 7:]], -1)
+
+
+def default_start_quat(Y, cfg):
+    """(x0 [B,13], P0 [B,12,12]) of the quaternion vehicle's filter_states when none is given.  x0: the first row of each recording
+    in Y [B,T,13] in which every component with a finite r is present (r[3..5] stand for the four numbers of the quaternion), taken as
+    the guess for row 0 with its quaternion normalised; components that are never measured start at 0, the attitude at the identity.
+    ValueError when a recording has no such row, or when that row's quaternion is zero.  P0 = diag(4 r), with P0_STAND_IN where r
+    is infinite."""
+    Y = np.asarray(Y, dtype=float)
+    r = np.array(list(cfg.r), dtype=float)
+    need = np.isfinite(r)
+    att = bool(need[3:6].any())
+    need13 = np.concatenate([need[:3], [att] * 4, need[6:]])
+    x0 = np.zeros((Y.shape[0], 13))
+    for b in range(Y.shape[0]):
+        full = np.flatnonzero(~np.isnan(Y[b][:, need13]).any(axis=1))
+        if full.size == 0:
+            raise ValueError(f"recording {b} has no row with every measured component present: give x0")
+        x0[b] = np.where(need13, Y[b, full[0]], 0.0)
+        if att:
+            n = np.linalg.norm(x0[b, 3:7])
+            if not n > 0:
+                raise ValueError(f"recording {b}: the quaternion of its first complete row is zero: give x0")
+            x0[b, 3:7] /= n
+        else:
+            x0[b, 3:7] = (1.0, 0.0, 0.0, 0.0)
     d = np.where(need, 4.0 * np.where(need, r, 0.0), P0_STAND_IN)
     return x0, np.repeat(np.diag(d)[None], Y.shape[0], axis=0)
 

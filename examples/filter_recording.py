@@ -18,7 +18,13 @@ the fit.  EM finds r within a few updates and moves q slowly (some 75 updates un
 itself here); stopped after 10 or 20, r has already shrunk to the truth while q is still far too large, and the RMSE is then worse
 than under the guess, so the loop runs to its tolerance.
 
-    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth] [--fit-noise]
+With --quat the vehicle is the quaternion one (fossen/BlueROV2_wrench.py) and the recording starts within 0.1 rad of pitch 90
+degrees, where the Euler-angle vehicles have their 1 / cos(theta): rov.filter_states then runs the multiplicative filter
+(brov_ukf_filter_quat), whose covariance lives in a 12-component error state.  The attitude errors are taken through
+estimate.quat_boxminus (rad at small angles); every third measured quaternion is reported negated, which the filter must not see.
+The small sizes (3 s, 7 draws).
+
+    python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth] [--fit-noise] [--quat]
 """
 import argparse
 import os
@@ -134,6 +140,59 @@ def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="r
                 **extra)
 
 
+def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True):
+    """The quaternion vehicle, started near vertical.  Returns dict(X [T+1,13], Y [T,13], x [T,13], std, innov [T,12], rmse_raw,
+    rmse_filtered: dict(position, attitude, velocity) over the measured entries of the second half, nis, loglik [draws + 1] with the
+    true vehicle at index 0, order, rank_true)"""
+    from bluerov2_dynamics_amd.fossen.BlueROV2_wrench import BlueROV2 as BlueROV2Quat, euler_to_quat
+    rov = BlueROV2Quat()
+    true = identify.copy_params(identify.params_of(rov))
+    for i, v in enumerate((0.15, -0.1, 0.03)):
+        true.current[i] = v
+    T = int(round(seconds / dt))
+    rng = np.random.default_rng(seed)
+    t = np.arange(T) * dt
+    U = 0.5 * np.sin(2 * np.pi * np.outer(t, np.linspace(0.3, 1.0, 6)) + rng.uniform(0, 6, 6)) * np.array([10.0, 10.0, 10.0, 0.5, 0.5, 0.5])
+    x0 = np.zeros(13)
+    x0[2] = 5.0
+    x0[3:7] = euler_to_quat(0.1, np.pi / 2 - rng.uniform(0.0, 0.1), -0.2)
+    X = engine.rollout_pop(rov.MODEL, integrator, [true], x0[None], U[None], dt, ctx=rov._ctx)["traj"][0, 0]
+    Y = estimate.quat_boxplus(X[:T], rng.normal(size=(T, 12)) * SIGMA)
+    gone = rng.uniform(size=(T, 12)) < dropout
+    gone[:, UNMEASURED] = True
+    Y[np.concatenate([gone[:, :3], np.repeat(gone[:, 3:4], 4, 1), gone[:, 6:]], 1)] = np.nan     # the attitude is measured as a whole
+    Y[::3, 3:7] *= -1.0                                                                          # q and -q are the same attitude
+    r = SIGMA ** 2
+    r[UNMEASURED] = np.inf
+    cfg = estimate.ukf(q=1e-6, r=r)
+    start = estimate.quat_boxplus(x0, rng.normal(size=12) * SIGMA)
+    P0 = np.diag(np.where(np.isfinite(r), 4.0 * SIGMA ** 2, estimate.P0_STAND_IN))
+    f = rov.filter_states(Y, U, dt, cfg, x0=start, P0=P0, params=true, integrator=integrator)
+    half = slice(T // 2, T)
+    att = ~np.isnan(Y[:, 3:7]).any(axis=1)
+    seen = np.concatenate([~np.isnan(Y[:, :3]), np.repeat(att[:, None], 3, 1), ~np.isnan(Y[:, 7:])], 1)[half]
+    e_raw = estimate.quat_boxminus(np.where(np.isnan(Y), X[:T], Y), X[:T])[half]                 # (what is not seen is masked below)
+    e_f = estimate.quat_boxminus(f["x"], X[:T])[half]
+    parts = dict(position=slice(0, 3), attitude=slice(3, 6), velocity=slice(6, 12))
+    rmse = lambda e: {k: float(np.sqrt(np.mean(e[:, c][seen[:, c]] ** 2))) for k, c in parts.items()}
+    rmse_raw, rmse_f = rmse(e_raw), rmse(e_f)
+    nis = float(np.nanmean(f["innov"] ** 2))
+    cands = [true] + drawn_vehicles(true, int(draws), seed + 1, rel_std)
+    ll = rov.log_likelihood_population(cands, Y, U, dt, cfg, x0=start, P0=P0, integrator=integrator)[:, 0]
+    order = np.argsort(-ll)
+    rank = int(np.flatnonzero(order == 0)[0])
+    if verbose:
+        pitch = np.degrees(np.arcsin(np.clip(2.0 * (X[:, 3] * X[:, 5] - X[:, 6] * X[:, 4]), -1.0, 1.0)))
+        print(f"{T} rows of {dt} s on the quaternion vehicle, pitch between {pitch.min():.1f} and {pitch.max():.1f} degrees, "
+              f"{f['n_updates']} scalar updates, smallest Cholesky pivot {f['min_pivot']:.2e}")
+        for k in parts:
+            print(f"RMSE over the second half, measured entries, {k}: raw {rmse_raw[k]:.4f}, filtered {rmse_f[k]:.4f}")
+        print(f"mean squared normalised innovation {nis:.2f} (1 when the noise model fits)")
+        print(f"the true vehicle ranks {rank + 1} of {len(cands)} by log-likelihood ({ll[0]:.1f}; best {ll[order[0]]:.1f}, worst {ll[order[-1]]:.1f})")
+    return dict(X=X, Y=Y, x=f["x"], std=f["std"], innov=f["innov"], rmse_raw=rmse_raw, rmse_filtered=rmse_f, nis=nis, loglik=ll, order=order,
+                rank_true=rank)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=10.0)
@@ -144,7 +203,12 @@ def main(argv=None):
     ap.add_argument("--small", action="store_true", help="3 s and 7 draws: runs in seconds")
     ap.add_argument("--smooth", action="store_true", help="also smooth the recording (rov.smooth_states) and print the smoothed RMSE")
     ap.add_argument("--fit-noise", action="store_true", help="fit q and r by EM from a wrong guess (rov.fit_noise) and print what it gains")
+    ap.add_argument("--quat", action="store_true", help="the quaternion vehicle from a start near pitch 90 degrees, in the small sizes")
     a = ap.parse_args(argv)
+    if a.quat:
+        if a.smooth or a.fit_noise:
+            ap.error("--quat: the quaternion vehicle has the filter only (no --smooth, no --fit-noise)")
+        return run_quat(rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed)
     if a.small:
         a.seconds, a.draws = 3.0, 7
     return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth,

@@ -337,7 +337,8 @@ BROV_API int brov_rollout_feedback_dev(brov_ctx* ctx, int model, int integrator,
  * (params[j], a HOST array as in brov_rollout_pop) filters B recordings of T rows each, in one launch whatever P, B and T are.
  * info[0], the innovation log-likelihood, says which candidate explains a recording best.
  * Models BROV_THRUSTER_EULER and BROV_WRENCH_EULER (n = 12 states, 2 n + 1 = 25 sigma points); both integrators and both lag
- * modes.  The quaternion model (its mean lives on a manifold) and the double-integrator models: BROV_ERR_ARG.  The thruster lag
+ * modes.  The quaternion model (its mean lives on a manifold: brov_ukf_filter_quat below is its filter) and the double-integrator
+ * models: BROV_ERR_ARG.  The thruster lag
  * depends on the commands only, never on the state, so all sigma points share one lag bank and the filter's state stays at 12.
  * The measurements are components of the state and R is diagonal, so the measurement update is a sequence of scalar Kalman
  * updates: exact, no unscented transform, no matrix inverse, and per-component dropouts come for free.
@@ -396,6 +397,61 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
                         const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
                         double* d_innov, double* d_xT, double* d_PT, double* d_info);
 
+/* ---- the filter on the quaternion model: a multiplicative UKF ------------------------------------------------------------------
+ * brov_ukf_filter_quat is brov_ukf_filter for BROV_WRENCH_QUAT, the vehicle that flies through pitch = +-90 degrees: candidate j
+ * filters B recordings of T rows, one launch.  Its arguments are brov_ukf_filter's without model, lag_mode and lag_io (this is the
+ * wrench model).
+ *
+ * State and error state.  The state is x[13] = p[3], q[4] (w first, Hamilton product, as everywhere in the library), nu[6].  The
+ * error state is delta[12] = dp[3], g[3], dnu[6].  P, q[12] and r[12] live in the error state; the record is brov_ukf, unchanged,
+ * with n = 12 in lambda, c, Wc_0 and W_i.  The attitude chart is twice the Gibbs vector, applied on the right, i.e. in the body
+ * frame, the side that brov_rollout_feedback's conj(q) (x) q_ref uses:
+ *     dq(g) = (1, g / 2) / sqrt(1 + |g|^2 / 4)
+ *     x [+] delta = (p + dp, q (x) dq(g), nu + dnu)
+ *     a [-] b = (p_a - p_b, 2 e_v / e_w, nu_a - nu_b)  with e = conj(q_b) (x) q_a
+ * The chart has no branch.  It is invariant to the sign and the norm of either quaternion, so a measured quaternion need not be
+ * unit.  It leaves the finite numbers only at exactly half a turn, where e_w = 0.
+ *
+ * Inputs, shared by the candidates: x0 [B][13]; P0 [B][12][12] (lower triangle read); U [B][T][6]; Y [B][T][13].  The position and
+ * velocity entries of Y are as in brov_ukf_filter: NaN means not measured.  The attitude of row t is measured only when none of
+ * Y[t][3..6] is NaN.  r[3..5] are the variances of the attitude measurement in chart units, which is rad^2 at small angles.
+ *
+ * For t = 0 .. T-1, starting from (x, P) = (x0, P0):
+ *   1. Update with row t.
+ *      a. Form z[12] once, from x as the row found it: z[0..2] = Y[t][0..2] - p;  z[3..5] = 2 e_v / e_w with
+ *         e = conj(q) (x) q_y;  z[6..11] = Y[t][7..12] - nu.
+ *      b. If the attitude is measured and a z[3..5] is not finite, stage 1 of row t fails before any update of the row is applied
+ *         (q_y = 0, or a measurement half a turn away).
+ *      c. Start with d = 0.  For i = 0 .. 11 in order, skipping where z[i] is NaN (not measured) or r[i] = +inf:
+ *             v = z[i] - d[i];  s = P[i][i] + r[i] (s <= 0 or not finite fails stage 1 as in brov_ukf_filter);  k = P[:, i] / s;
+ *             d += k v;  P[a][b] -= k[a] k[b] s, the same expression for both triangles;
+ *             l -= (ln(2 pi s) + v^2 / s) / 2;  innov[t][i] = v / sqrt(s).
+ *      d. x = x [+] d.
+ *      e. The outputs of the row: xf[t][13], pstd[t][12] and innov[t][12], NaN where skipped.
+ *      For position and velocity this is brov_ukf_filter's update exactly.  For the attitude it is the multiplicative update with
+ *      one reset per row.
+ *   2. Predict with U[t].  P = L L^T with brov_ukf_filter's Cholesky and pivot rule;  chi_0 = x, chi_i = x [+] (c L[:, i-1]),
+ *      chi_{i+12} = x [+] (-c L[:, i-1]).  Every chi advances one step through the general step of brov_rollout_pop for
+ *      BROV_WRENCH_QUAT, which normalises q.  d_i = chi_i' [-] chi_0';  m = sum_{i>=1} W_i d_i;  x = chi_0' [+] m;
+ *      P = Wc_0 m m^T + sum_{i>=1} W_i (d_i - m)(d_i - m)^T + diag(q).  Every sum runs in index order.  A non-finite entry of m or
+ *      x fails stage 2, as the non-finite predicted mean does in brov_ukf_filter.
+ * Neither is derived here: the prediction is not re-centred at the new mean (it is the usual first-order USQUE form), and P is not
+ * transported between the tangent spaces at a reset.
+ *
+ * Outputs, per candidate, each may be NULL: xf [P][B][T][13]; pstd, innov [P][B][T][12]; xT [P][B][13]; PT [P][B][12][12],
+ * bit-symmetric; info [P][B][4] as brov_ukf_filter.
+ * Unchanged from brov_ukf_filter: the failure handling (the problem stops alone, NaN rows, info), the continuation property (a call
+ * resumed from (xT, PT) gives the bits of the unbroken call), determinism, and every host-side refusal that applies, with the same
+ * words.  x0's quaternion is used as it comes: negating it negates the quaternion of xf and xT and changes no other bit.
+ * Not covered: the tape variant, the smoother, EM and output feedback keep refusing the quaternion model. */
+BROV_API int brov_ukf_filter_quat(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
+                         const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0, const double* P0,
+                         const double* U, const double* Y, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info);
+BROV_API int brov_ukf_filter_quat_dev(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
+                             const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                             const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd, double* d_innov,
+                             double* d_xT, double* d_PT, double* d_info);
+
 /* ---- state estimation after the fact: the unscented Rauch-Tung-Striebel smoother over the filter ------------------------------
  * The filter estimates row t from rows 0 .. t.  For a recording that is complete the smoothed estimate E[x_t | all rows] is the
  * better one: smaller errors, honest error bars in the first rows, better values of a component that is never measured.  It is a
@@ -448,7 +504,7 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
  * Refused on the host, before anything is copied, allocated or launched, with a text that names the function called: everything
  * brov_ukf_filter refuses, a negative tape_bytes, and a tape_bytes smaller than one block of recordings (P * 4 * T * 2496 bytes).
  * Deterministic (no atomics, fixed summation orders): two calls give the same bits.
- * Still missing: a quaternion model, full Q and R.
+ * Still missing: a smoother for the quaternion model (brov_ukf_filter_quat is its forward filter; it writes no tape), full Q and R.
  *
  * ---- fitting q and r: the sufficient statistics of expectation-maximisation (EM) ------------------------------------------------
  * Every call above takes a record whose q[12] and r[12] are guesses.  brov_ukf_rts_em_dev and brov_ukf_smooth_em[_dev] are the
