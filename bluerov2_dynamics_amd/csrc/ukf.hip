@@ -57,17 +57,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
     load_hot(p, h);
     const double dt = a.dt;
     const double NaN = __builtin_nan(""), INF = __builtin_inf();
-    // the entries of P this lane owns
-    int a0, b0, a1, b1;
-    ukf_entry(lane, a0, b0);
-    const bool two = lane + 64 < 78;
-    ukf_entry(two ? lane + 64 : lane, a1, b1);
-    // the sigma point of this lane: x + sc L[:, col]
-    const bool point = lane >= 1 && lane < UKF_NS;
-    const int col = point ? (lane - 1) % 12 : 0;
+    const UkfOwn own = ukf_own(lane);                         // the entries of P this lane owns
+    const int lr = own.lr;                                    // its row in the per-row phases
+    int col;                                                  // its sigma point: x + sc L[:, col]
+    double sc;
     const double cw = f->c;
-    const double sc = point ? (lane <= 12 ? cw : -cw) : 0.0;
-    const int lr = lane < 12 ? lane : 11;                     // the row of this lane in the per-row phases (lanes >= 12 repeat row 11)
+    ukf_point(lane, cw, col, sc);
 
     LagZ lz;
     double Xl[8][3];
@@ -75,10 +70,8 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         if constexpr (TRACK) load_row<24>(a.lag + row * 24, &Xl[0][0]);
         else lz.zero();
     }
-    double p0 = a.P0[b * 144 + a0 * 12 + b0], p1 = a.P0[b * 144 + a1 * 12 + b1];
-    S.P[a0][b0] = p0;
-    S.P[b0][a0] = p0;
-    if (two) { S.P[a1][b1] = p1; S.P[b1][a1] = p1; }
+    double p0 = a.P0[b * 144 + own.a0 * 12 + own.b0], p1 = a.P0[b * 144 + own.a1 * 12 + own.b1];
+    ukf_put_P(S, own, p0, p1);
     if (lane < 12) S.x[lane] = a.x0[b * 12 + lane];
     ukf_wave_sync();
 
@@ -96,36 +89,11 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         double inn = NaN;
         bool bad = false;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const double yi = ukf_uniform(y[i]), ri = f->r[i];
-            if (bad || yi != yi || ri == INF) continue;                // wave-uniform
-            const double s = ukf_uniform(S.P[i][i]) + ri;
-            if (!(s > 0.0) || s == INF) { bad = true; continue; }
-            double v = yi - ukf_uniform(S.x[i]);
-            if (i >= 3 && i < 6) v = ukf_wrap(v);
-            if (lane < 12) {
-                const double k = S.P[lane][i] / s;
-                S.k[lane] = k;
-                S.x[lane] += k * v;
-            }
-            ell -= 0.5 * (log(6.28318530717958647692e+00 * s) + v * v / s);
-            nupd += 1.0;
-            if (lane == i) inn = v / sqrt(s);
-            ukf_wave_sync();                                           // k, x written; every read of column i of P done
-            p0 -= S.k[a0] * S.k[b0] * s;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                p1 -= S.k[a1] * S.k[b1] * s;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-            ukf_wave_sync();                                           // P written
-        }
+        for (int i = 0; i < 12; ++i) ukf_update<true>(S, S.x, f, i, ukf_uniform(y[i]), own, p0, p1, lane, ell, nupd, inn, bad);
         if (bad) { failed = t; nan_from = t; break; }
         if constexpr (TAPE) {                                          // Pf_t: the entries this lane holds, 8-byte stores side by side
             tp[t * UKF_TAPE + lane] = p0;
-            if (two) tp[t * UKF_TAPE + 64 + lane] = p1;
+            if (own.two) tp[t * UKF_TAPE + 64 + lane] = p1;
         }
         if (lane < 12) {
             if (xfp) xfp[t * 12] = S.x[lane];
@@ -133,26 +101,11 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
             if (inp) inp[t * 12] = inn;
         }
         // ---- 2. predict with U[t] -------------------------------------------------------------------------------------------
-        // Cholesky, one lane per row, column by column: s_i = P[i][j] - sum_k L[i][k] L[j][k].  Lane j's own s is the pivot argument;
-        // row j, which the other lanes need for column j, is in the image since its last entry was written at column j - 1.
         double Lr[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) Lr[k] = S.P[lr][k];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            double s = Lr[j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
-            const double piv = ukf_lane(s, j);
-            double d = 1.0;
-            if (!bad) {
-                if (!(piv > 0.0) || piv == INF) bad = true;
-                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
-            }
-            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
-            if (lane < 12) S.L[lane][j] = Lr[j];
-            ukf_wave_sync();                                           // column j of L written
-        }
+        for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
         if (bad) { failed = t; nan_from = t + 1; break; }
         double x[12], u[NU];
 #pragma unroll
@@ -176,9 +129,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         const double wi = f->wi;
         bool finite = true;
         if (lane < 12) {
-            double m = 0.0;
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) m = fma(wi, S.D[i][lane], m);
+            const double m = ukf_mean_dev(S, wi, lane);
             const double xn = S.c0[lane] + m;
             S.m[lane] = m;
             S.x[lane] = xn;
@@ -190,30 +141,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         if constexpr (TAPE) {
             if (lane < 12) tp[t * UKF_TAPE + 78 + lane] = S.x[lane];  // xp_{t+1}
         }
-        {
-            const double wc0 = f->wc0;
-            const double ma = S.m[a0], mb = S.m[b0];
-            double acc = wc0 * (ma * mb);
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) acc = fma(wi, (S.D[i][a0] - ma) * (S.D[i][b0] - mb), acc);
-            if (a0 == b0) acc += f->q[a0];
-            p0 = acc;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                const double na = S.m[a1], nb = S.m[b1];
-                double acc1 = wc0 * (na * nb);
-#pragma unroll
-                for (int i = 1; i < UKF_NS; ++i) acc1 = fma(wi, (S.D[i][a1] - na) * (S.D[i][b1] - nb), acc1);
-                if (a1 == b1) acc1 += f->q[a1];
-                p1 = acc1;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-        }
+        ukf_cov(S, f, wi, own, p0, p1);
         if constexpr (TAPE) {
             tp[t * UKF_TAPE + 90 + lane] = p0;                         // Pp_{t+1}
-            if (two) tp[t * UKF_TAPE + 154 + lane] = p1;
+            if (own.two) tp[t * UKF_TAPE + 154 + lane] = p1;
             // C_{t+1}[ca][cb] = sum_j L[ca][j] (c W_i (d_{j+1} - d_{j+13})[cb]): L and D are still in the image
             const double g = cw * wi;
 #pragma unroll
@@ -232,13 +163,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
     const bool ok = failed < 0;
-    if (!ok && lane < 12) {
-        for (int64_t s = nan_from; s < T; ++s) {
-            if (xfp) xfp[s * 12] = NaN;
-            if (psp) psp[s * 12] = NaN;
-            if (inp) inp[s * 12] = NaN;
-        }
-    }
+    if (!ok) ukf_nan_rows(xfp, 12, psp, inp, lane, nan_from, T);
     if constexpr (TAPE) {
         // of a transition that did not complete xp, Pp and C are NaN; Pf_t stays when the update of row t was complete
         if (!ok) {
@@ -247,13 +172,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         if (lane == 0) a.nrows[(int64_t)blockIdx.y * B + b] = (double)nan_from;
     }
     if (a.xT && lane < 12) a.xT[row * 12 + lane] = ok ? S.x[lane] : NaN;
-    if (a.PT) {
-        for (int e = lane; e < 144; e += 64) a.PT[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
-    }
-    if (a.info && lane == 0) {
-        const double v[4] = {ok ? ell : -INF, nupd, (double)failed, minpiv};
-        store_row<4>(a.info + row * 4, v);
-    }
+    ukf_put_tail(S, a.PT, a.info, row, lane, ell, nupd, failed, minpiv);
     if constexpr (MODEL == MODEL_THRUSTER_EULER && TRACK) {
         if (ok && lane == 0) store_row<24>(a.lag + row * 24, &Xl[0][0]);      // a failed filter leaves its lag_io as it came
     }
@@ -299,19 +218,8 @@ __device__ __forceinline__ double ukf_em_term(const Lds& S, int i, double qi) {
     double u[12];
     ukf_fence();
 #pragma unroll
-    for (int j = 0; j < 12; ++j) {
-        double s = i == j ? 1.0 : 0.0;
-#pragma unroll
-        for (int k = 0; k < j; ++k) s = fma(-S.L[j][k], u[k], s);
-        u[j] = s / S.L[j][j];
-    }
-#pragma unroll
-    for (int j = 11; j >= 0; --j) {
-        double s = u[j];
-#pragma unroll
-        for (int k = j + 1; k < 12; ++k) s = fma(-S.L[k][j], u[k], s);
-        u[j] = s / S.L[j][j];
-    }
+    for (int j = 0; j < 12; ++j) u[j] = i == j ? 1.0 : 0.0;
+    ukf_solve_llt(S, u);
     double umu = 0.0, udx = 0.0;
 #pragma unroll
     for (int c = 0; c < 12; ++c) {
@@ -336,11 +244,9 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
     const int64_t loc = (int64_t)blockIdx.y * B + b;          // in the tape and nrows
     const int64_t row = (int64_t)blockIdx.y * a.Bs + b;       // in xf, the terminal pair and the outputs
     const double NaN = __builtin_nan(""), INF = __builtin_inf();
-    int a0, b0, a1, b1;
-    ukf_entry(lane, a0, b0);
-    const bool two = lane + 64 < 78;
-    ukf_entry(two ? lane + 64 : lane, a1, b1);
-    const int lr = lane < 12 ? lane : 11;
+    const UkfOwn own = ukf_own(lane);
+    const int a0 = own.a0, b0 = own.b0, a1 = own.a1, b1 = own.b1, lr = own.lr;
+    const bool two = own.two;
     const double nd = ukf_uniform(a.nrows[loc]);
     const int64_t n = nd >= 1.0 ? (nd < (double)T ? (int64_t)nd : T) : 0;
     const double* tp = a.tape + loc * T * UKF_TAPE;
@@ -403,9 +309,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         ps1 = tp[(n - 1) * UKF_TAPE + (two ? lane + 64 : lane)];
     }
     auto image_P = [&] {
-        S.P[a0][b0] = ps0;
-        S.P[b0][a0] = ps0;
-        if (two) { S.P[a1][b1] = ps1; S.P[b1][a1] = ps1; }
+        ukf_put_P(S, own, ps0, ps1);
         ukf_wave_sync();
     };
     auto put_row = [&](int64_t s) {
@@ -459,52 +363,20 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         for (int k = 0; k < 12; ++k) Lr[k] = S.rec[90 + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
         bool bad = false;
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            double s = Lr[j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
-            const double piv = ukf_lane(s, j);
-            double d = 1.0;
-            if (!bad) {
-                if (!(piv > 0.0) || piv == INF) bad = true;
-                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
-            }
-            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
-            if (lane < 12) S.L[lane][j] = Lr[j];
-            ukf_wave_sync();                                  // column j of L written
-        }
+        for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
         if (bad) { failed = t; break; }
         // row lr of G: w L^T = C[lr][:], then g L = w
         double g[12];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            double s = S.rec[168 + lr * 12 + j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fma(-S.L[j][k], g[k], s);
-            g[j] = s / S.L[j][j];
-        }
-#pragma unroll
-        for (int j = 11; j >= 0; --j) {
-            double s = g[j];
-#pragma unroll
-            for (int k = j + 1; k < 12; ++k) s = fma(-S.L[k][j], g[k], s);
-            g[j] = s / S.L[j][j];
-        }
+        for (int j = 0; j < 12; ++j) g[j] = S.rec[168 + lr * 12 + j];
+        ukf_solve_llt(S, g);
         if (lane < 12) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) S.G[lane][k] = g[k];
             S.dx[lane] = xsv - S.rec[78 + lane];              // not wrapped: xs, xp and xf live on the filter's continuous branch
         }
-        {
-            const double m0 = ps0 - S.rec[90 + lane];
-            S.M[a0][b0] = m0;
-            S.M[b0][a0] = m0;
-            if (two) {
-                const double m1 = ps1 - S.rec[154 + lane];
-                S.M[a1][b1] = m1;
-                S.M[b1][a1] = m1;
-            }
-        }
+        ukf_put(S.M, a0, b0, ps0 - S.rec[90 + lane]);
+        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[154 + lane]);
         ukf_wave_sync();                                      // G, dx, M written
         {
             double acc = 0.0;
@@ -559,10 +431,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
 
 hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a) {
     if (a.B <= 0 || P <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
-    if (a.em) hipLaunchKernelGGL(ukf_rts_kernel<true>, grid, dim3(64 * UKF_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(ukf_rts_kernel<false>, grid, dim3(64 * UKF_WAVES), 0, st, a);
-    return hipGetLastError();
+    return a.em ? ukf_launch(ukf_rts_kernel<true>, st, P, a) : ukf_launch(ukf_rts_kernel<false>, st, P, a);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -572,15 +441,10 @@ int ukf_waves_per_block() { return UKF_WAVES; }
 
 template <int MODEL, int INTEG, int LAGMODE, bool TAPE>
 static hipError_t launch_ukf_t(hipStream_t st, int P, const UkfArgs& a) {
-    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
     if constexpr (MODEL == MODEL_THRUSTER_EULER) {
-        if (a.lag) {
-            hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, true, TAPE>), grid, dim3(64 * UKF_WAVES), 0, st, a);
-            return hipGetLastError();
-        }
+        if (a.lag) return ukf_launch(ukf_filter_kernel<MODEL, INTEG, LAGMODE, true, TAPE>, st, P, a);
     }
-    hipLaunchKernelGGL((ukf_filter_kernel<MODEL, INTEG, LAGMODE, false, TAPE>), grid, dim3(64 * UKF_WAVES), 0, st, a);
-    return hipGetLastError();
+    return ukf_launch(ukf_filter_kernel<MODEL, INTEG, LAGMODE, false, TAPE>, st, P, a);
 }
 template <int MODEL, bool TAPE>
 static hipError_t launch_ukf_i(hipStream_t st, int integ, int lag_mode, int P, const UkfArgs& a) {

@@ -6,8 +6,9 @@
 // The filter's decomposition (ukf.hip's head comment): one wave per (candidate, run), candidate = blockIdx.y, UKF_WAVES runs per
 // block, the time loop inside the kernel, the wave's (x, P) image in LDS with the stride-13 rows, ukf_wave_sync between the phases
 // and no workgroup barrier after the quadrant table, so a ragged block or a run whose filter failed leaves alone.  The update and
-// the predict phases are ukf_filter_kernel's statements, in its order, so that the estimator is that filter bit for bit on the
-// rows (u_applied, y_out) this kernel records.  Between them, per step:
+// the predict phases call the functions ukf_filter_kernel calls (brov2_ukf.h: ukf_own, ukf_point, ukf_update<true>, ukf_cholesky_col,
+// ukf_mean_dev, ukf_cov, ukf_nan_rows, ukf_put_tail), in its order and around the same sigma step, so that the estimator is that
+// filter bit for bit on the rows (u_applied, y_out) this kernel records.  Between them, per step:
 //   measure   y = x_true + V[t], lane i its component.
 //   command   at a tick every lane evaluates the law of rollout_feedback_kernel (its statements, its fma order) on the tracking error
 //             of the filtered mean, read from the image; the feedback record comes through the constant address space, one gain row
@@ -69,17 +70,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
     const CFBK fb = as_constant_fbk(a.fb + (a.fb_per_candidate ? blockIdx.y : 0));
     const double dt = a.dt;
     const double NaN = __builtin_nan(""), INF = __builtin_inf();
-    // the entries of P this lane owns
-    int a0, b0, a1, b1;
-    ukf_entry(lane, a0, b0);
-    const bool two = lane + 64 < 78;
-    ukf_entry(two ? lane + 64 : lane, a1, b1);
-    // the sigma point of this lane: x + sc L[:, col]
-    const bool point = lane >= 1 && lane < UKF_NS;
-    const int col = point ? (lane - 1) % 12 : 0;
+    const UkfOwn own = ukf_own(lane);                         // the entries of P this lane owns
+    const int lr = own.lr;                                    // its row in the per-row phases
+    int col;                                                  // its sigma point: x + sc L[:, col]
+    double sc;
     const double cw = f->c;
-    const double sc = point ? (lane <= 12 ? cw : -cw) : 0.0;
-    const int lr = lane < 12 ? lane : 11;                     // the row of this lane in the per-row phases (lanes >= 12 repeat row 11)
+    ukf_point(lane, cw, col, sc);
 
     if constexpr (THR) {
         if (lane < 24) {
@@ -87,10 +83,8 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
             Q.flag[lane] = TRACK ? a.lag_est[row * 24 + lane] : 0.0;
         }
     }
-    double p0 = a.P0[b * 144 + a0 * 12 + b0], p1 = a.P0[b * 144 + a1 * 12 + b1];
-    S.P[a0][b0] = p0;
-    S.P[b0][a0] = p0;
-    if (two) { S.P[a1][b1] = p1; S.P[b1][a1] = p1; }
+    double p0 = a.P0[b * 144 + own.a0 * 12 + own.b0], p1 = a.P0[b * 144 + own.a1 * 12 + own.b1];
+    ukf_put_P(S, own, p0, p1);
     const int64_t hold = fb->hold;
     const double hdt = (double)hold * dt;
     const double* vp = a.V + b * T * 12 + lr;
@@ -125,36 +119,11 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
             if (yop) yop[t * 12] = yv;
         }
         ukf_wave_sync();                                               // y written
-        // ---- 1. update with row t: ukf_filter_kernel's ---------------------------------------------------------------------------
+        // ---- 1. update with row t, as in ukf_filter_kernel -------------------------------------------------------------------------
         double inn = NaN;
         bool bad = false;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const double yi = ukf_uniform(Q.y[i]), ri = f->r[i];
-            if (bad || yi != yi || ri == INF) continue;                // wave-uniform
-            const double s = ukf_uniform(S.P[i][i]) + ri;
-            if (!(s > 0.0) || s == INF) { bad = true; continue; }
-            double v = yi - ukf_uniform(S.x[i]);
-            if (i >= 3 && i < 6) v = ukf_wrap(v);
-            if (lane < 12) {
-                const double k = S.P[lane][i] / s;
-                S.k[lane] = k;
-                S.x[lane] += k * v;
-            }
-            ell -= 0.5 * (log(6.28318530717958647692e+00 * s) + v * v / s);
-            nupd += 1.0;
-            if (lane == i) inn = v / sqrt(s);
-            ukf_wave_sync();                                           // k, x written; every read of column i of P done
-            p0 -= S.k[a0] * S.k[b0] * s;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                p1 -= S.k[a1] * S.k[b1] * s;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-            ukf_wave_sync();                                           // P written
-        }
+        for (int i = 0; i < 12; ++i) ukf_update<true>(S, S.x, f, i, ukf_uniform(Q.y[i]), own, p0, p1, lane, ell, nupd, inn, bad);
         if (bad) { failed = t; nan_from = t; break; }
         if (lane < 12) {
             if (xfp) xfp[t * 12] = S.x[lane];
@@ -276,25 +245,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
             }
             ukf_wave_sync();                                           // the true state, the command and the sums written
         }
-        // ---- 2. predict with the applied command: ukf_filter_kernel's -------------------------------------------------------------
+        // ---- 2. predict with the applied command, as in ukf_filter_kernel -----------------------------------------------------------
         double Lr[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) Lr[k] = S.P[lr][k];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            double s = Lr[j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
-            const double piv = ukf_lane(s, j);
-            double d = 1.0;
-            if (!bad) {
-                if (!(piv > 0.0) || piv == INF) bad = true;
-                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
-            }
-            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
-            if (lane < 12) S.L[lane][j] = Lr[j];
-            ukf_wave_sync();                                           // column j of L written
-        }
+        for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
         if (bad) { failed = t; nan_from = t + 1; break; }
         double x[12], u[NU];
 #pragma unroll
@@ -341,9 +297,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
         const double wi = f->wi;
         bool finite = true;
         if (lane < 12) {
-            double m = 0.0;
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) m = fma(wi, S.D[i][lane], m);
+            const double m = ukf_mean_dev(S, wi, lane);
             const double xn = S.c0[lane] + m;
             S.m[lane] = m;
             S.x[lane] = xn;
@@ -352,27 +306,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
         const bool allfinite = __ballot(!finite) == 0;
         ukf_wave_sync();                                               // m, x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
-        {
-            const double wc0 = f->wc0;
-            const double ma = S.m[a0], mb = S.m[b0];
-            double acc = wc0 * (ma * mb);
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) acc = fma(wi, (S.D[i][a0] - ma) * (S.D[i][b0] - mb), acc);
-            if (a0 == b0) acc += f->q[a0];
-            p0 = acc;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                const double na = S.m[a1], nb = S.m[b1];
-                double acc1 = wc0 * (na * nb);
-#pragma unroll
-                for (int i = 1; i < UKF_NS; ++i) acc1 = fma(wi, (S.D[i][a1] - na) * (S.D[i][b1] - nb), acc1);
-                if (a1 == b1) acc1 += f->q[a1];
-                p1 = acc1;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-        }
+        ukf_cov(S, f, wi, own, p0, p1);
         ukf_wave_sync();                                               // P written
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
@@ -380,13 +314,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
     // stage 2) the rows xf, pstd, innov, u_applied [n ..), traj [n + 1 ..) and y_out [t + 1 ..) are NaN.
     const bool ok = failed < 0;
     if (!ok) {
+        ukf_nan_rows(xfp, 12, psp, inp, lane, nan_from, T);
         if (lane < 12) {
-            for (int64_t s = nan_from; s < T; ++s) {
-                if (xfp) xfp[s * 12] = NaN;
-                if (psp) psp[s * 12] = NaN;
-                if (inp) inp[s * 12] = NaN;
+            for (int64_t s = nan_from; s < T; ++s)
                 if (tjp) tjp[(s + 1) * 12 + lane] = NaN;
-            }
             for (int64_t s = failed + 1; s < T; ++s)
                 if (yop) yop[s * 12] = NaN;
         }
@@ -398,14 +329,8 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
         if (a.xT_true) a.xT_true[row * 12 + lane] = ok ? Q.xt[lane] : NaN;
         if (a.xT) a.xT[row * 12 + lane] = ok ? S.x[lane] : NaN;
     }
-    if (a.PT) {
-        for (int e = lane; e < 144; e += 64) a.PT[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
-    }
     if (a.metrics && lane < 7) a.metrics[row * 7 + lane] = ok ? Q.m[lane] : NaN;
-    if (a.info && lane == 0) {
-        const double v[4] = {ok ? ell : -INF, nupd, (double)failed, minpiv};
-        store_row<4>(a.info + row * 4, v);
-    }
+    ukf_put_tail(S, a.PT, a.info, row, lane, ell, nupd, failed, minpiv);
     if (ok) {                                                          // a failed run leaves z_io and both lag banks as they came
         if (a.z && lane < 6) a.z[row * 6 + lane] = Q.z[lane];
         if constexpr (THR && TRACK) {
@@ -422,15 +347,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_feedback_kernel(const UkfF
 // ---------------------------------------------------------------------------------------
 template <int MODEL, int INTEG, int LAGMODE>
 static hipError_t launch_ukf_fb_t(hipStream_t st, int P, const UkfFbArgs& a) {
-    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
     if constexpr (MODEL == MODEL_THRUSTER_EULER) {
-        if (a.lag_est) {
-            hipLaunchKernelGGL((ukf_feedback_kernel<MODEL, INTEG, LAGMODE, true>), grid, dim3(64 * UKF_WAVES), 0, st, a);
-            return hipGetLastError();
-        }
+        if (a.lag_est) return ukf_launch(ukf_feedback_kernel<MODEL, INTEG, LAGMODE, true>, st, P, a);
     }
-    hipLaunchKernelGGL((ukf_feedback_kernel<MODEL, INTEG, LAGMODE, false>), grid, dim3(64 * UKF_WAVES), 0, st, a);
-    return hipGetLastError();
+    return ukf_launch(ukf_feedback_kernel<MODEL, INTEG, LAGMODE, false>, st, P, a);
 }
 template <int MODEL>
 static hipError_t launch_ukf_fb_m(hipStream_t st, int integ, int lag_mode, int P, const UkfFbArgs& a) {

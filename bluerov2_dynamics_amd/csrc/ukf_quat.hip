@@ -5,7 +5,9 @@
 // the 12-component error state (dp, g, dnu) with g twice the Gibbs vector of a body-frame rotation.  That leaves the structure of
 // ukf_filter_kernel (ukf.hip) as it is -- 25 sigma points, a 12 x 12 image with stride-13 rows in the wave's own LDS, 78 triangle
 // entries on 64 lanes, one wave per (candidate, recording), UKF_WAVES per block, candidate = blockIdx.y, ukf_wave_sync between the
-// phases and no workgroup barrier after the quadrant table -- and touches the manifold in three places:
+// phases and no workgroup barrier after the quadrant table -- and its phases: the scalar update (ukf_update<false>, on the correction
+// d instead of the mean and without a wrap), the Cholesky, the mean deviation, the covariance sums and the closing outputs are the
+// functions of brov2_ukf.h that the Euler filters call.  What is this kernel's own is where it touches the manifold:
 //   innovation  z = y [-] x, formed once per row by every lane (redundantly: a few dozen FMAs and three divisions from the image);
 //               the scalar updates then work on the correction d in the error state, and one x = x [+] d closes the row;
 //   sigma       lane i builds chi_i = x [+] (+-c L[:, i-1]) and takes the step of rollout_pop_kernel for the quaternion model;
@@ -71,25 +73,18 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
     load_hot(p, h);
     const double dt = a.dt;
     const double NaN = __builtin_nan(""), INF = __builtin_inf();
-    // the entries of P this lane owns
-    int a0, b0, a1, b1;
-    ukf_entry(lane, a0, b0);
-    const bool two = lane + 64 < 78;
-    ukf_entry(two ? lane + 64 : lane, a1, b1);
-    // the sigma point of this lane: x [+] sc L[:, col]
-    const bool point = lane >= 1 && lane < UKF_NS;
-    const int col = point ? (lane - 1) % 12 : 0;
+    const UkfOwn own = ukf_own(lane);                         // the entries of P this lane owns
+    const int lr = own.lr;                                    // its row in the error state
+    int col;                                                  // its sigma point: x [+] sc L[:, col]
+    double sc;
     const double cw = f->c;
-    const double sc = point ? (lane <= 12 ? cw : -cw) : 0.0;
-    const int lr = lane < 12 ? lane : 11;                     // the row of this lane in the error state (lanes >= 12 repeat row 11)
+    ukf_point(lane, cw, col, sc);
     const int lx = lane < 13 ? lane : 12;                     // its component of the state (lanes >= 13 repeat component 12)
 
     LagZ lz;                                                  // (the wrench model has no lag: step_fast never looks at these)
     double Xl[8][3];
-    double p0 = a.P0[b * 144 + a0 * 12 + b0], p1 = a.P0[b * 144 + a1 * 12 + b1];
-    S.P[a0][b0] = p0;
-    S.P[b0][a0] = p0;
-    if (two) { S.P[a1][b1] = p1; S.P[b1][a1] = p1; }
+    double p0 = a.P0[b * 144 + own.a0 * 12 + own.b0], p1 = a.P0[b * 144 + own.a1 * 12 + own.b1];
+    ukf_put_P(S, own, p0, p1);
     if (lane < 13) S.x[lane] = a.x0[b * 13 + lane];
     ukf_wave_sync();
 
@@ -127,31 +122,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
         if (bad) { failed = t; nan_from = t; break; }                  // q_y = 0 or half a turn away: before any update of the row
         double inn = NaN;
 #pragma unroll
-        for (int i = 0; i < 12; ++i) {
-            const double zi = ukf_uniform(z[i]), ri = f->r[i];
-            if (bad || zi != zi || ri == INF) continue;                // wave-uniform
-            const double s = ukf_uniform(S.P[i][i]) + ri;
-            if (!(s > 0.0) || s == INF) { bad = true; continue; }
-            const double v = zi - ukf_uniform(S.d[i]);
-            if (lane < 12) {
-                const double k = S.P[lane][i] / s;
-                S.k[lane] = k;
-                S.d[lane] += k * v;
-            }
-            ell -= 0.5 * (log(6.28318530717958647692e+00 * s) + v * v / s);
-            nupd += 1.0;
-            if (lane == i) inn = v / sqrt(s);
-            ukf_wave_sync();                                           // k, d written; every read of column i of P done
-            p0 -= S.k[a0] * S.k[b0] * s;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                p1 -= S.k[a1] * S.k[b1] * s;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-            ukf_wave_sync();                                           // P written
-        }
+        for (int i = 0; i < 12; ++i) ukf_update<false>(S, S.d, f, i, ukf_uniform(z[i]), own, p0, p1, lane, ell, nupd, inn, bad);
         if (bad) { failed = t; nan_from = t; break; }
         {
             // x = x [+] d: one reset per row.  Every lane forms it; lane 0 stores its copy, as it stores c0 below
@@ -170,25 +141,11 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
             if (inp) inp[t * 12] = inn;
         }
         // ---- 2. predict with U[t] -------------------------------------------------------------------------------------------
-        // Cholesky as in ukf_filter_kernel: one lane per row, column by column, the pivot through v_readlane
         double Lr[12];
 #pragma unroll
         for (int k = 0; k < 12; ++k) Lr[k] = S.P[lr][k];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) {
-            double s = Lr[j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) s = fma(-Lr[k], S.L[j][k], s);
-            const double piv = ukf_lane(s, j);
-            double d = 1.0;
-            if (!bad) {
-                if (!(piv > 0.0) || piv == INF) bad = true;
-                else { d = sqrt(piv); minpiv = fmin(minpiv, d); }
-            }
-            Lr[j] = lr == j ? d : (lr > j ? s / d : 0.0);
-            if (lane < 12) S.L[lane][j] = Lr[j];
-            ukf_wave_sync();                                           // column j of L written
-        }
+        for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
         if (bad) { failed = t; nan_from = t + 1; break; }
         double x[13], u[NU];
         {
@@ -222,12 +179,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
         }
         ukf_wave_sync();                                               // D written
         const double wi = f->wi;
-        if (lane < 12) {
-            double m = 0.0;
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) m = fma(wi, S.D[i][lane], m);
-            S.m[lane] = m;
-        }
+        if (lane < 12) S.m[lane] = ukf_mean_dev(S, wi, lane);
         ukf_wave_sync();                                               // m written
         bool finite = true;
         {
@@ -246,46 +198,14 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
         const bool allfinite = __ballot(!finite) == 0;
         ukf_wave_sync();                                               // x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
-        {
-            const double wc0 = f->wc0;
-            const double ma = S.m[a0], mb = S.m[b0];
-            double acc = wc0 * (ma * mb);
-#pragma unroll
-            for (int i = 1; i < UKF_NS; ++i) acc = fma(wi, (S.D[i][a0] - ma) * (S.D[i][b0] - mb), acc);
-            if (a0 == b0) acc += f->q[a0];
-            p0 = acc;
-            S.P[a0][b0] = p0;
-            S.P[b0][a0] = p0;
-            if (two) {
-                const double na = S.m[a1], nb = S.m[b1];
-                double acc1 = wc0 * (na * nb);
-#pragma unroll
-                for (int i = 1; i < UKF_NS; ++i) acc1 = fma(wi, (S.D[i][a1] - na) * (S.D[i][b1] - nb), acc1);
-                if (a1 == b1) acc1 += f->q[a1];
-                p1 = acc1;
-                S.P[a1][b1] = p1;
-                S.P[b1][a1] = p1;
-            }
-        }
+        ukf_cov(S, f, wi, own, p0, p1);
         ukf_wave_sync();                                               // P written
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
     const bool ok = failed < 0;
-    if (!ok) {
-        for (int64_t s = nan_from; s < T; ++s) {
-            if (xfp && lane < 13) xfp[s * 13] = NaN;
-            if (psp && lane < 12) psp[s * 12] = NaN;
-            if (inp && lane < 12) inp[s * 12] = NaN;
-        }
-    }
+    if (!ok) ukf_nan_rows(xfp, 13, psp, inp, lane, nan_from, T);
     if (a.xT && lane < 13) a.xT[row * 13 + lane] = ok ? S.x[lane] : NaN;
-    if (a.PT) {
-        for (int e = lane; e < 144; e += 64) a.PT[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
-    }
-    if (a.info && lane == 0) {
-        const double v[4] = {ok ? ell : -INF, nupd, (double)failed, minpiv};
-        store_row<4>(a.info + row * 4, v);
-    }
+    ukf_put_tail(S, a.PT, a.info, row, lane, ell, nupd, failed, minpiv);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -294,10 +214,8 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
 // ---------------------------------------------------------------------------------------
 hipError_t launch_ukf_filter_quat(hipStream_t st, int integ, int P, const UkfArgs& a) {
     if (a.B <= 0 || P <= 0) return hipSuccess;
-    const dim3 grid((unsigned)((a.B + UKF_WAVES - 1) / UKF_WAVES), (unsigned)P);
-    if (integ == INTEG_EULER) hipLaunchKernelGGL(ukf_quat_filter_kernel<INTEG_EULER>, grid, dim3(64 * UKF_WAVES), 0, st, a);
-    else hipLaunchKernelGGL(ukf_quat_filter_kernel<INTEG_RK4>, grid, dim3(64 * UKF_WAVES), 0, st, a);
-    return hipGetLastError();
+    if (integ == INTEG_EULER) return ukf_launch(ukf_quat_filter_kernel<INTEG_EULER>, st, P, a);
+    return ukf_launch(ukf_quat_filter_kernel<INTEG_RK4>, st, P, a);
 }
 
 }  // namespace brov
