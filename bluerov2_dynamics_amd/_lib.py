@@ -197,6 +197,13 @@ SIGNATURES = {
                                             ctypes.c_double] + [c_void_p] * 10),
     "brov_ukf_filter_quat_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovUkf), i64, i64,
                                                 ctypes.c_double] + [c_void_p] * 10),
+    "brov_ukf_filter_tape_quat_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovUkf), i64,
+                                                     i64, ctypes.c_double] + [c_void_p] * 12),
+    "brov_ukf_rts_quat_dev": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 10),
+    "brov_ukf_smooth_quat": (ctypes.c_int, [c_void_p, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovUkf), i64, i64,
+                                            ctypes.c_double] + [c_void_p] * 15 + [i64]),
+    "brov_ukf_smooth_quat_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64, ctypes.POINTER(BrovUkf), i64, i64,
+                                                ctypes.c_double] + [c_void_p] * 15 + [i64]),
     "brov_ukf_filter_tape_dev": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, i64, ctypes.POINTER(BrovParams), i64,
                                                 ctypes.POINTER(BrovUkf), i64, i64, ctypes.c_double] + [c_void_p] * 13),
     "brov_ukf_rts_dev": (ctypes.c_int, [c_void_p, i64, i64, i64] + [c_void_p] * 10),

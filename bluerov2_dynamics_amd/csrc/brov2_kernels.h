@@ -72,7 +72,9 @@ int ukf_waves_per_block();      // recordings per block of the filter kernel and
 hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a);
 // The multiplicative filter on the quaternion model (ukf_quat.hip; include/brov2.h: brov_ukf_filter_quat holds the law).  UkfArgs with
 // x0 [B][13], Y [B][T][13], xf [P][B][T][13] and xT [P][B][13]; P0, pstd, innov, PT and the records stay in the 12-component error
-// state; lag, tape, nrows and Bs are not read.  One launch; T >= 1.
+// state; lag is not read.  tape != nullptr selects the tape variant, which alone reads tape [P][B][T][UKF_TAPE_QUAT], nrows [P][B] and
+// Bs, with the meaning they have in launch_ukf_filter.  One launch; T >= 1.
+constexpr int UKF_TAPE_QUAT = 313;   // doubles of one tape record: Pf [78] | xp [13] | Pp [78] | C [12][12]  (include/brov2.h)
 hipError_t launch_ukf_filter_quat(hipStream_t st, int integ, int P, const UkfArgs& a);
 // Backward (Rauch-Tung-Striebel) pass over a tape (ukf.hip; include/brov2.h: brov_ukf_rts_dev holds the law).  tape [P][B][T][UKF_TAPE]
 // and nrows [P][B] are a chunk's own; xf, the terminal pair and every output are laid out for Bs recordings per candidate and point
@@ -90,6 +92,9 @@ struct UkfRtsArgs {
 };
 constexpr int UKF_EM = 37;      // doubles of one em record: Sq [12] | Sr [12] | nr [12] | nq  (include/brov2.h)
 hipError_t launch_ukf_rts(hipStream_t st, int P, const UkfRtsArgs& a);
+// The backward pass of the quaternion model (ukf_quat.hip; include/brov2.h: brov_ukf_rts_quat_dev holds the law): UkfRtsArgs with tape
+// [P][B][T][UKF_TAPE_QUAT] and xf, xsT, xs 13 wide; the fields behind sinfo are not read.
+hipError_t launch_ukf_rts_quat(hipStream_t st, int P, const UkfRtsArgs& a);
 // Output-feedback closed loop (ukf_feedback.hip; include/brov2.h: brov_output_feedback holds the law): candidate j runs B closed loops
 // of T steps, the filter of launch_ukf_filter under fp[j] inside the loop, the law of launch_rollout_feedback on its estimate, the
 // plant under plant[j] (plant_per_candidate) or plant[0].  rec and fb hold one record or P.  x0_true, x0_est [B][12], P0 [B][12][12],

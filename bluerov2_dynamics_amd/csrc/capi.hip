@@ -1840,26 +1840,39 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     return a.finish();
 }
 
-// The backward pass alone, over a tape that brov_ukf_filter_tape_dev wrote (or that the caller edited: it is a plain array)
-int brov_ukf_rts_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
-                     const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo) {
+// The backward pass alone, over a tape that brov_ukf_filter_tape_dev wrote (or that the caller edited: it is a plain array); quat: over
+// a tape of brov_ukf_filter_tape_quat_dev, with xf, xs_T and xs 13 wide (brov_ukf_rts_quat_dev).  fn names the function called.
+static int ukf_rts_dev(brov_ctx* c, const std::string& fn, bool quat, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape,
+                       const double* d_nrows, const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps,
+                       double* d_Ps0, double* d_sinfo) {
     if (!c) return BROV_ERR_ARG;
-    if (P < 0 || B < 0 || T < 0) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: negative size");
-    if (P > 65535) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: P must be <= 65535");
-    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: B must be <= 2^31");
+    if (P < 0 || B < 0 || T < 0) return fail(c, BROV_ERR_ARG, fn + ": negative size");
+    if (P > 65535) return fail(c, BROV_ERR_ARG, fn + ": P must be <= 65535");
+    if (B > ((int64_t)1 << 31)) return fail(c, BROV_ERR_ARG, fn + ": B must be <= 2^31");
     if (P == 0 || B == 0) return BROV_OK;
-    if (T < 1) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: T must be >= 1");
-    if (!d_xf || !d_tape || !d_nrows) return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: NULL input");
+    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
+    if (!d_xf || !d_tape || !d_nrows) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
     if ((d_xs_T == nullptr) != (d_Ps_T == nullptr))
-        return fail(c, BROV_ERR_ARG, "brov_ukf_rts_dev: the terminal pair d_xs_T, d_Ps_T goes together (both or neither)");
+        return fail(c, BROV_ERR_ARG, fn + ": the terminal pair d_xs_T, d_Ps_T goes together (both or neither)");
     DeviceGuard g(c);
     UkfRtsArgs r{};
     r.B = B; r.T = T; r.Bs = B;
     r.xf = d_xf; r.tape = d_tape; r.nrows = d_nrows; r.xsT = d_xs_T; r.PsT = d_Ps_T;
     r.xs = d_xs; r.pstd = d_pstd_s; r.Ps = d_Ps; r.Ps0 = d_Ps0; r.sinfo = d_sinfo;
     CallTimer t(c);
-    HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
+    HIPCK(c, quat ? launch_ukf_rts_quat(c->stream, (int)P, r) : launch_ukf_rts(c->stream, (int)P, r));
     return BROV_OK;
+}
+
+int brov_ukf_rts_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                     const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo) {
+    return ukf_rts_dev(c, "brov_ukf_rts_dev", false, P, B, T, d_xf, d_tape, d_nrows, d_xs_T, d_Ps_T, d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo);
+}
+
+int brov_ukf_rts_quat_dev(brov_ctx* c, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape, const double* d_nrows,
+                          const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0,
+                          double* d_sinfo) {
+    return ukf_rts_dev(c, "brov_ukf_rts_quat_dev", true, P, B, T, d_xf, d_tape, d_nrows, d_xs_T, d_Ps_T, d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo);
 }
 
 // The backward pass with the sufficient statistics of the EM fit of q and r.  Of the filter's records it needs q and r alone.
@@ -1965,20 +1978,37 @@ int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, 
     return ukf_filter(c, true, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
 }
 
-// ---- the multiplicative filter on the quaternion model (ukf_quat.hip) ------------------------------------------------------------------
+// ---- the multiplicative filter on the quaternion model and its smoother (ukf_quat.hip) ------------------------------------------------
 // brov_ukf_filter's order: everything the host can refuse first, with the same words; then one upload of FastParams[P] and of the
 // derived records, one launch.  The state arrays are 13 wide, everything in the error state 12.
-static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B,
-                           int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* xf, double* pstd,
-                           double* innov, double* xT, double* PT, double* info) {
-    const char* who_ = "brov_ukf_filter_quat";
+// One body serves the filter, the tape filter and the smoother, as ukf_filter does for the Euler models: tape / nrows are the caller's
+// device buffers (brov_ukf_filter_tape_quat_dev), both or neither; sm holds the smoother's outputs (brov_ukf_smooth_quat[_dev]), and then
+// the tape is the ctx's buffer of at most tape_bytes, with ukf_filter's chunks and its keep / free rule.
+static int ukf_filter_quat(brov_ctx* c, bool host, const char* who_, int integ, int64_t P, const brov_params* params, int64_t nrec,
+                           const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
+                           const double* Y, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
+                           double* tape = nullptr, double* nrows = nullptr, const UkfSmoothOut* sm = nullptr, int64_t tape_bytes = 0) {
     bool empty;
     int rc = pop_call_ok(c, who_, BROV_WRENCH_QUAT, integ, BROV_LAG_PER_CALL, P, B, T, (int64_t)1 << 31, &empty);
-    if (rc || empty) return rc;
+    if (rc) return rc;
     const std::string fn = who_;
+    if ((tape == nullptr) != (nrows == nullptr)) return fail(c, BROV_ERR_ARG, fn + ": d_tape and d_nrows go together (both or neither)");
+    if (sm && tape_bytes < 0) return fail(c, BROV_ERR_ARG, fn + ": tape_bytes must be >= 0 (0: the default of 2 GiB)");
+    if (empty) return BROV_OK;
     if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
     if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
     if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    int64_t chunk = B;                          // recordings per launch
+    if (sm) {
+        const int W = ukf_waves_per_block();
+        const double per_rec = (double)P * (double)T * UKF_TAPE_QUAT * 8.0;      // tape bytes of one recording
+        const double budget = tape_bytes ? (double)tape_bytes : 2147483648.0;
+        if (budget < per_rec * W)
+            return fail(c, BROV_ERR_ARG, fn + ": tape_bytes is smaller than one block of recordings (P * " + std::to_string(W) + " * T * " +
+                                             std::to_string(UKF_TAPE_QUAT * 8) + " bytes)");
+        const double fit = std::floor(budget / per_rec);
+        if (fit < (double)B) chunk = (int64_t)fit / W * W;
+    }
     std::vector<UkfRec> rec;
     rc = ukf_records(c, fn, nrec, ukf, rec);
     if (rc) return rc;
@@ -1992,6 +2022,10 @@ static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const b
     args.rec_per_candidate = nrec > 1;
     args.B = B; args.T = T; args.dt = dt;
     args.Bs = B;
+    args.tape = tape;
+    args.nrows = nrows;
+    UkfRtsArgs back{};
+    back.B = B; back.T = T; back.Bs = B;
     FastParams* d_fp;
     UkfRec* d_rec;
     Arena a(c, host);
@@ -2001,6 +2035,14 @@ static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const b
         args.U = a.in(U, nin * T * 6);
         args.Y = a.in(Y, nin * T * 13);
         args.xf = xf ? a.out(xf, nout * T * 13) : nullptr;
+        if (sm) {
+            if (!xf) args.xf = a.take<double>(nout * T * 13);        // the backward pass reads xf: scratch when the caller has none
+            back.xs = sm->xs ? a.out(sm->xs, nout * T * 13) : nullptr;
+            back.pstd = sm->pstd_s ? a.out(sm->pstd_s, nout * T * 12) : nullptr;
+            back.Ps = sm->Ps ? a.out(sm->Ps, nout * T * 144) : nullptr;
+            back.Ps0 = sm->Ps0 ? a.out(sm->Ps0, nout * 144) : nullptr;
+            back.sinfo = sm->sinfo ? a.out(sm->sinfo, nout * 2) : nullptr;
+        }
         args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
         args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
         args.xT = xT ? a.out(xT, nout * 13) : nullptr;
@@ -2010,6 +2052,20 @@ static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const b
         d_rec = a.take<UkfRec>(nrec);
     });
     if (rc) return rc;
+    if (sm) {
+        // the ctx's tape: `chunk` recordings, then their nrows; ukf_filter's rule for keeping the buffer
+        const size_t tape_part = Arena::al((size_t)P * chunk * T * UKF_TAPE_QUAT * 8), need = tape_part + Arena::al((size_t)P * chunk * 8);
+        if (need > c->ukf_tape_cap || need < c->ukf_tape_cap / 2) {
+            HIPCK(c, hipStreamSynchronize(c->stream));
+            if (c->ukf_tape) (void)hipFree(c->ukf_tape);
+            c->ukf_tape = nullptr;
+            c->ukf_tape_cap = 0;
+            HIPCK(c, hipMalloc((void**)&c->ukf_tape, need));
+            c->ukf_tape_cap = need;
+        }
+        args.tape = reinterpret_cast<double*>(c->ukf_tape);
+        args.nrows = reinterpret_cast<double*>(c->ukf_tape + tape_part);
+    }
     HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
     HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
     HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
@@ -2017,7 +2073,22 @@ static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const b
     args.rec = d_rec;
     {
         CallTimer t(c);
-        HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, args));
+        if (!sm) HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, args));
+        for (int64_t b0 = 0; sm && b0 < B; b0 += chunk) {
+            auto at = [b0](auto* p, int64_t per) { return p ? p + b0 * per : p; };
+            UkfArgs f = args;
+            f.B = std::min(chunk, B - b0);
+            f.x0 = at(args.x0, 13); f.P0 = at(args.P0, 144); f.U = at(args.U, T * 6); f.Y = at(args.Y, T * 13);
+            f.xf = at(args.xf, T * 13); f.pstd = at(args.pstd, T * 12); f.innov = at(args.innov, T * 12);
+            f.xT = at(args.xT, 13); f.PT = at(args.PT, 144); f.info = at(args.info, 4);
+            HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, f));
+            UkfRtsArgs r = back;
+            r.B = f.B;
+            r.xf = f.xf; r.tape = f.tape; r.nrows = f.nrows;
+            r.xs = at(back.xs, T * 13); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
+            r.sinfo = at(back.sinfo, 2);
+            HIPCK(c, launch_ukf_rts_quat(c->stream, (int)P, r));
+        }
     }
     return a.finish();
 }
@@ -2025,13 +2096,40 @@ static int ukf_filter_quat(brov_ctx* c, bool host, int integ, int64_t P, const b
 int brov_ukf_filter_quat_dev(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
                              double dt, const double* d_x0, const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd,
                              double* d_innov, double* d_xT, double* d_PT, double* d_info) {
-    return ukf_filter_quat(c, false, integ, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_xf, d_pstd, d_innov, d_xT, d_PT, d_info);
+    // (its refusals name brov_ukf_filter_quat)
+    return ukf_filter_quat(c, false, "brov_ukf_filter_quat", integ, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_xf, d_pstd, d_innov, d_xT,
+                           d_PT, d_info);
 }
 
 int brov_ukf_filter_quat(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
                          double dt, const double* x0, const double* P0, const double* U, const double* Y, double* xf, double* pstd, double* innov,
                          double* xT, double* PT, double* info) {
-    return ukf_filter_quat(c, true, integ, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, xf, pstd, innov, xT, PT, info);
+    return ukf_filter_quat(c, true, "brov_ukf_filter_quat", integ, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, xf, pstd, innov, xT, PT, info);
+}
+
+int brov_ukf_filter_tape_quat_dev(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B,
+                                  int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U, const double* d_Y, double* d_xf,
+                                  double* d_pstd, double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_tape, double* d_nrows) {
+    return ukf_filter_quat(c, false, "brov_ukf_filter_tape_quat_dev", integ, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_xf, d_pstd,
+                           d_innov, d_xT, d_PT, d_info, d_tape, d_nrows);
+}
+
+int brov_ukf_smooth_quat_dev(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
+                             double dt, const double* d_x0, const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd,
+                             double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
+                             double* d_Ps0, double* d_sinfo, int64_t tape_bytes) {
+    const UkfSmoothOut sm{d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo};
+    return ukf_filter_quat(c, false, "brov_ukf_smooth_quat_dev", integ, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_xf, d_pstd, d_innov,
+                           d_xT, d_PT, d_info, nullptr, nullptr, &sm, tape_bytes);
+}
+
+int brov_ukf_smooth_quat(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,
+                         double dt, const double* x0, const double* P0, const double* U, const double* Y, double* xf, double* pstd, double* innov,
+                         double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps, double* Ps0, double* sinfo,
+                         int64_t tape_bytes) {
+    const UkfSmoothOut sm{xs, pstd_s, Ps, Ps0, sinfo};
+    return ukf_filter_quat(c, true, "brov_ukf_smooth_quat", integ, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, xf, pstd, innov, xT, PT, info,
+                           nullptr, nullptr, &sm, tape_bytes);
 }
 
 // ---- output-feedback closed loop: the filter inside the rollout (ukf_feedback.hip) ---------------------------------------------------

@@ -13,6 +13,10 @@
 //   sigma       lane i builds chi_i = x [+] (+-c L[:, i-1]) and takes the step of rollout_pop_kernel for the quaternion model;
 //   moments     lane i forms d_i = chi_i' [-] chi_0'; the mean deviation m is summed as in the Euler filter and x = chi_0' [+] m.
 // Lanes 25..63 repeat point 0, so all 64 lanes stay active through every cross-lane read, and a wave leaves only as a whole.
+//
+// The smoother over it (include/brov2.h: brov_ukf_filter_tape_quat_dev, brov_ukf_rts_quat_dev): the filter's tape variant, which is
+// ukf_filter_kernel's tape on this kernel's D with the 13-wide predicted mean (UKF_TAPE_QUAT doubles a record), and the backward
+// kernel ukf_quat_rts_kernel further down, ukf_rts_kernel with its manifold touches changed.
 #include "brov2_device.h"
 #include "brov2_fast.h"
 #include "brov2_kernels.h"
@@ -52,7 +56,9 @@ __device__ __forceinline__ void uq_state_plus(const double* x, const double* dl,
     for (int r = 6; r < 12; ++r) out[r + 1] = x[r + 1] + dl[r];
 }
 
-template <int INTEG>
+// TAPE: step t also records what the backward pass (ukf_quat_rts_kernel below) needs for the transition t -> t + 1.  Every tape store
+// sits behind `if constexpr (TAPE)`, as in ukf_filter_kernel; the TAPE = false instantiations are the code they were before.
+template <int INTEG, bool TAPE>
 __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const UkfArgs a) {
     constexpr int MODEL = MODEL_WRENCH_QUAT;
     constexpr int NU = Dims<MODEL>::NU;
@@ -66,7 +72,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
     const int64_t b = (int64_t)blockIdx.x * UKF_WAVES + wave;
     if (b >= B) return;                                       // a whole wave: no workgroup barrier follows
     UkfQuatLds& S = lds[wave];
-    const int64_t row = (int64_t)blockIdx.y * B + b;          // recording b of candidate blockIdx.y in the outputs
+    // recording b of candidate blockIdx.y in the outputs; with a tape the outputs of a chunk lie among those of Bs recordings
+    const int64_t row = (int64_t)blockIdx.y * (TAPE ? a.Bs : B) + b;
+    double* tp = nullptr;                                     // this problem's tape records
+    if constexpr (TAPE) tp = a.tape + ((int64_t)blockIdx.y * B + b) * T * UKF_TAPE_QUAT;
     const CFP p = as_constant(a.fp + blockIdx.y);
     const CUK f = as_constant_uk(a.rec + (a.rec_per_candidate ? blockIdx.y : 0));
     HotConsts h;
@@ -136,6 +145,10 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
             ukf_wave_sync();                                           // x written
             if (lane < 13 && xfp) xfp[t * 13] = S.x[lane];
         }
+        if constexpr (TAPE) {                                          // Pf_t, after the row's reset: the entries this lane holds
+            tp[t * UKF_TAPE_QUAT + lane] = p0;
+            if (own.two) tp[t * UKF_TAPE_QUAT + 64 + lane] = p1;
+        }
         if (lane < 12) {
             if (psp) psp[t * 12] = sqrt(S.P[lane][lane]);
             if (inp) inp[t * 12] = inn;
@@ -198,24 +211,256 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
         const bool allfinite = __ballot(!finite) == 0;
         ukf_wave_sync();                                               // x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
+        if constexpr (TAPE) {
+            if (lane < 13) tp[t * UKF_TAPE_QUAT + 78 + lane] = S.x[lane];        // xp_{t+1} = chi_0' [+] m
+        }
         ukf_cov(S, f, wi, own, p0, p1);
+        if constexpr (TAPE) {
+            tp[t * UKF_TAPE_QUAT + 91 + lane] = p0;                    // Pp_{t+1}
+            if (own.two) tp[t * UKF_TAPE_QUAT + 155 + lane] = p1;
+            // C_{t+1}[ca][cb] = sum_j L[ca][j] (c W_i (d_{j+1} - d_{j+13})[cb]): chi_i [-] x = +-c L[:, i-1], and L and D are still
+            // in the image
+            const double g = cw * wi;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int e = lane + 64 * k;
+                if (e < 144) {
+                    const int ca = e / 12, cb = e % 12;
+                    double acc = 0.0;
+#pragma unroll
+                    for (int j = 0; j < 12; ++j) acc = fma(S.L[ca][j], g * (S.D[j + 1][cb] - S.D[j + 13][cb]), acc);
+                    tp[t * UKF_TAPE_QUAT + 169 + e] = acc;
+                }
+            }
+        }
         ukf_wave_sync();                                               // P written
     }
     // ---- outputs -------------------------------------------------------------------------------------------------------------
     const bool ok = failed < 0;
     if (!ok) ukf_nan_rows(xfp, 13, psp, inp, lane, nan_from, T);
+    if constexpr (TAPE) {
+        // of a transition that did not complete xp, Pp and C are NaN; Pf_t stays when the update of row t was complete
+        if (!ok) {
+            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE_QUAT + 78 : failed * UKF_TAPE_QUAT) + lane; i < T * UKF_TAPE_QUAT; i += 64)
+                tp[i] = NaN;
+        }
+        if (lane == 0) a.nrows[(int64_t)blockIdx.y * B + b] = (double)nan_from;
+    }
     if (a.xT && lane < 13) a.xT[row * 13 + lane] = ok ? S.x[lane] : NaN;
     ukf_put_tail(S, a.PT, a.info, row, lane, ell, nupd, failed, minpiv);
 }
 
 // ---------------------------------------------------------------------------------------
-// launch: grid (blocks of UKF_WAVES recordings, P).  Of UkfArgs the fields lag, tape, nrows and Bs are not read; x0, Y, xf and xT
-// are 13 wide.
+// Backward (Rauch-Tung-Striebel) pass over the tape (include/brov2.h: brov_ukf_rts_quat_dev holds the law).  ukf_rts_kernel's
+// decomposition (ukf.hip, whose comment describes it): one wave per (candidate, recording), UKF_WAVES per block, the time loop --
+// downwards -- inside, ukf_wave_sync between phases and no workgroup barrier at all, the record fetched one transition ahead into 5
+// registers per lane (313 <= 320) with Pf's entries landing on their owners, the filter's Cholesky of Pp with the column loop here,
+// the gain row by ukf_solve_llt, M, G M and Ps as there, Ps in the owners' registers over the pass.  What is this kernel's own:
+//   xs    a 13-vector in the image.  xf_t comes in with the record (lanes 0..12) and goes to the image; lanes 0..11 form G delta,
+//         every lane forms xf_t [+] (G delta) and lane 0 stores it, as the filter stores its mean;
+//   delta xs_{t+1} [-] xp_{t+1} through uq_minus, formed by every lane; a component that is not finite (half a turn, a zero
+//         quaternion) fails the transition like a bad pivot: the test is a ballot, so the branch is wave-uniform.
+// No covariance is transported between the tangent spaces at xf_t, xp_{t+1} and xs_{t+1}: the filter's first-order practice.
+// ---------------------------------------------------------------------------------------
+struct UkfQuatRtsLds {
+    double rec[UKF_TAPE_QUAT];          // the tape record of the transition
+    double L[12][UKF_LD];               // Cholesky factor of Pp
+    double G[12][UKF_LD];               // the smoother gain
+    double M[12][UKF_LD];               // Ps_{t+1} - Pp_{t+1}, both triangles
+    double GM[12][UKF_LD];
+    double P[12][UKF_LD];               // Ps of the row last finished, both triangles
+    double xs[13], xf[13];              // xs of the row last finished; xf_t of the transition
+    double dx[12], gd[12];              // delta; G delta
+};
+
+__global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_rts_kernel(const UkfRtsArgs a) {
+    __shared__ UkfQuatRtsLds lds[UKF_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t B = a.B, T = a.T;
+    const int64_t b = (int64_t)blockIdx.x * UKF_WAVES + wave;
+    if (b >= B) return;                                       // a whole wave: there is no workgroup barrier
+    UkfQuatRtsLds& S = lds[wave];
+    const int64_t loc = (int64_t)blockIdx.y * B + b;          // in the tape and nrows
+    const int64_t row = (int64_t)blockIdx.y * a.Bs + b;       // in xf, the terminal pair and the outputs
+    const double NaN = __builtin_nan(""), INF = __builtin_inf();
+    const UkfOwn own = ukf_own(lane);
+    const int a0 = own.a0, b0 = own.b0, a1 = own.a1, b1 = own.b1, lr = own.lr;
+    const bool two = own.two;
+    const int lx = lane < 13 ? lane : 12;                     // its component of the state (lanes >= 13 repeat component 12)
+    const double nd = ukf_uniform(a.nrows[loc]);
+    const int64_t n = nd >= 1.0 ? (nd < (double)T ? (int64_t)nd : T) : 0;
+    const double* tp = a.tape + loc * T * UKF_TAPE_QUAT;
+    const double* xfp = a.xf + row * T * 13 + lx;
+    double* xsp = a.xs ? a.xs + row * T * 13 : nullptr;
+    double* psp = a.pstd ? a.pstd + row * T * 12 : nullptr;
+    double* Psp = a.Ps ? a.Ps + row * T * 144 : nullptr;
+    // row s of the outputs: NaN, or (the image's xs, the image's P)
+    auto put_nan = [&](int64_t s) {
+        if (xsp && lane < 13) xsp[s * 13 + lane] = NaN;
+        if (psp && lane < 12) psp[s * 12 + lane] = NaN;
+        if (Psp) {
+            for (int e = lane; e < 144; e += 64) Psp[s * 144 + e] = NaN;
+        }
+    };
+    for (int64_t s = n; s < T; ++s) put_nan(s);
+    if (n == 0) {
+        if (a.Ps0) {
+            for (int e = lane; e < 144; e += 64) a.Ps0[row * 144 + e] = NaN;
+        }
+        if (a.sinfo && lane == 0) {
+            const double v[2] = {NaN, NaN};
+            store_row<2>(a.sinfo + row * 2, v);
+        }
+        return;
+    }
+    // ---- start: the terminal pair of a later span, or the filter's last row ------------------------------------------------------
+    const bool terminal = a.xsT != nullptr && n == T;
+    double ps0, ps1;
+    if (terminal) {
+        if (lane < 13) S.xs[lane] = a.xsT[row * 13 + lane];
+        ps0 = a.PsT[row * 144 + a0 * 12 + b0];
+        ps1 = a.PsT[row * 144 + a1 * 12 + b1];
+    } else {
+        if (lane < 13) S.xs[lane] = xfp[(n - 1) * 13];
+        ps0 = tp[(n - 1) * UKF_TAPE_QUAT + lane];
+        ps1 = tp[(n - 1) * UKF_TAPE_QUAT + (two ? lane + 64 : lane)];
+    }
+    auto image_P = [&] {
+        ukf_put_P(S, own, ps0, ps1);
+        ukf_wave_sync();
+    };
+    auto put_row = [&](int64_t s) {
+        if (xsp && lane < 13) xsp[s * 13 + lane] = S.xs[lane];
+        if (psp && lane < 12) psp[s * 12 + lane] = sqrt(S.P[lane][lane]);
+        if (Psp) {
+            for (int e = lane; e < 144; e += 64) Psp[s * 144 + e] = S.P[e / 12][e % 12];
+        }
+    };
+    image_P();                                                // (xs written as well)
+    if (!terminal) put_row(n - 1);
+    // ---- the transitions, last first ---------------------------------------------------------------------------------------------
+    double r[5], xfv;
+    auto fetch = [&](int64_t t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r[k] = tp[t * UKF_TAPE_QUAT + 64 * k + lane];
+        r[4] = lane < UKF_TAPE_QUAT - 256 ? tp[t * UKF_TAPE_QUAT + 256 + lane] : 0.0;
+        xfv = xfp[t * 13];
+    };
+    int64_t t = terminal ? n - 1 : n - 2, failed = -1;
+    double minpiv = INF;
+    if (t >= 0) fetch(t);
+    for (; t >= 0; --t) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) S.rec[64 * k + lane] = r[k];
+        if (lane < UKF_TAPE_QUAT - 256) S.rec[256 + lane] = r[4];
+        if (lane < 13) S.xf[lane] = xfv;
+        const double pf0 = r[0], pf1 = r[1];                  // Pf's entries lie on their owners
+        if (t > 0) fetch(t - 1);
+        ukf_wave_sync();                                      // rec, xf written
+        // Cholesky of Pp, as in the filter
+        double Lr[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[91 + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
+        if (bad) { failed = t; break; }
+        // delta = xs_{t+1} [-] xp_{t+1}: every lane forms the attitude part, lane lr keeps component lr
+        double dl;
+        {
+            double sq[4], pq[4], gq[3];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) { sq[k] = S.xs[3 + k]; pq[k] = S.rec[81 + k]; }
+            uq_minus(sq, pq, gq);
+            const int c = lr < 3 ? lr : lr + 1;               // (of position and velocity) its component of the 13-wide state
+            const double lin = S.xs[c] - S.rec[78 + c];
+            dl = lr == 3 ? gq[0] : (lr == 4 ? gq[1] : (lr == 5 ? gq[2] : lin));
+        }
+        if (__ballot(!(fabs(dl) < INF)) != 0) { failed = t; break; }      // half a turn, a zero quaternion: like a bad pivot
+        // row lr of G: w L^T = C[lr][:], then g L = w
+        double g[12];
+#pragma unroll
+        for (int j = 0; j < 12; ++j) g[j] = S.rec[169 + lr * 12 + j];
+        ukf_solve_llt(S, g);
+        if (lane < 12) {
+#pragma unroll
+            for (int k = 0; k < 12; ++k) S.G[lane][k] = g[k];
+            S.dx[lane] = dl;
+        }
+        ukf_put(S.M, a0, b0, ps0 - S.rec[91 + lane]);
+        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[155 + lane]);
+        ukf_wave_sync();                                      // G, dx, M written; every read of xs done
+        if (lane < 12) {
+            double acc = 0.0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) acc = fma(g[k], S.dx[k], acc);
+            S.gd[lane] = acc;
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int e = lane + 64 * k;
+            if (e < 144) {
+                const int ga = e / 12, gb = e % 12;
+                double acc = 0.0;
+#pragma unroll
+                for (int c = 0; c < 12; ++c) acc = fma(S.G[ga][c], S.M[c][gb], acc);
+                S.GM[ga][gb] = acc;
+            }
+        }
+        ukf_wave_sync();                                      // gd, GM written
+        {
+            // xs_t = xf_t [+] (G delta): every lane forms it; lane 0 stores its copy
+            double xn[13];
+            uq_state_plus(S.xf, S.gd, xn);
+            if (lane == 0) {
+#pragma unroll
+                for (int q = 0; q < 13; ++q) S.xs[q] = xn[q];
+            }
+        }
+        {
+            double acc = 0.0;
+#pragma unroll
+            for (int c = 0; c < 12; ++c) acc = fma(S.GM[a0][c], S.G[b0][c], acc);
+            ps0 = pf0 + acc;
+            if (two) {
+                double acc1 = 0.0;
+#pragma unroll
+                for (int c = 0; c < 12; ++c) acc1 = fma(S.GM[a1][c], S.G[b1][c], acc1);
+                ps1 = pf1 + acc1;
+            }
+        }
+        image_P();                                            // (xs written as well)
+        put_row(t);
+    }
+    // ---- outputs -------------------------------------------------------------------------------------------------------------
+    const bool ok = failed < 0;
+    for (int64_t s = failed; s >= 0; --s) put_nan(s);
+    if (a.Ps0) {
+        for (int e = lane; e < 144; e += 64) a.Ps0[row * 144 + e] = ok ? S.P[e / 12][e % 12] : NaN;
+    }
+    if (a.sinfo && lane == 0) {
+        const double v[2] = {(double)failed, minpiv};
+        store_row<2>(a.sinfo + row * 2, v);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
+// launch: grid (blocks of UKF_WAVES recordings, P).  Of UkfArgs the field lag is not read, and tape, nrows and Bs by the tape
+// variant alone (tape != nullptr); x0, Y, xf and xT are 13 wide.  Of UkfRtsArgs the fields behind sinfo are not read.
 // ---------------------------------------------------------------------------------------
 hipError_t launch_ukf_filter_quat(hipStream_t st, int integ, int P, const UkfArgs& a) {
     if (a.B <= 0 || P <= 0) return hipSuccess;
-    if (integ == INTEG_EULER) return ukf_launch(ukf_quat_filter_kernel<INTEG_EULER>, st, P, a);
-    return ukf_launch(ukf_quat_filter_kernel<INTEG_RK4>, st, P, a);
+    if (a.tape) {
+        if (integ == INTEG_EULER) return ukf_launch(ukf_quat_filter_kernel<INTEG_EULER, true>, st, P, a);
+        return ukf_launch(ukf_quat_filter_kernel<INTEG_RK4, true>, st, P, a);
+    }
+    if (integ == INTEG_EULER) return ukf_launch(ukf_quat_filter_kernel<INTEG_EULER, false>, st, P, a);
+    return ukf_launch(ukf_quat_filter_kernel<INTEG_RK4, false>, st, P, a);
+}
+
+hipError_t launch_ukf_rts_quat(hipStream_t st, int P, const UkfRtsArgs& a) {
+    if (a.B <= 0 || P <= 0) return hipSuccess;
+    return ukf_launch(ukf_quat_rts_kernel, st, P, a);
 }
 
 }  // namespace brov

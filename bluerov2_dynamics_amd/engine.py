@@ -671,18 +671,12 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     return out
 
 
-def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS, ctx=None):
-    """The multiplicative unscented Kalman filter on the quaternion model (WRENCH_QUAT) for P vehicles x B recordings in one launch
-    (include/brov2.h: brov_ukf_filter_quat_dev holds the law).  The state is 13 wide (p, q with w first, nu); the covariance, cfg.q
-    and cfg.r live in the 12-component error state (dp, twice the Gibbs vector of a body-frame rotation, dnu).
+UKF_TAPE_QUAT = 313     # doubles of a tape record of the quaternion model (include/brov2.h: brov_ukf_filter_tape_quat_dev)
 
-    params_list, cfg and want as in ukf_filter.  Shared by the candidates: x0 [B,13], P0 [B,12,12] (lower triangle read), U [B,T,6],
-    Y [B,T,13] with NaN where a component was not measured (the attitude of a row counts as measured when none of its four numbers
-    is NaN; it need not be unit, nor on the hemisphere of the estimate).  Host and device arrays as in ukf_filter.
-    Returns dict(xf [P,B,T,13], pstd, innov [P,B,T,12], xT [P,B,13], PT [P,B,12,12], info [P,B,4]), with None for what was not
-    wanted.  The ctx's own parameters are left alone."""
-    want = tuple(want)
-    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
+
+def _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx):
+    """the argument handling that ukf_filter_quat and ukf_smooth_quat share: (ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y) with
+    the arrays on the device"""
     P = len(params_list)
     pa = (_lib.BrovParams * max(P, 1))(*params_list)
     cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
@@ -702,10 +696,37 @@ def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUT
         assert tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
     if host:
         x0, P0, U, Y = arr.upload(x0), arr.upload(P0), arr.upload(U), arr.upload(Y)
-    shapes = dict(_ukf_shapes(P, B, T), xf=(P, B, T, 13), xT=(P, B, 13))
+    return ctx, arr, host, P, B, T, pa, len(cfgs), ca, x0, P0, U, Y
+
+
+def _ukf_quat_shapes(P, B, T):
+    return dict(_ukf_shapes(P, B, T), xf=(P, B, T, 13), xT=(P, B, 13), xs=(P, B, T, 13))
+
+
+def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS, ctx=None, tape=False):
+    """The multiplicative unscented Kalman filter on the quaternion model (WRENCH_QUAT) for P vehicles x B recordings in one launch
+    (include/brov2.h: brov_ukf_filter_quat_dev holds the law).  The state is 13 wide (p, q with w first, nu); the covariance, cfg.q
+    and cfg.r live in the 12-component error state (dp, twice the Gibbs vector of a body-frame rotation, dnu).
+
+    params_list, cfg and want as in ukf_filter.  Shared by the candidates: x0 [B,13], P0 [B,12,12] (lower triangle read), U [B,T,6],
+    Y [B,T,13] with NaN where a component was not measured (the attitude of a row counts as measured when none of its four numbers
+    is NaN; it need not be unit, nor on the hemisphere of the estimate).  Host and device arrays as in ukf_filter.
+    Returns dict(xf [P,B,T,13], pstd, innov [P,B,T,12], xT [P,B,13], PT [P,B,12,12], info [P,B,4]), with None for what was not
+    wanted.  The ctx's own parameters are left alone.
+    tape=True (brov_ukf_filter_tape_quat_dev): the dict also holds tape [P,B,T,UKF_TAPE_QUAT], what ukf_rts_quat needs for every
+    transition, and nrows [P,B], the number of rows whose update completed; every other output carries the same bits."""
+    want = tuple(want)
+    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
+    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y = _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx)
+    shapes = _ukf_quat_shapes(P, B, T)
     out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
-    ctx.check(ctx.lib.brov_ukf_filter_quat_dev(ctx.h, INTEGRATORS[integrator], P, pa, len(cfgs), ca, B, T, float(dt), _dptr(x0), _dptr(P0),
-                                               _dptr(U), _dptr(Y), *(_dptr(out[k]) for k in UKF_OUTPUTS)), "brov_ukf_filter_quat_dev")
+    head = (ctx.h, INTEGRATORS[integrator], P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
+            *(_dptr(out[k]) for k in UKF_OUTPUTS))
+    if tape:
+        out["tape"], out["nrows"] = arr.empty((P, B, T, UKF_TAPE_QUAT)), arr.empty((P, B))
+        ctx.check(ctx.lib.brov_ukf_filter_tape_quat_dev(*head, _dptr(out["tape"]), _dptr(out["nrows"])), "brov_ukf_filter_tape_quat_dev")
+    else:
+        ctx.check(ctx.lib.brov_ukf_filter_quat_dev(*head), "brov_ukf_filter_quat_dev")
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out
@@ -796,14 +817,15 @@ def output_feedback(model, integrator, params_list, feedback, cfg, x0_true, x0_e
     return out
 
 
-def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _em=None):
+def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _em=None, _quat=False):
     """Backward (Rauch-Tung-Striebel) pass over the tape of ukf_filter(..., tape=True) (include/brov2.h: brov_ukf_rts_dev holds
     the law).  xf [P,B,T,12], tape [P,B,T,UKF_TAPE] and nrows [P,B] as that call returned them (the tape is a documented plain
     array).  terminal: (xs_T [P,B,12], Ps_T [P,B,12,12]), the smoothed estimate of row T from a later span, or None.  want: any of
     UKF_SMOOTH_OUTPUTS.  Host arrays or device arrays (all of one kind).  Returns dict(xs, pstd_s [P,B,T,12], Ps [P,B,T,12,12],
     Ps0 [P,B,12,12], sinfo [P,B,2] = first failed transition (-1: none), smallest pivot), with None for what was not wanted.
-    (_em = (cfg, Y): the call of ukf_rts_em.)"""
+    (_em = (cfg, Y): the call of ukf_rts_em.  _quat: the call of ukf_rts_quat.)"""
     want = tuple(want)
+    nx, rec = (13, UKF_TAPE_QUAT) if _quat else (12, UKF_TAPE)
     keys = UKF_SMOOTH_OUTPUTS + (("em",) if _em else ())
     assert all(w in keys for w in want), f"want must be among {keys}"
     host = isinstance(xf, (np.ndarray, list, tuple))
@@ -822,7 +844,7 @@ def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _
         arr = arrays_of(xf, ctx)
     arr.bind()
     P, B, T = (int(s) for s in ins[0].shape[:3])
-    want_shape = [(P, B, T, 12), (P, B, T, UKF_TAPE), (P, B), (P, B, 12), (P, B, 12, 12)]
+    want_shape = [(P, B, T, nx), (P, B, T, rec), (P, B), (P, B, nx), (P, B, 12, 12)]
     for v, shape in zip(ins, want_shape):
         assert tuple(int(s) for s in v.shape) == shape, f"shape {tuple(v.shape)} != {shape}"
     if Y is not None:
@@ -831,16 +853,27 @@ def ukf_rts(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None, _
         ins = [arr.upload(v) for v in ins]
         Y = None if Y is None else arr.upload(Y)
     ins += [None] * (5 - len(ins))
-    shapes = _ukf_shapes(P, B, T)
+    shapes = _ukf_quat_shapes(P, B, T) if _quat else _ukf_shapes(P, B, T)
     out = {k: (arr.empty(shapes[k]) if k in want or k == "em" else None) for k in keys}
     head = (ctx.h, P, B, T, *(_dptr(v) for v in ins), *(_dptr(out[k]) for k in UKF_SMOOTH_OUTPUTS))
     if _em:
         ctx.check(ctx.lib.brov_ukf_rts_em_dev(*head, len(cfgs), ca, _dptr(Y), _dptr(out["em"])), "brov_ukf_rts_em_dev")
+    elif _quat:
+        ctx.check(ctx.lib.brov_ukf_rts_quat_dev(*head), "brov_ukf_rts_quat_dev")
     else:
         ctx.check(ctx.lib.brov_ukf_rts_dev(*head), "brov_ukf_rts_dev")
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out
+
+
+def ukf_rts_quat(xf, tape, nrows, terminal=None, want=UKF_SMOOTH_OUTPUTS, ctx=None):
+    """ukf_rts for the quaternion model: the backward pass over the tape of ukf_filter_quat(..., tape=True) (include/brov2.h:
+    brov_ukf_rts_quat_dev holds the law).  xf [P,B,T,13], tape [P,B,T,UKF_TAPE_QUAT], nrows [P,B]; terminal: (xs_T [P,B,13], Ps_T
+    [P,B,12,12]) or None; the sign and the norm of xs_T's quaternion do not matter.  Returns dict(xs [P,B,T,13], pstd_s [P,B,T,12],
+    Ps [P,B,T,12,12], Ps0 [P,B,12,12], sinfo [P,B,2]): the smoothed quaternion keeps the sign and the norm of xf's, and everything
+    else lives in the 12-component error state.  A transition also fails (sinfo[0]) where xs_{t+1} and xp_{t+1} are half a turn apart."""
+    return ukf_rts(xf, tape, nrows, terminal=terminal, want=want, ctx=ctx, _quat=True)
 
 
 def ukf_rts_em(xf, tape, nrows, cfg, Y, terminal=None, want=UKF_SMOOTH_OUTPUTS + ("em",), ctx=None):
@@ -871,6 +904,23 @@ def ukf_smooth(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     else:
         ctx.check(ctx.lib.brov_ukf_smooth_dev(*head), "brov_ukf_smooth_dev")
     out["lag"] = lag_io
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
+def ukf_smooth_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS, tape_bytes=0, ctx=None):
+    """Filter and smooth on the quaternion model in one call (brov_ukf_smooth_quat_dev): the arguments and outputs of ukf_filter_quat
+    plus the outputs of ukf_rts_quat.  The tape stays inside the library as in ukf_smooth, in the same buffer of the ctx of at most
+    tape_bytes (0: 2 GiB); the chunks change no bit."""
+    want = tuple(want)
+    keys = UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS
+    assert all(w in keys for w in want), f"want must be among {keys}"
+    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y = _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx)
+    shapes = _ukf_quat_shapes(P, B, T)
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
+    ctx.check(ctx.lib.brov_ukf_smooth_quat_dev(ctx.h, INTEGRATORS[integrator], P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U),
+                                               _dptr(Y), *(_dptr(out[k]) for k in keys), int(tape_bytes)), "brov_ukf_smooth_quat_dev")
     if host:
         out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
     return out

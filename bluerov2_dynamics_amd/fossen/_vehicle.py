@@ -309,13 +309,30 @@ class VehicleBase:
         defaults as filter_states.  Returns the dict of filter_states plus xs [.,T,12] the smoothed means, std_s [.,T,12], Ps
         [.,T,12,12] the smoothed covariances, Ps0 [.,12,12] and failed_transition (-1: none, also where the filter completed no
         row and there was nothing to smooth), without the leading B when Y was one recording.  tape_bytes bounds the library's tape buffer (0: 2 GiB).
-        Thruster and Euler-wrench vehicles: the quaternion vehicle has no smoother and raises NotImplementedError."""
-        self._euler_only("smooth_states")
+        Thruster and Euler-wrench vehicles: on the quaternion vehicle this raises NotImplementedError; smooth_states_quat is its smoother."""
+        if self.MODEL == engine.WRENCH_QUAT:
+            raise NotImplementedError("smooth_states: thruster and Euler-wrench vehicles only; the quaternion vehicle has smooth_states_quat")
         single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
         r = engine.ukf_smooth(self.MODEL, integrator, [p], cfg, x0, P0, U, Y, dt, tape_bytes=tape_bytes, ctx=self._ctx)
+        return self._smooth_dict(r, single)
+
+    def _smooth_dict(self, r, single):
+        """the dict of smooth_states and smooth_states_quat, from engine.ukf_smooth's / ukf_smooth_quat's outputs at P = 1"""
         out = dict(self._filter_dict(r), xs=r["xs"][0], std_s=r["pstd_s"][0], Ps=r["Ps"][0], Ps0=r["Ps0"][0],
                    failed_transition=np.nan_to_num(r["sinfo"][0, :, 0], nan=-1.0).astype(np.int64))
         return {k: v[0] for k, v in out.items()} if single else out
+
+    def smooth_states_quat(self, Y, U, dt, cfg, x0=None, P0=None, params=None, integrator="euler", tape_bytes=0):
+        """smooth_states of the quaternion vehicle (engine.ukf_smooth_quat; include/brov2.h: brov_ukf_smooth_quat holds the law).  Arguments
+        and defaults as filter_states on that vehicle: Y [.,T,13], the default start of estimate.default_start_quat, the quaternion of a
+        given x0 normalised here.  Returns the dict of smooth_states with x, xs and xT 13 wide; std_s, Ps and Ps0 live in the
+        12-component error state, and the smoothed quaternion keeps the sign of the filtered one.
+        Thruster and Euler-wrench vehicles raise NotImplementedError: smooth_states is their smoother."""
+        if self.MODEL != engine.WRENCH_QUAT:
+            raise NotImplementedError("smooth_states_quat: the quaternion vehicle only; thruster and Euler-wrench vehicles have smooth_states")
+        single, Y, U, x0, P0, p = self._ukf_inputs(Y, U, cfg, x0, P0, params)
+        r = engine.ukf_smooth_quat(integrator, [p], cfg, x0, P0, U, Y, dt, tape_bytes=tape_bytes, ctx=self._ctx)
+        return self._smooth_dict(r, single)
 
     def log_likelihood_population(self, params_list, Y, U, dt, cfg, x0=None, P0=None, integrator="euler"):
         """Which of P vehicles explains noisy recordings best: the innovation log-likelihood of filter_states for every candidate

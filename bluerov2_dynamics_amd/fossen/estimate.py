@@ -3,7 +3,8 @@ VehicleBase.log_likelihood_population), the EM fit of its q and r (em_update, fi
 measurement noise that the output-feedback closed loop takes (measurement_noise).  include/brov2.h (brov_ukf_filter) is the specification of the law: per row a sequence of
 scalar Kalman updates with the measured components of the state (a NaN = not measured), then an unscented prediction through the
 vehicle's own step with 2 n + 1 = 25 sigma points.  The quaternion vehicle has the multiplicative form of the same filter
-(engine.ukf_filter_quat; brov_ukf_filter_quat); quat_boxplus, quat_boxminus and default_start_quat are its chart and its default start.
+(engine.ukf_filter_quat; brov_ukf_filter_quat) and its smoother (engine.ukf_smooth_quat, VehicleBase.smooth_states_quat;
+brov_ukf_smooth_quat) but no EM fit; quat_boxplus, quat_boxminus and default_start_quat are the chart and the default start of both.
 
 Nothing here runs on the device: the struct goes to the kernel through engine.ukf_filter, and fit_noise sums nothing itself (the
 statistics of an EM iteration come from engine.ukf_smooth)."""

@@ -22,7 +22,9 @@ With --quat the vehicle is the quaternion one (fossen/BlueROV2_wrench.py) and th
 degrees, where the Euler-angle vehicles have their 1 / cos(theta): rov.filter_states then runs the multiplicative filter
 (brov_ukf_filter_quat), whose covariance lives in a 12-component error state.  The attitude errors are taken through
 estimate.quat_boxminus (rad at small angles); every third measured quaternion is reported negated, which the filter must not see.
-The small sizes (3 s, 7 draws).
+The small sizes (3 s, 7 draws).  With --quat --smooth, rov.smooth_states_quat (brov_ukf_smooth_quat) runs instead of the filter alone
+and the smoothed RMSE of position, attitude and velocity is printed beside the filtered one; --quat --fit-noise is an error: the
+quaternion vehicle has no EM fit.
 
     python examples/filter_recording.py [--seconds 10 --draws 31 --std 0.1 --seed 0] [--small] [--smooth] [--fit-noise] [--quat]
 """
@@ -140,10 +142,11 @@ def run(seconds=10.0, dt=0.02, draws=31, rel_std=0.1, dropout=0.3, integrator="r
                 **extra)
 
 
-def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True):
+def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator="rk4", seed=0, verbose=True, smooth=False):
     """The quaternion vehicle, started near vertical.  Returns dict(X [T+1,13], Y [T,13], x [T,13], std, innov [T,12], rmse_raw,
     rmse_filtered: dict(position, attitude, velocity) over the measured entries of the second half, nis, loglik [draws + 1] with the
-    true vehicle at index 0, order, rank_true)"""
+    true vehicle at index 0, order, rank_true); with smooth also xs [T,13], std_s [T,12] of the smoother and rmse_smoothed, a dict
+    like rmse_filtered"""
     from bluerov2_dynamics_amd.fossen.BlueROV2_wrench import BlueROV2 as BlueROV2Quat, euler_to_quat
     rov = BlueROV2Quat()
     true = identify.copy_params(identify.params_of(rov))
@@ -167,7 +170,8 @@ def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator
     cfg = estimate.ukf(q=1e-6, r=r)
     start = estimate.quat_boxplus(x0, rng.normal(size=12) * SIGMA)
     P0 = np.diag(np.where(np.isfinite(r), 4.0 * SIGMA ** 2, estimate.P0_STAND_IN))
-    f = rov.filter_states(Y, U, dt, cfg, x0=start, P0=P0, params=true, integrator=integrator)
+    estimator = rov.smooth_states_quat if smooth else rov.filter_states
+    f = estimator(Y, U, dt, cfg, x0=start, P0=P0, params=true, integrator=integrator)
     half = slice(T // 2, T)
     att = ~np.isnan(Y[:, 3:7]).any(axis=1)
     seen = np.concatenate([~np.isnan(Y[:, :3]), np.repeat(att[:, None], 3, 1), ~np.isnan(Y[:, 7:])], 1)[half]
@@ -177,6 +181,9 @@ def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator
     rmse = lambda e: {k: float(np.sqrt(np.mean(e[:, c][seen[:, c]] ** 2))) for k, c in parts.items()}
     rmse_raw, rmse_f = rmse(e_raw), rmse(e_f)
     nis = float(np.nanmean(f["innov"] ** 2))
+    extra = {}
+    if smooth:
+        extra = dict(xs=f["xs"], std_s=f["std_s"], rmse_smoothed=rmse(estimate.quat_boxminus(f["xs"], X[:T])[half]))
     cands = [true] + drawn_vehicles(true, int(draws), seed + 1, rel_std)
     ll = rov.log_likelihood_population(cands, Y, U, dt, cfg, x0=start, P0=P0, integrator=integrator)[:, 0]
     order = np.argsort(-ll)
@@ -187,10 +194,12 @@ def run_quat(seconds=3.0, dt=0.02, draws=7, rel_std=0.1, dropout=0.3, integrator
               f"{f['n_updates']} scalar updates, smallest Cholesky pivot {f['min_pivot']:.2e}")
         for k in parts:
             print(f"RMSE over the second half, measured entries, {k}: raw {rmse_raw[k]:.4f}, filtered {rmse_f[k]:.4f}")
+        for k in parts if smooth else ():
+            print(f"smoothed (every row from all rows), {k}: RMSE {extra['rmse_smoothed'][k]:.4f} against {rmse_f[k]:.4f} filtered")
         print(f"mean squared normalised innovation {nis:.2f} (1 when the noise model fits)")
         print(f"the true vehicle ranks {rank + 1} of {len(cands)} by log-likelihood ({ll[0]:.1f}; best {ll[order[0]]:.1f}, worst {ll[order[-1]]:.1f})")
     return dict(X=X, Y=Y, x=f["x"], std=f["std"], innov=f["innov"], rmse_raw=rmse_raw, rmse_filtered=rmse_f, nis=nis, loglik=ll, order=order,
-                rank_true=rank)
+                rank_true=rank, **extra)
 
 
 def main(argv=None):
@@ -206,9 +215,9 @@ def main(argv=None):
     ap.add_argument("--quat", action="store_true", help="the quaternion vehicle from a start near pitch 90 degrees, in the small sizes")
     a = ap.parse_args(argv)
     if a.quat:
-        if a.smooth or a.fit_noise:
-            ap.error("--quat: the quaternion vehicle has the filter only (no --smooth, no --fit-noise)")
-        return run_quat(rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed)
+        if a.fit_noise:
+            ap.error("--quat: the quaternion vehicle has the filter and the smoother, no EM fit (no --fit-noise)")
+        return run_quat(rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth)
     if a.small:
         a.seconds, a.draws = 3.0, 7
     return run(a.seconds, draws=a.draws, rel_std=a.std, integrator="euler" if a.euler else "rk4", seed=a.seed, smooth=a.smooth,

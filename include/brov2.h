@@ -443,7 +443,8 @@ BROV_API int brov_ukf_filter_dev(brov_ctx* ctx, int model, int integrator, int l
  * Unchanged from brov_ukf_filter: the failure handling (the problem stops alone, NaN rows, info), the continuation property (a call
  * resumed from (xT, PT) gives the bits of the unbroken call), determinism, and every host-side refusal that applies, with the same
  * words.  x0's quaternion is used as it comes: negating it negates the quaternion of xf and xT and changes no other bit.
- * Not covered: the tape variant, the smoother, EM and output feedback keep refusing the quaternion model. */
+ * Its smoother is brov_ukf_smooth_quat further down (with brov_ukf_filter_tape_quat_dev and brov_ukf_rts_quat_dev).  Not covered:
+ * brov_ukf_filter, brov_ukf_smooth, EM and output feedback keep refusing the quaternion model. */
 BROV_API int brov_ukf_filter_quat(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
                          const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0, const double* P0,
                          const double* U, const double* Y, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info);
@@ -504,7 +505,7 @@ BROV_API int brov_ukf_filter_quat_dev(brov_ctx* ctx, int integrator, int64_t P, 
  * Refused on the host, before anything is copied, allocated or launched, with a text that names the function called: everything
  * brov_ukf_filter refuses, a negative tape_bytes, and a tape_bytes smaller than one block of recordings (P * 4 * T * 2496 bytes).
  * Deterministic (no atomics, fixed summation orders): two calls give the same bits.
- * Still missing: a smoother for the quaternion model (brov_ukf_filter_quat is its forward filter; it writes no tape), full Q and R.
+ * Still missing: full Q and R; for the quaternion model (brov_ukf_smooth_quat below is its smoother) the EM fit and output feedback.
  *
  * ---- fitting q and r: the sufficient statistics of expectation-maximisation (EM) ------------------------------------------------
  * Every call above takes a record whose q[12] and r[12] are guesses.  brov_ukf_rts_em_dev and brov_ukf_smooth_em[_dev] are the
@@ -568,6 +569,62 @@ BROV_API int brov_ukf_smooth_em_dev(brov_ctx* ctx, int model, int integrator, in
                            const double* d_P0, const double* d_U, const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd,
                            double* d_innov, double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps,
                            double* d_Ps0, double* d_sinfo, int64_t tape_bytes, double* d_em);
+
+/* ---- the smoother of the quaternion model ---------------------------------------------------------------------------------------
+ * Notation as in brov_ukf_filter_quat: the state is 13 wide, the error state 12 wide, [+] and [-] are that filter's chart.  The
+ * smoother is the first-order form, consistent with the filter it runs over: NO covariance is transported between the tangent
+ * spaces at xf_t, xp_{t+1} and xs_{t+1}, as the filter transports none at a reset.
+ *
+ * Tape.  brov_ukf_filter_tape_quat_dev is brov_ukf_filter_quat_dev plus d_tape and d_nrows, given together or not at all; with both
+ * NULL it is the plain call.  Every output of the plain call keeps its bits.  tape [P][B][T][313], a record of 313 doubles (2 504
+ * bytes), triangles packed as in the tape above:
+ *       0 ..  77   Pf_t, the covariance after the update of row t (in the error state at xf_t), lower triangle
+ *      78 ..  90   xp_{t+1}, the 13-wide predicted mean chi_0' [+] m
+ *      91 .. 168   Pp_{t+1}, the predicted covariance including diag(q), lower triangle
+ *     169 .. 312   C_{t+1} [12][12] row-major
+ * C_{t+1} = sum_{i>=1} W_i (chi_i [-] x)(d_i - m)^T.  chi_i [-] x = +- c L[:, i-1] by construction, so
+ *     C[a][b] = sum_{j=0..11} L[a][j] ((c W_i) (d_{j+1}[b] - d_{j+13}[b])),  summed in index order:
+ * the expression of the tape above on the quaternion filter's d.  nrows and the NaN rules for transitions that did not complete are
+ * those of brov_ukf_filter_tape_dev.
+ *
+ * Backward pass.  brov_ukf_rts_quat_dev takes the arguments of brov_ukf_rts_dev; d_xf, d_xs and d_xs_T are 13 wide and the tape 313.
+ * With n as there, it starts from (xs, Ps)_{n-1} = (xf, Pf)_{n-1}, or, with n = T and a terminal pair (xs_T [P][B][13], Ps_T
+ * [P][B][12][12], lower triangle read), from that pair.  Per transition t:
+ *     Pp_{t+1} = Lp Lp^T, the filter's Cholesky factorisation and pivot rule;
+ *     G = C_{t+1} Pp_{t+1}^-1 by the two substitutions per row of C;
+ *     delta = xs_{t+1} [-] xp_{t+1}, the attitude part through the chart, so it is blind to the sign and the norm of either
+ *         quaternion.  A delta that is not finite (half a turn between the two, or a zero quaternion) fails transition t exactly
+ *         like a bad pivot;
+ *     xs_t = xf_t [+] (G delta): the smoothed quaternion keeps the sign and the norm of xf_t;
+ *     Ps_t = Pf_t + G (Ps_{t+1} - Pp_{t+1}) G^T, one expression for both triangles: Ps is bit-symmetric.
+ * Outputs, each may be NULL: xs [P][B][T][13]; pstd_s [P][B][T][12]; Ps [P][B][T][12][12]; Ps0 [P][B][12][12]; sinfo [P][B][2].  As in
+ * brov_ukf_rts_dev: rows >= n are NaN and n = 0 leaves every output of the problem NaN, sinfo included; row n-1 (T-1 without a
+ * terminal pair) carries the bits of the filter, xs = xf and pstd_s = pstd; a failed transition t leaves xs, pstd_s and Ps of rows
+ * <= t and Ps0 NaN, rows > t valid and every other problem untouched, and the call returns BROV_OK; spans split in time chain
+ * through (xT, PT) forwards and (xs[0], Ps0) backwards and give the bits of the unbroken call; the refusals are the same.
+ * Negating x0's quaternion negates the quaternion of every xf and xs bit for bit and changes no other output; negating or scaling the
+ * quaternion of xs_T changes no bit.
+ *
+ * brov_ukf_smooth_quat[_dev] is both passes: the inputs of brov_ukf_filter_quat, the filter's outputs, the smoother's outputs and
+ * tape_bytes.  Chunking, the ctx-owned tape buffer (the one brov_ukf_smooth uses) and its keep / free rule are brov_ukf_smooth's;
+ * refused is what brov_ukf_filter_quat refuses, a negative tape_bytes, and a tape_bytes smaller than one block of recordings
+ * (P * 4 * T * 2504 bytes), before anything is copied, allocated or launched, with a text that names the function called. */
+BROV_API int brov_ukf_filter_tape_quat_dev(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
+                                  const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                                  const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd, double* d_innov,
+                                  double* d_xT, double* d_PT, double* d_info, double* d_tape, double* d_nrows);
+BROV_API int brov_ukf_rts_quat_dev(brov_ctx* ctx, int64_t P, int64_t B, int64_t T, const double* d_xf, const double* d_tape,
+                          const double* d_nrows, const double* d_xs_T, const double* d_Ps_T, double* d_xs, double* d_pstd_s, double* d_Ps,
+                          double* d_Ps0, double* d_sinfo);
+BROV_API int brov_ukf_smooth_quat(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
+                         const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* x0, const double* P0,
+                         const double* U, const double* Y, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
+                         double* xs, double* pstd_s, double* Ps, double* Ps0, double* sinfo, int64_t tape_bytes);
+BROV_API int brov_ukf_smooth_quat_dev(brov_ctx* ctx, int integrator, int64_t P, const brov_params* params /* [P], host */, int64_t nrec,
+                             const brov_ukf* ukf /* [nrec], host */, int64_t B, int64_t T, double dt, const double* d_x0,
+                             const double* d_P0, const double* d_U, const double* d_Y, double* d_xf, double* d_pstd, double* d_innov,
+                             double* d_xT, double* d_PT, double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0,
+                             double* d_sinfo, int64_t tape_bytes);
 
 /* ---- output-feedback closed loop: the filter inside the rollout kernel ----------------------------------------------------------
  * brov_rollout_feedback feeds the TRUE state back, and brov_ukf_filter runs over recordings whose commands are fixed.  A vehicle
