@@ -26,7 +26,11 @@ block, chunk and row edges of the seeding, and for the loop every kernel its dis
 edmdc_kmeans_lloyd_dev), every stopping rule and every empty-cluster rule.  The last family is the unscented RTS smoother (smooth: the
 eight TAPE = true instantiations of ukf_filter_kernel, each with a full and a ragged block, ukf_rts_kernel and the chunked
 brov_ukf_smooth; the shapes of ukf plus B = 13, T = 1, 2, 3 with and without a terminal pair, a tape budget with room for 4, 8 or 5
-recordings -- chunks 4 + 4 + 1, 8 + 5, 4 + 4 + 4 + 1, 5 rounded down to 4, nrec = P = 3 in chunks -- and strict subsets of the outputs)."""
+recordings -- chunks 4 + 4 + 1, 8 + 5, 4 + 4 + 4 + 1, 5 rounded down to 4, nrec = P = 3 in chunks -- and strict subsets of the outputs).
+The two families after it are the multiplicative filter and the smoother of the quaternion model (ukf_quat: the four instantiations of
+ukf_quat_filter_kernel; smooth_quat: its TAPE forms, ukf_quat_rts_kernel and the chunked brov_ukf_smooth_quat with the 313-double
+record): the shapes of ukf and smooth plus starts anywhere on the sphere, inverted with the yaw next to pi, near vertical, q_w < 0,
+an attitude block of P0 wide enough for the sigma points to leave the chart's linear range, and r = +inf on an attitude component."""
 import hashlib
 import json
 
@@ -36,7 +40,7 @@ NAMES = ("V0", "V1", "V2", "V3", "V4", "V5", "V6", "V7", "V8")      # tests/foss
 WRENCH_NAMES = ("V0", "V1", "V2", "V4", "V5", "V7")                 # tests/fossen_vehicles.py: WRENCH_NAMES
 N_CASES = 48                                                        # per family: four slices of 12
 N_CASES_EDMDC = 32                                                  # per EDMDc family: four slices of 8 (corner lists of 12 to 24)
-N_CASES_FILTER = 32                                                 # ukf, lmpc and smooth: four slices of 8 (corner lists of 17, 26 and 20)
+N_CASES_FILTER = 32                                                 # ukf, lmpc, smooth, ukf_quat, smooth_quat: four slices of 8 (corners: 17, 26, 20, 16, 20)
 N_CASES_KMEANS = 32                                                 # colstats, kmeanspp, lloyd: four slices of 8
 SEED = 2024
 
@@ -87,6 +91,12 @@ SETS = dict(
     smooth=dict(model=(0, 1), integ=("euler", "rk4"), lag_mode=(0, 1), lag=(True, False), P=(1, 2, 3), nrec=("1", "P"), alpha=(0.5, 1.0),
                 B=(1, 3, 4, 5, 8, 9, 13), T=(1, 2, 3, 12), measured=("std", "all", "none"), r_inf=(0, 1, 3), q_zero=(True, False),
                 wrap=(True, False), chunk=("whole", 4, 8, 5), terminal=(True, False), want=("all", "xs+sinfo", "Ps0", "pstd_s+Ps")),
+    ukf_quat=dict(integ=("euler", "rk4"), P=(1, 2, 3), nrec=("1", "P"), alpha=(0.5, 1.0), B=(1, 3, 4, 5, 8, 9, 13), T=(1, 2, 3, 12),
+                  measured=("std", "all", "none"), r_inf=(0, 1, 3), q_zero=(True, False), attitude=("level", "vertical", "sphere", "inverted"),
+                  spread=("std", "wide")),
+    smooth_quat=dict(integ=("euler", "rk4"), P=(1, 2, 3), nrec=("1", "P"), alpha=(0.5, 1.0), B=(1, 3, 4, 5, 8, 9, 13), T=(1, 2, 3, 12),
+                     measured=("std", "all", "none"), r_inf=(0, 1, 3), q_zero=(True, False), attitude=("level", "vertical", "sphere", "inverted"),
+                     spread=("std", "wide"), chunk=(0, 1, 2, 1.5), terminal=(True, False), want=("all", "xs+sinfo", "Ps0", "pstd_s+Ps")),
 )
 
 
@@ -907,6 +917,112 @@ def draw_smooth(rng):
                    _pick(rng, s["chunk"]), _pick(rng, s["terminal"]), _pick(rng, s["want"]))
 
 
+# ------------------------------------------------------------------------------------------ quaternion-model UKF and RTS smoother
+SMOOTH_QUAT_RECORD = 313 * 8                                        # bytes of a tape record of the quaternion model: 2504
+QUAT_BLOCK = 4                                                      # UKF_WAVES: the recordings of a block, the unit of `chunk`
+
+
+def _ukf_quat(rng, integ, P, nrec, alpha, B, T, measured, r_inf, q_zero, attitude, spread):
+    """nrec, measured, r_inf, q_zero as in _ukf (r_inf in the error state: component 7, then 2, then the attitude component 4 while 3 and
+    5 are updated).  attitude: the start of every recording -- "level" Euler angles in +-0.3, "vertical" the pitch within 0.1 rad of 90
+    degrees, x0's quaternion negated and every third measured quaternion times -2, "sphere" a uniformly random unit quaternion with the
+    sign as drawn, "inverted" the roll within 0.1 rad of pi and the yaw at +-(pi - 0.05).  spread: "wide" gives the attitude block of
+    P0 a sigma of QUAT_WIDE_SIGMA in chart units (tests/sweep_quat.py).  The recordings are simulated with the last candidate's vehicle."""
+    assert P * B * T <= UKF_ROWS, (P, B, T)
+    return dict(family="ukf_quat", integ=integ, P=P, nrec=_sym(nrec, P=P), nrec_as=nrec, alpha=alpha, B=B, T=T, measured=measured, r_inf=r_inf,
+                q_zero=bool(q_zero), attitude=attitude, spread=spread, names=_vehicles(rng, 2, P), seed=int(rng.integers(0, 1 << 30)))
+
+
+UKF_QUAT_CORNERS = (
+    # integ  P  nrec alpha B  T  measured r_inf q_zero attitude spread
+    ("euler", 2, "P", 1.0, 4, 12, "std", 1, False, "level", "std"),                # a full block alone
+    ("rk4", 3, "P", 0.5, 5, 12, "all", 0, True, "sphere", "wide"),                 # blockIdx.y = 2 reads its own record; 12 updates in every row
+    ("euler", 3, "P", 1.0, 5, 12, "all", 3, False, "inverted", "wide"),            # r = +inf on attitude component 4, 3 and 5 updated, every row
+    ("rk4", 1, "1", 1.0, 4, 12, "none", 1, False, "vertical", "std"),              # pure prediction over 12 rows
+    ("euler", 1, "1", 0.5, 1, 1, "none", 0, False, "vertical", "std"),             # B = 1, T = 1, no measurement
+    ("rk4", 2, "1", 0.5, 8, 12, "std", 1, True, "level", "std"),                   # two full blocks
+    ("euler", 1, "1", 1.0, 9, 12, "std", 0, False, "sphere", "std"),               # three blocks, the last with one wave
+    ("rk4", 1, "1", 1.0, 9, 2, "std", 3, False, "inverted", "std"),
+    ("euler", 2, "1", 0.5, 3, 3, "std", 1, True, "inverted", "std"),
+    ("rk4", 3, "P", 1.0, 3, 2, "all", 0, False, "level", "wide"),
+    ("euler", 1, "1", 1.0, 8, 1, "all", 0, False, "sphere", "wide"),
+    ("rk4", 2, "P", 0.5, 1, 12, "std", 1, False, "sphere", "std"),
+    ("euler", 3, "1", 0.5, 4, 3, "std", 0, False, "vertical", "wide"),
+    ("rk4", 2, "1", 1.0, 5, 1, "std", 1, False, "vertical", "std"),
+    ("euler", 1, "1", 1.0, 13, 12, "all", 0, True, "level", "std"),                # four blocks, the last with one wave
+    ("rk4", 3, "P", 1.0, 4, 3, "none", 3, False, "inverted", "wide"),
+)
+
+
+def _draw_quat_shape(rng, s, t_set):
+    while True:
+        P, B, T = _pick(rng, s["P"]), _pick(rng, s["B"]), _pick(rng, t_set)
+        if P * B * T <= UKF_ROWS:                                     # a draw beyond the row budget is drawn again
+            return P, B, T
+
+
+def draw_ukf_quat(rng):
+    s = SETS["ukf_quat"]
+    P, B, T = _draw_quat_shape(rng, s, s["T"])
+    return _ukf_quat(rng, _pick(rng, s["integ"]), P, _pick(rng, s["nrec"]), _pick(rng, s["alpha"]), B, T, _pick(rng, s["measured"]),
+                     _pick(rng, s["r_inf"]), _pick(rng, s["q_zero"]), _pick(rng, s["attitude"]), _pick(rng, s["spread"]))
+
+
+def smooth_quat_tape_bytes(c):
+    """the tape_bytes a case passes: room for `chunk` blocks of QUAT_BLOCK recordings (1.5: six recordings, which the host rounds down
+    to one block; 0: for all B, and never below the one block that the host demands)"""
+    return c["P"] * (max(c["B"], QUAT_BLOCK) if c["chunk"] == 0 else int(c["chunk"] * QUAT_BLOCK)) * c["T"] * SMOOTH_QUAT_RECORD
+
+
+def smooth_quat_chunks(c):
+    """the recordings per launch pair of brov_ukf_smooth_quat under smooth_quat_tape_bytes(c), by the rule of csrc/capi.hip:
+    ukf_filter_quat -- what fits, rounded down to whole blocks, unless all B fit"""
+    fit = smooth_quat_tape_bytes(c) // (c["P"] * c["T"] * SMOOTH_QUAT_RECORD)
+    step = c["B"] if fit >= c["B"] else fit // QUAT_BLOCK * QUAT_BLOCK
+    return [min(step, c["B"] - b0) for b0 in range(0, c["B"], step)]
+
+
+def _smooth_quat(rng, integ, P, nrec, alpha, B, T, measured, r_inf, q_zero, attitude, spread, chunk, terminal, want):
+    """the fields of _ukf_quat, then chunk: the blocks of recordings the tape budget of the chunked call has room for (0: all B);
+    terminal: the two-call path passes a terminal pair (tests/sweep_quat.py: terminal_pair); want as in _smooth"""
+    c = _ukf_quat(rng, integ, P, nrec, alpha, B, T, measured, r_inf, q_zero, attitude, spread)
+    c.update(family="smooth_quat", chunk=chunk, terminal=bool(terminal), want=list(SMOOTH_WANT[want]), want_as=want)
+    return c
+
+
+SMOOTH_QUAT_CORNERS = (
+    # integ  P  nrec alpha B  T  measured r_inf q_zero attitude spread chunk terminal want
+    ("euler", 2, "P", 1.0, 8, 12, "std", 1, False, "level", "std", 1, False, "all"),                # chunks 4 + 4 under Euler; two full blocks
+    ("rk4", 2, "P", 0.5, 8, 12, "std", 1, False, "sphere", "std", 0, True, "all"),                  # a pair at T = 12 from anywhere on the sphere
+    ("rk4", 3, "P", 1.0, 9, 3, "std", 0, False, "level", "std", 1, False, "all"),                   # nrec = P = 3 in chunks 4 + 4 + 1: loc != row at blockIdx.y = 2
+    ("euler", 3, "P", 0.5, 5, 12, "all", 3, False, "inverted", "wide", 1, False, "xs+sinfo"),       # chunks 4 + 1, xf scratch; +inf on attitude component 4
+    ("rk4", 3, "P", 1.0, 5, 12, "all", 0, True, "sphere", "wide", 0, False, "xs+sinfo"),            # xf scratch in one chunk; 12 updates a row
+    ("rk4", 1, "1", 1.0, 13, 12, "std", 1, False, "level", "std", 2, False, "all"),                 # chunks 8 + 5: a ragged second chunk
+    ("euler", 1, "1", 0.5, 1, 1, "none", 0, False, "vertical", "std", 0, False, "all"),             # B = 1, T = 1 without a pair: the loop never runs
+    ("rk4", 1, "1", 1.0, 4, 1, "std", 1, False, "vertical", "std", 0, True, "all"),                 # T = 1 with a pair: the loop starts at t = n - 1 = 0
+    ("euler", 2, "1", 1.0, 4, 2, "std", 1, False, "sphere", "std", 0, True, "Ps0"),                 # T = 2 with a pair
+    ("rk4", 2, "1", 0.5, 3, 2, "all", 0, False, "inverted", "std", 0, False, "all"),                # T = 2 without: fetch(t - 1) never taken
+    ("euler", 1, "1", 1.0, 9, 3, "std", 3, False, "inverted", "std", 1.5, True, "Ps0"),             # T = 3 with a pair; room for 6 rounded down: 4 + 4 + 1
+    ("rk4", 3, "1", 0.5, 3, 3, "none", 1, False, "level", "wide", 0, False, "pstd_s+Ps"),           # T = 3 without a pair
+    ("euler", 1, "1", 1.0, 8, 12, "none", 1, True, "level", "std", 1, False, "pstd_s+Ps"),          # pure prediction over 12 rows, in chunks
+    ("rk4", 1, "1", 1.0, 5, 12, "all", 0, True, "vertical", "std", 1, True, "all"),                 # chunks 4 + 1 under RK4
+    ("euler", 1, "1", 0.5, 13, 12, "std", 0, False, "vertical", "wide", 1, False, "all"),           # chunks 4 + 4 + 4 + 1: two middle chunks
+    ("rk4", 1, "1", 1.0, 8, 12, "std", 1, False, "inverted", "wide", 1.5, False, "all"),            # room for 6 of 8: chunks 4 + 4
+    ("euler", 2, "1", 0.5, 5, 12, "std", 1, False, "sphere", "wide", 0, True, "all"),
+    ("rk4", 1, "1", 1.0, 1, 12, "std", 1, False, "sphere", "std", 0, False, "all"),                 # B = 1 over 12 rows
+    ("euler", 3, "P", 1.0, 4, 12, "all", 0, False, "level", "std", 0, True, "all"),
+    ("rk4", 2, "1", 1.0, 4, 12, "std", 1, False, "level", "std", 0, False, "all"),                  # the corner of the terminal-pair and short-prefix test
+)
+
+
+def draw_smooth_quat(rng):
+    s = SETS["smooth_quat"]
+    P, B, T = _draw_quat_shape(rng, s, SMOOTH_T_DRAW)
+    return _smooth_quat(rng, _pick(rng, s["integ"]), P, _pick(rng, s["nrec"]), _pick(rng, s["alpha"]), B, T, _pick(rng, s["measured"]),
+                        _pick(rng, s["r_inf"]), _pick(rng, s["q_zero"]), _pick(rng, s["attitude"]), _pick(rng, s["spread"]), _pick(rng, s["chunk"]),
+                        _pick(rng, s["terminal"]), _pick(rng, s["want"]))
+
+
 # ------------------------------------------------------------------------------------------ the lists
 _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), feedback=(_feedback, FEEDBACK_CORNERS, draw_feedback),
              mppi=(_mppi, MPPI_CORNERS, draw_mppi), koopman_mppi=(_koopman_mppi, KOOPMAN_MPPI_CORNERS, draw_koopman_mppi),
@@ -915,11 +1031,12 @@ _MAKE = dict(rollout_pop=(_rollout_pop, ROLLOUT_POP_CORNERS, draw_rollout_pop), 
              pinv_apply=(_pinv_apply, PINV_APPLY_CORNERS, draw_pinv_apply), multistep=(_multistep, MULTISTEP_CORNERS, draw_multistep),
              simulate=(_simulate, SIMULATE_CORNERS, draw_simulate), ukf=(_ukf, UKF_CORNERS, draw_ukf), lmpc=(_lmpc, LMPC_CORNERS, draw_lmpc),
              colstats=(_colstats, COLSTATS_CORNERS, draw_colstats), kmeanspp=(_kmeanspp, KMEANSPP_CORNERS, draw_kmeanspp),
-             lloyd=(_lloyd, LLOYD_CORNERS, draw_lloyd), smooth=(_smooth, SMOOTH_CORNERS, draw_smooth))
+             lloyd=(_lloyd, LLOYD_CORNERS, draw_lloyd), smooth=(_smooth, SMOOTH_CORNERS, draw_smooth),
+             ukf_quat=(_ukf_quat, UKF_QUAT_CORNERS, draw_ukf_quat), smooth_quat=(_smooth_quat, SMOOTH_QUAT_CORNERS, draw_smooth_quat))
 FAMILIES = tuple(_MAKE)                                             # the order is part of the seeds: new families go last
 EDMDC_FAMILIES = ("lift", "gram", "pinv_apply", "multistep", "simulate")
 N_CORNERS = {f: len(_MAKE[f][1]) for f in FAMILIES}                 # 12 for the five older families
-FILTER_FAMILIES = ("ukf", "lmpc", "smooth")
+FILTER_FAMILIES = ("ukf", "lmpc", "smooth", "ukf_quat", "smooth_quat")
 KMEANS_FAMILIES = ("colstats", "kmeanspp", "lloyd")
 N_CASES_OF = {f: N_CASES_EDMDC if f in EDMDC_FAMILIES else N_CASES_FILTER if f in FILTER_FAMILIES else N_CASES_KMEANS if f in KMEANS_FAMILIES
               else N_CASES for f in FAMILIES}
@@ -1014,3 +1131,11 @@ def lloyd(seed=SEED):
 
 def smooth(seed=SEED):
     return cases("smooth", seed)
+
+
+def ukf_quat(seed=SEED):
+    return cases("ukf_quat", seed)
+
+
+def smooth_quat(seed=SEED):
+    return cases("smooth_quat", seed)

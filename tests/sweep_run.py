@@ -21,7 +21,9 @@ a lane is a (candidate, recording) filter or a problem.  The k-means families (c
 their references are exact (indices, labels and centres bit for bit), a reference asserts in prepare that every decision it takes
 is certified, no lane is left out, and the fourth figure of sweep_one is the smallest decision gap instead of a reference gap.  The
 unscented RTS smoother (smooth) is in tests/sweep_smooth.py, by the recipe above with the covariance measures of
-tests/ukf_smooth_cases.py: a lane is a (candidate, recording) problem, every case runs as two calls, as one call and chunked."""
+tests/ukf_smooth_cases.py: a lane is a (candidate, recording) problem, every case runs as two calls, as one call and chunked.  The
+filter and the smoother of the quaternion model (ukf_quat, smooth_quat) are in tests/sweep_quat.py, in the same shape, with the
+references of tests/ukf_quat_ref.py and tests/ukf_quat_smooth_ref.py and |e_w| > 0.5 in place of the wrap margin."""
 import numpy as np
 
 import feedback_ref as fr
@@ -30,6 +32,7 @@ import koopman_mppi_ref as kr
 import mppi_ref as mr
 import sweep_edmdc as se
 import sweep_kmeans as sk
+import sweep_quat as sq
 import sweep_smooth as ss
 import sweep_ukf_lmpc as su
 from oracle import fossen_params as fp
@@ -406,7 +409,7 @@ def compare_window_pop(case, ref, got):
 
 
 PREPARE = dict(rollout_pop=prepare_rollout_pop, feedback=prepare_feedback, mppi=prepare_mppi, koopman_mppi=prepare_koopman_mppi,
-               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE, **sk.PREPARE, **ss.PREPARE)
+               window_pop=prepare_window_pop, **se.PREPARE, **su.PREPARE, **sk.PREPARE, **ss.PREPARE, **sq.PREPARE)
 
 
 def sweep_one(eng, ctx, case, ref=None):
@@ -421,6 +424,8 @@ def sweep_one(eng, ctx, case, ref=None):
         e, e2 = su.sweep_one(eng, ctx, case, ref)
     elif fam in ss.PREPARE:
         e, e2 = ss.sweep_one(eng, ctx, case, ref)
+    elif fam in sq.PREPARE:
+        e, e2 = sq.sweep_one(eng, ctx, case, ref)
     elif fam in sk.PREPARE:
         e, e2 = sk.sweep_one(eng, ctx, case, ref)
         return e, e2, out, ref["min_gap"]

@@ -38,7 +38,21 @@ terminal pair, P = 1 and 3, B = 1, 4, 8, 9 and 13, a noise record per candidate 
 none, r = +inf on 0 and 3 components, q = 0, middle chunks and a ragged second chunk, a budget rounded down to whole blocks, and strict
 subsets of the outputs.  The identities after it: repeats and problems alone, a split at every row, failures in the second and third
 chunk, a terminal pair given to a short prefix, an nrows edited by the caller (include/brov2.h: the clamp) and the life of the ctx's
-tape buffer."""
+tape buffer.
+
+The filter and the smoother of the quaternion model (ukf_quat, smooth_quat) run 32 cases each in four slices of 8, by
+tests/sweep_quat.py, with the measures, the bound 1e-10 and the three runs per case of the smooth family and |e_w| > 0.5 in every
+[-] in place of the wrap margin.  Over the five problems of tests/ukf_quat_cases.py (P = 2, T = 12, B = 3 or 5, chunks 4 + 1, starts
+near level or near vertical, Euler in one of five) the lists add P = 1 and 3 (blockIdx.y = 2 reads its own noise record), T = 1, 2 and
+3 with and without a terminal pair, B = 1, 4, 8, 9 and 13, chunks 4 + 4, 4 + 4 + 1, 8 + 5 and 4 + 4 + 4 + 1, a budget of a block and a
+half, a noise record per candidate in chunks under both integrators, strict subsets of the outputs with and without chunks, rows
+with 12 updates and recordings with none, r = +inf on no component and on three with an attitude component among them, q = 0,
+starts anywhere on the sphere (half of them with q_w < 0), inverted with the yaw at +-(pi - 0.05), and an attitude block of P0 of
+sigma 0.3 in chart units.  Largest kernel error per slice against the 9e-14 of the pinned cases: ukf_quat 5.5e-14, 2.0e-13, 6.8e-14,
+9.0e-14; smooth_quat 2.1e-13, 5.7e-13, 5.1e-12, 7.5e-12 (the last two on wide, inverted starts whose own float64-to-long-double gap
+is 4.6e-12 and 5.0e-12); no lane left out.  The identities after them: repeats and problems alone with a noise record per
+candidate, a split at every row from a start on the sphere, the three stopping conditions in the second and third chunk of P = 3,
+a terminal pair given to a short prefix, and both smoothers alternating on one ctx's tape buffer."""
 import numpy as np
 import pytest
 
@@ -46,6 +60,7 @@ import mppi_ref as mr
 import sweep_cases as sc
 import sweep_edmdc as se
 import sweep_kmeans as sk
+import sweep_quat as sq
 import sweep_run as sr
 import sweep_smooth as ss
 import sweep_ukf_lmpc as su
@@ -87,6 +102,11 @@ def test_sweep(eng, ctx, family, part):
     if family == "smooth":
         print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e} (bound {ss.TOL:.0e}; two calls and one call, smoother, tape "
               f"and filter outputs), worst reference gap {gap:.2e}, lanes left out {left}")
+        return
+    if family in sq.PREPARE:
+        print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e} (bound {sq.TOL:.0e}; " +
+              ("two calls and one call, smoother, tape and filter outputs" if family == "smooth_quat" else "every filter output") +
+              f"), worst reference gap {gap:.2e}, lanes left out {left}")
         return
     if family in sc.EDMDC_FAMILIES:
         print(f"{family} slice {part}: {len(cases)} cases, worst kernel err {worst:.2e}, second figure (tests/sweep_edmdc.py: sweep_one) "
@@ -483,6 +503,187 @@ def test_smooth_tape_buffer_life():
             ss.same(ss.smooth(engine, kept, c, ins[id(c)]), fresh[id(c)], SM_ALL, ("call", step, "on one ctx", c))
             if step == 2:                                            # and a chunked call on the grown buffer, which needs less than half of it
                 ss.same(ss.smooth(engine, kept, c, ins[id(c)], tape_bytes=c["P"] * 4 * c["T"] * sc.SMOOTH_RECORD), fresh[id(c)], SM_ALL, ("chunked", c))
+    finally:
+        kept.close()
+
+
+# ------------------------------------------------------------------------------------------ ukf_quat, smooth_quat: the exact identities
+SQ_ALL = sq.F_OUTS + sq.S_OUTS
+SQ_TAPE = SQ_ALL + sq.TAPE_KEYS
+
+
+def _quat_corner(**want):
+    """the first corner of the smooth_quat list that holds `want` (a callable value is a predicate on the field)"""
+    return [c for c in sc.corners("smooth_quat") if all(v(c[k]) if callable(v) else c[k] == v for k, v in want.items())][0]
+
+
+@pytest.mark.parametrize("integ", ["euler", "rk4"])
+def test_smooth_quat_repeats_and_problems_alone(eng, ctx, integ):
+    """a corner with a noise record per candidate, P > 1 and 12 rows, run on its first B = 4, 8, 5 and 1 recordings: two calls give equal
+    bytes; candidate j alone (blockIdx.y = 0 with the record of candidate j) and recording b alone carry the bits they have in the
+    batch, in every filter and smoother output and in the tape; the one-call smoother says the same"""
+    c = _quat_corner(integ=integ, T=12, B=lambda v: v >= 8, P=lambda v: v > 1, nrec=lambda v: v > 1)
+    assert c["nrec"] == c["P"]
+    ins = sq.quat_inputs(c)
+    for B in (4, 8, 5, 1):
+        rec = slice(0, B)
+        a = sq.two_step(eng, ctx, c, ins, rec=rec)
+        assert np.all(a["nrows"] == c["T"]) and np.all(a["sinfo"][..., 0] == -1), (B, c)
+        sq.same(sq.two_step(eng, ctx, c, ins, rec=rec), a, SQ_TAPE, ("repeat", B, c))
+        one = sq.smooth(eng, ctx, c, ins, rec=rec)
+        sq.same(one, a, SQ_ALL, ("one call", B, c))
+        sq.same(sq.smooth(eng, ctx, c, ins, rec=rec), one, SQ_ALL, ("one call, repeated", B, c))
+        for j in range(c["P"]):
+            sq.same(sq.two_step(eng, ctx, c, ins, cand=slice(j, j + 1), rec=rec), a, SQ_TAPE, ("candidate alone", j, B, c), (0,), (j,))
+        for b in range(B):
+            sq.same(sq.two_step(eng, ctx, c, ins, rec=slice(b, b + 1)), a, SQ_TAPE, ("recording alone", b, B, c), (slice(None), 0), (slice(None), b))
+            sq.same(sq.smooth(eng, ctx, c, ins, rec=slice(b, b + 1)), a, SQ_ALL, ("recording alone, one call", b, B, c), (slice(None), 0), (slice(None), b))
+
+
+@pytest.mark.parametrize("attitude", ["sphere", "level"])
+def test_smooth_quat_split_at_every_row(eng, ctx, attitude):
+    """T = 12 rows = T1 + (12 - T1), for every T1 = 1 .. 11: filter rows 0 .. T1 - 1 with a tape, smooth rows T1 .. 11 from (xT, PT),
+    then the backward pass over the first span with the second's (xs[0], Ps0) as its terminal pair: the bits of the unbroken call in
+    xs, pstd_s, Ps and Ps0.  A start anywhere on the sphere and a level one, more than one candidate each."""
+    c = _quat_corner(attitude=attitude, T=12, P=lambda v: v > 1, measured="std")
+    ins = sq.quat_inputs(c)
+    whole = sq.smooth(eng, ctx, c, ins)
+    assert np.all(whole["info"][..., 2] == -1) and np.all(whole["sinfo"][..., 0] == -1), c
+    for T1 in range(1, c["T"]):
+        for j in range(c["P"]):                                      # x0 and P0 are shared by the candidates: resume one by one
+            cj = slice(j, j + 1)
+            first = sq.call(eng.ukf_filter_quat, ctx, c, ins, cand=cj, rows=slice(0, T1), extra=dict(tape=True))
+            second = sq.smooth(eng, ctx, c, ins, cand=cj, rows=slice(T1, None), x0=first["xT"][0], P0=first["PT"][0])
+            back = eng.ukf_rts_quat(first["xf"], first["tape"], first["nrows"], terminal=(second["xs"][:, :, 0], second["Ps0"]), ctx=ctx)
+            for k in sq.ROWS:
+                assert np.array_equal(np.concatenate([back[k], second[k]], axis=2), whole[k][cj]), (k, T1, j, c)
+            assert np.array_equal(back["Ps0"], whole["Ps0"][cj]), (T1, j, c)
+
+
+def _measured_component(ins, b, rmax):
+    """the last error component that row 0 of recording b measures with a finite r"""
+    y = ins["Y"][b, 0]
+    seen = [not np.isnan(y[i]) for i in range(3)] + [not np.isnan(y[3:7]).any()] * 3 + [not np.isnan(y[i + 1]) for i in range(6, 12)]
+    return [k for k in range(12) if seen[k] and np.isfinite(rmax[k])][-1]
+
+
+def test_smooth_quat_chunking_with_failures(eng, ctx):
+    """P = 3 candidates with a noise record each, B = 9 recordings, a tape budget of one block: chunks 4 + 4 + 1.  The corner of the
+    list with 12 rows instead of its 3 (the row budget of the references does not bind here: the reference runs on the failing
+    recording alone).  The three conditions under which a filter stops, by the mechanisms of tests/test_ukf_quat_smooth_gpu.py and
+    tests/test_ukf_quat_gpu.py -- a measured quaternion of zeros at row 3 (stage 1 fails before any update: n = 3), an infinite
+    command at row 6 (n = 7), P0[i][i] = -2 r[i] on the last measured component of row 0 (n = 0; the largest r[i] of the candidates)
+    -- in recording 5 (second chunk, wave slot 1, where the chunk-local index of the tape and of nrows is not the output row) and in
+    recording 8 (the lone recording of the third chunk): nrows, the NaN pattern of the rows and of the tape, info[2] and sinfo are the
+    reference's; the valid prefix is the problem cut to n rows, bit for bit; every other problem carries the bits of the clean
+    call; the chunked call equals the one-chunk call and the two calls.  These are numerical conditions of the input, which the
+    kernels detect and report."""
+    c3 = _quat_corner(P=3, nrec=3, B=9, chunk=1, measured="std", terminal=False)
+    c = dict(c3, T=12)
+    assert sc.smooth_quat_chunks(c) == [4, 4, 1]
+    ins = sq.quat_inputs(c)
+    P, B, T = c["P"], c["B"], c["T"]
+    clean = sq.two_step(eng, ctx, c, ins)
+    assert np.all(clean["nrows"] == T) and np.all(clean["sinfo"][..., 0] == -1), c
+    rmax = np.max([k.r for k in ins["cfgs"]], axis=0)
+    for b in (5, 8):
+        Yz = ins["Y"].copy()
+        Yz[b, 3, 3:7] = 0.0
+        U = ins["U"].copy()
+        U[b, 6, 0] = np.inf
+        comp = _measured_component(ins, b, rmax)
+        P0c = ins["P0"].copy()
+        P0c[b, comp, comp] = -2.0 * rmax[comp]
+        for n, stage, kw in ((3, 1, dict(Y=Yz)), (7, 2, dict(U=U)), (0, 1, dict(P0=P0c))):
+            what = (b, n, c)
+            got = sq.two_step(eng, ctx, c, ins, **kw)
+            with np.errstate(all="ignore"):
+                o = sq.ref_smooth(c, dict(ins, **kw), rec=slice(b, b + 1))
+            assert np.all(o["nrows"] == n) and np.all(o["info"][..., 2] == (n if stage == 1 else n - 1)), ("the reference stops there too", what)
+            assert np.array_equal(got["nrows"][:, b], o["nrows"][:, 0]) and np.array_equal(got["info"][:, b, 2], o["info"][:, 0, 2]), what
+            for k in sq.ROWS + ("tape", "xf", "pstd", "innov", "Ps0", "xT", "PT"):
+                assert _nan_like(got[k][:, b], o[k][:, 0]), (k, what)
+            assert np.array_equal(got["sinfo"][:, b, 0], o["sinfo"][:, 0, 0], equal_nan=True), what
+            assert uc.err(got["sinfo"][:, b, 1], o["sinfo"][:, 0, 1]) < sq.TOL, what
+            for k in sq.ROWS:
+                assert np.isnan(got[k][:, b, n:]).all() and np.isfinite(got[k][:, b, :n]).all(), (k, what)
+            if n:
+                cut = sq.smooth(eng, ctx, c, ins, rows=slice(0, n), **{k: (v[:, :n] if k in ("U", "Y") else v) for k, v in kw.items()})
+                for k in sq.ROWS:
+                    assert np.array_equal(got[k][:, b, :n], cut[k][:, b]), (k, "the valid prefix", what)
+                assert np.array_equal(got["Ps0"][:, b], cut["Ps0"][:, b]) and np.array_equal(got["sinfo"][:, b], cut["sinfo"][:, b]), what
+            for other in range(B):
+                if other != b:
+                    sq.same(got, clean, SQ_TAPE, ("another problem, with a failure in", other, what), (slice(None), other), (slice(None), other))
+            one = sq.smooth(eng, ctx, c, ins, **kw)
+            sq.same(one, got, SQ_ALL, ("one chunk against two calls", what))
+            sq.same(sq.smooth(eng, ctx, c, ins, tape_bytes=sc.smooth_quat_tape_bytes(c), **kw), one, SQ_ALL, ("chunks 4 + 4 + 1 against one chunk", what))
+
+
+def test_smooth_quat_terminal_pair_and_a_short_prefix(eng, ctx):
+    """a terminal pair (sweep_quat.terminal_pair, from the filter's own xT and PT where they are finite) in a call in which one problem
+    was stopped at n = 7 by an infinite command: that problem is the call without a pair, bit for bit (the law ignores the pair when
+    n < T); the problems with n = T move by more than 1e3 TOL.  The upper triangle of Ps_T is NaN.  With a pair and want = () every
+    output is None."""
+    c = _quat_corner(B=4, T=12, P=lambda v: v > 1, measured="std")
+    ins = sq.quat_inputs(c)
+    b, n = 2, 7
+    U = ins["U"].copy()
+    U[b, n - 1, 0] = np.inf
+    f = sq.call(eng.ukf_filter_quat, ctx, c, ins, extra=dict(tape=True), U=U)
+    want_n = np.full((c["P"], c["B"]), float(c["T"]))
+    want_n[:, b] = n
+    assert np.array_equal(f["nrows"], want_n), (f["nrows"], c)
+    clean = sq.call(eng.ukf_filter_quat, ctx, c, ins)
+    pair = sq.terminal_pair(c, dict(xT=np.where(np.isnan(f["xT"]), clean["xT"], f["xT"]), PT=np.where(np.isnan(f["PT"]), clean["PT"], f["PT"])))
+    assert np.isnan(pair[1][..., 0, 1]).all() and np.isfinite(pair[0]).all() and pair[0].shape == (c["P"], c["B"], 13)
+    without = eng.ukf_rts_quat(f["xf"], f["tape"], f["nrows"], ctx=ctx)
+    with_pair = eng.ukf_rts_quat(f["xf"], f["tape"], f["nrows"], terminal=pair, ctx=ctx)
+    sq.same(with_pair, without, sq.S_OUTS, ("a pair given to a short prefix", c), (slice(None), b), (slice(None), b))
+    assert np.isfinite(with_pair["xs"][:, b, :n]).all() and np.isnan(with_pair["xs"][:, b, n:]).all(), c
+    for other in range(c["B"]):
+        if other != b:
+            assert np.all(with_pair["sinfo"][:, other, 0] == -1) and np.isfinite(with_pair["Ps"][:, other]).all(), (other, c)
+            for j in range(c["P"]):
+                moved = uc.err(with_pair["xs"][j, other], without["xs"][j, other])
+                assert moved > 1e3 * sq.TOL, ("the pair must move a complete problem", moved, j, other, c)
+    optional = eng.ukf_rts_quat(f["xf"], f["tape"], f["nrows"], terminal=pair, want=(), ctx=ctx)      # a pair with every optional output NULL
+    assert all(v is None for v in optional.values())
+    sq.same(eng.ukf_rts_quat(f["xf"], f["tape"], f["nrows"], terminal=pair, want=("sinfo",), ctx=ctx), with_pair, ("sinfo",), ("sinfo alone", c))
+
+
+def test_smooth_tape_buffer_shared_by_both_smoothers():
+    """brov_ukf_smooth (records of 312 doubles) and brov_ukf_smooth_quat (313) use one tape buffer of the ctx.  They alternate on one
+    ctx so that the buffer grows, shrinks below half and grows again across the two: large quat, small Euler, large Euler, small
+    quat, large quat, with large B = 13, T = 12 and small B = 1, T = 1.  After the large Euler call a quaternion call in chunks of
+    8 + 5 needs between half and all of the buffer the Euler call grew, so it runs on that buffer.  Every call gives the bits it gives
+    on a fresh ctx."""
+    from bluerov2_dynamics_amd import _lib, engine
+    lq, sq_ = _quat_corner(B=13, T=12), _quat_corner(B=1, T=1)
+    le, se_ = _smooth_corner(B=13, T=12), _smooth_corner(B=1, T=1)
+    size = lambda c, rec, B: c["P"] * B * c["T"] * (rec + 8)       # tape and nrows of B recordings
+    assert 2 * size(se_, sc.SMOOTH_RECORD, 1) + 512 < size(lq, sc.SMOOTH_QUAT_RECORD, 13), "small Euler: below half of large quat"
+    assert 2 * size(sq_, sc.SMOOTH_QUAT_RECORD, 1) + 512 < size(le, sc.SMOOTH_RECORD, 13), "small quat: below half of large Euler"
+    assert sc.smooth_quat_chunks(lq) == [8, 5] and 2 * size(lq, sc.SMOOTH_QUAT_RECORD, 8) > size(le, sc.SMOOTH_RECORD, 13) + 512 \
+        and size(lq, sc.SMOOTH_QUAT_RECORD, 8) + 512 < size(le, sc.SMOOTH_RECORD, 13), "chunks of 8: kept on the Euler call's buffer"
+    runs = {"lq": lambda k, **kw: sq.smooth(engine, k, lq, ins["lq"], **kw), "sq": lambda k, **kw: sq.smooth(engine, k, sq_, ins["sq"], **kw),
+            "le": lambda k, **kw: ss.smooth(engine, k, le, ins["le"], **kw), "se": lambda k, **kw: ss.smooth(engine, k, se_, ins["se"], **kw)}
+    ins = dict(lq=sq.quat_inputs(lq), sq=sq.quat_inputs(sq_), le=su.ukf_inputs(le), se=su.ukf_inputs(se_))
+    keys = dict(lq=SQ_ALL, sq=SQ_ALL, le=SM_ALL, se=SM_ALL)
+    fresh = {}
+    for name in runs:
+        one = _lib.Context(0)
+        try:
+            fresh[name] = runs[name](one)
+        finally:
+            one.close()
+    kept = _lib.Context(0)
+    try:
+        for step, name in enumerate(("lq", "se", "le", "sq", "lq")):
+            same = sq.same if name.endswith("q") else ss.same
+            same(runs[name](kept), fresh[name], keys[name], ("call", step, name, "on one ctx"))
+            if step == 2:
+                sq.same(runs["lq"](kept, tape_bytes=sc.smooth_quat_tape_bytes(lq)), fresh["lq"], SQ_ALL, ("chunks 8 + 5 on the Euler call's buffer", lq))
     finally:
         kept.close()
 

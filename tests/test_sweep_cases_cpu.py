@@ -13,7 +13,11 @@ of any iteration of the certified Lloyd reference is undecided -- here for every
 The smoother family (smooth; tests/sweep_smooth.py) takes its reference from tests/ukf_smooth_ref.py with and without the case's
 terminal pair: a lane needs the gaps of tests/ukf_smooth_cases.py and of the filter below a tenth of 1e-10, wrap margins above 1e-6,
 forward and backward pivots above 1e-4 and every row and transition completed in both precisions; with at most 39 lanes a case the
-2 % cap again means that no lane is left out, and (f) the reference's clamp of an edited nrows is the header's."""
+2 % cap again means that no lane is left out, and (f) the reference's clamp of an edited nrows is the header's.
+The quaternion families (ukf_quat, smooth_quat; tests/sweep_quat.py) take theirs from tests/ukf_quat_ref.py and
+tests/ukf_quat_smooth_ref.py: a lane needs every gap below a tenth of 1e-10, |e_w| above 0.5 in every [-] taken, pivots above 1e-4 and
+every row and transition completed in both precisions; again no lane is left out.  (g) Their corner lists tell the law from every
+neighbour that the two references offer, by orders of magnitude more than the five pinned problems of tests/ukf_quat_cases.py do."""
 import numpy as np
 import pytest
 
@@ -22,9 +26,10 @@ import sweep_cases as sc
 SLICES = 4
 PINNED = dict(rollout_pop="b4f7b2290e6ab13c", feedback="4c9883ac5a6cc7c3", mppi="74fd85dc3ab0bb0a", koopman_mppi="ba6fde35b7fbdb03", window_pop="eb2644555a733e52",
               lift="62c586556d519270", gram="c447b4abb5b3d59e", pinv_apply="54c93dc0a5e3b343", multistep="552e6e4e744eb655", simulate="9f4f465e2cfbb921",
-              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88", colstats="36c523c381e38c6e", kmeanspp="ee864b94e8c1c124", lloyd="fedd81db4999f98f", smooth="805feafecaca48a9")
+              ukf="53cf8c7f5c12aeab", lmpc="473db34e0cdb6f88", colstats="36c523c381e38c6e", kmeanspp="ee864b94e8c1c124", lloyd="fedd81db4999f98f", smooth="805feafecaca48a9",
+              ukf_quat="b64cbbd87c7bbd2a", smooth_quat="fd328c6822245314")
 CORNERS = dict(rollout_pop=12, feedback=12, mppi=12, koopman_mppi=12, window_pop=12, lift=12, gram=24, pinv_apply=14, multistep=14, simulate=12, ukf=17, lmpc=26,
-               colstats=12, kmeanspp=14, lloyd=29, smooth=20)
+               colstats=12, kmeanspp=14, lloyd=29, smooth=20, ukf_quat=16, smooth_quat=20)
 LLOYD_LARGE_ON_CPU = 2                    # cases from 2^18 rows on whose reference is prepared here too: the first with bounds, the first without
 
 
@@ -152,6 +157,91 @@ def test_smoother_corner_pairs():
     assert all(not c["lag"] and c["lag_mode"] == 0 for c in allc if c["model"] == 1)
     assert all(sc.smooth_tape_bytes(c) >= c["P"] * 4 * c["T"] * sc.SMOOTH_RECORD for c in allc), "never below the one block the host demands"
     assert 3 * sum(c["T"] >= 2 for c in allc) >= 2 * len(allc), "at least two thirds of the cases have a transition"
+
+
+def _quat_has(family, **want):
+    """a corner of the family holds `want` (a callable value is a predicate on the field)"""
+    return any(all(v(c[k]) if callable(v) else c[k] == v for k, v in want.items()) for c in sc.corners(family))
+
+
+def test_quaternion_corner_pairs():
+    """the edges the ukf_quat and smooth_quat corner lists must contain, by name"""
+    chunked = lambda c: len(sc.smooth_quat_chunks(c)) > 1
+    for fam in ("ukf_quat", "smooth_quat"):
+        for integ in ("euler", "rk4"):
+            assert _quat_has(fam, integ=integ, B=4) and _quat_has(fam, integ=integ, B=5) and _quat_has(fam, integ=integ, P=3, nrec=3), (fam, integ)
+            for att in sc.SETS[fam]["attitude"]:
+                assert _quat_has(fam, integ=integ, attitude=att), (fam, integ, att)
+        assert _quat_has(fam, measured="all", T=12) and _quat_has(fam, measured="none", T=1) and _quat_has(fam, measured="none", T=12), fam
+        assert _quat_has(fam, measured="all", r_inf=3) and _quat_has(fam, measured="all", r_inf=0), fam
+        assert _quat_has(fam, attitude="sphere", spread="wide") and _quat_has(fam, attitude="inverted", spread="wide"), fam
+        assert _quat_has(fam, B=13, T=12) and _quat_has(fam, B=1, T=1), fam
+        assert all(c["P"] * c["B"] * c["T"] <= sc.UKF_ROWS and c["nrec"] in (1, c["P"]) for c in sc.cases(fam)), fam
+    s = sc.corners("smooth_quat")
+    for integ in ("euler", "rk4"):
+        assert any(c["integ"] == integ and chunked(c) for c in s), (integ, "a chunked call")
+        assert any(c["integ"] == integ and c["nrec"] == c["P"] > 1 and c["T"] == 12 and c["B"] >= 8 for c in s), (integ, "the corner of the repeat test")
+    for T in (1, 2, 3):
+        assert _quat_has("smooth_quat", T=T, terminal=True) and _quat_has("smooth_quat", T=T, terminal=False), T
+    sets = [sc.smooth_quat_chunks(c) for c in s]
+    for want in ([4, 4, 1], [4, 1], [8, 5], [4, 4]):
+        assert want in sets, (want, sets)
+    assert any(c["chunk"] == 1.5 and c["B"] > 4 and sc.smooth_quat_chunks(c)[0] == 4 for c in s), "1.5 blocks are rounded down to one"
+    assert any(c["P"] == 3 and c["nrec"] == 3 and chunked(c) for c in s), "a noise record per candidate at P = 3, chunked"
+    assert any(c["P"] == 3 and c["nrec"] == 3 and c["B"] == 9 and sc.smooth_quat_chunks(c) == [4, 4, 1] and c["measured"] == "std" and not c["terminal"]
+               for c in s), "the corner of test_smooth_quat_chunking_with_failures"
+    for want in sc.SMOOTH_WANT:
+        if want != "all":
+            assert any(c["want_as"] == want and chunked(c) for c in s) and any(c["want_as"] == want and not chunked(c) for c in s), want
+    for att in ("sphere", "level"):
+        assert any(c["attitude"] == att and c["T"] == 12 and c["P"] > 1 and c["measured"] == "std" for c in s), (att, "the corner of the split test")
+    assert any(c["B"] == 4 and c["T"] == 12 and c["P"] > 1 and c["measured"] == "std" for c in s), "the corner of the short-prefix test"
+    allc = sc.cases("smooth_quat")
+    assert all(sum(sc.smooth_quat_chunks(c)) == c["B"] and c["want"] == list(sc.SMOOTH_WANT[c["want_as"]]) for c in allc)
+    assert all(sc.smooth_quat_tape_bytes(c) >= c["P"] * 4 * c["T"] * sc.SMOOTH_QUAT_RECORD for c in allc), "never below the one block the host demands"
+    assert 3 * sum(c["T"] >= 2 for c in allc) >= 2 * len(allc), "at least two thirds of the cases have a transition"
+
+
+# (variant) -> (family, index in the corner list, the output that must tell it from the law)
+QUAT_NEIGHBOURS = dict(plus_left=("ukf_quat", 2, "xf"), minus_left=("ukf_quat", 2, "xf"), no_d=("ukf_quat", 2, "xf"), no_mean=("ukf_quat", 2, "xf"),
+                       no_wc0=("ukf_quat", 2, "PT"))
+QUAT_SMOOTH_NEIGHBOURS = dict(minus_left=("smooth_quat", 16, "xs"), dx_linear=("smooth_quat", 16, "xs"), plus_left=("smooth_quat", 16, "xs"),
+                              C_T=("smooth_quat", 16, "xs"), no_Pp=("smooth_quat", 16, "Ps"), dx_from_xf=("smooth_quat", 16, "xs"))
+
+
+def test_quaternion_corners_tell_the_law_from_its_neighbours():
+    """(g) every variant of ukf_quat_ref.VARIANTS on ukf_quat corner 2 (Euler, P = 3, inverted, wide, every entry measured) and every variant
+    of ukf_quat_smooth_ref.VARIANTS on smooth_quat corner 16 (Euler, P = 2, B = 5, sphere, wide, a terminal pair) lies more than 1e3 TOL
+    from the law in the named output; printed next to the figure of the pinned problem q_rk4"""
+    import sweep_quat as sq
+    import ukf_quat_cases as qc
+    import ukf_quat_ref as uq
+    import ukf_quat_smooth_ref as qs
+    assert set(QUAT_NEIGHBOURS) == set(uq.VARIANTS) and set(QUAT_SMOOTH_NEIGHBOURS) == set(qs.VARIANTS)
+    c = sc.corners("ukf_quat")[2]
+    assert (c["attitude"], c["spread"], c["measured"]) == ("inverted", "wide", "all")
+    ins = sq.quat_inputs(c)
+    law = sq.ref_filter(c, ins)
+    for v, (_, _, key) in QUAT_NEIGHBOURS.items():
+        with np.errstate(all="ignore"):
+            g = sq.filter_gaps(sq.ref_filter(c, ins, variant=v), law)[key]
+        pinned = qc.gaps(qc.reference("q_rk4", variant=v), qc.reference("q_rk4"))[key]
+        print(f"filter {v}: {key} apart by {g:.1e} on ukf_quat corner 2, by {pinned:.1e} on the pinned q_rk4")
+        assert g > 1e3 * sq.TOL, (v, key, g)
+        if v in ("plus_left", "minus_left"):
+            assert g > 50 * pinned, (v, "a wide inverted start must separate the side of the product far better than the pinned cases", g, pinned)
+    c = sc.corners("smooth_quat")[16]
+    assert (c["attitude"], c["spread"], c["terminal"]) == ("sphere", "wide", True)
+    ins = sq.quat_inputs(c)
+    plain = sq.ref_smooth(c, ins)
+    term = sq.terminal_pair(c, plain)
+    law = sq.with_terminal(plain, term, np.float64)
+    for v, (_, _, key) in QUAT_SMOOTH_NEIGHBOURS.items():
+        with np.errstate(all="ignore"):
+            g = qs.gaps(sq.with_terminal(plain, term, np.float64, v), law)[key]      # the forward pass is the law under every variant
+        pinned = qs.gaps(qs.reference("q_rk4", variant=v), qs.reference("q_rk4"))[key]
+        print(f"smoother {v}: {key} apart by {g:.1e} on smooth_quat corner 16, by {pinned:.1e} on the pinned q_rk4")
+        assert g > 1e3 * sq.TOL, (v, key, g)
 
 
 def test_reference_clamps_an_edited_nrows_as_the_header_says():
