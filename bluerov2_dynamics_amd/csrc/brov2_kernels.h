@@ -67,14 +67,21 @@ struct UkfArgs {
     double *tape, *nrows;
     int64_t Bs;
 };
-constexpr int UKF_TAPE = 312;   // doubles of one tape record: Pf [78] | xp [12] | Pp [78] | C [12][12]  (include/brov2.h)
+// One tape record of a model whose state is NX wide (include/brov2.h): Pf [78] | xp [NX] | Pp [78] | C [12][12], the triangles row by
+// row.  The offsets, in doubles; the filters' tape variants write through them, the backward kernels read through them.
+template <int NX_>
+struct UkfTapeRec {
+    static constexpr int NX = NX_, PF = 0, XP = PF + 78, PP = XP + NX, C = PP + 78, SIZE = C + 144;
+};
+constexpr int UKF_TAPE = UkfTapeRec<12>::SIZE;          // doubles of one tape record of the Euler models
 int ukf_waves_per_block();      // recordings per block of the filter kernel and of the backward kernel
 hipError_t launch_ukf_filter(hipStream_t st, int model, int integ, int lag_mode, int P, const UkfArgs& a);
 // The multiplicative filter on the quaternion model (ukf_quat.hip; include/brov2.h: brov_ukf_filter_quat holds the law).  UkfArgs with
 // x0 [B][13], Y [B][T][13], xf [P][B][T][13] and xT [P][B][13]; P0, pstd, innov, PT and the records stay in the 12-component error
 // state; lag is not read.  tape != nullptr selects the tape variant, which alone reads tape [P][B][T][UKF_TAPE_QUAT], nrows [P][B] and
 // Bs, with the meaning they have in launch_ukf_filter.  One launch; T >= 1.
-constexpr int UKF_TAPE_QUAT = 313;   // doubles of one tape record: Pf [78] | xp [13] | Pp [78] | C [12][12]  (include/brov2.h)
+constexpr int UKF_TAPE_QUAT = UkfTapeRec<13>::SIZE;     // ... and of the quaternion model
+static_assert(UKF_TAPE == 312 && UKF_TAPE_QUAT == 313, "the record sizes that include/brov2.h documents");
 hipError_t launch_ukf_filter_quat(hipStream_t st, int integ, int P, const UkfArgs& a);
 // Backward (Rauch-Tung-Striebel) pass over a tape (ukf.hip; include/brov2.h: brov_ukf_rts_dev holds the law).  tape [P][B][T][UKF_TAPE]
 // and nrows [P][B] are a chunk's own; xf, the terminal pair and every output are laid out for Bs recordings per candidate and point

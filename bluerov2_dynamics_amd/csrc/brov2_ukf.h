@@ -1,11 +1,12 @@
 // brov2_ukf.h -- what the unscented Kalman filter kernels share: the wave's LDS image, the cross-lane helpers and the one definition
 // of every phase that more than one of them runs.  The kernels are ukf_filter_kernel and ukf_rts_kernel (ukf.hip, whose head comment
-// describes the layout and the synchronisation), ukf_feedback_kernel (ukf_feedback.hip) and ukf_quat_filter_kernel (ukf_quat.hip);
-// they keep their time loop, the order of the phases, the ukf_wave_sync() between phases and the failure bookkeeping.  Every
-// function here is inlined, and a template on the image type where the images differ (UkfLds, UkfQuatLds and ukf.hip's UkfRtsLds all
-// have L and P; the first two share D, m and k).  A floating-point expression here is part of the filters' law -- operands,
-// association, explicit fma, index order of a sum: the filter inside the closed loop is the plain filter bit for bit because both call
-// this text.  How arguments are passed is fitted to the register allocator (values that a phase changes by reference, no array
+// describes the layout and the synchronisation), ukf_feedback_kernel (ukf_feedback.hip), and ukf_quat_filter_kernel and
+// ukf_quat_rts_kernel (ukf_quat.hip); they keep their time loop, the order of the phases, the ukf_wave_sync() between phases and the
+// failure bookkeeping.  Every function here is inlined, and a template on the image type where the images differ (UkfLds, UkfQuatLds
+// and the smoothers' UkfRtsLds and UkfQuatRtsLds all have L and P; the first two share D, m and k).  The tape's record layout, which
+// the tape filters write and the two backward kernels read, is UkfTapeRec<NX> of brov2_kernels.h.  A floating-point expression here
+// is part of the filters' law -- operands, association, explicit fma, index order of a sum: the filter inside the closed loop is the
+// plain filter bit for bit because both call this text.  How arguments are passed is fitted to the register allocator (values that a phase changes by reference, no array
 // copies, the column loop of the Cholesky in the caller): profiles/ukf_shared_phases.md has the resource table to check a change against.
 #pragma once
 #include "brov2_device.h"

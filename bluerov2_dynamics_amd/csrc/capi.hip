@@ -1713,13 +1713,17 @@ static int ukf_records(brov_ctx* c, const std::string& fn, int64_t nrec, const b
 // Everything the host can refuse comes first: nothing has been copied or launched when that fails.  Then one upload of FastParams[P]
 // and of the derived records, one launch.  host: the arrays are the caller's host memory.
 //
-// One body serves the filter, the tape filter and the smoother.  tape / nrows: the caller's device buffers (brov_ukf_filter_tape_dev),
-// both or neither.  sm: the smoother's outputs (brov_ukf_smooth[_dev]); then the tape is the ctx's own buffer of at most tape_bytes,
+// One body serves the filter, the tape filter and the smoother of both model families.  quat: the caller is one of the *_quat entry
+// points (ukf_quat.hip), which pass BROV_WRENCH_QUAT, BROV_LAG_PER_CALL and no lag_io: the state arrays are then 13 wide (everything
+// in the error state stays 12), a tape record has UKF_TAPE_QUAT doubles, and the launchers are the quaternion model's; the other
+// entry points refuse that model.  The backward launches of both families get the same UkfRtsArgs; the quaternion launcher does not
+// read rec, rec_per_candidate, Y and em (em is always null there), which the Euler EM call alone needs.  tape / nrows: the caller's device buffers (brov_ukf_filter_tape[_quat]_dev), both or neither.
+// sm: the smoother's outputs (brov_ukf_smooth*); then the tape is the ctx's own buffer of at most tape_bytes, one for both families,
 // filled and read back a chunk of recordings at a time: one filter launch and one backward launch per chunk, the chunk's pointers
 // moved to its first recording and the outputs laid out for all B (UkfArgs::Bs).  A problem never looks at another, so the chunking
 // changes no bit.  em_call: the caller is brov_ukf_smooth_em[_dev], whose backward launches are the EM instantiation and write em.
 struct UkfSmoothOut { double *xs, *pstd_s, *Ps, *Ps0, *sinfo; bool em_call = false; double* em = nullptr; };
-static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int integ, int lag_mode, int64_t P, const brov_params* params,
+static int ukf_filter(brov_ctx* c, bool host, const char* who_, bool quat, int model, int integ, int lag_mode, int64_t P, const brov_params* params,
                       int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
                       const double* Y, double* lag_io, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
                       double* tape = nullptr, double* nrows = nullptr, const UkfSmoothOut* sm = nullptr, int64_t tape_bytes = 0) {
@@ -1729,21 +1733,22 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     const std::string fn = who_;
     if ((tape == nullptr) != (nrows == nullptr)) return fail(c, BROV_ERR_ARG, fn + ": d_tape and d_nrows go together (both or neither)");
     if (sm && tape_bytes < 0) return fail(c, BROV_ERR_ARG, fn + ": tape_bytes must be >= 0 (0: the default of 2 GiB)");
-    if (model != BROV_THRUSTER_EULER && model != BROV_WRENCH_EULER)
+    if (!quat && model != BROV_THRUSTER_EULER && model != BROV_WRENCH_EULER)
         return fail(c, BROV_ERR_ARG, fn + ": the 12-state Euler models only (BROV_THRUSTER_EULER, BROV_WRENCH_EULER)");
     if (empty) return BROV_OK;
     if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
     if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
     if (sm && sm->em_call && !sm->em) return fail(c, BROV_ERR_ARG, fn + ": NULL em");
     if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
+    const int nx = NX(model), nu = NU(model), tape_rec = quat ? UKF_TAPE_QUAT : UKF_TAPE;     // widths of a state, a command, a record
     int64_t chunk = B;                          // recordings per launch
     if (sm) {
         const int W = ukf_waves_per_block();
-        const double per_rec = (double)P * (double)T * UKF_TAPE * 8.0;           // tape bytes of one recording
+        const double per_rec = (double)P * (double)T * tape_rec * 8.0;           // tape bytes of one recording
         const double budget = tape_bytes ? (double)tape_bytes : 2147483648.0;
         if (budget < per_rec * W)
             return fail(c, BROV_ERR_ARG, fn + ": tape_bytes is smaller than one block of recordings (P * " + std::to_string(W) + " * T * " +
-                                             std::to_string(UKF_TAPE * 8) + " bytes)");
+                                             std::to_string(tape_rec * 8) + " bytes)");
         const double fit = std::floor(budget / per_rec);
         if (fit < (double)B) chunk = (int64_t)fit / W * W;
     }
@@ -1755,7 +1760,6 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
     if (rc) return rc;
     DeviceGuard g(c);
-    const int nu = NU(model);
     const bool lag = lag_io && model == BROV_THRUSTER_EULER;
     const size_t nin = (size_t)B, nout = (size_t)P * B;
     UkfArgs args{};
@@ -1770,15 +1774,15 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     UkfRec* d_rec;
     Arena a(c, host);
     rc = a.lay(who_, [&] {
-        args.x0 = a.in(x0, nin * 12);
+        args.x0 = a.in(x0, nin * nx);
         args.P0 = a.in(P0, nin * 144);
         args.U = a.in(U, nin * T * nu);
-        args.Y = a.in(Y, nin * T * 12);
+        args.Y = a.in(Y, nin * T * nx);
         args.lag = lag ? a.inout(lag_io, nout * 24) : nullptr;
-        args.xf = xf ? a.out(xf, nout * T * 12) : nullptr;
+        args.xf = xf ? a.out(xf, nout * T * nx) : nullptr;
         if (sm) {
-            if (!xf) args.xf = a.take<double>(nout * T * 12);        // the backward pass reads xf: scratch when the caller has none
-            back.xs = sm->xs ? a.out(sm->xs, nout * T * 12) : nullptr;
+            if (!xf) args.xf = a.take<double>(nout * T * nx);        // the backward pass reads xf: scratch when the caller has none
+            back.xs = sm->xs ? a.out(sm->xs, nout * T * nx) : nullptr;
             back.pstd = sm->pstd_s ? a.out(sm->pstd_s, nout * T * 12) : nullptr;
             back.Ps = sm->Ps ? a.out(sm->Ps, nout * T * 144) : nullptr;
             back.Ps0 = sm->Ps0 ? a.out(sm->Ps0, nout * 144) : nullptr;
@@ -1787,7 +1791,7 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
         }
         args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
         args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
-        args.xT = xT ? a.out(xT, nout * 12) : nullptr;
+        args.xT = xT ? a.out(xT, nout * nx) : nullptr;
         args.PT = PT ? a.out(PT, nout * 144) : nullptr;
         args.info = info ? a.out(info, nout * 4) : nullptr;
         d_fp = a.take<FastParams>(P);
@@ -1797,7 +1801,7 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     if (sm) {
         // The ctx's tape: `chunk` recordings, then their nrows.  Nothing can refuse the call any more.  The buffer is kept for the next
         // call unless that one needs more, or less than half of it: a ctx does not sit on a large tape after one large call.
-        const size_t tape_part = Arena::al((size_t)P * chunk * T * UKF_TAPE * 8), need = tape_part + Arena::al((size_t)P * chunk * 8);
+        const size_t tape_part = Arena::al((size_t)P * chunk * T * tape_rec * 8), need = tape_part + Arena::al((size_t)P * chunk * 8);
         if (need > c->ukf_tape_cap || need < c->ukf_tape_cap / 2) {
             HIPCK(c, hipStreamSynchronize(c->stream));
             if (c->ukf_tape) (void)hipFree(c->ukf_tape);
@@ -1816,25 +1820,28 @@ static int ukf_filter(brov_ctx* c, bool host, const char* who_, int model, int i
     args.rec = d_rec;
     back.rec = d_rec;
     back.rec_per_candidate = args.rec_per_candidate;
+    auto filter = [&](const UkfArgs& f) {
+        return quat ? launch_ukf_filter_quat(c->stream, integ, (int)P, f) : launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, f);
+    };
     {
         CallTimer t(c);
-        if (!sm) HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, args));
+        if (!sm) HIPCK(c, filter(args));
         for (int64_t b0 = 0; sm && b0 < B; b0 += chunk) {
             auto at = [b0](auto* p, int64_t per) { return p ? p + b0 * per : p; };
             UkfArgs f = args;
             f.B = std::min(chunk, B - b0);
-            f.x0 = at(args.x0, 12); f.P0 = at(args.P0, 144); f.U = at(args.U, T * nu); f.Y = at(args.Y, T * 12);
-            f.lag = at(args.lag, 24); f.xf = at(args.xf, T * 12); f.pstd = at(args.pstd, T * 12); f.innov = at(args.innov, T * 12);
-            f.xT = at(args.xT, 12); f.PT = at(args.PT, 144); f.info = at(args.info, 4);
-            HIPCK(c, launch_ukf_filter(c->stream, model, integ, lag_mode, (int)P, f));
+            f.x0 = at(args.x0, nx); f.P0 = at(args.P0, 144); f.U = at(args.U, T * nu); f.Y = at(args.Y, T * nx);
+            f.lag = at(args.lag, 24); f.xf = at(args.xf, T * nx); f.pstd = at(args.pstd, T * 12); f.innov = at(args.innov, T * 12);
+            f.xT = at(args.xT, nx); f.PT = at(args.PT, 144); f.info = at(args.info, 4);
+            HIPCK(c, filter(f));
             UkfRtsArgs r = back;
             r.B = f.B;
             r.xf = f.xf; r.tape = f.tape; r.nrows = f.nrows;
-            r.xs = at(back.xs, T * 12); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
+            r.xs = at(back.xs, T * nx); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
             r.sinfo = at(back.sinfo, 2);
-            r.em = at(back.em, UKF_EM);
+            r.em = at(back.em, UKF_EM);                               // (the Euler models' EM call alone has em, and reads Y and rec)
             r.Y = f.Y;
-            HIPCK(c, launch_ukf_rts(c->stream, (int)P, r));
+            HIPCK(c, quat ? launch_ukf_rts_quat(c->stream, (int)P, r) : launch_ukf_rts(c->stream, (int)P, r));
         }
     }
     return a.finish();
@@ -1924,7 +1931,7 @@ int brov_ukf_smooth_em_dev(brov_ctx* c, int model, int integ, int lag_mode, int6
                            double* d_info, double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo, int64_t tape_bytes,
                            double* d_em) {
     const UkfSmoothOut sm{d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo, true, d_em};
-    return ukf_filter(c, false, "brov_ukf_smooth_em_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
+    return ukf_filter(c, false, "brov_ukf_smooth_em_dev", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
                       d_xf, d_pstd, d_innov, d_xT, d_PT, d_info, nullptr, nullptr, &sm, tape_bytes);
 }
 
@@ -1933,7 +1940,7 @@ int brov_ukf_smooth_em(brov_ctx* c, int model, int integ, int lag_mode, int64_t 
                        double* xf, double* pstd, double* innov, double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps,
                        double* Ps0, double* sinfo, int64_t tape_bytes, double* em) {
     const UkfSmoothOut sm{xs, pstd_s, Ps, Ps0, sinfo, true, em};
-    return ukf_filter(c, true, "brov_ukf_smooth_em", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov,
+    return ukf_filter(c, true, "brov_ukf_smooth_em", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov,
                       xT, PT, info, nullptr, nullptr, &sm, tape_bytes);
 }
 
@@ -1941,7 +1948,7 @@ int brov_ukf_filter_tape_dev(brov_ctx* c, int model, int integ, int lag_mode, in
                              const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* d_x0, const double* d_P0, const double* d_U,
                              const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
                              double* d_info, double* d_tape, double* d_nrows) {
-    return ukf_filter(c, false, "brov_ukf_filter_tape_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
+    return ukf_filter(c, false, "brov_ukf_filter_tape_dev", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io,
                       d_xf, d_pstd, d_innov, d_xT, d_PT, d_info, d_tape, d_nrows);
 }
 
@@ -1950,7 +1957,7 @@ int brov_ukf_smooth_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t
                         double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT, double* d_info,
                         double* d_xs, double* d_pstd_s, double* d_Ps, double* d_Ps0, double* d_sinfo, int64_t tape_bytes) {
     const UkfSmoothOut sm{d_xs, d_pstd_s, d_Ps, d_Ps0, d_sinfo};
-    return ukf_filter(c, false, "brov_ukf_smooth_dev", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf,
+    return ukf_filter(c, false, "brov_ukf_smooth_dev", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf,
                       d_pstd, d_innov, d_xT, d_PT, d_info, nullptr, nullptr, &sm, tape_bytes);
 }
 
@@ -1959,7 +1966,7 @@ int brov_ukf_smooth(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, 
                     double* xf, double* pstd, double* innov, double* xT, double* PT, double* info, double* xs, double* pstd_s, double* Ps,
                     double* Ps0, double* sinfo, int64_t tape_bytes) {
     const UkfSmoothOut sm{xs, pstd_s, Ps, Ps0, sinfo};
-    return ukf_filter(c, true, "brov_ukf_smooth", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT,
+    return ukf_filter(c, true, "brov_ukf_smooth", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT,
                       PT, info, nullptr, nullptr, &sm, tape_bytes);
 }
 
@@ -1968,129 +1975,24 @@ int brov_ukf_filter_dev(brov_ctx* c, int model, int integ, int lag_mode, int64_t
                         const double* d_Y, double* d_lag_io, double* d_xf, double* d_pstd, double* d_innov, double* d_xT, double* d_PT,
                         double* d_info) {
     // (its refusals have always named brov_ukf_filter)
-    return ukf_filter(c, false, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf, d_pstd, d_innov,
+    return ukf_filter(c, false, "brov_ukf_filter", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, d_x0, d_P0, d_U, d_Y, d_lag_io, d_xf, d_pstd, d_innov,
                       d_xT, d_PT, d_info);
 }
 
 int brov_ukf_filter(brov_ctx* c, int model, int integ, int lag_mode, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf,
                     int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U, const double* Y, double* lag_io,
                     double* xf, double* pstd, double* innov, double* xT, double* PT, double* info) {
-    return ukf_filter(c, true, "brov_ukf_filter", model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
+    return ukf_filter(c, true, "brov_ukf_filter", false, model, integ, lag_mode, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, lag_io, xf, pstd, innov, xT, PT, info);
 }
 
 // ---- the multiplicative filter on the quaternion model and its smoother (ukf_quat.hip) ------------------------------------------------
-// brov_ukf_filter's order: everything the host can refuse first, with the same words; then one upload of FastParams[P] and of the
-// derived records, one launch.  The state arrays are 13 wide, everything in the error state 12.
-// One body serves the filter, the tape filter and the smoother, as ukf_filter does for the Euler models: tape / nrows are the caller's
-// device buffers (brov_ukf_filter_tape_quat_dev), both or neither; sm holds the smoother's outputs (brov_ukf_smooth_quat[_dev]), and then
-// the tape is the ctx's buffer of at most tape_bytes, with ukf_filter's chunks and its keep / free rule.
+// The *_quat entry points: ukf_filter's body (its order of refusals, with the same words) on 13-wide state arrays, without lag.
 static int ukf_filter_quat(brov_ctx* c, bool host, const char* who_, int integ, int64_t P, const brov_params* params, int64_t nrec,
                            const brov_ukf* ukf, int64_t B, int64_t T, double dt, const double* x0, const double* P0, const double* U,
                            const double* Y, double* xf, double* pstd, double* innov, double* xT, double* PT, double* info,
                            double* tape = nullptr, double* nrows = nullptr, const UkfSmoothOut* sm = nullptr, int64_t tape_bytes = 0) {
-    bool empty;
-    int rc = pop_call_ok(c, who_, BROV_WRENCH_QUAT, integ, BROV_LAG_PER_CALL, P, B, T, (int64_t)1 << 31, &empty);
-    if (rc) return rc;
-    const std::string fn = who_;
-    if ((tape == nullptr) != (nrows == nullptr)) return fail(c, BROV_ERR_ARG, fn + ": d_tape and d_nrows go together (both or neither)");
-    if (sm && tape_bytes < 0) return fail(c, BROV_ERR_ARG, fn + ": tape_bytes must be >= 0 (0: the default of 2 GiB)");
-    if (empty) return BROV_OK;
-    if (T < 1) return fail(c, BROV_ERR_ARG, fn + ": T must be >= 1");
-    if (!params || !ukf || !x0 || !P0 || !U || !Y) return fail(c, BROV_ERR_ARG, fn + ": NULL input");
-    if (nrec != 1 && nrec != P) return fail(c, BROV_ERR_ARG, fn + ": nrec must be 1 or P");
-    int64_t chunk = B;                          // recordings per launch
-    if (sm) {
-        const int W = ukf_waves_per_block();
-        const double per_rec = (double)P * (double)T * UKF_TAPE_QUAT * 8.0;      // tape bytes of one recording
-        const double budget = tape_bytes ? (double)tape_bytes : 2147483648.0;
-        if (budget < per_rec * W)
-            return fail(c, BROV_ERR_ARG, fn + ": tape_bytes is smaller than one block of recordings (P * " + std::to_string(W) + " * T * " +
-                                             std::to_string(UKF_TAPE_QUAT * 8) + " bytes)");
-        const double fit = std::floor(budget / per_rec);
-        if (fit < (double)B) chunk = (int64_t)fit / W * W;
-    }
-    std::vector<UkfRec> rec;
-    rc = ukf_records(c, fn, nrec, ukf, rec);
-    if (rc) return rc;
-    std::vector<FastParams> fp;
-    std::vector<double> phi;
-    rc = derive_candidates(c, integ, (int)P, params, 0, dt, false, fp, phi);
-    if (rc) return rc;
-    DeviceGuard g(c);
-    const size_t nin = (size_t)B, nout = (size_t)P * B;
-    UkfArgs args{};
-    args.rec_per_candidate = nrec > 1;
-    args.B = B; args.T = T; args.dt = dt;
-    args.Bs = B;
-    args.tape = tape;
-    args.nrows = nrows;
-    UkfRtsArgs back{};
-    back.B = B; back.T = T; back.Bs = B;
-    FastParams* d_fp;
-    UkfRec* d_rec;
-    Arena a(c, host);
-    rc = a.lay(who_, [&] {
-        args.x0 = a.in(x0, nin * 13);
-        args.P0 = a.in(P0, nin * 144);
-        args.U = a.in(U, nin * T * 6);
-        args.Y = a.in(Y, nin * T * 13);
-        args.xf = xf ? a.out(xf, nout * T * 13) : nullptr;
-        if (sm) {
-            if (!xf) args.xf = a.take<double>(nout * T * 13);        // the backward pass reads xf: scratch when the caller has none
-            back.xs = sm->xs ? a.out(sm->xs, nout * T * 13) : nullptr;
-            back.pstd = sm->pstd_s ? a.out(sm->pstd_s, nout * T * 12) : nullptr;
-            back.Ps = sm->Ps ? a.out(sm->Ps, nout * T * 144) : nullptr;
-            back.Ps0 = sm->Ps0 ? a.out(sm->Ps0, nout * 144) : nullptr;
-            back.sinfo = sm->sinfo ? a.out(sm->sinfo, nout * 2) : nullptr;
-        }
-        args.pstd = pstd ? a.out(pstd, nout * T * 12) : nullptr;
-        args.innov = innov ? a.out(innov, nout * T * 12) : nullptr;
-        args.xT = xT ? a.out(xT, nout * 13) : nullptr;
-        args.PT = PT ? a.out(PT, nout * 144) : nullptr;
-        args.info = info ? a.out(info, nout * 4) : nullptr;
-        d_fp = a.take<FastParams>(P);
-        d_rec = a.take<UkfRec>(nrec);
-    });
-    if (rc) return rc;
-    if (sm) {
-        // the ctx's tape: `chunk` recordings, then their nrows; ukf_filter's rule for keeping the buffer
-        const size_t tape_part = Arena::al((size_t)P * chunk * T * UKF_TAPE_QUAT * 8), need = tape_part + Arena::al((size_t)P * chunk * 8);
-        if (need > c->ukf_tape_cap || need < c->ukf_tape_cap / 2) {
-            HIPCK(c, hipStreamSynchronize(c->stream));
-            if (c->ukf_tape) (void)hipFree(c->ukf_tape);
-            c->ukf_tape = nullptr;
-            c->ukf_tape_cap = 0;
-            HIPCK(c, hipMalloc((void**)&c->ukf_tape, need));
-            c->ukf_tape_cap = need;
-        }
-        args.tape = reinterpret_cast<double*>(c->ukf_tape);
-        args.nrows = reinterpret_cast<double*>(c->ukf_tape + tape_part);
-    }
-    HIPCK(c, h2d_copy(c, d_fp, fp.data(), (size_t)P * sizeof(FastParams)));
-    HIPCK(c, h2d_copy(c, d_rec, rec.data(), (size_t)nrec * sizeof(UkfRec)));
-    HIPCK(c, hipStreamSynchronize(c->stream));   // fp and rec are locals
-    args.fp = d_fp;
-    args.rec = d_rec;
-    {
-        CallTimer t(c);
-        if (!sm) HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, args));
-        for (int64_t b0 = 0; sm && b0 < B; b0 += chunk) {
-            auto at = [b0](auto* p, int64_t per) { return p ? p + b0 * per : p; };
-            UkfArgs f = args;
-            f.B = std::min(chunk, B - b0);
-            f.x0 = at(args.x0, 13); f.P0 = at(args.P0, 144); f.U = at(args.U, T * 6); f.Y = at(args.Y, T * 13);
-            f.xf = at(args.xf, T * 13); f.pstd = at(args.pstd, T * 12); f.innov = at(args.innov, T * 12);
-            f.xT = at(args.xT, 13); f.PT = at(args.PT, 144); f.info = at(args.info, 4);
-            HIPCK(c, launch_ukf_filter_quat(c->stream, integ, (int)P, f));
-            UkfRtsArgs r = back;
-            r.B = f.B;
-            r.xf = f.xf; r.tape = f.tape; r.nrows = f.nrows;
-            r.xs = at(back.xs, T * 13); r.pstd = at(back.pstd, T * 12); r.Ps = at(back.Ps, T * 144); r.Ps0 = at(back.Ps0, 144);
-            r.sinfo = at(back.sinfo, 2);
-            HIPCK(c, launch_ukf_rts_quat(c->stream, (int)P, r));
-        }
-    }
-    return a.finish();
+    return ukf_filter(c, host, who_, true, BROV_WRENCH_QUAT, integ, BROV_LAG_PER_CALL, P, params, nrec, ukf, B, T, dt, x0, P0, U, Y, nullptr, xf,
+                      pstd, innov, xT, PT, info, tape, nrows, sm, tape_bytes);
 }
 
 int brov_ukf_filter_quat_dev(brov_ctx* c, int integ, int64_t P, const brov_params* params, int64_t nrec, const brov_ukf* ukf, int64_t B, int64_t T,

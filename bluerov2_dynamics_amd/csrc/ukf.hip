@@ -139,12 +139,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
         ukf_wave_sync();                                               // m, x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
         if constexpr (TAPE) {
-            if (lane < 12) tp[t * UKF_TAPE + 78 + lane] = S.x[lane];  // xp_{t+1}
+            if (lane < 12) tp[t * UKF_TAPE + UkfTapeRec<12>::XP + lane] = S.x[lane];  // xp_{t+1}
         }
         ukf_cov(S, f, wi, own, p0, p1);
         if constexpr (TAPE) {
-            tp[t * UKF_TAPE + 90 + lane] = p0;                         // Pp_{t+1}
-            if (own.two) tp[t * UKF_TAPE + 154 + lane] = p1;
+            tp[t * UKF_TAPE + UkfTapeRec<12>::PP + lane] = p0;                         // Pp_{t+1}
+            if (own.two) tp[t * UKF_TAPE + UkfTapeRec<12>::PP + 64 + lane] = p1;
             // C_{t+1}[ca][cb] = sum_j L[ca][j] (c W_i (d_{j+1} - d_{j+13})[cb]): L and D are still in the image
             const double g = cw * wi;
 #pragma unroll
@@ -155,7 +155,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
                     double acc = 0.0;
 #pragma unroll
                     for (int j = 0; j < 12; ++j) acc = fma(S.L[ca][j], g * (S.D[j + 1][cb] - S.D[j + 13][cb]), acc);
-                    tp[t * UKF_TAPE + 168 + e] = acc;
+                    tp[t * UKF_TAPE + UkfTapeRec<12>::C + e] = acc;
                 }
             }
         }
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_filter_kernel(const UkfArg
     if constexpr (TAPE) {
         // of a transition that did not complete xp, Pp and C are NaN; Pf_t stays when the update of row t was complete
         if (!ok) {
-            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE + 78 : failed * UKF_TAPE) + lane; i < T * UKF_TAPE; i += 64) tp[i] = NaN;
+            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE + UkfTapeRec<12>::XP : failed * UKF_TAPE) + lane; i < T * UKF_TAPE; i += 64) tp[i] = NaN;
         }
         if (lane == 0) a.nrows[(int64_t)blockIdx.y * B + b] = (double)nan_from;
     }
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         // Cholesky of Pp, as in the filter
         double Lr[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[90 + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
+        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[UkfTapeRec<12>::PP + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
         bool bad = false;
 #pragma unroll
         for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
@@ -368,15 +368,15 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_rts_kernel(const UkfRtsArg
         // row lr of G: w L^T = C[lr][:], then g L = w
         double g[12];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) g[j] = S.rec[168 + lr * 12 + j];
+        for (int j = 0; j < 12; ++j) g[j] = S.rec[UkfTapeRec<12>::C + lr * 12 + j];
         ukf_solve_llt(S, g);
         if (lane < 12) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) S.G[lane][k] = g[k];
-            S.dx[lane] = xsv - S.rec[78 + lane];              // not wrapped: xs, xp and xf live on the filter's continuous branch
+            S.dx[lane] = xsv - S.rec[UkfTapeRec<12>::XP + lane];              // not wrapped: xs, xp and xf live on the filter's continuous branch
         }
-        ukf_put(S.M, a0, b0, ps0 - S.rec[90 + lane]);
-        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[154 + lane]);
+        ukf_put(S.M, a0, b0, ps0 - S.rec[UkfTapeRec<12>::PP + lane]);
+        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[UkfTapeRec<12>::PP + 64 + lane]);
         ukf_wave_sync();                                      // G, dx, M written
         {
             double acc = 0.0;

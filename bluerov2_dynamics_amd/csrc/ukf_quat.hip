@@ -212,12 +212,12 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
         ukf_wave_sync();                                               // x written
         if (!allfinite) { failed = t; nan_from = t + 1; break; }
         if constexpr (TAPE) {
-            if (lane < 13) tp[t * UKF_TAPE_QUAT + 78 + lane] = S.x[lane];        // xp_{t+1} = chi_0' [+] m
+            if (lane < 13) tp[t * UKF_TAPE_QUAT + UkfTapeRec<13>::XP + lane] = S.x[lane];        // xp_{t+1} = chi_0' [+] m
         }
         ukf_cov(S, f, wi, own, p0, p1);
         if constexpr (TAPE) {
-            tp[t * UKF_TAPE_QUAT + 91 + lane] = p0;                    // Pp_{t+1}
-            if (own.two) tp[t * UKF_TAPE_QUAT + 155 + lane] = p1;
+            tp[t * UKF_TAPE_QUAT + UkfTapeRec<13>::PP + lane] = p0;                    // Pp_{t+1}
+            if (own.two) tp[t * UKF_TAPE_QUAT + UkfTapeRec<13>::PP + 64 + lane] = p1;
             // C_{t+1}[ca][cb] = sum_j L[ca][j] (c W_i (d_{j+1} - d_{j+13})[cb]): chi_i [-] x = +-c L[:, i-1], and L and D are still
             // in the image
             const double g = cw * wi;
@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
                     double acc = 0.0;
 #pragma unroll
                     for (int j = 0; j < 12; ++j) acc = fma(S.L[ca][j], g * (S.D[j + 1][cb] - S.D[j + 13][cb]), acc);
-                    tp[t * UKF_TAPE_QUAT + 169 + e] = acc;
+                    tp[t * UKF_TAPE_QUAT + UkfTapeRec<13>::C + e] = acc;
                 }
             }
         }
@@ -241,7 +241,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_filter_kernel(const U
     if constexpr (TAPE) {
         // of a transition that did not complete xp, Pp and C are NaN; Pf_t stays when the update of row t was complete
         if (!ok) {
-            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE_QUAT + 78 : failed * UKF_TAPE_QUAT) + lane; i < T * UKF_TAPE_QUAT; i += 64)
+            for (int64_t i = (nan_from > failed ? failed * UKF_TAPE_QUAT + UkfTapeRec<13>::XP : failed * UKF_TAPE_QUAT) + lane; i < T * UKF_TAPE_QUAT; i += 64)
                 tp[i] = NaN;
         }
         if (lane == 0) a.nrows[(int64_t)blockIdx.y * B + b] = (double)nan_from;
@@ -360,7 +360,7 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_rts_kernel(const UkfR
         // Cholesky of Pp, as in the filter
         double Lr[12];
 #pragma unroll
-        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[91 + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
+        for (int k = 0; k < 12; ++k) Lr[k] = S.rec[UkfTapeRec<13>::PP + (k <= lr ? lr * (lr + 1) / 2 + k : k * (k + 1) / 2 + lr)];
         bool bad = false;
 #pragma unroll
         for (int j = 0; j < 12; ++j) ukf_cholesky_col(S, Lr, j, lane, lr, bad, minpiv);
@@ -370,25 +370,25 @@ __global__ void __launch_bounds__(64 * UKF_WAVES) ukf_quat_rts_kernel(const UkfR
         {
             double sq[4], pq[4], gq[3];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) { sq[k] = S.xs[3 + k]; pq[k] = S.rec[81 + k]; }
+            for (int k = 0; k < 4; ++k) { sq[k] = S.xs[3 + k]; pq[k] = S.rec[UkfTapeRec<13>::XP + 3 + k]; }
             uq_minus(sq, pq, gq);
             const int c = lr < 3 ? lr : lr + 1;               // (of position and velocity) its component of the 13-wide state
-            const double lin = S.xs[c] - S.rec[78 + c];
+            const double lin = S.xs[c] - S.rec[UkfTapeRec<13>::XP + c];
             dl = lr == 3 ? gq[0] : (lr == 4 ? gq[1] : (lr == 5 ? gq[2] : lin));
         }
         if (__ballot(!(fabs(dl) < INF)) != 0) { failed = t; break; }      // half a turn, a zero quaternion: like a bad pivot
         // row lr of G: w L^T = C[lr][:], then g L = w
         double g[12];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) g[j] = S.rec[169 + lr * 12 + j];
+        for (int j = 0; j < 12; ++j) g[j] = S.rec[UkfTapeRec<13>::C + lr * 12 + j];
         ukf_solve_llt(S, g);
         if (lane < 12) {
 #pragma unroll
             for (int k = 0; k < 12; ++k) S.G[lane][k] = g[k];
             S.dx[lane] = dl;
         }
-        ukf_put(S.M, a0, b0, ps0 - S.rec[91 + lane]);
-        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[155 + lane]);
+        ukf_put(S.M, a0, b0, ps0 - S.rec[UkfTapeRec<13>::PP + lane]);
+        if (two) ukf_put(S.M, a1, b1, ps1 - S.rec[UkfTapeRec<13>::PP + 64 + lane]);
         ukf_wave_sync();                                      // G, dx, M written; every read of xs done
         if (lane < 12) {
             double acc = 0.0;

@@ -597,12 +597,14 @@ def rollout_feedback(model, integrator, params_list, feedback, x0, ref, dt, T=No
 UKF_OUTPUTS = ("xf", "pstd", "innov", "xT", "PT", "info")
 UKF_SMOOTH_OUTPUTS = ("xs", "pstd_s", "Ps", "Ps0", "sinfo")
 UKF_TAPE = 312          # doubles of a tape record (include/brov2.h: brov_ukf_filter_tape_dev)
+UKF_TAPE_QUAT = 313     # doubles of a tape record of the quaternion model (include/brov2.h: brov_ukf_filter_tape_quat_dev)
 UKF_EM = 37             # doubles of an em record: Sq [12] | Sr [12] | nr [12] | nq (include/brov2.h: brov_ukf_rts_em_dev)
 
 
-def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx):
-    """the argument handling that ukf_filter and ukf_smooth share: (ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io) with
-    the arrays on the device"""
+def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx, nx=12):
+    """the argument handling that the filters and smoothers of both model families share: (ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0,
+    U, Y, lag_io) with the arrays on the device.  nx = 13: the *_quat calls, whose state is 13 wide (and which have no lag).  nx
+    follows the function called, not the model: ukf_filter with WRENCH_QUAT goes on with 12-wide arrays and is refused by the library."""
     P = len(params_list)
     pa = (_lib.BrovParams * max(P, 1))(*params_list)
     cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
@@ -618,9 +620,9 @@ def _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx):
         ctx = _ctx_of(x0, ctx)
         arr = arrays_of(x0, ctx)
     arr.bind()
-    assert len(U.shape) == 3 and int(U.shape[2]) == nu, f"U must be [B,T,nu] with nu = {nu}"
+    assert len(U.shape) == 3 and int(U.shape[2]) == nu, "U must be [B,T,6]" if nx == 13 else f"U must be [B,T,nu] with nu = {nu}"
     B, T = int(U.shape[0]), int(U.shape[1])
-    for name, v, shape in (("x0", x0, (B, 12)), ("P0", P0, (B, 12, 12)), ("Y", Y, (B, T, 12))):
+    for name, v, shape in (("x0", x0, (B, nx)), ("P0", P0, (B, 12, 12)), ("Y", Y, (B, T, nx))):
         assert tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
     track = model == THRUSTER_EULER and lag is not None
     if track:
@@ -640,6 +642,44 @@ def _ukf_shapes(P, B, T):
                 xs=(P, B, T, 12), pstd_s=(P, B, T, 12), Ps=(P, B, T, 12, 12), Ps0=(P, B, 12, 12), sinfo=(P, B, 2), em=(P, B, UKF_EM))
 
 
+def _ukf_quat_shapes(P, B, T):
+    return dict(_ukf_shapes(P, B, T), xf=(P, B, T, 13), xT=(P, B, 13), xs=(P, B, T, 13))
+
+
+def _ukf_call(quat, smooth, model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag, lag_mode, want, ctx, tape=False, tape_bytes=0):
+    """the one body of ukf_filter[_quat] (tape) and, with smooth, of ukf_smooth[_quat] (tape_bytes; "em" among want selects the EM call).
+    quat: the *_quat entry points, whose ABI has no model, lag_mode and lag_io, on 13-wide states; their dict has no "lag"."""
+    want = tuple(want)
+    keys = UKF_OUTPUTS + (UKF_SMOOTH_OUTPUTS if smooth else ())
+    allowed = keys + (("em",) if smooth and not quat else ())
+    assert all(w in allowed for w in want), f"want must be among {allowed}"
+    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx, 13 if quat else 12)
+    shapes = _ukf_quat_shapes(P, B, T) if quat else _ukf_shapes(P, B, T)
+    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
+    sizes, ins, outs = (P, pa, ncfg, ca, B, T, float(dt)), (_dptr(x0), _dptr(P0), _dptr(U), _dptr(Y)), tuple(_dptr(out[k]) for k in keys)
+    if quat:
+        head = (ctx.h, INTEGRATORS[integrator], *sizes, *ins, *outs)
+    else:
+        head = (ctx.h, model, INTEGRATORS[integrator], lag_mode, *sizes, *ins, _dptr(lag_io), *outs)
+    q = "_quat" if quat else ""
+    if smooth:
+        fn, tail = f"brov_ukf_smooth{q}_dev", (int(tape_bytes),)
+        if "em" in want:
+            out["em"] = arr.empty(shapes["em"])
+            fn, tail = "brov_ukf_smooth_em_dev", tail + (_dptr(out["em"]),)
+    elif tape:
+        out["tape"], out["nrows"] = arr.empty((P, B, T, UKF_TAPE_QUAT if quat else UKF_TAPE)), arr.empty((P, B))
+        fn, tail = f"brov_ukf_filter_tape{q}_dev", (_dptr(out["tape"]), _dptr(out["nrows"]))
+    else:
+        fn, tail = f"brov_ukf_filter{q}_dev", ()
+    ctx.check(getattr(ctx.lib, fn)(*head, *tail), fn)
+    if not quat:
+        out["lag"] = lag_io
+    if host:
+        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
+    return out
+
+
 def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, lag_mode=LAG_PER_CALL, want=UKF_OUTPUTS, ctx=None, tape=False):
     """Unscented Kalman filter on the Fossen model for P vehicles x B recordings in one launch (include/brov2.h:
     brov_ukf_filter_dev holds the law): candidate j filters the noisy state rows Y under params_list[j].
@@ -653,54 +693,7 @@ def ukf_filter(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     and WRENCH_EULER.  The ctx's own parameters are left alone.
     tape=True (brov_ukf_filter_tape_dev): the dict also holds tape [P,B,T,UKF_TAPE], what ukf_rts needs for every transition, and
     nrows [P,B], the number of rows whose update completed; every other output carries the same bits."""
-    want = tuple(want)
-    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
-    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx)
-    shapes = _ukf_shapes(P, B, T)
-    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
-    head = (ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
-            _dptr(lag_io), *(_dptr(out[k]) for k in UKF_OUTPUTS))
-    if tape:
-        out["tape"], out["nrows"] = arr.empty((P, B, T, UKF_TAPE)), arr.empty((P, B))
-        ctx.check(ctx.lib.brov_ukf_filter_tape_dev(*head, _dptr(out["tape"]), _dptr(out["nrows"])), "brov_ukf_filter_tape_dev")
-    else:
-        ctx.check(ctx.lib.brov_ukf_filter_dev(*head), "brov_ukf_filter_dev")
-    out["lag"] = lag_io
-    if host:
-        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
-    return out
-
-
-UKF_TAPE_QUAT = 313     # doubles of a tape record of the quaternion model (include/brov2.h: brov_ukf_filter_tape_quat_dev)
-
-
-def _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx):
-    """the argument handling that ukf_filter_quat and ukf_smooth_quat share: (ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y) with
-    the arrays on the device"""
-    P = len(params_list)
-    pa = (_lib.BrovParams * max(P, 1))(*params_list)
-    cfgs = [cfg] if isinstance(cfg, _lib.BrovUkf) else list(cfg)
-    ca = (_lib.BrovUkf * max(len(cfgs), 1))(*cfgs)
-    host = isinstance(x0, (np.ndarray, list, tuple))
-    if host:
-        ctx = ctx or default_context()
-        arr = _NativeArrays(ctx)
-        x0, P0, U, Y = as_f64(x0), as_f64(P0), as_f64(U), as_f64(Y)
-    else:
-        ctx = _ctx_of(x0, ctx)
-        arr = arrays_of(x0, ctx)
-    arr.bind()
-    assert len(U.shape) == 3 and int(U.shape[2]) == 6, "U must be [B,T,6]"
-    B, T = int(U.shape[0]), int(U.shape[1])
-    for name, v, shape in (("x0", x0, (B, 13)), ("P0", P0, (B, 12, 12)), ("Y", Y, (B, T, 13))):
-        assert tuple(int(s) for s in v.shape) == shape, f"{name} shape {tuple(v.shape)} != {shape}"
-    if host:
-        x0, P0, U, Y = arr.upload(x0), arr.upload(P0), arr.upload(U), arr.upload(Y)
-    return ctx, arr, host, P, B, T, pa, len(cfgs), ca, x0, P0, U, Y
-
-
-def _ukf_quat_shapes(P, B, T):
-    return dict(_ukf_shapes(P, B, T), xf=(P, B, T, 13), xT=(P, B, 13), xs=(P, B, T, 13))
+    return _ukf_call(False, False, model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag, lag_mode, want, ctx, tape=tape)
 
 
 def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS, ctx=None, tape=False):
@@ -715,21 +708,7 @@ def ukf_filter_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUT
     wanted.  The ctx's own parameters are left alone.
     tape=True (brov_ukf_filter_tape_quat_dev): the dict also holds tape [P,B,T,UKF_TAPE_QUAT], what ukf_rts_quat needs for every
     transition, and nrows [P,B], the number of rows whose update completed; every other output carries the same bits."""
-    want = tuple(want)
-    assert all(w in UKF_OUTPUTS for w in want), f"want must be among {UKF_OUTPUTS}"
-    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y = _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx)
-    shapes = _ukf_quat_shapes(P, B, T)
-    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in UKF_OUTPUTS}
-    head = (ctx.h, INTEGRATORS[integrator], P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
-            *(_dptr(out[k]) for k in UKF_OUTPUTS))
-    if tape:
-        out["tape"], out["nrows"] = arr.empty((P, B, T, UKF_TAPE_QUAT)), arr.empty((P, B))
-        ctx.check(ctx.lib.brov_ukf_filter_tape_quat_dev(*head, _dptr(out["tape"]), _dptr(out["nrows"])), "brov_ukf_filter_tape_quat_dev")
-    else:
-        ctx.check(ctx.lib.brov_ukf_filter_quat_dev(*head), "brov_ukf_filter_quat_dev")
-    if host:
-        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
-    return out
+    return _ukf_call(True, False, WRENCH_QUAT, integrator, params_list, cfg, x0, P0, U, Y, dt, None, LAG_PER_CALL, want, ctx, tape=tape)
 
 
 OUTPUT_FEEDBACK_OUTPUTS = ("traj", "y", "u", "xf", "pstd", "innov", "xT_true", "xT", "PT", "metrics", "info")
@@ -890,40 +869,14 @@ def ukf_smooth(model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag=None, 
     one filter launch and one backward launch each, which changes no bit.
     want may also hold "em" (brov_ukf_smooth_em_dev): em [P,B,UKF_EM], the sufficient statistics of the EM fit of q and r as in
     ukf_rts_em; every other output keeps its bits.  want=("info", "sinfo", "em") is one EM iteration and stores no rows."""
-    want = tuple(want)
-    keys = UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS
-    assert all(w in keys + ("em",) for w in want), f"want must be among {keys + ('em',)}"
-    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y, lag_io = _ukf_inputs(model, params_list, cfg, x0, P0, U, Y, lag, ctx)
-    shapes = _ukf_shapes(P, B, T)
-    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
-    head = (ctx.h, model, INTEGRATORS[integrator], lag_mode, P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U), _dptr(Y),
-            _dptr(lag_io), *(_dptr(out[k]) for k in keys), int(tape_bytes))
-    if "em" in want:
-        out["em"] = arr.empty(shapes["em"])
-        ctx.check(ctx.lib.brov_ukf_smooth_em_dev(*head, _dptr(out["em"])), "brov_ukf_smooth_em_dev")
-    else:
-        ctx.check(ctx.lib.brov_ukf_smooth_dev(*head), "brov_ukf_smooth_dev")
-    out["lag"] = lag_io
-    if host:
-        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
-    return out
+    return _ukf_call(False, True, model, integrator, params_list, cfg, x0, P0, U, Y, dt, lag, lag_mode, want, ctx, tape_bytes=tape_bytes)
 
 
 def ukf_smooth_quat(integrator, params_list, cfg, x0, P0, U, Y, dt, want=UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS, tape_bytes=0, ctx=None):
     """Filter and smooth on the quaternion model in one call (brov_ukf_smooth_quat_dev): the arguments and outputs of ukf_filter_quat
     plus the outputs of ukf_rts_quat.  The tape stays inside the library as in ukf_smooth, in the same buffer of the ctx of at most
     tape_bytes (0: 2 GiB); the chunks change no bit."""
-    want = tuple(want)
-    keys = UKF_OUTPUTS + UKF_SMOOTH_OUTPUTS
-    assert all(w in keys for w in want), f"want must be among {keys}"
-    ctx, arr, host, P, B, T, pa, ncfg, ca, x0, P0, U, Y = _ukf_quat_inputs(params_list, cfg, x0, P0, U, Y, ctx)
-    shapes = _ukf_quat_shapes(P, B, T)
-    out = {k: (arr.empty(shapes[k]) if k in want else None) for k in keys}
-    ctx.check(ctx.lib.brov_ukf_smooth_quat_dev(ctx.h, INTEGRATORS[integrator], P, pa, ncfg, ca, B, T, float(dt), _dptr(x0), _dptr(P0), _dptr(U),
-                                               _dptr(Y), *(_dptr(out[k]) for k in keys), int(tape_bytes)), "brov_ukf_smooth_quat_dev")
-    if host:
-        out = {k: (None if v is None else arr.download(v)) for k, v in out.items()}
-    return out
+    return _ukf_call(True, True, WRENCH_QUAT, integrator, params_list, cfg, x0, P0, U, Y, dt, None, LAG_PER_CALL, want, ctx, tape_bytes=tape_bytes)
 
 
 def mppi_step(model, integrator, params_list, cfg, x, ref, U_nom, dt, K, H=None, lag=None, lag_mode=LAG_PER_CALL, seed=0, eps=None,
